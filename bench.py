@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — measures the MSM / inner-product hot path on MI355X and prints ONE JSON line.
 
-  python bench.py --gpus N --steps K --warmup W [--workload headline|prove|verify|msm]
+  python bench.py --gpus N --steps K --warmup W [--workload headline|prove|verify|msm] [--full] [--dump-outputs DIR]
 
-BASELINE.json's metric has two halves — R1CS constraints proved/s and batch verifies/s — so the default workload
-("headline") runs both on the same box: the top-level fields are the prove half (cfg3: 2^20-constraint proofs), and the
-"verify" object carries the batch-verify half (cfg4: 4096 proofs of 2^14 constraints per GPU) with its own value, roofline
-and cpu_baseline.  The reference's own benchmark workload is benches/r1cs_secq256k1.rs:156-190 (prove) and :201-250 (verify).
+BASELINE.json's metric has two halves — R1CS constraints proved/s and batch verifies/s.  The top-level fields of the default
+workload ("headline") are the prove half (cfg3: 2^20-constraint proofs); a plain run does only that: set up, warm up, time K
+steps, print the line.  With --full the same run also carries the "verify" object, the batch-verify half (cfg4: 4096 proofs of
+2^14 constraints per GPU) with its own value, roofline and cpu_baseline, the prove half's roofline, post-run checks and
+cpu_baseline, and the other configurations of BASELINE.json.  --dump-outputs DIR writes the proofs of the last timed step.
+The reference's own benchmark workload is benches/r1cs_secq256k1.rs:156-190 (prove) and :201-250 (verify).
 
 A "step" is one pass of the hot path over one batch of synthetic input.  `--gpus N` with N > 1 and no WORLD_SIZE in the
 environment starts N ranks itself (torch.distributed.run, one process per GPU, before this process touches the GPU); under a
@@ -14,7 +16,7 @@ launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.  Units are sharded across rank
 all-gather of one 64-byte partial point (and a status word) per rank and step — in the verify workload, where several batches are
 in flight per GPU, gathered for all steps at once at the end of the timed region.
 
-Documented multi-GPU commands (SCALE): `bench.py --gpus N` (prove replicas + proof-sharded verify),
+Documented multi-GPU commands (SCALE): `bench.py --gpus N --full` (prove replicas + proof-sharded verify + cfg5),
 `bench.py --gpus N --workload verify`, `bench.py --gpus N --workload prove --shard windows --logn 22` (cfg5: one proof at a
 time, Pippenger windows and the IPA folds partitioned across the ranks), `bench.py --gpus N --workload msm --shard windows`.
 
@@ -583,7 +585,7 @@ def run_prove(args, rank, world, local):
         pipe.run(100, args.batch * args.warmup, [None] * (args.batch * args.warmup))
     nproofs = args.batch * args.steps
     flat = [None] * nproofs
-    pipe.keep_info = {0, nproofs - 1}
+    pipe.keep_info = {0, nproofs - 1} if args.full else set()
     barrier(world)
     cpu0 = cgroup_cpu_stat()
     t0 = time.perf_counter()
@@ -591,10 +593,15 @@ def run_prove(args, rank, world, local):
     barrier(world)
     host_cpu = cgroup_cpu_delta(cpu0, time.perf_counter() - t0)
     dt = max_over_ranks(time.perf_counter() - t0, world)
-    # The proofs that were timed are checked (after the timed region): the first and the last of the run go through the GPU verifier
-    # — Verifier::verify, src/r1cs/verifier.rs:549-600 — and a copy with one flipped bit of t_x must be rejected; the run fails otherwise.
-    # The precomputed tables the proofs came through are walked entry by entry (bp_gens_tables_check).
-    verified = 0
+    if args.dump_outputs and rank == 0:
+        # what a caller of prove() receives: the proofs of the last timed step (seeded statements: the same bytes on every run)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = np.stack([np.frombuffer(p, dtype=np.uint8) for p, _ in flat[-args.batch:]])
+        np.save(os.path.join(args.dump_outputs, "proofs.npy"), last.astype(np.float32))
+    # The proofs that were timed are checked (after the timed region, with --full): the first and the last of the run go through the GPU
+    # verifier — Verifier::verify, src/r1cs/verifier.rs:549-600 — and a copy with one flipped bit of t_x must be rejected; the run fails
+    # otherwise.  The precomputed tables the proofs came through are walked entry by entry (bp_gens_tables_check).
+    verified = 0 if args.full else None
     for i in sorted(pipe.keep_info):
         commits, pubs = pipe.infos[i]
         proof = flat[i][0]
@@ -608,7 +615,7 @@ def run_prove(args, rank, world, local):
             raise RuntimeError("bench: a tampered copy of timed proof %d was not rejected (status %d)" % (i, rc))
         verified += 1
     t_chk = time.perf_counter()
-    tables_bad = list(engs[0].gens_tables_check()) if (tab_info or msm_tab_info) else None
+    tables_bad = list(engs[0].gens_tables_check()) if (args.full and (tab_info or msm_tab_info)) else None
     t_chk = time.perf_counter() - t_chk
     if tables_bad and any(tables_bad):
         raise RuntimeError("bench: precomputed table entries fail the chain-rule check: %r" % (tables_bad,))
@@ -624,21 +631,24 @@ def run_prove(args, rank, world, local):
     stages = np.zeros(8)
     for (_, tm) in flat:
         stages += np.array(tm)
-    # kernel durations for the roofline: ONE more proof, alone on the GPU, after the timed region — HIP-event times taken while
+    # kernel durations for the roofline (--full): ONE more proof, alone on the GPU, after the timed region — HIP-event times taken while
     # several streams share the GPU include the other streams' kernels
-    engs[0].set_profiling(True)     # (HIP events only here: the timed pipeline above runs without them)
-    engs[0].reset_profiling()
-    iso = E.Statement(args.curve, E.SC_SQUARE_CHAIN, [N, 0], statement_seed(120, 0))
-    t_iso = time.perf_counter()
-    iso.precompute()                                 # the TranscriptRng head of prove(): sequential by the reference's construction, one core
-    rng_head_ms = (time.perf_counter() - t_iso) * 1e3
-    t_iso = time.perf_counter()
-    iso.prove(engs[0])
-    alone_ms = (time.perf_counter() - t_iso) * 1e3   # everything after the head, this proof alone on the GPU (with HIP-event profiling on)
-    iso.free()
-    fold_ms, fold_n = engs[0].kernel_time(3)
-    acc_ms = engs[0].kernel_time(0)[0]
-    msm_ms = engs[0].kernel_time(1)[0]
+    rng_head_ms = alone_ms = None
+    fold_n = 0
+    if args.full:
+        engs[0].set_profiling(True)     # (HIP events only here: the timed pipeline above runs without them)
+        engs[0].reset_profiling()
+        iso = E.Statement(args.curve, E.SC_SQUARE_CHAIN, [N, 0], statement_seed(120, 0))
+        t_iso = time.perf_counter()
+        iso.precompute()                                 # the TranscriptRng head of prove(): sequential by the reference's construction, one core
+        rng_head_ms = (time.perf_counter() - t_iso) * 1e3
+        t_iso = time.perf_counter()
+        iso.prove(engs[0])
+        alone_ms = (time.perf_counter() - t_iso) * 1e3   # everything after the head, this proof alone on the GPU (with HIP-event profiling on)
+        iso.free()
+        fold_ms, fold_n = engs[0].kernel_time(3)
+        acc_ms = engs[0].kernel_time(0)[0]
+        msm_ms = engs[0].kernel_time(1)[0]
     names = ["prove_total", "-", "transcript_rng", "uploads", "commit_msms", "flatten_constraints", "poly_kernels", "ipa"]
     res = {
         "metric": "r1cs_constraints_proved_per_sec", "value": N * (1 if window_sharded else world) * nproofs / dt, "unit": "constraints/s", "n_gpus": world,
@@ -649,7 +659,8 @@ def run_prove(args, rank, world, local):
                                % (args.logn, CURVES[args.curve], args.batch, P, args.host_threads, args.build_threads),
                    "constraints_per_proof": N, "proofs_per_step": args.batch, "gpu_streams": P, "host_threads": args.host_threads, "build_threads": args.build_threads,
                    "curve": CURVES[args.curve], "parallelism": ("window-sharded x%d" if window_sharded else "replicas x%d") % world,
-                   "verified": verified, "verified_note": "timed proofs 0 and %d verified on the GPU after the timed region, a tampered copy of each rejected" % (nproofs - 1),
+                   "verified": verified, "verified_note": ("timed proofs 0 and %d verified on the GPU after the timed region, a tampered copy of each rejected" % (nproofs - 1))
+                   if args.full else "not checked (--full verifies two timed proofs)",
                    "table_entries_failing_check": tables_bad, "tables_check_s": t_chk if tables_bad is not None else None, "collectives": coll_info,
                    "pipeline_thread_seconds_per_wall_second": pipe_util, "host_cpu_in_timed_region": host_cpu, "host_cpu": host_cpu_info(),
                    "in_pipeline_latency_ms": float(stages[0]) / nproofs * 1e3, "alone_ms_after_rng_head": alone_ms, "rng_head_ms": rng_head_ms,
@@ -758,7 +769,7 @@ def run_prove(args, rank, world, local):
                                               "note": "upper figures: every term costed at the ordinary schedule's %d mixed additions; 7/9 of the terms take the fixed-base schedule (13)" % madds_per_term},
                            "kernels": kernels}
     # ---- the same pipeline with the precomputed tables released: what the 150 GB of HBM buy ----
-    if args.tables_off_steps > 0 and (tab_info or msm_tab_info) and not window_sharded:
+    if args.full and args.tables_off_steps > 0 and (tab_info or msm_tab_info) and not window_sharded:
         engs[0].set_profiling(False)
         engs[0].gens_fold_tables(0)
         engs[0].gens_msm_tables(0)
@@ -775,7 +786,7 @@ def run_prove(args, rank, world, local):
         res["config"]["tables_off"] = {"value": N * world * n_off / dt_off, "unit": "constraints/s", "steps": args.tables_off_steps, "ms_per_step": dt_off / args.tables_off_steps * 1e3,
                                        "hbm_spent_on_tables_GB": (tab_info["GB"] if tab_info else 0.0) + (msm_tab_info["GB"] if msm_tab_info else 0.0),
                                        "note": "same pipeline, same statements family, fold tables and fixed-base MSM rows released"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU baseline is reported at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU baseline is reported at N = 1 only
         res["cpu_baseline"] = cpu_baseline_prove(args)
     for e in engs[1:] + engs[:1]:
         e.close()
@@ -1078,6 +1089,7 @@ def run_cfg5(args, rank, world, local):
     a5.batch, a5.steps, a5.warmup = 8, max(1, min(args.steps, args.cfg5_steps)), 0       # 8 statements = one lockstep group of the TranscriptRng stage
     a5.inflight, a5.tables_off_steps, a5.msm_tables = 1, 0, 0
     a5.window = 8
+    a5.dump_outputs = None
     t0 = time.perf_counter()
     r = run_prove(a5, rank, world, local)
     out = {"metric": "r1cs_constraints_proved_per_sec", "value": r["value"], "unit": r["unit"], "n_gpus": world, "scaling": "strong", "steps": a5.steps,
@@ -1107,18 +1119,20 @@ def auto_window(logn, world):
 
 def run_headline(args, rank, world, local):
     """both halves of BASELINE.json's metric on one box: prove (top level), then batch verify ("verify"); with N > 1 ranks also the
-    north_star's partition of one large proof ("cfg5")"""
+    north_star's partition of one large proof ("cfg5").  Without --full only the prove half runs: `value` is its figure."""
     import copy
 
     res = run_prove(args, rank, world, local)
-    ver = run_verify(args, rank, world, local)
     res["metric"] = "r1cs_constraints_proved_per_sec (+ r1cs_batch_verifies_per_sec under \"verify\")"
-    res["verify"] = ver
     res["hbm_spent_on_tables_GB"] = ((res["config"].get("first_round_fold_tables") or {}).get("GB", 0.0)) + ((res["config"].get("fixed_base_msm_tables") or {}).get("GB", 0.0))
+    if not args.full:
+        return res
+    res["verify"] = run_verify(args, rank, world, local)
 
     def leg(name, fn, **over):
         """one more configuration of BASELINE.json in the same line; a failing leg is recorded, the line still comes"""
         a = copy.copy(args)
+        a.dump_outputs = None          # (the outputs are the headline's timed proofs)
         for k_, v_ in over.items():
             setattr(a, k_, v_)
         t_leg = time.perf_counter()
@@ -1213,10 +1227,17 @@ def main():
                     help="multi-GPU partition: msm workload: terms | Pippenger windows; prove workload: replicas (default) | windows = every rank proves the same statements with window-sharded MSMs")
     ap.add_argument("--curve", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="headline workload at --gpus 1: only prove (cfg3) + verify (cfg4), without the cfg1 / cfg2 / zorro / 2^22 legs")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the prove workload's post-run checks (timed proofs verified, tables "
+                    "checked), roofline, tables-off run and CPU baseline; the headline's verify half and its other configurations (cfg1 / cfg2 / zorro / 2^22, "
+                    "cfg5 and the strong cfg4 with --gpus N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="prove / headline workload: after the timed steps, write the proofs of the last "
+                    "timed step to DIR/proofs.npy (one row per proof, its bytes as float32)")
+    ap.add_argument("--headline-only", action="store_true", help="headline workload at --gpus 1 with --full: only prove (cfg3) + verify (cfg4), without the cfg1 / cfg2 / zorro / 2^22 legs")
     ap.add_argument("--verify-strong", action="store_true", help="verify workload with --gpus N: ONE batch of --proofs sharded across the ranks (BASELINE cfg4 as stated) instead of --proofs per GPU")
     ap.add_argument("--strict-exit", action="store_true", help="exit with status 3 (after printing the line) when a leg of the run failed, e.g. the multi-GPU cfg5 leg")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("headline", "prove"):
+        ap.error("--dump-outputs: the headline and prove workloads only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))        # this process has not touched the GPU
     rank, world, local = dist_setup(args.gpus)

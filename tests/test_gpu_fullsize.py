@@ -406,3 +406,33 @@ def test_auto_tables_2pow14_against_oracle_bytes(oracle, curve):
             assert e.verify_scenario(sc, prm, got.proof, got.commitments, got.publics) == 0
     finally:
         e.close()
+
+
+def test_bench_dump_outputs_are_the_last_timed_steps_proofs(oracle, tmp_path):
+    """bench.py --dump-outputs DIR writes the proofs of the last timed step, one row of float32 bytes per proof: exactly the oracle's
+    proofs of the same seeded statements, so two runs (or two builds) with the same arguments write the same arrays"""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    logn, batch, steps = 10, 2, 2
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "prove", "--logn", str(logn), "--batch", str(batch),
+                        "--steps", str(steps), "--warmup", "0", "--inflight", "2", "--fold-tables", "0", "--msm-tables", "0", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["steps"] == steps and res["ms_per_step"] > 0
+    got = np.load(str(out / "proofs.npy"))
+    assert got.dtype == np.float32 and got.shape[0] == batch
+    N = 1 << logn
+    for j in range(batch):
+        ref = oracle.r1cs_prove(0, oracle.SC_SQUARE_CHAIN, [N, 0], bench.statement_seed(0, (steps - 1) * batch + j), N, m_cap=8)
+        assert ref.rc == 0
+        assert got[j].astype(np.uint8).tobytes() == ref.proof, j

@@ -371,7 +371,20 @@ def test_msm_gens_fixed_base_rows_match_ordinary_schedule(eng, oracle):
 def test_native_rccl_collectives_world_of_one():
     """bp_rccl_unique_id / bp_ctx_rccl_init / the library's own ncclAllGather (include/arkbp.h "Native collectives") on the one GPU of
     the test box: the communicator comes up (RCCL bound at run time), an all-gather returns the rank's block, the stats count it,
-    and a ctx with a world-1 communicator still computes the same MSM (nothing to exchange)."""
+    and a ctx with a world-1 communicator still computes the same MSM (nothing to exchange).  Own process: the library binds the RCCL
+    the process has already mapped, and a torch imported earlier in the test process (tests/test_distributed_cpu.py) maps its own
+    copy, built against torch's HIP runtime rather than the one the library was loaded with."""
+    import os
+    import subprocess
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_gpu_primitives as t; t._rccl_world_of_one(); print('rccl ok')" % (os.path.dirname(here), here)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "rccl ok" in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
+def _rccl_world_of_one():
     import ark_bulletproofs_amd as A
     from ark_bulletproofs_amd import engine as E
     from oracle import pyoracle as O

@@ -32,7 +32,7 @@ stats)
   stats prove_single -- python3 $R/tools/one_proof.py 20 2
   stats verify -- python3 $R/bench.py --workload verify --steps 5 --warmup 1 --verify-inflight 1 --no-cpu-baseline
   stats msm_2p16 -- python3 $R/bench.py --workload msm --terms 65536 --steps 20 --warmup 3 --no-cpu-baseline
-  stats bench_default -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --headline-only ;;
+  stats bench_default -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --headline-only --full ;;
 pmc)
   pmc prove2p20 -- python3 $R/tools/one_proof.py 20 1
   pmc verify4096 -- python3 $R/bench.py --workload verify --steps 1 --warmup 0 --verify-inflight 1 --no-cpu-baseline
