@@ -255,8 +255,11 @@ struct bp_ctx {
     DevBuf vfe_in, vfe_msg, vfe_chal, vfe_ws, vfe_small;
     void* h_vfe = nullptr;                    // pinned staging: [proof bytes | commitments | transcript states | small results]
     size_t h_vfe_cap = 0;
+    DevBuf vfe2_sched, vfe2_voff, vfe2_vq, vfe2_vcid, vfe2_gch, vfe2_coef;   // two-phase batches: per-batch schedule, terms on commitments, gadget challenges, coefficient tables
+    void* h_vfe2 = nullptr;                   // pinned: [gadget challenges | per-proof coefficient tables]
+    size_t h_vfe2_cap = 0;
     std::map<std::string, std::shared_ptr<void>> vfe_classes;   // (shared recording, m, k, transcript position) -> VfeClassDev<C>
-    bool tune_vfy_device = true;              // BP_TUNE_VFY_DEVICE
+    int tune_vfy_device = 1;                  // BP_TUNE_VFY_DEVICE: 0 host replay, 1 single-phase like-instances on the device, 2 two-phase ones too
     uint64_t fb_runs = 0, fb_runs_sharded = 0; // fixed-base MSMs completed on this ctx / of those, on a rank's share of the terms of a sharded proof
     uint64_t vfe_batches = 0, vfe_fallbacks = 0;                 // batches the device front end completed / handed to the host replay
     void* h_vstage[2] = {nullptr, nullptr};   // pinned staging halves of the batch-verify pipeline
@@ -2462,18 +2465,23 @@ static int cs_batch_verify(bp_ctx* c, size_t count, bp_cs* const* vs, const uint
     VfyProvider<C> prov;
     prov.m_of = [&](size_t k) { return vs[k]->cs<C>()->V.size(); };
     prov.get = [&](size_t k, VfyInstance<C>& out) -> int { out.cs = vs[k]->cs<C>(); return BP_OK; };
-    // like-instances of one single-phase recording (bp_verifier_new_like): the device front end continues their transcripts from
-    // where Verifier::commit left them
+    // like-instances of one recording (bp_verifier_new_like): the device front end continues their transcripts from where
+    // Verifier::commit left them.  Randomized constraints (BP_TUNE_VFY_DEVICE = 2): every instance's callbacks run on its own handle
+    // (a C callback records through the handle it receives), with the challenges its transcript produced on the device
+    const bool two_ok = c->tune_vfy_device >= 2;
     prov.dev_batch = [&](VfyDevBatch<C>& db) -> bool {
         const host::ConstraintSystem<C>* c0 = vs[0]->cs<C>();
-        if (!c0->base || !c0->tr) return false;
+        if (!c0->base || !c0->tr || (!c0->deferred.empty() && !two_ok)) return false;
         for (size_t k = 0; k < count; k++) {
             const host::ConstraintSystem<C>* ck = vs[k]->cs<C>();
-            if (ck->base != c0->base || ck->cs_off.size() != 1 || !ck->deferred.empty() || ck->phase2 || ck->num_vars != c0->num_vars || ck->V.size() != c0->V.size() || !ck->tr) return false;
+            if (ck->base != c0->base || ck->cs_off.size() != 1 || ck->deferred.size() != c0->deferred.size() || ck->phase2 || ck->num_vars != c0->num_vars || ck->V.size() != c0->V.size() ||
+                !ck->tr)
+                return false;
         }
         db.src = c0; db.m = c0->V.size(); db.absorb_commitments = false; db.shared_state = false;
         db.state_of = [&](size_t k) { return (const host::Strobe*)&vs[k]->cs<C>()->tr->s; };
         db.commit_xy = [&](size_t k) { return (const uint64_t*)vs[k]->cs<C>()->V.data(); };
+        if (!c0->deferred.empty()) db.cs_of = [&](size_t k) { return vs[k]->cs<C>(); };
         return true;
     };
     for (size_t k = 0; k < count; k++) { vs[k]->consumed = true; vs[k]->running = true; }
@@ -2777,6 +2785,7 @@ int bp_ctx_create(int curve, int device, bp_ctx** out) {
     HIPCHK(hipSetDevice(device));
     bp_ctx* c = new bp_ctx();
     c->curve = curve; c->device = device;
+    if (const char* v = getenv("ARKBP_VFY_DEVICE")) { if (*v >= '0' && *v <= '2' && !v[1]) c->tune_vfy_device = *v - '0'; }   // the default of BP_TUNE_VFY_DEVICE
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; g_err = hipGetErrorString(e); return BP_E_HIP; }
     *out = c;
@@ -2799,9 +2808,10 @@ void bp_ctx_destroy(bp_ctx* c) {
     c->templates.clear();
     c->vfe_classes.clear();
     for (auto b : bufs) b->release();
-    DevBuf* vbufs[] = {&c->vfe_in, &c->vfe_msg, &c->vfe_chal, &c->vfe_ws, &c->vfe_small};
+    DevBuf* vbufs[] = {&c->vfe_in, &c->vfe_msg, &c->vfe_chal, &c->vfe_ws, &c->vfe_small, &c->vfe2_sched, &c->vfe2_voff, &c->vfe2_vq, &c->vfe2_vcid, &c->vfe2_gch, &c->vfe2_coef};
     for (auto b : vbufs) b->release();
     if (c->h_vfe) (void)hipHostFree(c->h_vfe);
+    if (c->h_vfe2) (void)hipHostFree(c->h_vfe2);
     c->dt_tab.release(); c->dt_part.release(); c->pc_dt.release(); c->dt_a2.release(); c->dt_b2.release(); c->dt_ticket.release();
     if (c->h_dt) (void)hipHostFree(c->h_dt);
     if (c->h_totals) (void)hipHostFree(c->h_totals);
@@ -2896,7 +2906,7 @@ int bp_ctx_set_tuning(bp_ctx* c, int knob, uint64_t value) {
         case BP_TUNE_FOLD_QUAD_MAX: c->tune_fold_quad_max = (size_t)value; return BP_OK;
         case BP_TUNE_WAIT_SLEEP: if (value > 1000) return BP_E_ARG; c->tune_wait_sleep = value == 1 ? 30u : (unsigned)value; return BP_OK;
         case BP_TUNE_MSM_CHUNK_CAP: if (value && (value < 8 || value > 64)) return BP_E_ARG; c->tune_msm_chunk_cap = (size_t)value; return BP_OK;
-        case BP_TUNE_VFY_DEVICE: c->tune_vfy_device = value != 0; return BP_OK;
+        case BP_TUNE_VFY_DEVICE: c->tune_vfy_device = value >= 2 ? 2 : (int)value; return BP_OK;
         case BP_TUNE_DIRECT_MAX: if (value > ((uint64_t)1 << 16)) return BP_E_ARG; c->tune_direct_max = (size_t)value; return BP_OK;
     }
     return BP_E_ARG;
@@ -3517,6 +3527,19 @@ int bp_debug_vfe_schedule_replay(const uint8_t state203[203], int absorb_commitm
     if (!state203 || !items || !seeds_out || k >= 32 || state203[200] >= host::Strobe::RATE || m > 65535) return BP_E_ARG;
     vfe::Schedule sc;
     if (!vfe::build_verifier_schedule(sc, state203[200], state203[201], absorb_commitments != 0, m, k, n)) { g_err = "vfe schedule: unsupported shape"; return BP_E_ARG; }
+    uint64_t st[25];
+    memcpy(st, state203, 200);
+    vfe::run_schedule_cpu(sc, st, items, seeds_out, [](uint64_t* s) { host::keccakf((host::u64*)s); });
+    if (nblocks_out) *nblocks_out = (uint32_t)sc.blocks.size();
+    return BP_OK;
+}
+int bp_debug_vfe_schedule_replay_2phase(const uint8_t state203[203], int absorb_commitments, uint64_t m, uint32_t k, uint64_t n, const char* const* labels, size_t nlabels,
+                                        const uint8_t* items, uint8_t* seeds_out, uint32_t* nblocks_out) {
+    if (!state203 || !items || !seeds_out || (nlabels && !labels) || k >= 32 || state203[200] >= host::Strobe::RATE || m > 65535 || nlabels > 4096) return BP_E_ARG;
+    std::vector<std::string> gl;
+    for (size_t i = 0; i < nlabels; i++) { if (!labels[i]) return BP_E_ARG; gl.emplace_back(labels[i]); }
+    vfe::Schedule sc;
+    if (!vfe::build_verifier_schedule_2phase(sc, state203[200], state203[201], absorb_commitments != 0, m, k, n, gl)) { g_err = "vfe schedule: unsupported shape"; return BP_E_ARG; }
     uint64_t st[25];
     memcpy(st, state203, 200);
     vfe::run_schedule_cpu(sc, st, items, seeds_out, [](uint64_t* s) { host::keccakf((host::u64*)s); });

@@ -17,6 +17,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <utility>
 #include <vector>
@@ -683,7 +684,24 @@ template <class C> struct ConstraintSystem {
         return BP_OK;
     }
     void specify_randomized_constraints(std::function<int(ConstraintSystem&)> cb) { deferred.push_back(std::move(cb)); }
-    F4 challenge_scalar(const char* label) { return TP<C>::challenge_scalar(*tr, label); }
+    // Preset challenges (batch_verify_device runs a like-instance's randomized phase with the challenges its transcript produced on
+    // the device): challenge_scalar hands out preset[i] for the i-th call and checks its label against preset_labels[i]; a label that
+    // differs or a call past the end sets preset_bad (the caller then declines the batch) and returns 0.  chal_log: a live run
+    // records the labels and values it drew.
+    const F4* preset = nullptr;
+    const std::vector<std::string>* preset_labels = nullptr;
+    size_t preset_at = 0;
+    bool preset_bad = false;
+    std::vector<std::pair<std::string, F4>>* chal_log = nullptr;
+    F4 challenge_scalar(const char* label) {
+        if (preset_labels) {
+            if (preset_at >= preset_labels->size() || (*preset_labels)[preset_at] != label) { preset_bad = true; return S::zero(); }
+            return preset[preset_at++];
+        }
+        const F4 c = TP<C>::challenge_scalar(*tr, label);
+        if (chal_log) chal_log->emplace_back(std::string(label), c);
+        return c;
+    }
     // create_randomized_constraints (prover.rs:418-441 / verifier.rs:353-376)
     int run_randomized() {
         has_pending = false;
@@ -693,6 +711,21 @@ template <class C> struct ConstraintSystem {
         std::vector<std::function<int(ConstraintSystem&)>> cbs; cbs.swap(deferred);
         for (auto& cb : cbs) { int rc = cb(*this); if (rc) return rc; }
         return BP_OK;
+    }
+    // what run_randomized changes, so that a run with preset challenges can be undone (the host replay then runs the callbacks again)
+    struct RandSnap {
+        size_t nterms = 0, noff = 0, num_vars = 0, n1 = 0, pending = 0;
+        bool phase2 = false, has_pending = false;
+        std::vector<std::function<int(ConstraintSystem&)>> deferred;
+    };
+    void snapshot(RandSnap& s) const {
+        s.nterms = cs_terms.size(); s.noff = cs_off.size(); s.num_vars = num_vars; s.n1 = n1; s.pending = pending;
+        s.phase2 = phase2; s.has_pending = has_pending; s.deferred = deferred;
+    }
+    void restore(RandSnap& s) {
+        cs_terms.resize(s.nterms); cs_off.resize(s.noff); num_vars = s.num_vars; n1 = s.n1; pending = s.pending;
+        phase2 = s.phase2; has_pending = s.has_pending; deferred = s.deferred;
+        preset = nullptr; preset_labels = nullptr; preset_at = 0; preset_bad = false; chal_log = nullptr;
     }
     size_t base_nq() const { return base ? base->nq() : 0; }
     size_t num_constraints() const { return base_nq() + cs_off.size() - 1; }

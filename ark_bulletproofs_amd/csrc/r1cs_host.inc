@@ -1276,12 +1276,16 @@ template <class C> struct VfyInstance {
 // front end needs instead of per-instance recorders.  The transcripts stand either before the commitments (one shared state; the
 // device appends the m "V" messages of Verifier::commit, verifier.rs:279-287) or right after them (recorded handles).
 template <class C> struct VfyDevBatch {
-    const host::ConstraintSystem<C>* src = nullptr;          // frozen phase-1 recording, nothing recorded on top, no randomized phase
+    const host::ConstraintSystem<C>* src = nullptr;          // frozen phase-1 recording, nothing recorded on top, randomized phase not run yet
     size_t m = 0;                                            // commitments per instance
     bool absorb_commitments = false;
     bool shared_state = false;                               // state_of(k) is one object for every k
     std::function<const host::Strobe*(size_t)> state_of;     // the transcript of instance k
     std::function<const uint64_t*(size_t)> commit_xy;        // its m commitments, ark layout (x || y: 8 words per point)
+    // two-phase (src->deferred non-empty): the recorder on which instance k's randomized phase runs — needed when its callbacks
+    // record through a handle (bp_cs); absent: a like-instance of src made for the purpose (the closures record into the recorder
+    // they receive)
+    std::function<host::ConstraintSystem<C>*(size_t)> cs_of;
 };
 template <class C> struct VfyProvider {
     std::function<size_t(size_t)> m_of;                          // number of commitments of instance k (cheap; sizes the tails)
@@ -1308,30 +1312,60 @@ template <class C> struct VfeClassDev {
     std::weak_ptr<const host::FrozenRecording> base;
     const host::FrozenRecording* base_ptr = nullptr;
     DevBuf sched, voff, vq, vc, coefs, iota;
-    bool own_coefs = false;
+    bool coefs_up = false;       // coefs holds this class's coefficient table (uploaded by the first batch that needs it)
     std::string tkey;            // structure digest of the template this class evaluates with
     size_t N = 0;
     ~VfeClassDev() { sched.release(); voff.release(); vq.release(); vc.release(); coefs.release(); iota.release(); }
 };
+// Two-phase batches (BP_TUNE_VFY_DEVICE = 2): what the reference instance's live randomized phase recorded.  Every other instance's
+// callbacks must reproduce it with their own challenges: same labels, multipliers, constraint offsets and term variables, a +-1 where
+// it has +-1, one value per coefficient id.  The coefficient ids are the canonical numbering of the whole recording (CanonState):
+// [0, nbase) the shared phase-1 values, then the phase-2 ones.
+static constexpr size_t VFY2_TABLE_BUDGET = (size_t)256 << 20;   // bytes of per-proof gadget challenges + coefficient tables per batch
+template <class C> struct Vfe2Ref {
+    std::vector<std::string> labels;     // gadget challenges in drawing order
+    std::vector<F4> chal0;               // instance 0's, from its live transcript
+    size_t n = 0, n1 = 0, nbase = 0, ncoef = 0;
+    std::vector<size_t> off;             // the phase-2 part: constraint offsets (cs_off)
+    std::vector<host::Var> vars;         // its terms' variables
+    std::vector<u32> cid;                // its terms' coefficient ids
+    std::vector<F4> base_coefs;          // ids [0, nbase)
+};
+// An event on the ctx's stream, polled with sleeps (HIP's own synchronisation busy-waits on this stack; see event_wait)
+static hipError_t vfe_poll(bp_ctx* ctx, hipEvent_t ev) {
+    wait_thread_setup();
+    const long ns = 1000L * (ctx->tune_wait_sleep ? (long)ctx->tune_wait_sleep : 100L);
+    for (;;) {
+        const hipError_t e = hipEventQuery(ev);
+        if (e != hipErrorNotReady) return e;
+        struct timespec ts = {0, ns};
+        nanosleep(&ts, nullptr);
+    }
+}
 template <class C>
 static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& db, const uint8_t* proofs, const size_t* poff, const F4* alphas, double* timing,
                                uint64_t* point_out, bool& handled) {
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
+    typedef host::ConstraintSystem<C> CS;
     handled = false;
     static const bool off = getenv("ARKBP_VFY_HOST") != nullptr;   // A/B switch: the host replay for every batch
     if (off || ctx->host_only || !ctx->tune_vfy_device || !db.src || !count || ctx->shard_world > 1) return BP_OK;
-    const host::ConstraintSystem<C>& src = *db.src;
-    if (!src.base || src.cs_off.size() != 1 || !src.deferred.empty() || src.phase2 || src.num_vars != src.base->num_vars) return BP_OK;
+    const CS& src = *db.src;
+    const bool two = !src.deferred.empty();   // randomized constraints: the device derives every challenge, the host runs the callbacks
+    if (two && ctx->tune_vfy_device < 2) return BP_OK;
+    if (!src.base || src.cs_off.size() != 1 || src.phase2 || src.num_vars != src.base->num_vars) return BP_OK;
     const size_t plen = poff[1] - poff[0];
     if (plen < 539 || (plen - 539) % 66) return BP_OK;
-    const size_t k = (plen - 539) / 66, m = db.m, n = src.num_vars, N = host::next_pow2(n);
-    if (k >= 32 || N != ((size_t)1 << k) || ctx->gens_cap < N) return BP_OK;          // (VerificationError / InvalidGeneratorsLength: the host path's to report)
+    const size_t k = (plen - 539) / 66, m = db.m;
+    if (k >= 32) return BP_OK;
     for (size_t i = 0; i < count; i++) if (poff[i + 1] - poff[i] != plen) return BP_OK;
     for (const auto& vt : src.base->vterms) if (vt.j >= m) return BP_OK;                // (a weaker statement than the recorded one: BP_E_ARG there)
     const size_t tail = 6 + m + 5 + 2 * k, nV = db.absorb_commitments ? m : 0;
     const size_t nitems = nV + 11 + 2 * k + 3;
     if (count > 65535 || m > 65535 || count * tail >= ((size_t)1 << 31) || nitems * vfe::ITEM_WORDS * count >= ((size_t)1 << 32)) return BP_OK;
+    const size_t nblocks = (count + VFY_BLOCK - 1) / VFY_BLOCK;
+    if (nblocks > 96) return BP_OK;                                                      // (one result slot per block)
     const host::Strobe* s0 = db.state_of(0);
     if (!s0) return BP_OK;
     if (!db.shared_state) for (size_t i = 1; i < count; i++) { const host::Strobe* si = db.state_of(i); if (!si || si->pos != s0->pos || si->pos_begin != s0->pos_begin) return BP_OK; }
@@ -1342,66 +1376,168 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
         if (!ctx->pool || hi - lo == 1) { for (size_t i = lo; i < hi; i++) fn(i); return; }
         ctx->pool->run(lo, hi, fn);
     };
+    const F4 one = S::one(), mone = S::neg(S::one());
     // the circuit template (constraint matrices on the GPU, keyed by structure) and this class's device-side constants
-    host::ConstraintSystem<C> like;
+    CS like;
     like.init_like(src);
-    like.n1 = like.num_vars;   // single phase: every multiplier is a phase-1 multiplier (run_randomized with nothing deferred)
     host::CanonState scratch;
-    const host::CanonState& cst = like.canonical(scratch, nullptr);
-    const host::Digest dg = cst.digest(like.n1, n, like.num_constraints());
-    const std::string tkey((const char*)&dg, sizeof dg);
-    auto tit = ctx->templates.find(tkey);
-    if (tit == ctx->templates.end()) {
-        if (ctx->templates.size() >= VFY_TEMPLATE_CACHE) { HIPCHK(ctx_stream_wait(ctx)); ctx->templates.clear(); ctx->vfe_classes.clear(); }
-        VTemplate<C>* t = new VTemplate<C>();
-        std::shared_ptr<void> holder(t, [](void* q) { delete (VTemplate<C>*)q; });
-        BPCHK(build_template<C>(ctx, like, *t));
-        tit = ctx->templates.emplace(tkey, holder).first;
-    }
-    const std::shared_ptr<void> tkeep = tit->second;
-    const VTemplate<C>& T = *(const VTemplate<C>*)tkeep.get();
-    if (T.n != n || T.n1 != n || T.q != like.num_constraints() || T.ncoef != cst.coefs.size()) { g_err = "batch_verify: structure digest collision"; return BP_E_ARG; }
-    char ckeyb[96];
-    snprintf(ckeyb, sizeof ckeyb, "%p/%zu/%zu/%u/%u/%d", (const void*)src.base.get(), m, k, (unsigned)s0->pos, (unsigned)s0->pos_begin, (int)db.absorb_commitments);
-    const std::string ckey(ckeyb);
-    std::shared_ptr<void> ckeep;
-    {
-        auto cit = ctx->vfe_classes.find(ckey);
-        if (cit != ctx->vfe_classes.end()) {
-            VfeClassDev<C>* c = (VfeClassDev<C>*)cit->second.get();
-            if (c->base.lock().get() == src.base.get() && c->tkey == tkey) ckeep = cit->second;   // (same recording still alive, same template)
-            else ctx->vfe_classes.erase(cit);
+    size_t n = src.num_vars, N = host::next_pow2(n);
+    host::Digest dg;
+    Vfe2Ref<C> ref;
+    std::vector<u32> v2off, v2q, v2cid;   // two-phase: the terms on commitments by commitment (CSR), coefficient ids
+    std::shared_ptr<void> tkeep;
+    auto template_for = [&](const CS& rec, const host::CanonState& cst) -> int {   // look up / build (upload + sync) the template of `rec`
+        dg = cst.digest(rec.n1, n, rec.num_constraints());
+        const std::string tkey((const char*)&dg, sizeof dg);
+        auto tit = ctx->templates.find(tkey);
+        if (tit == ctx->templates.end()) {
+            if (ctx->templates.size() >= VFY_TEMPLATE_CACHE) { HIPCHK(ctx_stream_wait(ctx)); ctx->templates.clear(); ctx->vfe_classes.clear(); }
+            VTemplate<C>* t = new VTemplate<C>();
+            std::shared_ptr<void> holder(t, [](void* q) { delete (VTemplate<C>*)q; });
+            BPCHK(build_template<C>(ctx, rec, *t));
+            tit = ctx->templates.emplace(tkey, holder).first;
         }
+        tkeep = tit->second;
+        const VTemplate<C>& T = *(const VTemplate<C>*)tkeep.get();
+        if (T.n != n || T.n1 != rec.n1 || T.q != rec.num_constraints() || T.ncoef != cst.coefs.size()) { g_err = "batch_verify: structure digest collision"; return BP_E_ARG; }
+        return BP_OK;
+    };
+    if (!two) {
+        like.n1 = like.num_vars;   // single phase: every multiplier is a phase-1 multiplier (run_randomized with nothing deferred)
+        if (N != ((size_t)1 << k) || ctx->gens_cap < N) return BP_OK;          // (VerificationError / InvalidGeneratorsLength: the host path's to report)
+        BPCHK(template_for(like, like.canonical(scratch, nullptr)));
+    } else {
+        // the reference instance: instance 0's randomized phase for real, on a copy of its transcript through S1 (verifier.rs:403-415)
+        host::Transcript t0;
+        t0.s = *s0;
+        if (db.absorb_commitments) for (size_t j = 0; j < m; j++) { A4 v; memcpy(&v, db.commit_xy(0) + 8 * j, 64); host::TP<C>::append_point(t0, "V", v); }
+        t0.append_u64("m", m);
+        A4 p3[3];
+        static const char* const lab3[3] = {"A_I1", "A_O1", "S1"};
+        for (int j = 0; j < 3; j++) {
+            if (!host::Grp<C>::deser_compressed(p3[j], proofs + poff[0] + 33 * j) || !host::TP<C>::validate_and_append_point(t0, lab3[j], p3[j])) {
+                ctx->vfe_fallbacks++;   // something the reference rejects: the host replay reports it
+                return BP_OK;
+            }
+        }
+        CS* r0 = db.cs_of ? db.cs_of(0) : &like;
+        typename CS::RandSnap snap0;
+        r0->snapshot(snap0);
+        host::Transcript* tr_save = r0->tr;
+        std::vector<std::pair<std::string, F4>> log;
+        r0->tr = &t0; r0->chal_log = &log;
+        const int rrc = r0->run_randomized();
+        r0->chal_log = nullptr; r0->tr = tr_save;
+        bool ok = !rrc && r0->cs_off.size() >= 1 && r0->n1 == src.base->num_vars && log.size() <= 4096;
+        if (ok) {
+            n = r0->num_vars; N = host::next_pow2(n);
+            ok = N == ((size_t)1 << k) && ctx->gens_cap >= N;
+        }
+        int trc = BP_OK;
+        if (ok) {
+            for (auto& e : log) { ref.labels.push_back(e.first); ref.chal0.push_back(e.second); }
+            ref.n = n; ref.n1 = r0->n1;
+            ref.off = r0->cs_off;
+            // coefficient ids: the canonical walk over both parts (the numbering canonical() and build_template produce)
+            host::CanonState cw;
+            std::vector<host::VTerm> vts;   // (j, q, c.v[0] = id)
+            auto vsink = [&](size_t q, const host::Term& t, u32 cid) { if (t.v.k == host::VK_COMMITTED) { host::VTerm v{t.v.i, (u32)q, F4{}}; v.c.v[0] = cid; vts.push_back(v); } };
+            cw.walk(src.base->terms.data(), src.base->off.data(), src.base->nq(), 0, one, mone, vsink);
+            ref.nbase = cw.coefs.size(); ref.base_coefs = cw.coefs;
+            cw.walk(r0->cs_terms.data(), r0->cs_off.data(), r0->cs_off.size() - 1, r0->base_nq(), one, mone, [&](size_t q, const host::Term& t, u32 cid) {
+                ref.vars.push_back(t.v); ref.cid.push_back(cid); vsink(q, t, cid);
+            });
+            ref.ncoef = cw.coefs.size();
+            for (u32 c : ref.cid) if (!(c & (host::CID_ONE | host::CID_MONE)) && c >= (1u << 30)) ok = false;
+            for (const auto& v : vts) if (v.j >= m) ok = false;
+            if (ok) {
+                v2off.assign(m + 1, 0); v2q.resize(vts.size()); v2cid.resize(vts.size());
+                for (const auto& v : vts) v2off[v.j + 1]++;
+                for (size_t j = 0; j < m; j++) v2off[j + 1] += v2off[j];
+                std::vector<u32> cur(v2off.begin(), v2off.end() - 1);
+                for (const auto& v : vts) { const u32 at = cur[v.j]++; v2q[at] = v.q; v2cid[at] = (u32)v.c.v[0]; }
+                trc = template_for(*r0, r0->canonical(scratch, nullptr));
+            }
+        }
+        r0->restore(snap0);
+        if (trc) return trc;
+        if (!ok) return BP_OK;
+        if (count * (ref.labels.size() + ref.ncoef) * 32 > VFY2_TABLE_BUDGET) return BP_OK;   // (stated in include/arkbp.h)
     }
-    if (!ckeep) {
-        if (ctx->vfe_classes.size() >= 16) { HIPCHK(ctx_stream_wait(ctx)); ctx->vfe_classes.clear(); }
-        VfeClassDev<C>* c = new VfeClassDev<C>();
-        ckeep.reset(c, [](void* q) { delete (VfeClassDev<C>*)q; });
-        c->base = src.base; c->base_ptr = src.base.get(); c->tkey = tkey; c->N = N;
+    const VTemplate<C>& T = *(const VTemplate<C>*)tkeep.get();
+    const std::string tkey((const char*)&dg, sizeof dg);
+    const size_t G = ref.labels.size(), ncoef = two ? ref.ncoef : 0;
+    std::shared_ptr<void> ckeep;
+    bool own_coefs = false;
+    const u32 *d_sched = nullptr, *d_voff = nullptr, *d_vq = nullptr, *d_vc = nullptr, *d_iota = nullptr;
+    std::vector<uint32_t> enc2;
+    if (!two) {
+        char ckeyb[96];
+        snprintf(ckeyb, sizeof ckeyb, "%p/%zu/%zu/%u/%u/%d", (const void*)src.base.get(), m, k, (unsigned)s0->pos, (unsigned)s0->pos_begin, (int)db.absorb_commitments);
+        const std::string ckey(ckeyb);
+        {
+            auto cit = ctx->vfe_classes.find(ckey);
+            if (cit != ctx->vfe_classes.end()) {
+                VfeClassDev<C>* c = (VfeClassDev<C>*)cit->second.get();
+                if (c->base.lock().get() == src.base.get() && c->tkey == tkey) ckeep = cit->second;   // (same recording still alive, same template)
+                else ctx->vfe_classes.erase(cit);
+            }
+        }
+        if (!ckeep) {
+            if (ctx->vfe_classes.size() >= 16) { HIPCHK(ctx_stream_wait(ctx)); ctx->vfe_classes.clear(); }
+            VfeClassDev<C>* c = new VfeClassDev<C>();
+            ckeep.reset(c, [](void* q) { delete (VfeClassDev<C>*)q; });
+            c->base = src.base; c->base_ptr = src.base.get(); c->tkey = tkey; c->N = N;
+            vfe::Schedule sched;
+            if (!vfe::build_verifier_schedule(sched, s0->pos, s0->pos_begin, db.absorb_commitments, m, (uint32_t)k, N)) return BP_OK;
+            const std::vector<uint32_t> enc = sched.encode();
+            // terms on committed variables by commitment (CSR over j; constraint order inside a commitment)
+            std::vector<u32> voff(m + 1, 0), vq(src.base->vterms.size());
+            std::vector<F4> vc(src.base->vterms.size());
+            for (const auto& vt : src.base->vterms) voff[vt.j + 1]++;
+            for (size_t j = 0; j < m; j++) voff[j + 1] += voff[j];
+            { std::vector<u32> cur(voff.begin(), voff.end() - 1); for (const auto& vt : src.base->vterms) { const u32 at = cur[vt.j]++; vq[at] = vt.q; vc[at] = vt.c; } }
+            std::vector<u32> iota(VFY_BLOCK);
+            for (size_t i = 0; i < VFY_BLOCK; i++) iota[i] = (u32)i;
+            BPCHK(c->sched.ensure(enc.size() * 4)); BPCHK(c->voff.ensure(voff.size() * 4)); BPCHK(c->vq.ensure(std::max<size_t>(vq.size(), 1) * 4));
+            BPCHK(c->vc.ensure(std::max<size_t>(vc.size(), 1) * 32)); BPCHK(c->iota.ensure(iota.size() * 4));
+            HIPCHK(hipMemcpyAsync(c->sched.p, enc.data(), enc.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(c->voff.p, voff.data(), voff.size() * 4, hipMemcpyHostToDevice, st));
+            if (!vq.empty()) HIPCHK(hipMemcpyAsync(c->vq.p, vq.data(), vq.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(c->iota.p, iota.data(), iota.size() * 4, hipMemcpyHostToDevice, st));
+            if (!vc.empty()) BPCHK(upload_scalars<C>(ctx, (u32*)c->vc.p, vc.data(), vc.size()));
+            HIPCHK(ctx_stream_wait(ctx));   // (the host arrays above are locals)
+            ctx->vfe_classes[ckey] = ckeep;
+        }
+        VfeClassDev<C>& cls = *(VfeClassDev<C>*)ckeep.get();
+        // the coefficient table is decided per batch: the template may have been evicted and rebuilt since, from an instance of the
+        // same structure with other public constants
+        const host::CanonState& cst = like.canonical(scratch, nullptr);
+        own_coefs = T.ncoef && memcmp(T.coefs_host.data(), cst.coefs.data(), T.ncoef * 32) != 0;
+        if (own_coefs && !cls.coefs_up) {
+            BPCHK(cls.coefs.ensure(T.ncoef * 32)); BPCHK(upload_scalars<C>(ctx, (u32*)cls.coefs.p, cst.coefs.data(), T.ncoef));
+            HIPCHK(ctx_stream_wait(ctx));
+            cls.coefs_up = true;
+        }
+        d_sched = (u32*)cls.sched.p; d_voff = (u32*)cls.voff.p; d_vq = (u32*)cls.vq.p; d_vc = (u32*)cls.vc.p; d_iota = (u32*)cls.iota.p;
+    } else {
         vfe::Schedule sched;
-        if (!vfe::build_verifier_schedule(sched, s0->pos, s0->pos_begin, db.absorb_commitments, m, (uint32_t)k, N)) return BP_OK;
-        const std::vector<uint32_t> enc = sched.encode();
-        // terms on committed variables by commitment (CSR over j; constraint order inside a commitment)
-        std::vector<u32> voff(m + 1, 0), vq(src.base->vterms.size());
-        std::vector<F4> vc(src.base->vterms.size());
-        for (const auto& vt : src.base->vterms) voff[vt.j + 1]++;
-        for (size_t j = 0; j < m; j++) voff[j + 1] += voff[j];
-        { std::vector<u32> cur(voff.begin(), voff.end() - 1); for (const auto& vt : src.base->vterms) { const u32 at = cur[vt.j]++; vq[at] = vt.q; vc[at] = vt.c; } }
+        if (!vfe::build_verifier_schedule_2phase(sched, s0->pos, s0->pos_begin, db.absorb_commitments, m, (uint32_t)k, N, ref.labels)) return BP_OK;
+        enc2 = sched.encode();
         std::vector<u32> iota(VFY_BLOCK);
         for (size_t i = 0; i < VFY_BLOCK; i++) iota[i] = (u32)i;
-        BPCHK(c->sched.ensure(enc.size() * 4)); BPCHK(c->voff.ensure(voff.size() * 4)); BPCHK(c->vq.ensure(std::max<size_t>(vq.size(), 1) * 4));
-        BPCHK(c->vc.ensure(std::max<size_t>(vc.size(), 1) * 32)); BPCHK(c->iota.ensure(iota.size() * 4));
-        HIPCHK(hipMemcpyAsync(c->sched.p, enc.data(), enc.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(c->voff.p, voff.data(), voff.size() * 4, hipMemcpyHostToDevice, st));
-        if (!vq.empty()) HIPCHK(hipMemcpyAsync(c->vq.p, vq.data(), vq.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(c->iota.p, iota.data(), iota.size() * 4, hipMemcpyHostToDevice, st));
-        if (!vc.empty()) BPCHK(upload_scalars<C>(ctx, (u32*)c->vc.p, vc.data(), vc.size()));
-        c->own_coefs = T.ncoef && memcmp(T.coefs_host.data(), cst.coefs.data(), T.ncoef * 32) != 0;   // same gadget, other public constants
-        if (c->own_coefs) { BPCHK(c->coefs.ensure(T.ncoef * 32)); BPCHK(upload_scalars<C>(ctx, (u32*)c->coefs.p, cst.coefs.data(), T.ncoef)); }
+        BPCHK(ctx->vfe2_sched.ensure(enc2.size() * 4 + VFY_BLOCK * 4)); BPCHK(ctx->vfe2_voff.ensure(v2off.size() * 4));
+        BPCHK(ctx->vfe2_vq.ensure(std::max<size_t>(v2q.size(), 1) * 4)); BPCHK(ctx->vfe2_vcid.ensure(std::max<size_t>(v2cid.size(), 1) * 4));
+        HIPCHK(hipMemcpyAsync(ctx->vfe2_sched.p, enc2.data(), enc2.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->vfe2_sched.as<u32>() + enc2.size(), iota.data(), VFY_BLOCK * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->vfe2_voff.p, v2off.data(), v2off.size() * 4, hipMemcpyHostToDevice, st));
+        if (!v2q.empty()) {
+            HIPCHK(hipMemcpyAsync(ctx->vfe2_vq.p, v2q.data(), v2q.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ctx->vfe2_vcid.p, v2cid.data(), v2cid.size() * 4, hipMemcpyHostToDevice, st));
+        }
         HIPCHK(ctx_stream_wait(ctx));   // (the host arrays above are locals)
-        ctx->vfe_classes[ckey] = ckeep;
+        d_sched = ctx->vfe2_sched.as<u32>(); d_iota = d_sched + enc2.size(); d_voff = ctx->vfe2_voff.as<u32>(); d_vq = ctx->vfe2_vq.as<u32>(); d_vc = ctx->vfe2_vcid.as<u32>();
     }
-    VfeClassDev<C>& cls = *(VfeClassDev<C>*)ckeep.get();
     // staging: [proof bytes | commitments | transcript states], 256-byte aligned parts
     auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t b_proofs = up256(count * plen), b_V = up256(count * m * 64), b_st = up256((db.shared_state ? 1 : count) * 200), b_al = up256(count * 32);
@@ -1412,6 +1548,16 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
         HIPCHK(hipHostMalloc(&ctx->h_vfe, b_in + b_in / 8 + 4096));
         ctx->h_vfe_cap = b_in + b_in / 8 + 4096;
     }
+    // two-phase: [gadget challenges count x G | coefficient tables count x ncoef] (ark words, host form)
+    const size_t b_gch = count * G * 32, b_tab = count * ncoef * 32;
+    if (two && ctx->h_vfe2_cap < b_gch + b_tab + 64) {
+        if (ctx->h_vfe2) { HIPCHK(ctx_stream_wait(ctx)); HIPCHK(hipHostFree(ctx->h_vfe2)); }
+        ctx->h_vfe2 = nullptr; ctx->h_vfe2_cap = 0;
+        HIPCHK(hipHostMalloc(&ctx->h_vfe2, b_gch + b_tab + (b_gch + b_tab) / 8 + 64));
+        ctx->h_vfe2_cap = b_gch + b_tab + (b_gch + b_tab) / 8 + 64;
+    }
+    F4* h_gch = two ? (F4*)ctx->h_vfe2 : nullptr;
+    F4* h_tab = two ? (F4*)((char*)ctx->h_vfe2 + b_gch) : nullptr;
     uint8_t* hs = (uint8_t*)ctx->h_vfe;
     uint8_t* h_small = hs + ctx->h_vfe_cap - 4096;      // results: [deltas (<= 96 slots) | sums 2 | status]
     {
@@ -1428,13 +1574,12 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
         memcpy(hs + b_proofs + b_V + b_st, alphas, count * 32);
     }
     if (timing) timing[4] = now_s() - t_entry;
-    const size_t nblocks = (count + VFY_BLOCK - 1) / VFY_BLOCK;
-    if (nblocks > 96) return BP_OK;
     BPCHK(ctx->vfe_in.ensure(b_in));
     BPCHK(ctx->vfe_msg.ensure(nitems * vfe::ITEM_WORDS * count * 8));
-    BPCHK(ctx->vfe_chal.ensure(count * (6 + k) * 32));
+    BPCHK(ctx->vfe_chal.ensure(count * (6 + k + G) * 32));
     BPCHK(ctx->vfe_ws.ensure(count * 34 * 32));
     BPCHK(ctx->vfe_small.ensure(4096));
+    if (two) { BPCHK(ctx->vfe2_gch.ensure(std::max<size_t>(b_gch, 32))); BPCHK(ctx->vfe2_coef.ensure(std::max<size_t>(b_tab, 32))); }
     const size_t Ttot = count * tail;
     BPCHK(ctx->r_g.ensure((2 + 2 * N + Ttot) * 32));
     BPCHK(ctx->r_tail.ensure(std::max<size_t>(Ttot, 1) * 64));
@@ -1449,30 +1594,105 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     u32* d_status = ctx->vfe_small.as<u32>();            // [status | pad .. | sums at word 64]
     u32* d_sums = d_status + 64;
     const uint8_t* d_in = (const uint8_t*)ctx->vfe_in.p;
+    // from here on the stream reads pinned memory of this call: a decline waits for it first (the host replay reuses the buffers)
+    struct Drain { bp_ctx* c; bool armed; ~Drain() { if (armed) (void)hipStreamSynchronize(c->stream); } } drain{ctx, true};
     HIPCHK(hipMemsetAsync(sc, 0, (2 + 2 * N) * 32, st));
     HIPCHK(hipMemsetAsync(d_status, 0, 256, st));
     HIPCHK(hipMemcpyAsync(ctx->vfe_in.p, hs, b_in, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((count + 255) / 256)), dim3(256), 0, st, (const u32*)(d_in + b_proofs + b_V + b_st), d_alpha, (u32)count);
     vfe::Shape sh;
     sh.P = (uint32_t)count; sh.m = (uint32_t)m; sh.nV = (uint32_t)nV; sh.k = (uint32_t)k; sh.plen = (uint32_t)plen; sh.tail = (uint32_t)tail; sh.nitems = (uint32_t)nitems;
+    sh.G = (uint32_t)G;
     {
         ScopedK tk(ctx, BP_K_VFE_POINTS);
         if (vfe::launch_points(C::ID, st, sh, d_in, (const u32*)(d_in + b_proofs), (uint64_t*)ctx->vfe_msg.p, ctx->r_tail.as<u32>(), d_status)) { g_err = "k_vfe_points: launch failed"; return BP_E_HIP; }
     }
     {
         ScopedK tk(ctx, BP_K_VFE_SPONGE);
-        if (vfe::launch_sponge(C::ID, st, sh, (u32*)cls.sched.p, (const uint64_t*)(d_in + b_proofs + b_V), db.shared_state ? 0u : 25u, (const uint64_t*)ctx->vfe_msg.p,
-                               ctx->vfe_chal.as<u32>(), nullptr)) { g_err = "k_vfe_sponge: launch failed"; return BP_E_HIP; }
+        if (vfe::launch_sponge(C::ID, st, sh, d_sched, (const uint64_t*)(d_in + b_proofs + b_V), db.shared_state ? 0u : 25u, (const uint64_t*)ctx->vfe_msg.p,
+                               ctx->vfe_chal.as<u32>(), nullptr, two ? ctx->vfe2_gch.as<u32>() : nullptr)) { g_err = "k_vfe_sponge: launch failed"; return BP_E_HIP; }
     }
-    {
+    if (!ctx->sync_ev) HIPCHK(hipEventCreateWithFlags(&ctx->sync_ev, hipEventDisableTiming));
+    if (!two) {
         ScopedK tk(ctx, BP_K_VFE_PREPARE);
-        if (vfe::launch_prepare(C::ID, st, sh, d_in, ctx->vfe_chal.as<u32>(), d_alpha, (u32*)cls.voff.p, (u32*)cls.vq.p, (u32*)cls.vc.p, ctx->v_params.as<u32>(), d_tail_sc,
+        if (vfe::launch_prepare(C::ID, st, sh, d_in, ctx->vfe_chal.as<u32>(), d_alpha, d_voff, d_vq, d_vc, ctx->v_params.as<u32>(), d_tail_sc,
                                 ctx->vfe_ws.as<u32>(), d_sums)) { g_err = "k_vfe_consts: launch failed"; return BP_E_HIP; }
-    }
-    for (size_t blk = 0; blk < nblocks; blk++) {
-        const size_t lo = blk * VFY_BLOCK, nb = std::min(count, lo + VFY_BLOCK) - lo;
-        BPCHK(verify_launch_template_group<C>(ctx, T, ctx->v_params.as<u32>() + lo * VFY_PB_WORDS, (u32*)cls.iota.p, cls.own_coefs ? (u32*)cls.coefs.p : nullptr, nb, N, k,
-                                              acc_g, acc_h, ctx->r_small.as<u32>() + blk * 8, true));
+        for (size_t blk = 0; blk < nblocks; blk++) {
+            const size_t lo = blk * VFY_BLOCK, nb = std::min(count, lo + VFY_BLOCK) - lo;
+            VfeClassDev<C>& cls = *(VfeClassDev<C>*)ckeep.get();
+            BPCHK(verify_launch_template_group<C>(ctx, T, ctx->v_params.as<u32>() + lo * VFY_PB_WORDS, d_iota, own_coefs ? (u32*)cls.coefs.p : nullptr, nb, N, k,
+                                                  acc_g, acc_h, ctx->r_small.as<u32>() + blk * 8, true));
+        }
+    } else {
+        // the gadget challenges (and the kernels' reject bits) come back while k_vfe_consts runs; the host then runs every instance's
+        // callbacks with its challenges, block by block, each block's launches behind its tables
+        if (b_gch) HIPCHK(hipMemcpyAsync(h_gch, ctx->vfe2_gch.p, b_gch, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_small + 98 * 32, d_status, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(ctx->sync_ev, st));
+        {
+            ScopedK tk(ctx, BP_K_VFE_PREPARE);
+            if (vfe::launch_consts(C::ID, st, sh, d_in, ctx->vfe_chal.as<u32>(), d_alpha, ctx->v_params.as<u32>(), d_tail_sc, ctx->vfe_ws.as<u32>(), d_sums)) {
+                g_err = "k_vfe_consts: launch failed"; return BP_E_HIP;
+            }
+        }
+        HIPCHK(vfe_poll(ctx, ctx->sync_ev));
+        u32 status0; memcpy(&status0, h_small + 98 * 32, 4);
+        if (status0) { ctx->vfe_fallbacks++; return BP_OK; }
+        for (size_t g = 0; g < G; g++) if (h_gch[g] != ref.chal0[g]) return BP_OK;   // (the device's transcript is not instance 0's: never expected)
+        u32* d_coef = ctx->vfe2_coef.as<u32>();
+        for (size_t blk = 0; blk < nblocks; blk++) {
+            const size_t lo = blk * VFY_BLOCK, nb = std::min(count, lo + VFY_BLOCK) - lo;
+            std::atomic<bool> bad{false};
+            parallel_range(lo, lo + nb, [&](size_t i) {
+                if (bad.load(std::memory_order_relaxed)) return;
+                std::unique_ptr<CS> tmp;
+                CS* ci;
+                typename CS::RandSnap snap;
+                if (db.cs_of) { ci = db.cs_of(i); ci->snapshot(snap); }
+                else { tmp.reset(new CS()); tmp->init_like(src); ci = tmp.get(); }
+                host::Transcript sink;   // ("r1cs-2phase" is appended here: the device's sponge has absorbed it already)
+                memset(&sink.s, 0, sizeof sink.s);
+                host::Transcript* tr_save = ci->tr;
+                ci->tr = &sink;
+                ci->preset = h_gch + i * G; ci->preset_labels = &ref.labels; ci->preset_at = 0; ci->preset_bad = false;
+                const int rc = ci->run_randomized();
+                bool ok = !rc && !ci->preset_bad && ci->preset_at == G && ci->num_vars == ref.n && ci->n1 == ref.n1 && ci->cs_off == ref.off &&
+                          ci->cs_terms.size() == ref.vars.size();
+                F4* tab = h_tab + i * ncoef;
+                if (ok) {
+                    std::vector<char> set(ncoef - ref.nbase, 0);
+                    for (size_t j = 0; j < ref.nbase; j++) tab[j] = ref.base_coefs[j];
+                    for (size_t t = 0; ok && t < ref.vars.size(); t++) {
+                        const host::Term& tm = ci->cs_terms[t];
+                        const u32 cid = ref.cid[t];
+                        if (tm.v.k != ref.vars[t].k || tm.v.i != ref.vars[t].i) ok = false;
+                        else if (cid & host::CID_ONE) ok = tm.c == one;
+                        else if (cid & host::CID_MONE) ok = tm.c == mone;
+                        else if (cid < ref.nbase) ok = tm.c == tab[cid];
+                        else if (!set[cid - ref.nbase]) { tab[cid] = tm.c; set[cid - ref.nbase] = 1; }
+                        else ok = tm.c == tab[cid];
+                    }
+                    for (size_t j = 0; ok && j < set.size(); j++) ok = set[j] != 0;
+                }
+                ci->tr = tr_save;
+                if (db.cs_of) ci->restore(snap);
+                if (!ok) bad.store(true, std::memory_order_relaxed);
+            });
+            if (bad.load()) return BP_OK;   // a callback that records another structure (or draws other challenges): the host replay decides
+            u32* d_tab = d_coef + lo * ncoef * 8;
+            if (ncoef) {
+                HIPCHK(hipMemcpyAsync(d_tab, h_tab + lo * ncoef, nb * ncoef * 32, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((nb * ncoef + 255) / 256)), dim3(256), 0, st, d_tab, d_tab, (u32)(nb * ncoef));
+            }
+            {
+                ScopedK tk(ctx, BP_K_VFE_PREPARE);
+                if (vfe::launch_wv_tab(C::ID, st, sh, (uint32_t)lo, (uint32_t)nb, ctx->v_params.as<u32>(), d_voff, d_vq, d_vc, d_tab, (uint32_t)(ncoef * 8), d_tail_sc)) {
+                    g_err = "k_vfe_wv_tab: launch failed"; return BP_E_HIP;
+                }
+            }
+            BPCHK(verify_launch_template_group<C>(ctx, T, ctx->v_params.as<u32>() + lo * VFY_PB_WORDS, d_iota, ncoef ? d_tab : nullptr, nb, N, k,
+                                                  acc_g, acc_h, ctx->r_small.as<u32>() + blk * 8, false));
+        }
     }
     hipLaunchKernelGGL(k_scalars_to_canon<FrP>, dim3((u32)((2 * N + 255) / 256)), dim3(256), 0, st, sc + 2 * 8, (u32)(2 * N));
     HIPCHK(hipMemcpyAsync(h_small, ctx->r_small.p, nblocks * 32, hipMemcpyDeviceToHost, st));
@@ -1481,18 +1701,9 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     const double t_drain = now_s();
     // ONE wait per batch, ~10 ms long: poll and sleep (HIP's own synchronisation calls busy-wait on this stack: a core per batch in
     // flight for nothing; see event_wait)
-    {
-        if (!ctx->sync_ev) HIPCHK(hipEventCreateWithFlags(&ctx->sync_ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(ctx->sync_ev, st));
-        wait_thread_setup();
-        for (;;) {
-            const hipError_t e = hipEventQuery(ctx->sync_ev);
-            if (e == hipSuccess) break;
-            if (e != hipErrorNotReady) HIPCHK(e);
-            struct timespec ts = {0, 100000L};
-            nanosleep(&ts, nullptr);
-        }
-    }
+    HIPCHK(hipEventRecord(ctx->sync_ev, st));
+    HIPCHK(vfe_poll(ctx, ctx->sync_ev));
+    drain.armed = false;
     HIPCHK(hipGetLastError());
     u32 status; memcpy(&status, h_small + 98 * 32, 4);
     if (status) { ctx->vfe_fallbacks++; return BP_OK; }   // something the reference rejects: the host replay decides which error, in instance order
@@ -1788,6 +1999,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
             for (size_t p = 0; p < nb; p++) used.insert(std::string((const char*)&rep[p].vp.digest, sizeof rep[p].vp.digest));
             HIPCHK(ctx_stream_wait(ctx));   // earlier blocks' launches may still read the evicted templates' device arrays
             for (auto it = ctx->templates.begin(); it != ctx->templates.end();) { if (used.count(it->first)) ++it; else it = ctx->templates.erase(it); }
+            ctx->vfe_classes.clear();   // (a class names its template by digest: a rebuilt one may hold other constants)
         }
         for (size_t p = 0; p < nb; p++) {
             const VerifyPrep<C>& vp = rep[p].vp;
@@ -2083,7 +2295,7 @@ static int batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenario
     // transcripts from the state before the commitments — label, r1cs domain separator, the scenario's own prefix
     host::Transcript proto;
     prov.dev_batch = [&](VfyDevBatch<C>& db) -> bool {
-        if (!src[0] || src[0]->m != ms[0] || !src[0]->cs.deferred.empty()) return false;
+        if (!src[0] || src[0]->m != ms[0] || (!src[0]->cs.deferred.empty() && ctx->tune_vfy_device < 2)) return false;
         for (size_t k = 1; k < count; k++) if (src[k] != src[0] || ms[k] != ms[0]) return false;
         proto = host::Transcript(host::scenario_label(scenarios[0]));
         host::TP<C>::r1cs_domain_sep(proto);

@@ -221,7 +221,7 @@ template <class F> __device__ __forceinline__ Fe challenge_from_seed(const u32 s
 // ---- k_vfe_sponge --------------------------------------------------------------------------------------------------------
 template <class C> __global__ void __launch_bounds__(64)
 k_vfe_sponge(const u32* __restrict__ sched, const u64* __restrict__ state0, u32 state_stride, const u64* __restrict__ msg, u32 P, u32 nchal,
-             u32* __restrict__ chal, u8* __restrict__ seeds) {
+             u32* __restrict__ chal, u8* __restrict__ seeds, u32 nbase, u32* __restrict__ gch) {
     typedef typename C::Fr F;
     __shared__ u64 st[25 * 64];
     const u32 lane = threadIdx.x, p_raw = blockIdx.x * 64u + lane;
@@ -271,6 +271,11 @@ k_vfe_sponge(const u32* __restrict__ sched, const u64* __restrict__ state0, u32 
 #pragma unroll
                     for (int j = 0; j < 8; j++) so32[j] = seed[j];
                 }
+                if (gch && sq >= nbase) {   // a gadget challenge: ark words for the host's randomized-phase callbacks
+                    u32 w[8];
+                    fe_store_ark<F>(w, c);
+                    store_words8(gch + ((size_t)p * (nchal - nbase) + (sq - nbase)) * 8, w);
+                }
             }
         }
 #pragma unroll
@@ -288,7 +293,7 @@ k_vfe_consts(Shape sh, const u8* __restrict__ proofs, const u32* __restrict__ ch
     typedef typename C::Fr F;
     const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= sh.P) return;
-    const u32 k = sh.k, m = sh.m, nchal = 6 + k;
+    const u32 k = sh.k, m = sh.m, nchal = 6 + k + sh.G;
     const u32* ch = chal + (size_t)p * nchal * 8;
     const u8* pr = proofs + (size_t)p * sh.plen;
     auto scalar_at = [&](u32 off) { u32 w[8]; load_le_words8(w, pr + off); return fe_load_canon<F>(w); };
@@ -365,6 +370,30 @@ k_vfe_wv(Shape sh, const u32* __restrict__ pb_in, const u32* __restrict__ voff, 
     store_fe_canon<F>(tail_sc + ((size_t)p * sh.tail + 6 + j) * 8, fe_mul<F>(wv, load_fe_dev<F>(pb + 512 + 48)));
 }
 
+// The same for proofs [p0, p0 + np) of a two-phase batch, coefficients by id: vcid[e] is CID_ONE / CID_MONE or an index into the
+// proof's own table (coefs + (p - p0) * coef_stride): a phase-2 term on a commitment carries the proof's challenge (`x[i] - z`).
+static constexpr u32 VCID_ONE = 0x80000000u, VCID_MONE = 0x40000000u, VCID_MASK = 0x3fffffffu;   // host_proto.hpp CID_*
+template <class C> __global__ void __launch_bounds__(256)
+k_vfe_wv_tab(Shape sh, u32 p0, u32 np, const u32* __restrict__ pb_in, const u32* __restrict__ voff, const u32* __restrict__ vq, const u32* __restrict__ vcid,
+             const u32* __restrict__ coefs, u32 coef_stride, u32* __restrict__ tail_sc) {
+    typedef typename C::Fr F;
+    const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (u64)np * sh.m) return;
+    const u32 pl = (u32)(gid / sh.m), j = (u32)(gid % sh.m), p = p0 + pl;
+    const u32* pb = pb_in + (size_t)p * PB_WORDS;
+    const u32* tab = coefs + (size_t)pl * coef_stride;
+    Fe acc = fe_zero<F>();
+    for (u32 e = voff[j], e1 = voff[j + 1]; e < e1; e++) {
+        const u32 cid = vcid[e];
+        const Fe zq = pow_table<F>(pb, vq[e] + 1u);
+        if (cid & VCID_ONE) acc = fe_addr<F>(acc, zq);
+        else if (cid & VCID_MONE) acc = fe_addr<F>(acc, fe_neg<F, 4>(zq));
+        else acc = fe_addr<F>(acc, fe_mul<F>(zq, load_fe_dev<F>(tab + (size_t)(cid & VCID_MASK) * 8)));
+    }
+    const Fe wv = fe_neg<F, 4>(acc);
+    store_fe_canon<F>(tail_sc + ((size_t)p * sh.tail + 6 + j) * 8, fe_mul<F>(wv, load_fe_dev<F>(pb + 512 + 48)));
+}
+
 // sums[0] = sum_p in[2p], sums[1] = sum_p in[2p + 1] (ark words out)
 template <class C> __global__ void __launch_bounds__(256)
 k_vfe_sum2(const u32* __restrict__ in, u32 P, u32* __restrict__ sums) {
@@ -391,8 +420,10 @@ template <class C> static int t_points(hipStream_t st, const Shape& sh, const u8
     hipLaunchKernelGGL(k_vfe_points<C>, dim3((u32)((total + 255) / 256)), dim3(256), 0, st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
-template <class C> static int t_sponge(hipStream_t st, const Shape& sh, const u32* d_sched, const u64* d_state0, u32 stride, const u64* d_msg, u32* d_chal, u8* d_seeds) {
-    hipLaunchKernelGGL(k_vfe_sponge<C>, dim3((sh.P + 63) / 64), dim3(64), 0, st, d_sched, d_state0, stride, d_msg, sh.P, 6 + sh.k, d_chal, d_seeds);
+template <class C> static int t_sponge(hipStream_t st, const Shape& sh, const u32* d_sched, const u64* d_state0, u32 stride, const u64* d_msg, u32* d_chal, u8* d_seeds,
+                                       u32* d_gch) {
+    hipLaunchKernelGGL(k_vfe_sponge<C>, dim3((sh.P + 63) / 64), dim3(64), 0, st, d_sched, d_state0, stride, d_msg, sh.P, 6 + sh.k + sh.G, d_chal, d_seeds, 6 + sh.k,
+                       sh.G ? d_gch : nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 template <class C> static int t_prepare(hipStream_t st, const Shape& sh, const u8* d_proofs, const u32* d_chal, const u32* d_alpha, const u32* d_voff, const u32* d_vq,
@@ -404,13 +435,36 @@ template <class C> static int t_prepare(hipStream_t st, const Shape& sh, const u
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+template <class C> static int t_consts(hipStream_t st, const Shape& sh, const u8* d_proofs, const u32* d_chal, const u32* d_alpha, u32* d_pb, u32* d_tail_sc, u32* d_ws,
+                                       u32* d_sums) {
+    u32* d_sB = d_ws + (size_t)sh.P * 32 * 8;
+    hipLaunchKernelGGL(k_vfe_consts<C>, dim3((sh.P + 63) / 64), dim3(64), 0, st, sh, d_proofs, d_chal, d_alpha, d_pb, d_tail_sc, d_ws, d_sB);
+    hipLaunchKernelGGL(k_vfe_sum2<C>, dim3(1), dim3(256), 0, st, d_sB, sh.P, d_sums);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+template <class C> static int t_wv_tab(hipStream_t st, const Shape& sh, u32 p0, u32 np, const u32* d_pb, const u32* d_voff, const u32* d_vq, const u32* d_vcid,
+                                       const u32* d_coefs, u32 coef_stride, u32* d_tail_sc) {
+    if (!sh.m || !np) return 0;
+    hipLaunchKernelGGL(k_vfe_wv_tab<C>, dim3((u32)(((u64)np * sh.m + 255) / 256)), dim3(256), 0, st, sh, p0, np, d_pb, d_voff, d_vq, d_vcid, d_coefs, coef_stride, d_tail_sc);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 int launch_points(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_V, uint64_t* d_msg, uint32_t* d_tail_pts, uint32_t* d_status) {
     return curve == 0 ? t_points<Secq>(st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status) : t_points<Zorro>(st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status);
 }
 int launch_sponge(int curve, hipStream_t st, const Shape& sh, const uint32_t* d_sched, const uint64_t* d_state0, uint32_t state_stride, const uint64_t* d_msg, uint32_t* d_chal,
-                  uint8_t* d_seeds_or_null) {
-    return curve == 0 ? t_sponge<Secq>(st, sh, d_sched, d_state0, state_stride, d_msg, d_chal, d_seeds_or_null)
-                      : t_sponge<Zorro>(st, sh, d_sched, d_state0, state_stride, d_msg, d_chal, d_seeds_or_null);
+                  uint8_t* d_seeds_or_null, uint32_t* d_gch) {
+    return curve == 0 ? t_sponge<Secq>(st, sh, d_sched, d_state0, state_stride, d_msg, d_chal, d_seeds_or_null, d_gch)
+                      : t_sponge<Zorro>(st, sh, d_sched, d_state0, state_stride, d_msg, d_chal, d_seeds_or_null, d_gch);
+}
+int launch_consts(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_chal, const uint32_t* d_alpha, uint32_t* d_pb, uint32_t* d_tail_sc,
+                  uint32_t* d_ws, uint32_t* d_sums) {
+    return curve == 0 ? t_consts<Secq>(st, sh, d_proofs, d_chal, d_alpha, d_pb, d_tail_sc, d_ws, d_sums) : t_consts<Zorro>(st, sh, d_proofs, d_chal, d_alpha, d_pb, d_tail_sc, d_ws, d_sums);
+}
+int launch_wv_tab(int curve, hipStream_t st, const Shape& sh, uint32_t p0, uint32_t np, const uint32_t* d_pb, const uint32_t* d_voff, const uint32_t* d_vq,
+                  const uint32_t* d_vcid, const uint32_t* d_coefs, uint32_t coef_stride, uint32_t* d_tail_sc) {
+    return curve == 0 ? t_wv_tab<Secq>(st, sh, p0, np, d_pb, d_voff, d_vq, d_vcid, d_coefs, coef_stride, d_tail_sc)
+                      : t_wv_tab<Zorro>(st, sh, p0, np, d_pb, d_voff, d_vq, d_vcid, d_coefs, coef_stride, d_tail_sc);
 }
 int launch_prepare(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_chal, const uint32_t* d_alpha, const uint32_t* d_voff,
                    const uint32_t* d_vq, const uint32_t* d_vc, uint32_t* d_pb, uint32_t* d_tail_sc, uint32_t* d_ws, uint32_t* d_sums) {

@@ -18,6 +18,7 @@ struct Shape {
     uint32_t plen;     // bytes per compressed proof: 539 + 66 k
     uint32_t tail;     // tail terms per proof in the mega-check: 6 + m + 5 + 2 k
     uint32_t nitems;   // ItemMap::count()
+    uint32_t G = 0;    // gadget challenges per proof (two-phase statements): challenges per proof = 6 + k + G
 };
 
 // status bits raised by the kernels (any bit: the batch goes through the host replay instead, which reports the reference's error)
@@ -34,9 +35,10 @@ static constexpr uint32_t ST_FRAMING = 4;       // L_vec / R_vec length fields d
 int launch_points(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_V, uint64_t* d_msg, uint32_t* d_tail_pts, uint32_t* d_status);
 
 // k_vfe_sponge: one lane per proof runs the schedule (vfe_sched.hpp) from its transcript state; d_state0: 25 words per proof
-// (state_stride = 25) or one shared state (0).  d_chal: P x (6 + k) x 8 words, resident form, order y z u x w u_1..u_k r.
+// (state_stride = 25) or one shared state (0).  d_chal: P x (6 + k + G) x 8 words, resident form, order y z u x w u_1..u_k r g_1..g_G.
+// d_gch (two-phase, optional): P x G x 8 words, the gadget challenges once more as ark words (what the host's callbacks receive).
 int launch_sponge(int curve, hipStream_t st, const Shape& sh, const uint32_t* d_sched, const uint64_t* d_state0, uint32_t state_stride, const uint64_t* d_msg, uint32_t* d_chal,
-                  uint8_t* d_seeds_or_null);
+                  uint8_t* d_seeds_or_null, uint32_t* d_gch = nullptr);
 
 // k_vfe_consts + k_vfe_wv + k_vfe_sum2: everything of verification_scalars that is not of length N (verifier.rs:462-541 minus the
 // g / h scalars).  d_alpha: P x 8 resident.  d_pb: P parameter blocks (r1cs.cuh VFY_PB_WORDS, resident form).  d_tail_sc: P x tail x 8
@@ -44,6 +46,15 @@ int launch_sponge(int curve, hipStream_t st, const Shape& sh, const uint32_t* d_
 // resident).  d_ws: P x 32 x 8 words scratch.  d_sums: 2 x 8 words (ark form): sum_p alpha_p sB_p, sum_p alpha_p sBb_p.
 int launch_prepare(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_chal, const uint32_t* d_alpha, const uint32_t* d_voff,
                    const uint32_t* d_vq, const uint32_t* d_vc, uint32_t* d_pb, uint32_t* d_tail_sc, uint32_t* d_ws, uint32_t* d_sums);
+
+// The two-phase split of launch_prepare: the coefficients of a randomized statement's phase-2 terms are known per proof only after
+// the host ran its callbacks, so k_vfe_consts + k_vfe_sum2 go first (launch_consts) and the committed-variable sums per block of
+// proofs after (launch_wv_tab).  d_vcid: the terms' coefficient ids (host_proto.hpp CID_ONE / CID_MONE flags, else an index into
+// the proof's own table); d_coefs: the tables of proofs [p0, p0 + np), coef_stride words apart, resident form.
+int launch_consts(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_chal, const uint32_t* d_alpha, uint32_t* d_pb, uint32_t* d_tail_sc,
+                  uint32_t* d_ws, uint32_t* d_sums);
+int launch_wv_tab(int curve, hipStream_t st, const Shape& sh, uint32_t p0, uint32_t np, const uint32_t* d_pb, const uint32_t* d_voff, const uint32_t* d_vq,
+                  const uint32_t* d_vcid, const uint32_t* d_coefs, uint32_t coef_stride, uint32_t* d_tail_sc);
 
 }  // namespace vfe
 }  // namespace arkbp

@@ -15,6 +15,7 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace arkbp {
@@ -138,13 +139,23 @@ struct ItemMap {
 // single-phase statement with m commitments and k inner-product rounds over N = 2^k padded multipliers.  The transcript stands
 // at (pos, pos_begin): before the commitments when absorb_commitments (they are then items 0 .. m-1), else right after them.
 // Challenges come out in the order y, z, u, x, w, u_1 .. u_k, r (6 + k of them).
-static inline bool build_verifier_schedule(Schedule& out, uint8_t pos, uint8_t pos_begin, bool absorb_commitments, uint64_t m, uint32_t k, uint64_t N) {
+// The two-phase variant (gadget_labels non-null): after S1 the randomized phase appends "dom-sep" / "r1cs-2phase" and squeezes one
+// challenge_scalar per gadget challenge, labels in recorded order (verifier.rs:353-376) — the callbacks append nothing, so the schedule
+// is still a function of the shape.  The gadget challenges take the indices after r: y z u x w u_1..u_k r g_1..g_G (6 + k + G).
+static inline bool build_verifier_schedule_t(Schedule& out, uint8_t pos, uint8_t pos_begin, bool absorb_commitments, uint64_t m, uint32_t k, uint64_t N,
+                                             const std::vector<std::string>* gadget_labels) {
     SchedStrobe s(pos, pos_begin);
     const ItemMap im{absorb_commitments ? (uint32_t)m : 0u, k};
     if (absorb_commitments) for (uint32_t j = 0; j < (uint32_t)m; j++) s.append_message_item("V", im.commitment(j), 65);   // Verifier::commit (verifier.rs:279-287)
     s.append_u64("m", m);
     s.append_message_item("A_I1", im.point(0), 65); s.append_message_item("A_O1", im.point(1), 65); s.append_message_item("S1", im.point(2), 65);
-    s.append_message_const("dom-sep", "r1cs-1phase", 11);
+    const uint32_t G = gadget_labels ? (uint32_t)gadget_labels->size() : 0u;
+    if (gadget_labels) {
+        s.append_message_const("dom-sep", "r1cs-2phase", 11);
+        for (const std::string& l : *gadget_labels) s.challenge32(l.c_str());
+    } else {
+        s.append_message_const("dom-sep", "r1cs-1phase", 11);
+    }
     s.append_message_item("A_I2", im.point(3), 65); s.append_message_item("A_O2", im.point(4), 65); s.append_message_item("S2", im.point(5), 65);
     s.challenge32("y"); s.challenge32("z");
     s.append_message_item("T_1", im.point(6), 65); s.append_message_item("T_3", im.point(7), 65); s.append_message_item("T_4", im.point(8), 65);
@@ -160,9 +171,20 @@ static inline bool build_verifier_schedule(Schedule& out, uint8_t pos, uint8_t p
     }
     s.challenge32("r");   // drawn from a clone upstream (verifier.rs:516-519): nothing reads the original afterwards
     s.finish();
-    if (!s.ok || s.out.nchal != 6 + k) return false;
+    if (!s.ok || s.out.nchal != 6 + k + G) return false;
+    for (Block& b : s.out.blocks)   // squeeze order g_1..g_G y z .. r -> index order y z .. r g_1..g_G
+        if (b.squeeze != NO_SQUEEZE) b.squeeze = b.squeeze < G ? 6 + k + b.squeeze : b.squeeze - G;
     out = std::move(s.out);
     return true;
+}
+static inline bool build_verifier_schedule(Schedule& out, uint8_t pos, uint8_t pos_begin, bool absorb_commitments, uint64_t m, uint32_t k, uint64_t N) {
+    return build_verifier_schedule_t(out, pos, pos_begin, absorb_commitments, m, k, N, nullptr);
+}
+static inline bool build_verifier_schedule_2phase(Schedule& out, uint8_t pos, uint8_t pos_begin, bool absorb_commitments, uint64_t m, uint32_t k, uint64_t N,
+                                                  const std::vector<std::string>& gadget_labels) {
+    if (gadget_labels.empty() || gadget_labels.size() > 4096) return false;
+    for (const std::string& l : gadget_labels) if (l.size() > 4096 || l.find('\0') != std::string::npos) return false;
+    return build_verifier_schedule_t(out, pos, pos_begin, absorb_commitments, m, k, N, &gadget_labels);
 }
 
 // CPU interpreter of a schedule (tests; the device kernel does the same per lane): state = 25 words, items = count x 72 bytes;

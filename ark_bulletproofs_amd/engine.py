@@ -919,6 +919,10 @@ Engine.debug_rccl_allgather = _debug_rccl_allgather
 
 
 # ---- verifier front end on the device (csrc/vfe.hip): test hooks ----------------------------------------------------------
+TUNE_VFY_DEVICE = 11                 # include/arkbp.h BP_TUNE_VFY_DEVICE (Engine.set_tuning)
+VFY_DEVICE_OFF, VFY_DEVICE_SINGLE_PHASE, VFY_DEVICE_TWO_PHASE = 0, 1, 2   # its values: host replay / single-phase like-instances (default) / two-phase ones too
+
+
 def vfe_schedule_replay(state203, absorb_commitments, m, k, n, items):
     """CPU run of the data-independent sponge schedule of one verification (bp_debug_vfe_schedule_replay).  items: (count, 72)
     uint8.  Returns ((6 + k, 32) uint8 challenge seeds, number of Keccak-f permutations)."""
@@ -927,6 +931,20 @@ def vfe_schedule_replay(state203, absorb_commitments, m, k, n, items):
     nb = C.c_uint32(0)
     check(lib().bp_debug_vfe_schedule_replay(bytes(state203), int(bool(absorb_commitments)), C.c_uint64(m), C.c_uint32(k), C.c_uint64(n), ptr(items), ptr(seeds), C.byref(nb)),
           "bp_debug_vfe_schedule_replay")
+    return seeds, nb.value
+
+
+def vfe_schedule_replay_2phase(state203, absorb_commitments, m, k, n, labels, items):
+    """The same for a two-phase statement (bp_debug_vfe_schedule_replay_2phase): after S1 the "r1cs-2phase" separator and one
+    challenge per gadget label (bytes, drawing order).  Returns ((6 + k + G, 32) uint8 seeds in the order y z u x w u_1..u_k r
+    g_1..g_G, number of Keccak-f permutations)."""
+    items = np.ascontiguousarray(items, dtype=np.uint8)
+    G = len(labels)
+    seeds = np.zeros((6 + k + G, 32), dtype=np.uint8)
+    nb = C.c_uint32(0)
+    arr = (C.c_char_p * max(G, 1))(*[bytes(l) for l in labels])
+    check(lib().bp_debug_vfe_schedule_replay_2phase(bytes(state203), int(bool(absorb_commitments)), C.c_uint64(m), C.c_uint32(k), C.c_uint64(n), arr, C.c_size_t(G),
+                                                    ptr(items), ptr(seeds), C.byref(nb)), "bp_debug_vfe_schedule_replay_2phase")
     return seeds, nb.value
 
 

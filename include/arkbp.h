@@ -438,7 +438,9 @@ int bp_ctx_reset_profiling(bp_ctx* ctx);
 #define BP_TUNE_MSM_CHUNK_CAP 9   /* entries per first-level chunk of the mid-size (fixed-shape) MSM pipeline: 8 .. 64; 0 = default (16 for callers that keep
                                      the GPU full; fitted per MSM to whole waves per SIMD for the bp_msm* entry points).  Results never depend on it */
 #define BP_TUNE_VFY_DEVICE 11    /* 1 (default): batch verification of like-instances of one single-phase statement runs its per-proof front end on the
-                                  * GPU (see "verifier front end on the device" below); 0: always the host replay (A/B, tests) */
+                                  * GPU (see "verifier front end on the device" below); 2: like-instances of two-phase statements
+                                  * (specify_randomized_constraints) too; 0: always the host replay (A/B, tests).  Values above 2 act as 2.
+                                  * ARKBP_VFY_DEVICE=0/1/2 in the environment sets the default of every ctx created afterwards */
 #define BP_TUNE_DIRECT_MAX 12    /* statements whose padded size is at most this (default 8192, at most 2^16; 0 = never) are proved over DIRECT WINDOW
                                   * TABLES of the first generators (d * 16^w * base, 60 KiB per base, built by the first such proof of the ctx): every
                                   * MSM of Prover::prove (src/r1cs/prover.rs:516-649) and of InnerProductProof::create
@@ -479,8 +481,17 @@ int bp_debug_glv_decompose(int curve, const uint64_t t[4], uint32_t masks[20], u
  * (src/r1cs/proof.rs:83-91), the merlin transcript replay of verification_scalars (verifier.rs:403-460, 516-519;
  * src/inner_product_proof.rs:266-280; src/transcript.rs:45-102: Keccak-f[1600] / STROBE-128 / ChaCha20 -> Fr::rand) and the
  * O(k + m) challenge arithmetic (:462-541).  Anything unusual (malformed bytes, an identity point that
- * validate_and_append_point rejects, mixed shapes, randomized constraints) takes the host replay instead, which reports the
- * reference's error.  ARKBP_VFY_HOST=1 in the environment forces the host replay (A/B).
+ * validate_and_append_point rejects, mixed shapes) takes the host replay instead, which reports the reference's error.
+ * ARKBP_VFY_HOST=1 in the environment forces the host replay (A/B).
+ * Two-phase statements (randomized constraints) take this path with BP_TUNE_VFY_DEVICE = 2 only: the device derives every
+ * challenge, the gadget challenges of the callbacks included; the host then runs each instance's callbacks with its own
+ * challenges preset — on the instance's own handle, so a C callback records through the bp_cs it receives, and
+ * bp_cs_challenge_scalar returns the preset value for the expected label — and the device consumes the per-proof coefficient
+ * tables they produce.  Instance 0's callbacks run once beforehand on a copy of its live transcript; they fix the labels and
+ * the phase-2 structure.  The batch goes to the host replay instead when any instance draws other labels, records another
+ * structure (multipliers, constraint offsets, variables, which coefficients are +-1 or shared), or when the per-proof gadget
+ * challenges and coefficient tables would exceed 256 MiB.  The callbacks then run again there: nothing they recorded under
+ * the preset challenges is kept.
  *
  * bp_debug_vfe_schedule_replay (host only, no GPU): builds the data-independent sponge schedule of one verification — transcript
  * at state203 (bp_transcript_export_state), m commitments (absorbed as items 0..m-1 when absorb_commitments), k rounds, n = the
@@ -491,9 +502,15 @@ int bp_debug_glv_decompose(int curve, const uint64_t t[4], uint32_t masks[20], u
  * each; commit_xy count x m x 8 words, ark layout; states203: count x 203 bytes, or one when shared_state): seeds_out as above per
  * proof, chal_out the derived challenge scalars (count x (6 + k) x 4 ark words), *status_out the OR of the kernels' reject bits
  * (1 malformed, 2 identity under validation, 4 framing).
- * bp_ctx_vfe_stats: batches the device front end completed / batches it handed to the host replay on this ctx. */
+ * bp_debug_vfe_schedule_replay_2phase (host only): the same for a two-phase statement whose callbacks draw the gadget challenges
+ * labels[0..nlabels) in this order ("r1cs-2phase" separator after S1, the squeezes before A_I2); seeds_out: (6 + k + nlabels) x 32
+ * bytes in the order y z u x w u_1..u_k r g_1..g_nlabels.
+ * bp_ctx_vfe_stats: batches the device front end completed / batches it handed to the host replay on this ctx (two-phase
+ * batches included). */
 int bp_debug_vfe_schedule_replay(const uint8_t state203[203], int absorb_commitments, uint64_t m, uint32_t k, uint64_t n, const uint8_t* items, uint8_t* seeds_out,
                                  uint32_t* nblocks_out);
+int bp_debug_vfe_schedule_replay_2phase(const uint8_t state203[203], int absorb_commitments, uint64_t m, uint32_t k, uint64_t n, const char* const* labels, size_t nlabels,
+                                        const uint8_t* items, uint8_t* seeds_out, uint32_t* nblocks_out);
 int bp_debug_vfe_challenges(bp_ctx* ctx, size_t count, const uint8_t* proofs, size_t proof_len, const uint64_t* commit_xy, size_t m, const uint8_t* states203,
                             int shared_state, int absorb_commitments, uint8_t* seeds_out, uint64_t* chal_out, uint32_t* status_out);
 int bp_ctx_vfe_stats(bp_ctx* ctx, uint64_t* device_batches, uint64_t* host_fallbacks);
