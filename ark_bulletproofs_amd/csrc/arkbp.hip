@@ -25,6 +25,7 @@
 #include "r1cs.cuh"
 #include "pedersen.cuh"
 #include "small.cuh"
+#include "small_batch.cuh"
 #include "vfe.hpp"
 #include "vfe_sched.hpp"
 static_assert(arkbp::vfe::PB_WORDS == arkbp::VFY_PB_WORDS, "parameter block layout shared by vfe.hip and r1cs.cuh");
@@ -321,6 +322,13 @@ struct bp_ctx {
     u32* h_dt = nullptr;             // pinned: the results of one launch (or its partial points, see msm_direct_launch)
     u32 dt_pending_parts = 1;        // partial points per MSM on their way to h_dt
     uint64_t dt_runs = 0;            // MSMs answered from the direct tables
+    // bp_prover_prove_batch: its own device arena and pinned staging (never the single-proof workspaces above), and its counters
+    size_t tune_prove_batch = 0;     // BP_TUNE_PROVE_BATCH: most instances per lockstep group (0 = as many as PB_ARENA_BUDGET allows)
+    DevBuf pb_arena;
+    void* h_pb = nullptr;            // pinned
+    size_t h_pb_cap = 0;
+    uint64_t pb_lockstep = 0, pb_single = 0, pb_groups = 0;
+    double pb_ipa_s = 0;             // seconds of lockstep inner-product rounds in the current call
     uint64_t folds_deferred = 0, folds_tab2 = 0;   // first folds deferred / second folds that came straight from the tables (bp_ctx_fold_stats)
     IpaState ipa_step;         // bp_ipa_begin .. bp_ipa_finish
     bool ipa_step_active = false;
@@ -2770,6 +2778,8 @@ __attribute__((target("avx512f"))) static int dbg_challenge_x8(void* const* trs,
 }
 #endif
 
+#include "prove_batch.inc"   // bp_prover_prove_batch, bp_prover_commit_batch (the C entry points are declared extern "C" by the header)
+
 extern "C" {
 
 int bp_device_count(void) {
@@ -2813,6 +2823,8 @@ void bp_ctx_destroy(bp_ctx* c) {
     if (c->h_vfe) (void)hipHostFree(c->h_vfe);
     if (c->h_vfe2) (void)hipHostFree(c->h_vfe2);
     c->dt_tab.release(); c->dt_part.release(); c->pc_dt.release(); c->dt_a2.release(); c->dt_b2.release(); c->dt_ticket.release();
+    c->pb_arena.release();
+    if (c->h_pb) (void)hipHostFree(c->h_pb);
     if (c->h_dt) (void)hipHostFree(c->h_dt);
     if (c->h_totals) (void)hipHostFree(c->h_totals);
     if (c->h_T) (void)hipHostFree(c->h_T);
@@ -2907,6 +2919,7 @@ int bp_ctx_set_tuning(bp_ctx* c, int knob, uint64_t value) {
         case BP_TUNE_WAIT_SLEEP: if (value > 1000) return BP_E_ARG; c->tune_wait_sleep = value == 1 ? 30u : (unsigned)value; return BP_OK;
         case BP_TUNE_MSM_CHUNK_CAP: if (value && (value < 8 || value > 64)) return BP_E_ARG; c->tune_msm_chunk_cap = (size_t)value; return BP_OK;
         case BP_TUNE_VFY_DEVICE: c->tune_vfy_device = value >= 2 ? 2 : (int)value; return BP_OK;
+        case BP_TUNE_PROVE_BATCH: if (value > 65535) return BP_E_ARG; c->tune_prove_batch = (size_t)value; return BP_OK;
         case BP_TUNE_DIRECT_MAX: if (value > ((uint64_t)1 << 16)) return BP_E_ARG; c->tune_direct_max = (size_t)value; return BP_OK;
     }
     return BP_E_ARG;

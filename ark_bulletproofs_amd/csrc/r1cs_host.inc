@@ -355,10 +355,22 @@ template <class C> static void prove_precompute_batch(host::ConstraintSystem<C>*
 #endif
 }
 
+// bp_prover_prove_batch (prove_batch.inc): a statement whose inner-product argument would run over the direct window tables may hand
+// it to a lockstep group instead.  take(N, slot) gives the group slot that receives a, b and the factor vectors (false: run it here).
+// A taken proof returns with everything but L_vec, R_vec, a and b filled in, and its transcript right after the domain separator.
+struct IpaDeferSlot { u32 *a = nullptr, *b = nullptr, *cG = nullptr, *cH = nullptr; };
+struct IpaDefer {
+    std::function<bool(size_t N, IpaDeferSlot& slot)> take;
+    bool taken = false;
+    size_t N = 0;
+    F4 w;
+};
+
 // Prover::prove_and_return_transcript (src/r1cs/prover.rs:454-831)
 template <class C>
 static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8* rng_bytes, host::ProofData& proof, StageTimes& tm,
-                      ProvePre<C>* pre_in = nullptr, const HostCsc* csc = nullptr /* constraint index built with the statement (single-phase) */) {
+                      ProvePre<C>* pre_in = nullptr, const HostCsc* csc = nullptr /* constraint index built with the statement (single-phase) */,
+                      IpaDefer* defer = nullptr) {
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
     typedef host::Grp<C> G;
@@ -677,6 +689,15 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     mark("l(x), r(x), Q");
 
     t0 = now_s();
+    IpaDeferSlot dslot;
+    const bool deferred = defer && direct && !cyclic && N >= 2 && ctx->dt_cap >= N && defer->take(N, dslot);
+    if (deferred) {   // (the same copies ipa_create_dev's direct path makes of the factor vectors)
+        HIPCHK(hipMemcpyAsync(dslot.a, ctx->ipa_a.p, N * 32, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(dslot.b, ctx->ipa_b.p, N * 32, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(dslot.cG, ctx->ipa_Gf.p, N * 32, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(dslot.cH, ctx->ipa_Hf.p, N * 32, hipMemcpyDeviceToDevice, st));
+        defer->taken = true; defer->N = N; defer->w = w;
+    }
     TP::innerproduct_domain_sep(tr, N);
     size_t lg = 0; while (((size_t)1 << lg) < N) lg++;
     std::vector<uint64_t> Lw(8 * std::max<size_t>(lg, 1)), Rw(8 * std::max<size_t>(lg, 1));
@@ -691,7 +712,8 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     // G_factors = [1]*n1 ++ [u]*(N-n1) (prover.rs:781-784): constant on each half of the first fold iff n1 is 0, N/2 or >= N
     F4 gfh[2] = {n1 >= N / 2 ? S::one() : u, n1 >= N ? S::one() : u};
     const bool gf_const_halves = N >= 2 && (n1 == 0 || n1 == N / 2 || n1 >= N);
-    if (cyclic)
+    if (deferred) {}
+    else if (cyclic)
         BPCHK(ipa_create_cyclic<C>(ctx, ctx->ipa_Q.as<u32>(), ctx->ipa_Gf.as<u32>(), ctx->ipa_Hf.as<u32>(), ctx->d_G.as<u32>(), ctx->d_H.as<u32>(), ctx->ipa_a.as<u32>(),
                                    ctx->ipa_b.as<u32>(), N, fn, Lw.data(), Rw.data(), aw, bw, gf_const_halves ? gfh : nullptr, gf_const_halves ? ypw : nullptr,
                                    gf_const_halves ? ctx->r_ypow.as<u32>() + 32 * 8 : nullptr, &w));
@@ -706,12 +728,14 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     proof.A_I1 = A_I1; proof.A_O1 = A_O1; proof.S1 = S1; proof.A_I2 = A_I2; proof.A_O2 = A_O2; proof.S2 = S2;
     proof.T_1 = T_1; proof.T_3 = T_3; proof.T_4 = T_4; proof.T_5 = T_5; proof.T_6 = T_6;
     proof.t_x = t_x; proof.t_x_blinding = t_x_blinding; proof.e_blinding = e_blinding;
-    proof.L_vec.resize(lg); proof.R_vec.resize(lg);
-    for (size_t i = 0; i < lg; i++) {
-        memcpy(proof.L_vec[i].x.v, &Lw[8 * i], 32); memcpy(proof.L_vec[i].y.v, &Lw[8 * i + 4], 32);
-        memcpy(proof.R_vec[i].x.v, &Rw[8 * i], 32); memcpy(proof.R_vec[i].y.v, &Rw[8 * i + 4], 32);
+    if (!deferred) {
+        proof.L_vec.resize(lg); proof.R_vec.resize(lg);
+        for (size_t i = 0; i < lg; i++) {
+            memcpy(proof.L_vec[i].x.v, &Lw[8 * i], 32); memcpy(proof.L_vec[i].y.v, &Lw[8 * i + 4], 32);
+            memcpy(proof.R_vec[i].x.v, &Rw[8 * i], 32); memcpy(proof.R_vec[i].y.v, &Rw[8 * i + 4], 32);
+        }
+        memcpy(proof.a.v, aw, 32); memcpy(proof.b.v, bw, 32);
     }
-    memcpy(proof.a.v, aw, 32); memcpy(proof.b.v, bw, 32);
     // secret hygiene (prover.rs:74-94, 805-812): wipe the witness-derived device vectors
     DevBuf* wipe[] = {&ctx->r_aL, &ctx->r_aR, &ctx->r_aO, &ctx->r_sL, &ctx->r_sR, &ctx->ipa_a, &ctx->ipa_b, &ctx->cyc_a, &ctx->cyc_b, &ctx->dt_a2, &ctx->dt_b2};
     {

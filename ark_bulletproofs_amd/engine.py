@@ -1029,3 +1029,76 @@ def _fold_stats(self):
 
 
 Engine.fold_stats = _fold_stats
+
+
+def _prover_handle(p):
+    """bp_cs* of a ProverCS or a scenario Statement (bp_stmt_as_prover)"""
+    if isinstance(p, Statement):
+        return C.c_void_p(lib().bp_stmt_as_prover(p.h))
+    return p.h
+
+
+def _prove_batch(self, provers, rng_bytes=None, timing=None, return_rc=False):
+    """bp_prover_prove_batch over ProverCS objects and/or Statements (every one consumed).  rng_bytes: one 32-byte string per
+    instance, or None when every prover has its rng already.  Returns [(status, proof_bytes)] in instance order (b"" for a failed
+    instance) — a failing instance does not raise; the call raises only when the up-front checks refuse the whole batch.
+    return_rc: return (the call's status — the first non-zero instance status —, the list) instead."""
+    n = len(provers)
+    if n == 0:
+        return (0, []) if return_rc else []
+    hs = (C.c_void_p * n)(*[_prover_handle(p) for p in provers])
+    rb = None
+    if rng_bytes is not None:
+        if len(rng_bytes) != n or any(len(r) != 32 for r in rng_bytes):
+            raise ValueError("prove_batch: one 32-byte rng string per instance")
+        rb = b"".join(bytes(r) for r in rng_bytes)
+    stride = 1 << 12
+    out = C.create_string_buffer(stride * n)
+    lens = (C.c_size_t * n)()
+    st = (C.c_int * n)()
+    tm = (C.c_double * 8)()
+    rc = lib().bp_prover_prove_batch(self.ctx, C.c_size_t(n), hs, rb, out, C.c_size_t(stride), lens, st, tm)
+    if timing is not None:
+        timing[:] = list(tm)
+    if rc != 0 and all(s == 0 for s in st):   # refused as a whole (nothing consumed) or a device error before any instance
+        check(rc, "bp_prover_prove_batch")
+    raw = out.raw
+    res = [(st[k], raw[k * stride: k * stride + lens[k]]) for k in range(n)]
+    return (rc, res) if return_rc else res
+
+
+def _prover_commit_batch(self, provers, values, blindings):
+    """bp_prover_commit_batch: values[k] / blindings[k] are the (m_k, 4) ark-word arrays of prover k.  Returns [(V (m_k, 8), variables)]."""
+    n = len(provers)
+    if n == 0:
+        return []
+    vs = [u64arr(v, 4) for v in values]
+    bs = [u64arr(b, 4) for b in blindings]
+    if any(a.shape != b.shape for a, b in zip(vs, bs)) or len(vs) != n or len(bs) != n:
+        raise ValueError("prover_commit_batch: one (values, blindings) pair of equal length per prover")
+    m = [len(a) for a in vs]
+    tot = sum(m)
+    v = np.ascontiguousarray(np.concatenate(vs) if tot else np.zeros((0, 4), dtype=np.uint64))
+    b = np.ascontiguousarray(np.concatenate(bs) if tot else np.zeros((0, 4), dtype=np.uint64))
+    V = np.zeros((max(tot, 1), 8), dtype=np.uint64)
+    vars_ = np.zeros((max(tot, 1), 2), dtype=np.uint32)
+    hs = (C.c_void_p * n)(*[_prover_handle(p) for p in provers])
+    me = (C.c_size_t * n)(*m)
+    check(lib().bp_prover_commit_batch(self.ctx, C.c_size_t(n), hs, me, ptr(v), ptr(b), ptr(V), ptr(vars_)), "bp_prover_commit_batch")
+    res, off = [], 0
+    for k in range(n):
+        res.append((V[off: off + m[k]].copy(), _vars_out(vars_[off: off + m[k]])))
+        off += m[k]
+    return res
+
+
+def _prove_batch_stats(self):
+    """(instances whose inner-product argument ran in a lockstep group, instances proved one at a time, lockstep groups)"""
+    a, b, g = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().bp_ctx_prove_batch_stats(self.ctx, C.byref(a), C.byref(b), C.byref(g)), "bp_ctx_prove_batch_stats")
+    return a.value, b.value, g.value
+
+
+Engine.prove_batch = _prove_batch
+Engine.prover_commit_batch = _prover_commit_batch
+Engine.prove_batch_stats = _prove_batch_stats

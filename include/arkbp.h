@@ -344,6 +344,33 @@ int bp_prover_set_rng(bp_cs* prover, const uint8_t rng_bytes[32]);
 int bp_prover_precompute(bp_cs* prover, const uint8_t rng_bytes_or_null[32]);
 int bp_prover_precompute_batch(bp_cs** provers, size_t count);
 int bp_prover_prove(bp_ctx* ctx, bp_cs* prover, const uint8_t rng_bytes_or_null[32], uint8_t* proof_out, size_t* proof_len, double* timing);
+/* Batch proving: `count` statements in one call, equivalent to bp_prover_prove(ctx, provers[k], rng_k, ..) for k = 0 .. count-1 in
+ * order — the same proof bytes, the same transcript states afterwards, the same status per instance.
+ *   rng_bytes: count x 32 bytes, or NULL when every prover has its rng already (bp_prover_set_rng / bp_prover_precompute).
+ *   proofs_out: proof k at proofs_out + k * proof_stride, its length in proof_lens[k] (0 for a failed instance).
+ *   status (count, may be NULL): instance k's own result.  timing (8 doubles, may be NULL): total, lockstep inner-product rounds,
+ *   TranscriptRng, upload, commitments, flatten, t(x) and evaluations, inner-product arguments proved one at a time (seconds).
+ * Up-front checks, before any work: every prover live, of the ctx's curve and given once; no two borrow one transcript; rng bytes
+ * present (and equal to precomputed ones); proof_stride at least the length of a proof with lg(gens capacity) rounds.  A failed
+ * check returns BP_E_ARG and consumes no prover.  Otherwise every prover is consumed; an instance fails on its own (a callback's
+ * non-zero return, BP_E_MISSING inside a randomized phase, BP_E_GENS_LENGTH) without changing any other instance's bytes, and the
+ * call returns the first non-zero status in instance order.  A host-only ctx returns BP_E_NO_DEVICE after the checks and consumes
+ * nothing.  Randomized-phase callbacks of different instances may run in any order.
+ * Grouping: every instance runs the stages of prove() up to its inner-product argument; those whose argument runs over the direct
+ * window tables (padded size 2 .. BP_TUNE_DIRECT_MAX) then run it in LOCKSTEP groups of equal padded size — one launch per stage
+ * and one host wait per Fiat-Shamir round for the whole group — and every other instance proves as bp_prover_prove would, inside
+ * the same call.  The bytes are identical either way.  A batch leaves the ctx's single-proof path as it was: a bp_prover_prove
+ * afterwards gives the bytes it gives on a fresh ctx.
+ * bp_prover_commit_batch: `Prover::commit` for several provers, equal to bp_prover_commit(provers[k], ctx, v + .., v_blinding + ..,
+ * m_each[k], ..) in order, with every commitment of the batch computed in one launch and normalised with one inversion.  v,
+ * v_blinding, V_xy_out and vars_out hold the sum of m_each entries, prover after prover.
+ * bp_ctx_prove_batch_stats: instances whose inner-product argument ran in a lockstep group / instances bp_prover_prove_batch proved
+ * one at a time / lockstep groups, since ctx creation. */
+int bp_prover_prove_batch(bp_ctx* ctx, size_t count, bp_cs* const* provers, const uint8_t* rng_bytes, uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens,
+                          int* status, double* timing);
+int bp_prover_commit_batch(bp_ctx* ctx, size_t count, bp_cs* const* provers, const size_t* m_each, const uint64_t* v, const uint64_t* v_blinding, uint64_t* V_xy_out,
+                           bp_var* vars_out);
+int bp_ctx_prove_batch_stats(bp_ctx* ctx, uint64_t* lockstep_instances, uint64_t* single_instances, uint64_t* groups);
 /* `verifier.verify(&proof, &pc_gens, &bp_gens)` (verifier.rs:549-557): consumes the verifier */
 int bp_verifier_verify(bp_ctx* ctx, bp_cs* verifier, const uint8_t* proof, size_t proof_len);
 /* `batch_verify(prng, instances, &pc_gens, &bp_gens)` (verifier.rs:604-691): instance k = (verifiers[k], the k-th of the
@@ -446,6 +473,8 @@ int bp_ctx_reset_profiling(bp_ctx* ctx);
                                   * MSM of Prover::prove (src/r1cs/prover.rs:516-649) and of InnerProductProof::create
                                   * (src/inner_product_proof.rs:86-213) becomes a sum of table entries, G and H are never folded.  This is the
                                   * latency path for the reference's own benchmark range (benches/r1cs_secq256k1.rs:152-250, 2 .. 2046 multipliers) */
+#define BP_TUNE_PROVE_BATCH 13   /* most instances per lockstep group of bp_prover_prove_batch (0 = default: as many as a 256 MB device arena
+                                  * holds; at most 65535, groups above 16384 are split) */
 int bp_ctx_set_tuning(bp_ctx* ctx, int knob, uint64_t value);
 
 /* The O(N) part of `Verifier::verification_scalars` (src/r1cs/verifier.rs:465-514, s from inner_product_proof.rs:279-311) for a
