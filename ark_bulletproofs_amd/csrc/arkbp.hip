@@ -26,6 +26,7 @@
 #include "pedersen.cuh"
 #include "small.cuh"
 #include "small_batch.cuh"
+#include "small_batch_front.cuh"
 #include "vfe.hpp"
 #include "vfe_sched.hpp"
 static_assert(arkbp::vfe::PB_WORDS == arkbp::VFY_PB_WORDS, "parameter block layout shared by vfe.hip and r1cs.cuh");
@@ -329,6 +330,12 @@ struct bp_ctx {
     size_t h_pb_cap = 0;
     uint64_t pb_lockstep = 0, pb_single = 0, pb_groups = 0;
     double pb_ipa_s = 0;             // seconds of lockstep inner-product rounds in the current call
+    // ... and the stages in front of the argument run group-wide (prove_batch.inc "front groups"): what is public lives in pf_aux
+    int tune_pb_front = 1;           // BP_TUNE_PROVE_BATCH_FRONT
+    DevBuf pf_aux;
+    void* h_pf = nullptr;            // pinned: witness staging, the aux block, results
+    size_t h_pf_cap = 0;
+    uint64_t pf_instances = 0, pf_groups = 0, pf_waits = 0;
     uint64_t folds_deferred = 0, folds_tab2 = 0;   // first folds deferred / second folds that came straight from the tables (bp_ctx_fold_stats)
     IpaState ipa_step;         // bp_ipa_begin .. bp_ipa_finish
     bool ipa_step_active = false;
@@ -2824,6 +2831,8 @@ void bp_ctx_destroy(bp_ctx* c) {
     if (c->h_vfe2) (void)hipHostFree(c->h_vfe2);
     c->dt_tab.release(); c->dt_part.release(); c->pc_dt.release(); c->dt_a2.release(); c->dt_b2.release(); c->dt_ticket.release();
     c->pb_arena.release();
+    c->pf_aux.release();
+    if (c->h_pf) (void)hipHostFree(c->h_pf);
     if (c->h_pb) (void)hipHostFree(c->h_pb);
     if (c->h_dt) (void)hipHostFree(c->h_dt);
     if (c->h_totals) (void)hipHostFree(c->h_totals);
@@ -2920,6 +2929,7 @@ int bp_ctx_set_tuning(bp_ctx* c, int knob, uint64_t value) {
         case BP_TUNE_MSM_CHUNK_CAP: if (value && (value < 8 || value > 64)) return BP_E_ARG; c->tune_msm_chunk_cap = (size_t)value; return BP_OK;
         case BP_TUNE_VFY_DEVICE: c->tune_vfy_device = value >= 2 ? 2 : (int)value; return BP_OK;
         case BP_TUNE_PROVE_BATCH: if (value > 65535) return BP_E_ARG; c->tune_prove_batch = (size_t)value; return BP_OK;
+        case BP_TUNE_PROVE_BATCH_FRONT: if (value > 1) return BP_E_ARG; c->tune_pb_front = (int)value; return BP_OK;
         case BP_TUNE_DIRECT_MAX: if (value > ((uint64_t)1 << 16)) return BP_E_ARG; c->tune_direct_max = (size_t)value; return BP_OK;
     }
     return BP_E_ARG;

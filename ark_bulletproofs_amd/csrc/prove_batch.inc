@@ -1,10 +1,18 @@
 // Included by arkbp.hip after r1cs_host.inc.  bp_prover_prove_batch: many statements in one call, the inner-product arguments of
 // like-sized small statements in LOCKSTEP groups (small_batch.cuh).
 //
-// Every instance runs r1cs_prove up to its inner-product argument (commitments, randomized phase, flatten, t(x), evaluations — on the
-// ctx's single-proof workspaces, one instance after the other, as bp_prover_prove would).  An instance whose argument runs over the
-// direct window tables then hands a, b and its factor vectors to the open group of its padded size N (IpaDefer) instead of running
-// lg N rounds of its own.  A group runs when it is full, when an instance of another size needs the arena, or at the end of the
+// FRONT GROUPS (BP_TUNE_PROVE_BATCH_FRONT = 1, pf_* below): an instance whose argument runs over the direct window tables and whose
+// constraints can be indexed (HostCsc) runs EVERY stage group-wide.  Instances of equal phase-1 multiplier count n1 form a front group:
+// one import launch and one k_dt_accum_multi launch give all A_I1 / A_O1 / S1, ONE host wait.  The randomized phases run on the calling
+// thread; the survivors are re-partitioned by padded size N and every part goes on as a group of its own: the phase-2 TranscriptRng
+// draws on the ctx's host pool, one import launch for the whole witness, the phase-2 commitments (ONE wait), then ztables / flatten /
+// t(x) / the T commitments behind one another (ONE wait), l(x) / r(x) straight into the slots pb_run_group reads, and the lockstep
+// rounds.  A member that stops qualifying after its randomized phase continues through r1cs_prove's resume entry.
+//
+// Every other instance runs r1cs_prove up to its inner-product argument (commitments, randomized phase, flatten, t(x), evaluations — on
+// the ctx's single-proof workspaces, one instance after the other, as bp_prover_prove would; with the knob at 0 every instance does).
+// An instance whose argument runs over the direct window tables then hands a, b and its factor vectors to the open group of its padded
+// size N (IpaDefer) instead of running lg N rounds of its own.  A group runs when it is full, when an instance of another size needs the arena, or at the end of the
 // call: per round ONE upload of the descriptors and challenges, k_dt_round_multi, k_dt_accum_multi (+ k_dt_finish), ONE copy back and
 // ONE host wait for every proof of the group; the transcript steps of all proofs run on the ctx's host pool.  L, R, a and b are the
 // values the single-proof schedule computes, so every byte of every proof is.
@@ -21,6 +29,10 @@ static size_t pb_proof_len(size_t lg) { return 11 * 33 + 3 * 32 + 2 * (8 + 33 * 
 struct PbLayout {
     size_t N = 0, cap = 0, gf = 0, nblk = 0;
     size_t per_vec = 0, o_b = 0, o_a2 = 0, o_b2 = 0, o_cG = 0, o_cH = 0, o_sL = 0, o_sR = 0, o_part = 0;   // one proof's vectors
+    // ... and what the front stages keep there: the witness a_L, a_R, a_O and the t(x) partials in room of their own; s_L in the a2 | b2
+    // pair and s_R, w_L, w_R, w_O in the rounds' scalar vectors — those are first written by round 1 / round 0, after l(x), r(x) are out
+    size_t o_waL = 0, o_waR = 0, o_waO = 0, o_wsL = 0, o_wsR = 0, o_wwL = 0, o_wwR = 0, o_wwO = 0, o_tp = 0;
+    size_t ts_off = 0, bl_off = 0;   // the group's t(x) sums (6 x 32 bytes per proof) and blinding factors (8 x 32): inside the wiped range
     size_t vec_end = 0, cnt_off = 0, desc_off = 0, jobs_off = 0, acc_off = 0, res_off = 0, ab_off = 0, total = 0;   // the arena
     size_t stage_bytes = 0, stage_res = 0, stage_ab = 0;   // the pinned staging: [descriptors | jobs], results, a / b
     void make(size_t N_, size_t cap_) {
@@ -31,8 +43,12 @@ struct PbLayout {
         if (nblk * 2 * cap > 256) nblk = std::max<size_t>(1, std::min<size_t>(1024, (units + 127) / 128));
         o_b = pb_align(N * 32); o_a2 = o_b + pb_align(N * 32); o_b2 = o_a2 + pb_align(N * 16); o_cG = o_b2 + pb_align(N * 16);
         o_cH = o_cG + pb_align(N * 32); o_sL = o_cH + pb_align(N * 32); o_sR = o_sL + pb_align((2 * N + 2) * 32);
-        o_part = o_sR + pb_align((2 * N + 2) * 32); per_vec = o_part + pb_align((gf + 1) * 64);
-        vec_end = per_vec * cap;
+        o_part = o_sR + pb_align((2 * N + 2) * 32);
+        o_waL = o_part + pb_align((gf + 1) * 64); o_waR = o_waL + pb_align(N * 32); o_waO = o_waR + pb_align(N * 32); o_tp = o_waO + pb_align(N * 32);
+        per_vec = o_tp + pb_align(gf * 6 * 32);
+        o_wsL = o_a2; o_wsR = o_sL; o_wwL = o_sL + N * 32; o_wwR = o_sL + 2 * N * 32; o_wwO = o_sL + 3 * N * 32;   // (a2 | b2: >= 32 N bytes, sL | sR: >= 128 N)
+        ts_off = per_vec * cap; bl_off = ts_off + pb_align(cap * 192);
+        vec_end = bl_off + cap * 256;
         cnt_off = vec_end; desc_off = cnt_off + pb_align(cap * 64);   // (counters: 64 bytes = 16 words per proof, DtRoundGeom)
         jobs_off = desc_off + cap * sizeof(DtRoundDesc);
         acc_off = pb_align(jobs_off + 2 * cap * sizeof(DtJob));
@@ -81,6 +97,13 @@ template <class S> static void pb_inv_many(const F4* in, size_t count, F4* out) 
     for (size_t i = count; i-- > 0;) { out[i] = S::mul(inv, pref[i]); inv = S::mul(inv, in[i]); }
 }
 
+static void pb_pool_ensure(bp_ctx* ctx, size_t B) {
+    if (!ctx->pool && B > 1) ctx->pool.reset(new host::HostPool(std::max(1u, ctx->tune_host_threads ? (unsigned)ctx->tune_host_threads : host::host_pool_threads()) - 1));
+}
+static void pb_on_pool(bp_ctx* ctx, size_t count, const std::function<void(size_t)>& fn) {
+    if (!ctx->pool || count <= 1) { for (size_t c = 0; c < count; c++) fn(c); return; }
+    ctx->pool->run(0, count, fn);
+}
 // the lg N rounds of every member's inner-product argument, then a and b.  On success the members' proofs are complete.
 template <class C> static int pb_run_group(bp_ctx* ctx, PbGroup<C>& g) {
     typedef typename C::Fr FrP;
@@ -109,12 +132,9 @@ template <class C> static int pb_run_group(bp_ctx* ctx, PbGroup<C>& g) {
     std::vector<A4> aff(2 * B);
     // the per-proof ticket counters start every group at zero (an aborted launch of an earlier call cannot leave one behind)
     HIPCHK(hipMemsetAsync(ar + L.cnt_off, 0, B * 64, st));
-    if (!ctx->pool && B > 1) ctx->pool.reset(new host::HostPool(std::max(1u, ctx->tune_host_threads ? (unsigned)ctx->tune_host_threads : host::host_pool_threads()) - 1));
+    pb_pool_ensure(ctx, B);
     const size_t chunk = 64, nchunks = (B + chunk - 1) / chunk;
-    auto on_pool = [&](const std::function<void(size_t)>& fn) {
-        if (!ctx->pool || nchunks == 1) { for (size_t c = 0; c < nchunks; c++) fn(c); return; }
-        ctx->pool->run(0, nchunks, fn);
-    };
+    auto on_pool = [&](const std::function<void(size_t)>& fn) { pb_on_pool(ctx, nchunks, fn); };
     auto fill_desc = [&](size_t j, bool fold) {
         DtRoundDesc& d = hd[j];
         if (fold) { memcpy(d.u, u[j].v, 32); memcpy(d.ui, ui[j].v, 32); } else { memset(d.u, 0, 32); memset(d.ui, 0, 32); }
@@ -186,6 +206,424 @@ template <class C> static int pb_run_group(bp_ctx* ctx, PbGroup<C>& g) {
     return BP_OK;
 }
 
+
+// ---- front groups ----------------------------------------------------------------------------------------------------------------
+static constexpr size_t PF_PHASE1_MAX = 16384;   // most members of a front group (3 table sums each: launches are split below 65536 rows)
+
+template <class C> struct PfMember {
+    size_t k = 0;                       // instance index in the call
+    bp_cs* s = nullptr;
+    host::ConstraintSystem<C>* cs = nullptr;
+    ProvePre<C>* pre = nullptr;
+    const HostCsc* csc = nullptr;
+    std::unique_ptr<HostCsc> csc_late;  // two-phase statements: indexed after the randomized phase
+    size_t n1 = 0, n = 0, N = 0;
+    A4 c1[3];                           // A_I1, A_O1, S1
+    F4 bl2[3], tb[5];                   // i_b2, o_b2, s_b2; the blinding factors of T_1, T_3 .. T_6
+    F4 y, z, ztab[32];
+    std::vector<F4> wV;
+    F4 w;
+    bool csc_ok = true;
+};
+
+static int pf_stage_ensure(bp_ctx* c, size_t bytes) {
+    if (c->h_pf_cap >= bytes) return BP_OK;
+    if (c->h_pf) HIPCHK(hipHostFree(c->h_pf));
+    c->h_pf = nullptr; c->h_pf_cap = 0;
+    HIPCHK(hipHostMalloc(&c->h_pf, bytes + bytes / 4 + 4096));
+    c->h_pf_cap = bytes + bytes / 4 + 4096;
+    return BP_OK;
+}
+static int pb_stage_ensure(bp_ctx* c, size_t bytes) {   // the rounds' staging (pb_run_group)
+    if (c->h_pb_cap >= bytes) return BP_OK;
+    if (c->h_pb) (void)hipHostFree(c->h_pb);
+    c->h_pb = nullptr; c->h_pb_cap = 0;
+    if (hipHostMalloc(&c->h_pb, bytes) != hipSuccess) { c->h_pb = nullptr; g_err = "prove_batch: pinned staging"; return BP_E_HIP; }
+    c->h_pb_cap = bytes;
+    return BP_OK;
+}
+// workgroups per table sum, as pb_run_group sizes a round's
+static size_t pf_nblk(size_t maxterms, size_t njobs) {
+    const size_t units = maxterms * DT_UNITS_PER_TERM;
+    size_t nblk = std::max<size_t>(1, (units + 63) / 64);
+    if (nblk * njobs > 256) nblk = std::max<size_t>(1, std::min<size_t>(1024, (units + 127) / 128));
+    return nblk;
+}
+// njobs table sums: k_dt_accum_multi (+ k_dt_finish), results at d_res[job]
+template <class C> static int pf_accum(bp_ctx* ctx, const DtJob* d_jobs, size_t njobs, size_t nblk, u32* d_acc, u32* d_res) {
+    ScopedK tk(ctx, BP_K_MSM_ACCUM);
+    for (size_t lo = 0; lo < njobs; lo += 32768) {
+        const size_t cnt = std::min<size_t>(32768, njobs - lo);
+        hipLaunchKernelGGL(k_dt_accum_multi<C>, dim3((u32)nblk, (u32)cnt), dim3(256), 0, ctx->stream, ctx->dt_tab.as<u32>(), d_jobs + lo,
+                           nblk == 1 ? d_res + lo * 24 : d_acc + lo * nblk * 24);
+        if (nblk > 1) hipLaunchKernelGGL(k_dt_finish<C>, dim3((u32)cnt), dim3(256), 0, ctx->stream, (const u32*)(d_acc + lo * nblk * 24), (u32)nblk, d_res + lo * 24);
+    }
+    HIPCHK(hipGetLastError());
+    ctx->dt_runs += njobs;
+    return BP_OK;
+}
+static void pf_points_in(const void* res, size_t count, J4* out) {
+    const u64* r = (const u64*)res;
+    for (size_t i = 0; i < count; i++) { const u64* P = r + 12 * i; memcpy(out[i].X.v, P, 32); memcpy(out[i].Y.v, P + 4, 32); memcpy(out[i].Z.v, P + 8, 32); }
+}
+
+// Phase 1 of a front group (equal n1): A_I1, A_O1, S1 of every member into its transcript
+template <class C> static int pf_phase1(bp_ctx* ctx, std::vector<PfMember<C>>& mem, StageTimes& tm) {
+    typedef typename C::Fr FrP;
+    typedef host::Fld<FrP> S;
+    typedef host::TP<C> TP;
+    const size_t B = mem.size(), n1 = mem[0].n1;
+    hipStream_t st = ctx->stream;
+    pb_pool_ensure(ctx, B);
+    std::vector<J4> pts(3 * B);
+    double t0 = now_s();
+    if (n1 == 0) {   // no multipliers in this phase (a k-shuffle's phase 1): single Pedersen terms on the host's tables, as r1cs_prove
+        host::PedersenGens<C> pc; pc.B = ctx->pc_B; pc.B_blinding = ctx->pc_Bb;
+        pb_on_pool(ctx, B, [&](size_t j) {
+            const ProvePre<C>& pre = *mem[j].pre;
+            pts[3 * j] = pc.commit_jac(S::zero(), pre.i_b1); pts[3 * j + 1] = pc.commit_jac(S::zero(), pre.o_b1); pts[3 * j + 2] = pc.commit_jac(S::zero(), pre.s_b1);
+        });
+    } else {
+        const size_t vb = pb_align(n1 * 32), p1 = 5 * vb, bl_off = p1 * B;             // the arena, for this phase: [B x 5 vectors | blinding factors]
+        const size_t nblk = pf_nblk(2 * n1 + 1, 3 * B);
+        const size_t s_bl = B * 5 * n1 * 32, s_jobs = s_bl + pb_align(B * 96), s_res = s_jobs + pb_align(3 * B * sizeof(DtJob)), s_end = s_res + 3 * B * 96;
+        const size_t a_acc = pb_align(3 * B * sizeof(DtJob)), a_res = a_acc + pb_align(3 * B * nblk * 96), a_end = a_res + 3 * B * 96;
+        BPCHK(ctx->pb_arena.ensure(bl_off + pb_align(B * 96)));
+        BPCHK(ctx->pf_aux.ensure(a_end));
+        BPCHK(pf_stage_ensure(ctx, s_end));
+        char* hs = (char*)ctx->h_pf;
+        char* ar = (char*)ctx->pb_arena.p;
+        char* ax = (char*)ctx->pf_aux.p;
+        DtJob* hj = (DtJob*)(hs + s_jobs);
+        pb_on_pool(ctx, B, [&](size_t j) {
+            const host::ConstraintSystem<C>& cs = *mem[j].cs;
+            const ProvePre<C>& pre = *mem[j].pre;
+            char* w = hs + j * 5 * n1 * 32;
+            const F4* src[5] = {cs.a_L.data(), cs.a_R.data(), cs.a_O.data(), pre.s_L.data(), pre.s_R.data()};
+            for (int v = 0; v < 5; v++) memcpy(w + (size_t)v * n1 * 32, src[v], n1 * 32);
+            const F4 bl[3] = {pre.i_b1, pre.o_b1, pre.s_b1};
+            memcpy(hs + s_bl + j * 96, bl, 96);
+            const u32* base = (const u32*)(ar + j * p1);
+            const u32* blp = (const u32*)(ar + bl_off + j * 96);
+            const u32* xs[3] = {base, base + 2 * vb / 4, base + 3 * vb / 4};
+            const u32* ys[3] = {base + vb / 4, nullptr, base + 4 * vb / 4};
+            for (int o = 0; o < 3; o++) {
+                DtJob& jb = hj[3 * j + o];
+                memset(&jb, 0, sizeof jb);
+                int ns = 0;
+                jb.seg[ns++] = DtSeg{xs[o], dt_base_G(ctx, 0), (u32)n1, 1, 0, 0};
+                if (ys[o]) jb.seg[ns++] = DtSeg{ys[o], dt_base_H(ctx, 0), (u32)n1, 1, 0, 0};
+                jb.seg[ns++] = DtSeg{blp + 8 * o, dt_base_pc(1), 1, 2, 0, 0};
+                jb.nseg = (u32)ns; jb.terms = (u32)(n1 * (ys[o] ? 2 : 1) + 1);
+            }
+        });
+        tm.upload += now_s() - t0; t0 = now_s();
+        PfGeom geo; memset(&geo, 0, sizeof geo);
+        geo.arena = ar; geo.per_proof = p1; geo.aL = 0; geo.aR = (u32)vb; geo.aO = (u32)(2 * vb); geo.sL = (u32)(3 * vb); geo.sR = (u32)(4 * vb);
+        hipLaunchKernelGGL(k_pf_import<FrP>, dim3((u32)((5 * n1 + 255) / 256), (u32)B), dim3(256), 0, st, (const u32*)hs, (const PfDesc*)nullptr, (u32)n1, geo);
+        HIPCHK(hipMemcpyAsync(ar + bl_off, hs + s_bl, B * 96, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ax, hs + s_jobs, 3 * B * sizeof(DtJob), hipMemcpyHostToDevice, st));
+        BPCHK((pf_accum<C>(ctx, (const DtJob*)ax, 3 * B, nblk, (u32*)(ax + a_acc), (u32*)(ax + a_res))));
+        HIPCHK(hipMemcpyAsync(hs + s_res, ax + a_res, 3 * B * 96, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemsetAsync(ar, 0, bl_off + pb_align(B * 96), st));   // secret hygiene: this phase's copy of the witness
+        HIPCHK(ctx_stream_wait(ctx));
+        HIPCHK(hipGetLastError());
+        ctx->pf_waits++;
+        pf_points_in(hs + s_res, 3 * B, pts.data());
+        memset(hs, 0, s_jobs);   // the staged witness and blinding factors
+    }
+    const size_t chunk = 64, nchunks = (B + chunk - 1) / chunk;
+    std::vector<A4> aff(3 * B);
+    pb_on_pool(ctx, nchunks, [&](size_t c) {
+        const size_t lo = c * chunk, hi = std::min(B, lo + chunk);
+        pb_to_aff<C>(pts.data() + 3 * lo, 3 * (hi - lo), aff.data() + 3 * lo);
+        for (size_t j = lo; j < hi; j++) {
+            host::Transcript& tr = *mem[j].cs->tr;
+            for (int o = 0; o < 3; o++) mem[j].c1[o] = aff[3 * j + o];
+            TP::append_point(tr, "A_I1", aff[3 * j]); TP::append_point(tr, "A_O1", aff[3 * j + 1]); TP::append_point(tr, "S1", aff[3 * j + 2]);
+        }
+    });
+    tm.commit_msm += now_s() - t0;
+    return BP_OK;
+}
+
+// A part of a front group after the randomized phases (equal padded size N): everything up to and including the lockstep rounds.
+// Members whose constraints cannot be indexed after all come back in `leavers` (nothing of theirs was touched).
+template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMember<C>*>& part, size_t N, std::vector<host::ProofData>& pfs, StageTimes& tm,
+                                                 std::vector<PfMember<C>*>& leavers, size_t& secret_stage_bytes) {
+    typedef typename C::Fr FrP;
+    typedef host::Fld<FrP> S;
+    typedef host::Grp<C> G;
+    typedef host::TP<C> TP;
+    hipStream_t st = ctx->stream;
+    pb_pool_ensure(ctx, part.size());
+    double t0 = now_s();
+    // the constraint index of the two-phase members
+    pb_on_pool(ctx, part.size(), [&](size_t j) {
+        PfMember<C>& m = *part[j];
+        const HostCsc* have = m.s->csc.get();
+        if (have && have->n == m.n && have->q == m.cs->num_constraints()) { m.csc = have; return; }
+        m.csc_late.reset(new HostCsc());
+        m.csc_ok = build_host_csc<C>(*m.cs, *m.csc_late);
+        m.csc = m.csc_late.get();
+    });
+    {
+        std::vector<PfMember<C>*> keep;
+        for (auto* m : part) (m->csc_ok ? keep : leavers).push_back(m);
+        part.swap(keep);
+    }
+    tm.flatten += now_s() - t0;
+    const size_t B = part.size();
+    if (!B) return BP_OK;
+    PbLayout L; L.make(N, B);
+    BPCHK(ctx->pb_arena.ensure(L.total));
+    BPCHK(pb_stage_ensure(ctx, L.stage_bytes));
+    // the aux buffer (32-bit words) and the pinned staging
+    std::vector<PfDesc> descs(B);
+    size_t nmax = 0, nzmax = 0, B2 = 0, in_words = 0;
+    const size_t a_jobs2 = pb_align(B * sizeof(PfDesc));
+    for (size_t j = 0; j < B; j++) if (part[j]->n > part[j]->n1) B2++;
+    const size_t a_jobsT = a_jobs2 + pb_align(3 * B2 * sizeof(DtJob)), a_data = a_jobsT + pb_align(5 * B * sizeof(DtJob));
+    size_t at = a_data;
+    for (size_t j = 0; j < B; j++) {
+        const PfMember<C>& m = *part[j];
+        PfDesc& d = descs[j];
+        memset(&d, 0, sizeof d);
+        const size_t nnz = m.csc->ment.size(), nc = m.csc->coefs.size();
+        d.n = (u32)m.n; d.n1 = (u32)m.n1; d.nzhi = (u32)((m.csc->q + 1) >> 8) + 1;
+        d.in_off = in_words; in_words += 5 * m.n * 8;
+        d.moff = (u32)(at / 4); at += pb_align((m.n + 1) * 4);
+        d.ment = (u32)(at / 4); at += pb_align(std::max<size_t>(nnz, 1) * 4);
+        d.mc = (u32)(at / 4); at += pb_align(std::max<size_t>(nnz, 1) * 4);
+        d.coefs = (u32)(at / 4); at += pb_align(nc * 32);
+        nmax = std::max(nmax, m.n); nzmax = std::max<size_t>(nzmax, d.nzhi);
+    }
+    const size_t a_u2 = at;                       // [B][96] scalars: z^(2^j) (32), y^(2^k) | y^-(2^k) (64)
+    const size_t a_xu = a_u2 + B * 96 * 32;
+    at = a_xu + pb_align(B * sizeof(PfXu));
+    for (size_t j = 0; j < B; j++) {
+        descs[j].ztab = (u32)((a_u2 + j * 96 * 32) / 4); descs[j].ypow = descs[j].ztab + 32 * 8;
+        descs[j].Z = (u32)(at / 4); at += (256 + (size_t)descs[j].nzhi) * 32;
+    }
+    const size_t nblk2 = B2 ? pf_nblk(2 * (nmax - part[0]->n1) + 1, 3 * B2) : 1;
+    const size_t a_acc2 = pb_align(at), a_res2 = a_acc2 + pb_align(3 * B2 * nblk2 * 96), a_resT = a_res2 + pb_align(3 * B2 * 96), a_end = a_resT + 5 * B * 96;
+    if (a_end >= ((size_t)1 << 34)) { g_err = "prove_batch: a front group's tables exceed 16 GB"; return BP_E_ARG; }
+    BPCHK(ctx->pf_aux.ensure(a_end));
+    const size_t s_bl = in_words * 4, s_u1 = s_bl + B * 256, s_u2 = s_u1 + a_u2, s_xu = s_u2 + B * 96 * 32, s_res2 = s_xu + pb_align(B * sizeof(PfXu)),
+                 s_ts = s_res2 + pb_align(3 * B2 * 96), s_resT = s_ts + pb_align(B * 192), s_end = s_resT + 5 * B * 96;
+    BPCHK(pf_stage_ensure(ctx, s_end));
+    secret_stage_bytes = s_u1;   // the witness and the blinding factors, in front of everything public
+    char* hs = (char*)ctx->h_pf;
+    char* ar = (char*)ctx->pb_arena.p;
+    char* ax = (char*)ctx->pf_aux.p;
+    PfGeom geo; memset(&geo, 0, sizeof geo);
+    geo.arena = ar; geo.per_proof = L.per_vec;
+    geo.aL = (u32)L.o_waL; geo.aR = (u32)L.o_waR; geo.aO = (u32)L.o_waO; geo.sL = (u32)L.o_wsL; geo.sR = (u32)L.o_wsR;
+    geo.wL = (u32)L.o_wwL; geo.wR = (u32)L.o_wwR; geo.wO = (u32)L.o_wwO; geo.tpart = (u32)L.o_tp;
+    geo.a = 0; geo.b = (u32)L.o_b; geo.cG = (u32)L.o_cG; geo.cH = (u32)L.o_cH;
+    geo.tsum = (u32*)(ar + L.ts_off);
+    auto wit = [&](size_t j, size_t off) { return (const u32*)(ar + j * L.per_vec + off); };
+    std::vector<size_t> job2_of(B, 0);
+    { size_t q = 0; for (size_t j = 0; j < B; j++) if (part[j]->n > part[j]->n1) job2_of[j] = q++; }
+    DtJob* hj2 = (DtJob*)(hs + s_u1 + a_jobs2);
+    DtJob* hjT = (DtJob*)(hs + s_u1 + a_jobsT);
+    // phase-2 blinding draws: the Keccak chain is sequential inside a proof and independent across proofs
+    t0 = now_s();
+    pb_on_pool(ctx, B, [&](size_t j) {
+        PfMember<C>& m = *part[j];
+        ProvePre<C>& pre = *m.pre;
+        host::TranscriptRng& rng = *pre.rng;
+        const size_t n = m.n, n1 = m.n1;
+        for (auto& b : m.bl2) b = S::zero();
+        const bool has2 = n > n1;
+        if (has2) { m.bl2[0] = host::rand_fe<FrP>(rng); m.bl2[1] = host::rand_fe<FrP>(rng); m.bl2[2] = host::rand_fe<FrP>(rng); }
+        pre.s_L.resize(n); pre.s_R.resize(n);
+        for (size_t i = n1; i < n; i++) pre.s_L[i] = host::rand_fe<FrP>(rng);
+        for (size_t i = n1; i < n; i++) pre.s_R[i] = host::rand_fe<FrP>(rng);
+        for (auto& b : m.tb) b = host::rand_fe<FrP>(rng);   // T_1, T_3 .. T_6: the next draws whatever t(x) turns out to be (r1cs_prove)
+    });
+    tm.rng += now_s() - t0; t0 = now_s();
+    // staging of the witness, the descriptors, the jobs of both commitment stages, the constraint index and its coefficients
+    pb_on_pool(ctx, B, [&](size_t j) {
+        PfMember<C>& m = *part[j];
+        ProvePre<C>& pre = *m.pre;
+        const size_t n = m.n, n1 = m.n1;
+        const bool has2 = n > n1;
+        char* w = hs + descs[j].in_off * 4;
+        const F4* src[5] = {m.cs->a_L.data(), m.cs->a_R.data(), m.cs->a_O.data(), pre.s_L.data(), pre.s_R.data()};
+        for (int v = 0; v < 5; v++) memcpy(w + (size_t)v * n * 32, src[v], n * 32);
+        F4 bl[8] = {m.bl2[0], m.bl2[1], m.bl2[2], m.tb[0], m.tb[1], m.tb[2], m.tb[3], m.tb[4]};
+        memcpy(hs + s_bl + j * 256, bl, 256);
+        const u32* blp = (const u32*)(ar + L.bl_off + j * 256);
+        if (has2) {
+            const size_t n2 = n - n1;
+            const u32* xs[3] = {wit(j, L.o_waL) + n1 * 8, wit(j, L.o_waO) + n1 * 8, wit(j, L.o_wsL) + n1 * 8};
+            const u32* ys[3] = {wit(j, L.o_waR) + n1 * 8, nullptr, wit(j, L.o_wsR) + n1 * 8};
+            for (int o = 0; o < 3; o++) {
+                DtJob& jb = hj2[3 * job2_of[j] + o];
+                memset(&jb, 0, sizeof jb);
+                int ns = 0;
+                jb.seg[ns++] = DtSeg{xs[o], dt_base_G(ctx, n1), (u32)n2, 1, 0, 0};
+                if (ys[o]) jb.seg[ns++] = DtSeg{ys[o], dt_base_H(ctx, n1), (u32)n2, 1, 0, 0};
+                jb.seg[ns++] = DtSeg{blp + 8 * o, dt_base_pc(1), 1, 2, 0, 0};
+                jb.nseg = (u32)ns; jb.terms = (u32)(n2 * (ys[o] ? 2 : 1) + 1);
+            }
+        }
+        const int slot[5] = {0, 2, 3, 4, 5};
+        for (int o = 0; o < 5; o++) {   // T_i = t_i * B + blinding_i * B_blinding, t_i read where the t(x) kernels leave it
+            DtJob& jb = hjT[5 * j + o];
+            memset(&jb, 0, sizeof jb);
+            jb.nseg = 2; jb.terms = 2;
+            jb.seg[0] = DtSeg{geo.tsum + (j * 6 + slot[o]) * 8, dt_base_pc(0), 1, 2, 0, 0};
+            jb.seg[1] = DtSeg{blp + 8 * (3 + o), dt_base_pc(1), 1, 2, 0, 0};
+        }
+        char* u1 = hs + s_u1;
+        memcpy(u1 + j * sizeof(PfDesc), &descs[j], sizeof(PfDesc));
+        const HostCsc& cc = *m.csc;
+        memcpy(u1 + (size_t)descs[j].moff * 4, cc.moff.data(), (n + 1) * 4);
+        if (!cc.ment.empty()) { memcpy(u1 + (size_t)descs[j].ment * 4, cc.ment.data(), cc.ment.size() * 4); memcpy(u1 + (size_t)descs[j].mc * 4, cc.mc.data(), cc.mc.size() * 4); }
+        F4* co = (F4*)(u1 + (size_t)descs[j].coefs * 4);
+        for (size_t i = 0; i < cc.coefs.size(); i++) co[i] = to_resident<FrP>(cc.coefs[i]);
+    });
+    tm.upload += now_s() - t0; t0 = now_s();
+    HIPCHK(hipMemcpyAsync(ax, hs + s_u1, a_u2, hipMemcpyHostToDevice, st));   // descriptors, jobs, constraint indices, coefficients: one copy
+    HIPCHK(hipMemcpyAsync(ar + L.bl_off, hs + s_bl, B * 256, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_pf_import<FrP>, dim3((u32)((5 * nmax + 255) / 256), (u32)B), dim3(256), 0, st, (const u32*)hs, (const PfDesc*)ax, 0u, geo);
+    HIPCHK(hipGetLastError());
+    std::vector<A4> aff2(3 * B2);
+    if (B2) {
+        BPCHK((pf_accum<C>(ctx, (const DtJob*)(ax + a_jobs2), 3 * B2, nblk2, (u32*)(ax + a_acc2), (u32*)(ax + a_res2))));
+        HIPCHK(hipMemcpyAsync(hs + s_res2, ax + a_res2, 3 * B2 * 96, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx_stream_wait(ctx));
+        HIPCHK(hipGetLastError());
+        ctx->pf_waits++;
+    }
+    tm.commit_msm += now_s() - t0; t0 = now_s();
+    // A_I2, A_O2, S2 -> y, z; the power tables; wV
+    const size_t chunk = 64, nchunks = (B + chunk - 1) / chunk;
+    std::vector<J4> pts2(3 * B2);
+    if (B2) pf_points_in(hs + s_res2, 3 * B2, pts2.data());
+    {   // (one inversion per chunk of the phase-2 members)
+        const size_t nc2 = (B2 + chunk - 1) / chunk;
+        pb_on_pool(ctx, nc2, [&](size_t c) { const size_t lo = c * chunk, hi = std::min(B2, lo + chunk); pb_to_aff<C>(pts2.data() + 3 * lo, 3 * (hi - lo), aff2.data() + 3 * lo); });
+    }
+    pb_on_pool(ctx, B, [&](size_t j) {
+        PfMember<C>& m = *part[j];
+        host::Transcript& tr = *m.cs->tr;
+        host::ProofData& pf = pfs[m.k];
+        const bool has2 = m.n > m.n1;
+        pf.A_I1 = m.c1[0]; pf.A_O1 = m.c1[1]; pf.S1 = m.c1[2];
+        pf.A_I2 = has2 ? aff2[3 * job2_of[j]] : G::aff_inf(); pf.A_O2 = has2 ? aff2[3 * job2_of[j] + 1] : G::aff_inf(); pf.S2 = has2 ? aff2[3 * job2_of[j] + 2] : G::aff_inf();
+        TP::append_point(tr, "A_I2", pf.A_I2); TP::append_point(tr, "A_O2", pf.A_O2); TP::append_point(tr, "S2", pf.S2);
+        m.y = TP::challenge_scalar(tr, "y"); m.z = TP::challenge_scalar(tr, "z");
+        F4* u2 = (F4*)(hs + s_u2) + j * 96;
+        { F4 c = m.z; for (int i = 0; i < 32; i++) { m.ztab[i] = c; u2[i] = to_resident<FrP>(c); c = S::sqr(c); } }
+        { F4 c = m.y, ci = S::inv(m.y); for (int i = 0; i < 32; i++) { u2[32 + i] = to_resident<FrP>(c); u2[64 + i] = to_resident<FrP>(ci); c = S::sqr(c); ci = S::sqr(ci); } }
+        // wV on the host: the few terms on committed variables, z^(q+1) carried from term to term (as r1cs_prove)
+        m.wV.assign(m.cs->v.size(), S::zero());
+        auto pow_z = [&](u32 e) { F4 r = S::one(); for (u32 i = 0; e; e >>= 1, i++) if (e & 1) r = S::mul(r, m.ztab[i]); return r; };
+        F4 zq = S::one(), zstep = S::one();
+        u32 cur = 0, last_d = 0;
+        for (const auto& t2 : m.csc->vterms) {
+            const u32 q1 = t2.q + 1;
+            if (cur == 0) zq = pow_z(q1);
+            else if (q1 != cur) { const u32 d = q1 - cur; if (d != last_d) { zstep = pow_z(d); last_d = d; } zq = S::mul(zq, zstep); }
+            cur = q1;
+            m.wV[t2.j] = S::sub(m.wV[t2.j], S::mul(zq, t2.c));
+        }
+    });
+    HIPCHK(hipMemcpyAsync(ax + a_u2, hs + s_u2, B * 96 * 32, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_r1cs_ztables_multi<C>, dim3((u32)((std::max<size_t>(256, nzmax) + 255) / 256), (u32)B), dim3(256), 0, st, (u32*)ax, (const PfDesc*)ax);
+    hipLaunchKernelGGL(k_r1cs_flatten_multi<C>, dim3((u32)((nmax + 255) / 256), (u32)B), dim3(256), 0, st, (const u32*)ax, (const PfDesc*)ax, geo);
+    HIPCHK(hipGetLastError());
+    tm.flatten += now_s() - t0; t0 = now_s();
+    {
+        const u32 gb = (u32)((nmax + 255) / 256);
+        ScopedK tk(ctx, BP_K_R1CS_POLY);
+        hipLaunchKernelGGL(k_r1cs_poly_t_multi<C>, dim3(gb, (u32)B), dim3(256), 0, st, (const u32*)ax, (const PfDesc*)ax, geo);
+        if (gb > 1) hipLaunchKernelGGL(k_r1cs_sum_multi<C>, dim3((u32)B), dim3(256), 0, st, geo, gb);
+    }
+    HIPCHK(hipGetLastError());
+    BPCHK((pf_accum<C>(ctx, (const DtJob*)(ax + a_jobsT), 5 * B, 1, (u32*)nullptr, (u32*)(ax + a_resT))));
+    HIPCHK(hipMemcpyAsync(hs + s_ts, ar + L.ts_off, B * 192, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hs + s_resT, ax + a_resT, 5 * B * 96, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx_stream_wait(ctx));
+    HIPCHK(hipGetLastError());
+    ctx->pf_waits++;
+    // T appends, u, x, t_x, t_x_blinding, e_blinding, w
+    std::vector<J4> ptsT(5 * B);
+    std::vector<A4> affT(5 * B);
+    pf_points_in(hs + s_resT, 5 * B, ptsT.data());
+    PfXu* hxu = (PfXu*)(hs + s_xu);
+    pb_on_pool(ctx, nchunks, [&](size_t c) {
+        const size_t lo = c * chunk, hi = std::min(B, lo + chunk);
+        pb_to_aff<C>(ptsT.data() + 5 * lo, 5 * (hi - lo), affT.data() + 5 * lo);
+        for (size_t j = lo; j < hi; j++) {
+            PfMember<C>& m = *part[j];
+            host::Transcript& tr = *m.cs->tr;
+            host::ProofData& pf = pfs[m.k];
+            const ProvePre<C>& pre = *m.pre;
+            F4 tco[6];
+            memcpy(tco, hs + s_ts + j * 192, 192);
+            const A4* Tc = affT.data() + 5 * j;
+            pf.T_1 = Tc[0]; pf.T_3 = Tc[1]; pf.T_4 = Tc[2]; pf.T_5 = Tc[3]; pf.T_6 = Tc[4];
+            TP::append_point(tr, "T_1", Tc[0]); TP::append_point(tr, "T_3", Tc[1]); TP::append_point(tr, "T_4", Tc[2]); TP::append_point(tr, "T_5", Tc[3]);
+            TP::append_point(tr, "T_6", Tc[4]);
+            const F4 u = TP::challenge_scalar(tr, "u"), x = TP::challenge_scalar(tr, "x");
+            F4 t2b = S::zero();
+            for (size_t i = 0; i < m.wV.size(); i++) t2b = S::add(t2b, S::mul(m.cs->v_blinding[i], m.wV[i]));
+            auto poly6 = [&](const F4& c1, const F4& c2, const F4& c3, const F4& c4, const F4& c5, const F4& c6) {  // util.rs:107-109
+                F4 acc = S::add(S::mul(x, c6), c5);
+                acc = S::add(S::mul(acc, x), c4); acc = S::add(S::mul(acc, x), c3); acc = S::add(S::mul(acc, x), c2); acc = S::add(S::mul(acc, x), c1);
+                return S::mul(acc, x);
+            };
+            pf.t_x = poly6(tco[0], tco[1], tco[2], tco[3], tco[4], tco[5]);
+            pf.t_x_blinding = poly6(m.tb[0], t2b, m.tb[1], m.tb[2], m.tb[3], m.tb[4]);
+            const F4 i_b = S::add(pre.i_b1, S::mul(u, m.bl2[0])), o_b = S::add(pre.o_b1, S::mul(u, m.bl2[1])), s_b = S::add(pre.s_b1, S::mul(u, m.bl2[2]));
+            pf.e_blinding = S::mul(x, S::add(i_b, S::mul(x, S::add(o_b, S::mul(x, s_b)))));
+            TP::append_scalar(tr, "t_x", pf.t_x); TP::append_scalar(tr, "t_x_blinding", pf.t_x_blinding); TP::append_scalar(tr, "e_blinding", pf.e_blinding);
+            m.w = TP::challenge_scalar(tr, "w");
+            memcpy(hxu[j].x, x.v, 32); memcpy(hxu[j].u, u.v, 32);
+            TP::innerproduct_domain_sep(tr, N);
+            pf.L_vec.resize(pb_lg(N)); pf.R_vec.resize(pb_lg(N));
+        }
+    });
+    HIPCHK(hipMemcpyAsync(ax + a_xu, hs + s_xu, B * sizeof(PfXu), hipMemcpyHostToDevice, st));
+    {
+        ScopedK tk(ctx, BP_K_R1CS_POLY);
+        hipLaunchKernelGGL(k_r1cs_poly_eval_multi<C>, dim3((u32)((N + 255) / 256), (u32)B), dim3(256), 0, st, (const u32*)ax, (const PfDesc*)ax, (const PfXu*)(ax + a_xu), geo, (u32)N);
+    }
+    HIPCHK(hipGetLastError());
+    tm.poly += now_s() - t0;
+    PbGroup<C> g;
+    g.lay = L; g.open = true;
+    for (size_t j = 0; j < B; j++) g.mem.push_back(PbMember<C>{part[j]->k, part[j]->cs->tr, &pfs[part[j]->k], part[j]->w});
+    BPCHK(pb_run_group<C>(ctx, g));
+    ctx->pf_instances += B; ctx->pf_groups++;
+    return BP_OK;
+}
+// ... and the secret hygiene of a part on EVERY way out: the host copies of the blinding vectors (r1cs_prove's closing wipe), the
+// witness and blinding factors in the pinned staging, and — when a stage failed before the group's closing memset — the arena
+template <class C> static int pf_run_part(bp_ctx* ctx, std::vector<PfMember<C>*>& part, size_t N, std::vector<host::ProofData>& pfs, StageTimes& tm,
+                                          std::vector<PfMember<C>*>& leavers) {
+    typedef host::Fld<typename C::Fr> S;
+    size_t secret_stage_bytes = 0;
+    const std::vector<PfMember<C>*> all = part;
+    const int rc = pf_run_part_stages<C>(ctx, part, N, pfs, tm, leavers, secret_stage_bytes);
+    for (auto* m : all) {
+        if (std::find(leavers.begin(), leavers.end(), m) != leavers.end()) continue;   // (a leaver's vectors are r1cs_prove's to wipe)
+        for (auto& x : m->pre->s_L) x = S::zero();
+        for (auto& x : m->pre->s_R) x = S::zero();
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);   // (nothing reads the staging any more)
+        if (ctx->pb_arena.p) (void)hipMemsetAsync(ctx->pb_arena.p, 0, ctx->pb_arena.cap, ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    if (ctx->h_pf && secret_stage_bytes) memset(ctx->h_pf, 0, std::min(secret_stage_bytes, ctx->h_pf_cap));
+    return rc;
+}
+
 template <class C>
 static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens, int* status, double* timing) {
     const double t_begin = now_s();
@@ -218,8 +656,8 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
     std::vector<size_t> order(count);
     for (size_t k = 0; k < count; k++) order[k] = k;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return hs[a]->cs<C>()->a_L.size() < hs[b]->cs<C>()->a_L.size(); });
-    for (size_t oi = 0; oi < count; oi++) {
-        const size_t k = order[oi];
+    // one instance through r1cs_prove (resume1: it left a front group after its randomized phase); `left`: instances still to come
+    auto prove_single = [&](size_t k, size_t left, const A4* resume1) {
         bp_cs* s = hs[k];
         auto* pre = C::ID == 0 ? (ProvePre<C>*)&s->pre0 : (ProvePre<C>*)&s->pre1;
         if (!s->csc_tried) {
@@ -232,15 +670,10 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
             if (grp.open && (grp.lay.N != N || grp.mem.size() >= grp.lay.cap)) flush();
             if (!grp.open) {
                 size_t cap = cap_knob ? cap_knob : std::max<size_t>(1, std::min(PB_GROUP_MAX, PB_ARENA_BUDGET / PbLayout::per_proof(N)));
-                cap = std::max<size_t>(1, std::min(cap, count - oi));
+                cap = std::max<size_t>(1, std::min(cap, left));
                 grp.lay.make(N, cap);
                 if (c->pb_arena.ensure(grp.lay.total)) return false;
-                if (c->h_pb_cap < grp.lay.stage_bytes) {
-                    if (c->h_pb) (void)hipHostFree(c->h_pb);
-                    c->h_pb = nullptr; c->h_pb_cap = 0;
-                    if (hipHostMalloc(&c->h_pb, grp.lay.stage_bytes) != hipSuccess) { c->h_pb = nullptr; return false; }
-                    c->h_pb_cap = grp.lay.stage_bytes;
-                }
+                if (pb_stage_ensure(c, grp.lay.stage_bytes)) return false;
                 grp.open = true;
             }
             const size_t j = grp.mem.size();
@@ -249,7 +682,7 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
             return true;
         };
         s->consumed = true; s->running = true;
-        const int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pfs[k], tm, pre, s->csc.get(), &defer);
+        const int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pfs[k], tm, pre, s->csc.get(), &defer, resume1);
         s->running = false;
         if (defer.taken) {
             grp.mem.push_back(PbMember<C>{k, s->cs<C>()->tr, &pfs[k], defer.w});
@@ -260,6 +693,79 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
             st[k] = rc;
             if (!rc) c->pb_single++;
         }
+    };
+    // does instance k run its front stages in a group?  (what can be known before its randomized phase)
+    // the tables are built when the first candidate appears (as r1cs_prove builds them for the first small statement); a failure there
+    // means "does not qualify": the instance takes the single route and reports the error as its own status
+    const size_t reach_max = c->tune_pb_front && c->shard_world <= 1 && c->tune_direct_max >= 2 ? std::min(c->gens_cap, c->tune_direct_max) : 0;
+    size_t reach = 0;
+    bool dt_tried = false;
+    auto qualifies = [&](size_t k) -> bool {
+        bp_cs* s = hs[k];
+        const host::ConstraintSystem<C>& cs = *s->cs<C>();
+        if (reach_max < 2 || cs.base || cs.a_L.size() > reach_max) return false;
+        if (cs.deferred.empty() && (cs.a_L.size() < 2 || host::next_pow2(cs.a_L.size()) > reach_max)) return false;
+        if (!dt_tried) {
+            dt_tried = true;
+            bool ready = false;
+            if (dt_ensure<C>(c, 2, ready) == BP_OK && ready) reach = std::min(c->dt_cap, c->tune_direct_max);   // (built for min(generators, BP_TUNE_DIRECT_MAX))
+        }
+        if (!reach || cs.a_L.size() > reach) return false;
+        if (!cs.deferred.empty()) return true;   // two-phase: its padded size and its constraint index exist after the randomized phase
+        const size_t N = host::next_pow2(cs.a_L.size());
+        if (cs.a_L.size() == 0 || N < 2 || N > reach) return false;
+        if (!s->csc_tried) {
+            s->csc.reset(new HostCsc());
+            if (!build_host_csc<C>(cs, *s->csc)) s->csc.reset();
+            s->csc_tried = true;
+        }
+        return s->csc && s->csc->n == cs.a_L.size() && s->csc->q == cs.num_constraints();
+    };
+    for (size_t oi = 0; oi < count;) {
+        if (!qualifies(order[oi])) { prove_single(order[oi], count - oi, nullptr); oi++; continue; }
+        // a front group: the qualifying instances that follow with the same phase-1 multiplier count
+        const size_t n1 = hs[order[oi]]->cs<C>()->a_L.size();
+        size_t cap1 = cap_knob ? cap_knob : std::min(PF_PHASE1_MAX, std::max<size_t>(1, PB_ARENA_BUDGET / (5 * pb_align(std::max<size_t>(n1, 1) * 32) + 256)));
+        std::vector<PfMember<C>> mem;
+        while (oi < count && mem.size() < cap1 && hs[order[oi]]->cs<C>()->a_L.size() == n1 && qualifies(order[oi])) {
+            PfMember<C> m;
+            bp_cs* sk = hs[order[oi]];
+            m.k = order[oi]; m.s = sk; m.cs = sk->cs<C>(); m.pre = C::ID == 0 ? (ProvePre<C>*)&sk->pre0 : (ProvePre<C>*)&sk->pre1; m.n1 = n1;
+            sk->consumed = true; sk->running = true;
+            mem.push_back(std::move(m));
+            oi++;
+        }
+        flush();   // (the arena is the front group's from here)
+        int rc = pf_phase1<C>(c, mem, tm);
+        // randomized phases, on the calling thread; a member that fails is dropped with its transcript where bp_prover_prove leaves it
+        std::map<size_t, std::vector<PfMember<C>*>> parts;
+        std::vector<PfMember<C>*> leavers;
+        for (auto& m : mem) {
+            if (rc) { st[m.k] = rc; continue; }
+            const int r = m.cs->run_randomized();
+            if (r) { st[m.k] = r; continue; }
+            m.n = m.cs->a_L.size(); m.N = host::next_pow2(m.n);
+            if (c->gens_cap < m.N) { st[m.k] = BP_E_GENS_LENGTH; continue; }
+            if (m.n == 0 || m.N < 2 || m.N > reach || m.cs->base) { leavers.push_back(&m); continue; }
+            parts[m.N].push_back(&m);
+        }
+        for (auto& pr : parts) {
+            const size_t N = pr.first;
+            const size_t capN = cap_knob ? cap_knob : std::max<size_t>(1, std::min(PB_GROUP_MAX, PB_ARENA_BUDGET / PbLayout::per_proof(N)));
+            for (size_t lo = 0; lo < pr.second.size(); lo += capN) {
+                std::vector<PfMember<C>*> part(pr.second.begin() + lo, pr.second.begin() + std::min(pr.second.size(), lo + capN));
+                const std::vector<PfMember<C>*> all = part;
+                const int r = pf_run_part<C>(c, part, N, pfs, tm, leavers);
+                for (auto* m : all) {
+                    if (std::find(leavers.begin(), leavers.end(), m) != leavers.end()) continue;
+                    grouped[m->k] = 1;
+                    if (r) st[m->k] = r;
+                }
+            }
+        }
+        for (auto& m : mem) m.s->running = false;
+        // members that stopped qualifying: the rest of r1cs_prove on the single-proof workspaces
+        for (auto* m : leavers) prove_single(m->k, 1, m->c1);
     }
     flush();
     // 3. serialisation, per-instance status
@@ -356,5 +862,12 @@ int bp_ctx_prove_batch_stats(bp_ctx* c, uint64_t* lockstep_instances, uint64_t* 
     if (lockstep_instances) *lockstep_instances = c->pb_lockstep;
     if (single_instances) *single_instances = c->pb_single;
     if (groups) *groups = c->pb_groups;
+    return BP_OK;
+}
+int bp_ctx_prove_batch_front_stats(bp_ctx* c, uint64_t* front_instances, uint64_t* front_groups, uint64_t* front_waits) {
+    if (!c) return BP_E_ARG;
+    if (front_instances) *front_instances = c->pf_instances;
+    if (front_groups) *front_groups = c->pf_groups;
+    if (front_waits) *front_waits = c->pf_waits;
     return BP_OK;
 }

@@ -21,13 +21,13 @@ template <class F> __device__ __forceinline__ Fe pow_from_table(const u32* __res
 
 // ypow: 64 x 8 words: y^(2^k) for k < 32, then y^-(2^k) for k < 32.
 // partials: gridDim.x x 6 x 8 words.
-template <class C> __global__ void __launch_bounds__(256)
-k_r1cs_poly_t(const u32* __restrict__ aL, const u32* __restrict__ aR, const u32* __restrict__ aO, const u32* __restrict__ sL,
-              const u32* __restrict__ sR, const u32* __restrict__ wL, const u32* __restrict__ wR, const u32* __restrict__ wO,
-              const u32* __restrict__ ypow, u32 n, u32* __restrict__ partials, u32* __restrict__ final_ark = nullptr /* one workgroup: the six sums
-              in ark words, as k_r1cs_sum would leave them (a small statement saves that launch) */) {
+// (the body as a device function: k_r1cs_poly_t_multi, small_batch_front.cuh, runs it per proof of a group; `block_partials`: this
+// workgroup's six slots)
+template <class C> __device__ __forceinline__ void
+r1cs_poly_t_body(const u32* __restrict__ aL, const u32* __restrict__ aR, const u32* __restrict__ aO, const u32* __restrict__ sL,
+                 const u32* __restrict__ sR, const u32* __restrict__ wL, const u32* __restrict__ wR, const u32* __restrict__ wO,
+                 const u32* __restrict__ ypow, u32 n, u32* __restrict__ block_partials, u32* __restrict__ final_ark, u32* __restrict__ sh) {
     typedef typename C::Fr F;
-    __shared__ u32 sh[9 * 256];
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     Fe t[6];
 #pragma unroll
@@ -52,14 +52,21 @@ k_r1cs_poly_t(const u32* __restrict__ aL, const u32* __restrict__ aR, const u32*
         Fe s = block_sum_fe<F>(fe_wred<F>(t[k]), sh);
         if (threadIdx.x == 0) {
             if (final_ark) { u32 w[8]; fe_store_ark<F>(w, s); store_words8(final_ark + (size_t)k * 8, w); }
-            else store_fe_dev<F>(partials + ((size_t)blockIdx.x * 6 + k) * 8, s);
+            else store_fe_dev<F>(block_partials + (size_t)k * 8, s);
         }
     }
 }
-// out: cnt x 8 words, ark Montgomery layout (read by the host)
-template <class C> __global__ void __launch_bounds__(256) k_r1cs_sum(const u32* __restrict__ partials, u32 nparts, u32 cnt, u32* __restrict__ out) {
-    typedef typename C::Fr F;
+template <class C> __global__ void __launch_bounds__(256)
+k_r1cs_poly_t(const u32* __restrict__ aL, const u32* __restrict__ aR, const u32* __restrict__ aO, const u32* __restrict__ sL,
+              const u32* __restrict__ sR, const u32* __restrict__ wL, const u32* __restrict__ wR, const u32* __restrict__ wO,
+              const u32* __restrict__ ypow, u32 n, u32* __restrict__ partials, u32* __restrict__ final_ark = nullptr /* one workgroup: the six sums
+              in ark words, as k_r1cs_sum would leave them (a small statement saves that launch) */) {
     __shared__ u32 sh[9 * 256];
+    r1cs_poly_t_body<C>(aL, aR, aO, sL, sR, wL, wR, wO, ypow, n, partials + (size_t)blockIdx.x * 6 * 8, final_ark, sh);
+}
+// out: cnt x 8 words, ark Montgomery layout (read by the host)
+template <class C> __device__ __forceinline__ void r1cs_sum_body(const u32* __restrict__ partials, u32 nparts, u32 cnt, u32* __restrict__ out, u32* __restrict__ sh) {
+    typedef typename C::Fr F;
     for (u32 k = 0; k < cnt; k++) {
         Fe s = fe_zero<F>();
         for (u32 j = threadIdx.x; j < nparts; j += 256) s = fe_addr<F>(s, load_fe_dev<F>(partials + ((size_t)j * cnt + k) * 8));
@@ -71,17 +78,21 @@ template <class C> __global__ void __launch_bounds__(256) k_r1cs_sum(const u32* 
         }
     }
 }
+template <class C> __global__ void __launch_bounds__(256) k_r1cs_sum(const u32* __restrict__ partials, u32 nparts, u32 cnt, u32* __restrict__ out) {
+    __shared__ u32 sh[9 * 256];
+    r1cs_sum_body<C>(partials, nparts, cnt, out, sh);
+}
 
 // x, u: ark Montgomery words.  Writes l_vec, r_vec, Gf, Hf for i < N (padded length).
-template <class C> __global__ void __launch_bounds__(256)
-k_r1cs_poly_eval(const u32* __restrict__ aL, const u32* __restrict__ aR, const u32* __restrict__ aO, const u32* __restrict__ sL,
-                 const u32* __restrict__ sR, const u32* __restrict__ wL, const u32* __restrict__ wR, const u32* __restrict__ wO,
-                 const u32* __restrict__ ypow, u32 n, u32 n1, u32 N, Words8 xw, Words8 uw, u32* __restrict__ lvec, u32* __restrict__ rvec,
-                 u32* __restrict__ Gf, u32* __restrict__ Hf) {
+template <class C> __device__ __forceinline__ void
+r1cs_poly_eval_body(const u32* __restrict__ aL, const u32* __restrict__ aR, const u32* __restrict__ aO, const u32* __restrict__ sL,
+                    const u32* __restrict__ sR, const u32* __restrict__ wL, const u32* __restrict__ wR, const u32* __restrict__ wO,
+                    const u32* __restrict__ ypow, u32 n, u32 n1, u32 N, const u32 (&xw)[8], const u32 (&uw)[8], u32* __restrict__ lvec, u32* __restrict__ rvec,
+                    u32* __restrict__ Gf, u32* __restrict__ Hf) {
     typedef typename C::Fr F;
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const Fe x = fe_load_ark<F>(xw.w);
+    const Fe x = fe_load_ark<F>(xw);
     const Fe yi = pow_from_table<F>(ypow, i), yni = pow_from_table<F>(ypow + 32 * 8, i);
     const size_t o = (size_t)i * 8;
     Fe lv, rv;
@@ -104,9 +115,16 @@ k_r1cs_poly_eval(const u32* __restrict__ aL, const u32* __restrict__ aR, const u
     }
     store_fe_dev<F>(lvec + o, lv);
     store_fe_dev<F>(rvec + o, rv);
-    const Fe gf = i < n1 ? fe_one<F>() : fe_load_ark<F>(uw.w);
+    const Fe gf = i < n1 ? fe_one<F>() : fe_load_ark<F>(uw);
     store_fe_dev<F>(Gf + o, gf);
     store_fe_dev<F>(Hf + o, fe_mul<F>(yni, gf));
+}
+template <class C> __global__ void __launch_bounds__(256)
+k_r1cs_poly_eval(const u32* __restrict__ aL, const u32* __restrict__ aR, const u32* __restrict__ aO, const u32* __restrict__ sL,
+                 const u32* __restrict__ sR, const u32* __restrict__ wL, const u32* __restrict__ wR, const u32* __restrict__ wO,
+                 const u32* __restrict__ ypow, u32 n, u32 n1, u32 N, Words8 xw, Words8 uw, u32* __restrict__ lvec, u32* __restrict__ rvec,
+                 u32* __restrict__ Gf, u32* __restrict__ Hf) {
+    r1cs_poly_eval_body<C>(aL, aR, aO, sL, sR, wL, wR, wO, ypow, n, n1, N, xw.w, uw.w, lvec, rvec, Gf, Hf);
 }
 
 // Verifier scalars.  chal: u_sq[k] (resident words, creation order); consts: resident words
@@ -482,16 +500,19 @@ k_vfy_tail_scale(u32* __restrict__ tails, const u32* __restrict__ alphas, const 
 // multiplier index i: the entries of columns i of W_L, W_R, W_O in constraint order); after the challenge z is known one launch
 // evaluates w_L, w_R, w_O = z^(q+1)-weighted column sums on the GPU instead of the host's pass over all terms + 3 uploads.
 // Z: 256 + nzhi resident scalars, z^e = Z[e & 255] * Z[256 + (e >> 8)].
-template <class C> __global__ void __launch_bounds__(256)
-k_r1cs_ztables(const u32* __restrict__ ztab /* z^(2^j), 32 resident scalars */, u32 nzhi, u32* __restrict__ Z) {
+template <class C> __device__ __forceinline__ void r1cs_ztables_body(const u32* __restrict__ ztab, u32 nzhi, u32* __restrict__ Z) {
     typedef typename C::Fr F;
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < 256) store_fe_dev<F>(Z + (size_t)t * 8, pow_table<F>(ztab, t));
     if (t < nzhi) store_fe_dev<F>(Z + (size_t)(256 + t) * 8, pow_table<F>(ztab, t << 8));
 }
 template <class C> __global__ void __launch_bounds__(256)
-k_r1cs_flatten(const u32* __restrict__ m_off, const u32* __restrict__ m_ent, const u32* __restrict__ m_c, const u32* __restrict__ coefs,
-               const u32* __restrict__ Z, u32 n, u32* __restrict__ wL_out, u32* __restrict__ wR_out, u32* __restrict__ wO_out) {
+k_r1cs_ztables(const u32* __restrict__ ztab /* z^(2^j), 32 resident scalars */, u32 nzhi, u32* __restrict__ Z) {
+    r1cs_ztables_body<C>(ztab, nzhi, Z);
+}
+template <class C> __device__ __forceinline__ void
+r1cs_flatten_body(const u32* __restrict__ m_off, const u32* __restrict__ m_ent, const u32* __restrict__ m_c, const u32* __restrict__ coefs,
+                  const u32* __restrict__ Z, u32 n, u32* __restrict__ wL_out, u32* __restrict__ wR_out, u32* __restrict__ wO_out) {
     typedef typename C::Fr F;
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -511,6 +532,11 @@ k_r1cs_flatten(const u32* __restrict__ m_off, const u32* __restrict__ m_ent, con
     store_fe_dev<F>(wL_out + (size_t)i * 8, wL);
     store_fe_dev<F>(wR_out + (size_t)i * 8, wR);
     store_fe_dev<F>(wO_out + (size_t)i * 8, wO);
+}
+template <class C> __global__ void __launch_bounds__(256)
+k_r1cs_flatten(const u32* __restrict__ m_off, const u32* __restrict__ m_ent, const u32* __restrict__ m_c, const u32* __restrict__ coefs,
+               const u32* __restrict__ Z, u32 n, u32* __restrict__ wL_out, u32* __restrict__ wR_out, u32* __restrict__ wO_out) {
+    r1cs_flatten_body<C>(m_off, m_ent, m_c, coefs, Z, n, wL_out, wR_out, wO_out);
 }
 
 // resident form -> canonical integers, in place

@@ -370,7 +370,9 @@ struct IpaDefer {
 template <class C>
 static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8* rng_bytes, host::ProofData& proof, StageTimes& tm,
                       ProvePre<C>* pre_in = nullptr, const HostCsc* csc = nullptr /* constraint index built with the statement (single-phase) */,
-                      IpaDefer* defer = nullptr) {
+                      IpaDefer* defer = nullptr,
+                      const A4* resume1 = nullptr /* bp_prover_prove_batch, a member that leaves its front group after the randomized phase: A_I1, A_O1,
+                      S1 are in the transcript and the phase has run — neither happens again; the whole witness goes up to the workspaces here */) {
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
     typedef host::Grp<C> G;
@@ -391,7 +393,7 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     if (!pre.rng) prove_precompute<C>(cs, rng_bytes, pre);
     host::TranscriptRng& rng = *pre.rng;
     tm.rng += pre.t_rng;
-    const size_t n1 = cs.a_L.size();
+    const size_t n1 = resume1 ? cs.n1 : cs.a_L.size();
     if (ctx->gens_cap < n1) return BP_E_GENS_LENGTH;
     const F4 i_b1 = pre.i_b1, o_b1 = pre.o_b1, s_b1 = pre.s_b1;
     std::vector<F4>& s_L = pre.s_L;
@@ -423,8 +425,9 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     t0 = now_s();
     A4 A_I1, A_O1, S1;
     bool direct1 = false;
-    if (n1) BPCHK(dt_ensure<C>(ctx, host::next_pow2(n1), direct1));
-    if (n1 == 0) {   // no multipliers in this phase (a k-shuffle's phase 1): three single Pedersen terms on the host's tables, one inversion
+    if (n1 && !resume1) BPCHK(dt_ensure<C>(ctx, host::next_pow2(n1), direct1));
+    if (resume1) { A_I1 = resume1[0]; A_O1 = resume1[1]; S1 = resume1[2]; }
+    else if (n1 == 0) {   // no multipliers in this phase (a k-shuffle's phase 1): three single Pedersen terms on the host's tables, one inversion
         const J4 j3[3] = {pc.commit_jac(S::zero(), i_b1), pc.commit_jac(S::zero(), o_b1), pc.commit_jac(S::zero(), s_b1)};
         A4 o3[3];
         to_aff_batch<C>(j3, 3, o3);
@@ -443,9 +446,11 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     }
     tm.commit_msm += now_s() - t0;
     mark("commit phase 1");
-    TP::append_point(tr, "A_I1", A_I1); TP::append_point(tr, "A_O1", A_O1); TP::append_point(tr, "S1", S1);
-
-    { int rc = cs.run_randomized(); if (rc) return rc; }
+    if (!resume1) {
+        TP::append_point(tr, "A_I1", A_I1); TP::append_point(tr, "A_O1", A_O1); TP::append_point(tr, "S1", S1);
+        int rc = cs.run_randomized();
+        if (rc) return rc;
+    }
 
     mark("randomized phase");
     const size_t n = cs.a_L.size(), n2 = n - n1, N = host::next_pow2(n);

@@ -1099,6 +1099,14 @@ def _prove_batch_stats(self):
     return a.value, b.value, g.value
 
 
+def _prove_batch_front_stats(self):
+    """(instances whose front stages ran group-wide, front groups after the re-partition by padded size, host waits of those stages)"""
+    a, g, w = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().bp_ctx_prove_batch_front_stats(self.ctx, C.byref(a), C.byref(g), C.byref(w)), "bp_ctx_prove_batch_front_stats")
+    return a.value, g.value, w.value
+
+
 Engine.prove_batch = _prove_batch
 Engine.prover_commit_batch = _prover_commit_batch
 Engine.prove_batch_stats = _prove_batch_stats
+Engine.prove_batch_front_stats = _prove_batch_front_stats

@@ -356,21 +356,30 @@ int bp_prover_prove(bp_ctx* ctx, bp_cs* prover, const uint8_t rng_bytes_or_null[
  * non-zero return, BP_E_MISSING inside a randomized phase, BP_E_GENS_LENGTH) without changing any other instance's bytes, and the
  * call returns the first non-zero status in instance order.  A host-only ctx returns BP_E_NO_DEVICE after the checks and consumes
  * nothing.  Randomized-phase callbacks of different instances may run in any order.
- * Grouping: every instance runs the stages of prove() up to its inner-product argument; those whose argument runs over the direct
- * window tables (padded size 2 .. BP_TUNE_DIRECT_MAX) then run it in LOCKSTEP groups of equal padded size — one launch per stage
- * and one host wait per Fiat-Shamir round for the whole group — and every other instance proves as bp_prover_prove would, inside
- * the same call.  The bytes are identical either way.  A batch leaves the ctx's single-proof path as it was: a bp_prover_prove
- * afterwards gives the bytes it gives on a fresh ctx.
+ * Grouping: an instance whose inner-product argument runs over the direct window tables (padded size 2 .. BP_TUNE_DIRECT_MAX, ctx
+ * not sharded, enough generators) and whose constraints can be indexed runs EVERY stage of prove() in a group.  Instances are taken in
+ * order of their phase-1 multiplier count; those of equal count form a FRONT GROUP (at most BP_TUNE_PROVE_BATCH of them): witness
+ * upload, the A_I / A_O / S commitments, flatten, t(x), the T commitments and l(x) / r(x) are one launch per stage for all members, with
+ * one host wait per Fiat-Shamir step of the group (BP_TUNE_PROVE_BATCH_FRONT).  Randomized phases run on the calling thread in
+ * between; afterwards the surviving members are re-partitioned by padded size, and every part finishes the front stages and runs its
+ * inner-product arguments in LOCKSTEP — one launch per stage and one host wait per round for the whole part.  Every other instance
+ * proves as bp_prover_prove would, inside the same call (its argument still joins a lockstep group when it runs over the direct
+ * tables).  The bytes are identical either way.  With front groups, timing[2..6] are totals over the groups' stages (the wall time a
+ * stage took for all members of a group, not a sum over instances).  A batch leaves the ctx's single-proof path as it was: a
+ * bp_prover_prove afterwards gives the bytes it gives on a fresh ctx.
  * bp_prover_commit_batch: `Prover::commit` for several provers, equal to bp_prover_commit(provers[k], ctx, v + .., v_blinding + ..,
  * m_each[k], ..) in order, with every commitment of the batch computed in one launch and normalised with one inversion.  v,
  * v_blinding, V_xy_out and vars_out hold the sum of m_each entries, prover after prover.
  * bp_ctx_prove_batch_stats: instances whose inner-product argument ran in a lockstep group / instances bp_prover_prove_batch proved
- * one at a time / lockstep groups, since ctx creation. */
+ * one at a time / lockstep groups, since ctx creation.
+ * bp_ctx_prove_batch_front_stats: instances whose front stages ran group-wide / front groups (counted after the re-partition by padded
+ * size) / host waits for the GPU made by those stages (the waits of the argument's rounds are not included), since ctx creation. */
 int bp_prover_prove_batch(bp_ctx* ctx, size_t count, bp_cs* const* provers, const uint8_t* rng_bytes, uint8_t* proofs_out, size_t proof_stride, size_t* proof_lens,
                           int* status, double* timing);
 int bp_prover_commit_batch(bp_ctx* ctx, size_t count, bp_cs* const* provers, const size_t* m_each, const uint64_t* v, const uint64_t* v_blinding, uint64_t* V_xy_out,
                            bp_var* vars_out);
 int bp_ctx_prove_batch_stats(bp_ctx* ctx, uint64_t* lockstep_instances, uint64_t* single_instances, uint64_t* groups);
+int bp_ctx_prove_batch_front_stats(bp_ctx* ctx, uint64_t* front_instances, uint64_t* front_groups, uint64_t* front_waits);
 /* `verifier.verify(&proof, &pc_gens, &bp_gens)` (verifier.rs:549-557): consumes the verifier */
 int bp_verifier_verify(bp_ctx* ctx, bp_cs* verifier, const uint8_t* proof, size_t proof_len);
 /* `batch_verify(prng, instances, &pc_gens, &bp_gens)` (verifier.rs:604-691): instance k = (verifiers[k], the k-th of the
@@ -475,6 +484,9 @@ int bp_ctx_reset_profiling(bp_ctx* ctx);
                                   * latency path for the reference's own benchmark range (benches/r1cs_secq256k1.rs:152-250, 2 .. 2046 multipliers) */
 #define BP_TUNE_PROVE_BATCH 13   /* most instances per lockstep group of bp_prover_prove_batch (0 = default: as many as a 256 MB device arena
                                   * holds; at most 65535, groups above 16384 are split) */
+#define BP_TUNE_PROVE_BATCH_FRONT 14   /* 1 (default): bp_prover_prove_batch runs the stages in front of the inner-product argument group-wide
+                                  * too (see "Batch proving"); 0: those stages run one instance after the other on the single-proof
+                                  * workspaces (A/B, tests).  Results never depend on it */
 int bp_ctx_set_tuning(bp_ctx* ctx, int knob, uint64_t value);
 
 /* The O(N) part of `Verifier::verification_scalars` (src/r1cs/verifier.rs:465-514, s from inner_product_proof.rs:279-311) for a

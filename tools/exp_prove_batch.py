@@ -5,6 +5,8 @@ The direct window tables are built on the first ctx and shared before anything i
 
   python tools/exp_prove_batch.py [curve] [k ...]      the table (one JSON line per k)
   python tools/exp_prove_batch.py --one CURVE K B      one batch of B (for rocprofv3 --kernel-trace --stats), prints its host timing
+  --front 0|1 anywhere on the line sets BP_TUNE_PROVE_BATCH_FRONT on every ctx (default: the library's, 1): 0 runs the stages in front of
+  the inner-product argument one instance at a time.  Each (c) row also carries the front counters (instances, groups, host waits).
 """
 import json
 import os
@@ -16,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ark_bulletproofs_amd as A  # noqa: E402
 from ark_bulletproofs_amd.engine import Statement  # noqa: E402
 
+FRONT = None   # --front: BP_TUNE_PROVE_BATCH_FRONT (knob 14) for every ctx
 STAGES = ["total", "lockstep_ipa", "rng", "upload", "commit", "flatten", "poly", "ipa_single"]
 
 
@@ -27,6 +30,12 @@ def engine(curve, gens=4096):
     e = A.Engine(curve=curve)
     e.gens_derive(gens)
     e.gens_direct_tables(gens)   # built here, so that share_gens_from hands them over
+    return front(e)
+
+
+def front(e):
+    if FRONT is not None:
+        e.set_tuning(14, FRONT)
     return e
 
 
@@ -43,13 +52,13 @@ def one_batch(curve, k, B):
     s = stmts(e, k, B, 2)
     tm = [0.0] * 8
     wall, cpu = timed(lambda: e.prove_batch(s, timing=tm))
-    print(json.dumps({"curve": curve, "k": k, "B": B, "wall_s": wall, "cpu_s": cpu, "stages_s": dict(zip(STAGES, tm))}), flush=True)
+    print(json.dumps({"curve": curve, "k": k, "B": B, "wall_s": wall, "cpu_s": cpu, "stages_s": dict(zip(STAGES, tm)), "front": list(e.prove_batch_front_stats())}), flush=True)
     e.close()
 
 
 def table(curve, ks):
     e = engine(curve)
-    others = [A.Engine(curve=curve) for _ in range(7)]
+    others = [front(A.Engine(curve=curve)) for _ in range(7)]
     for o in others:
         o.share_gens_from(e)
     engs = [e] + others
@@ -88,9 +97,11 @@ def table(curve, ks):
             s = stmts(e, k, B, 40)
             tm = [0.0] * 8
             res = []
+            f0 = e.prove_batch_front_stats()
             w, c = timed(lambda: res.extend(e.prove_batch(s, timing=tm)))
             assert all(st == 0 for st, _ in res)
             row["c%d_out" % B] = [round(B / w), round(1e3 * c / B, 3)]
+            row["c%d_front" % B] = [b - a for a, b in zip(f0, e.prove_batch_front_stats())]
             row["c%d_stages_ms_per_proof" % B] = {n: round(1e3 * t / B, 4) for n, t in zip(STAGES, tm)}
             w, c = timed(lambda: e.prove_batch(stmts(e, k, B, 41)))
             row["c%d_in" % B] = [round(B / w), round(1e3 * c / B, 3)]
@@ -101,6 +112,10 @@ def table(curve, ks):
 
 
 if __name__ == "__main__":
+    if "--front" in sys.argv:
+        i = sys.argv.index("--front")
+        FRONT = int(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
     if len(sys.argv) > 1 and sys.argv[1] == "--one":
         one_batch(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
     else:
