@@ -2351,6 +2351,13 @@ template <class C> __global__ void k_dbg_point(int op, const u32* p, const u32* 
     aff_store_ark<C>(w, a);
     store_words8(out + (size_t)i * 16, w); store_words8(out + (size_t)i * 16 + 8, w + 8);
 }
+// raw-representative unit ops: the kernels live in a translation unit of their own (csrc/dbg_raw.hip), so that this unit's device code
+// is not touched by them; word counts per case as in csrc/dbg_raw.cuh
+namespace arkbp {
+int dbg_raw_launch_field(hipStream_t st, int field, int op, const u32* in, u32* out, u32 n);
+int dbg_raw_launch_point(hipStream_t st, int curve, int op, const u32* in, u32* out, u32 n);
+}
+static constexpr int RAW_F_IN = 36, RAW_F_OUT = 18, RAW_F_COUNT = 13, RAW_P_IN = 54, RAW_P_OUT = 28, RAW_P_COUNT = 7, RAW_P_QADD = 4;
 
 template <class C> static int dbg_rng_draws(void* transcript, const uint64_t* witness, size_t nw, const uint8_t* seeds, int lanes, size_t count, uint64_t* out) {
     typedef typename C::Fr FrP; typedef host::Fld<FrP> S;
@@ -3706,6 +3713,34 @@ int bp_debug_point_op(bp_ctx* c, int op, const uint64_t* p, const uint64_t* q, c
     else hipLaunchKernelGGL(k_dbg_point<Zorro>, dim3(gb), dim3(64), 0, c->stream, op, dp, dq, c->io_scal.as<u32>(), c->io_out.as<u32>(), (u32)n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, c->io_out.p, n * 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(ctx_stream_wait(c));
+    return BP_OK;
+}
+/* raw limbs in, raw limbs out (csrc/dbg_raw.cuh lists the ops and the layouts) */
+int bp_debug_field_raw(bp_ctx* c, int field, int op, const uint32_t* in, uint32_t* out, size_t n) {
+    if (!c || !in || !out || field < 0 || field > 3 || op < 0 || op >= RAW_F_COUNT || !n || n > ((size_t)1 << 24)) return BP_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    BPCHK(c->io_pts.ensure(n * RAW_F_IN * 4)); BPCHK(c->io_out.ensure(n * RAW_F_OUT * 4));
+    HIPCHK(hipMemcpyAsync(c->io_pts.p, in, n * RAW_F_IN * 4, hipMemcpyHostToDevice, c->stream));
+    const u32* pi = c->io_pts.as<u32>();
+    u32* po = c->io_out.as<u32>();
+    dbg_raw_launch_field(c->stream, field, op, pi, po, (u32)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, po, n * RAW_F_OUT * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(ctx_stream_wait(c));
+    return BP_OK;
+}
+int bp_debug_point_raw(bp_ctx* c, int op, const uint32_t* in, uint32_t* out, size_t n) {
+    if (!c || !in || !out || op < 0 || op >= RAW_P_COUNT || !n || n > ((size_t)1 << 22)) return BP_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t lanes = op < RAW_P_QADD ? 1 : 4, obytes = n * lanes * RAW_P_OUT * 4;
+    BPCHK(c->io_pts.ensure(n * RAW_P_IN * 4)); BPCHK(c->io_out.ensure(obytes));
+    HIPCHK(hipMemcpyAsync(c->io_pts.p, in, n * RAW_P_IN * 4, hipMemcpyHostToDevice, c->stream));
+    const u32* pi = c->io_pts.as<u32>();
+    u32* po = c->io_out.as<u32>();
+    dbg_raw_launch_point(c->stream, c->curve, op, pi, po, (u32)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, po, obytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(ctx_stream_wait(c));
     return BP_OK;
 }

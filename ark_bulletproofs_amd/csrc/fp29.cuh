@@ -24,10 +24,20 @@
 //   fe_mul / fe_sqr   in: L(a)*L(b) <= 6, V(a)*V(b) <= 900   out: L = 1, V < V(a)V(b)/32 + 1
 //   fe_mul2           a*b + c*d, one reduction: L(a)L(b) + L(c)L(d) <= 6, V(a)V(b) + V(c)V(d) <= 900; out as fe_mul
 //   fe_add            limb-wise, no carry                    out: L = La + Lb, V = Va + Vb
-//   fe_sub<K>         in: L(a) <= 2, L(b) < 4, V(b) < K      out: L = 1, V = Va + K
+//   fe_sub<K>         in: L(a) <= 2, limb-wise b.l[i] <= SUBK<K>[i] (below)   out: L = 1, V = Va + K - Vb <= Va + K
+//                     SUBK<K> is K*p with 2^31 moved into each of limbs 0..7 from the limb above (4 units there), so limbs 0..7 of
+//                     SUBK<K> are >= 2^31 - 4 and limb 8 is floor(K*p / 2^232) - 4.  Hence: limbs 0..7 of b <= 2^31 - 4 (L(b) < 4)
+//                     and b.l[8] <= floor(K*p / 2^232) - 4.  For a normalised b that is b < (floor(K*p / 2^232) - 3) * 2^232, which
+//                     b <= K*p - 4 * 2^232 guarantees: V(b) <= K - 2^-21 (p > 2^254).  "V(b) < K" alone is NOT enough: a b within
+//                     4 * 2^232 below K*p makes limb 8 wrap.  Every call site keeps V(b) at least 0.4 below K (ec.cuh, ecq.cuh: the
+//                     closest are the X3 subtractions, V(b) <= 3.6 under K = 4).
 //   fe_norm           carry pass                              out: L = 1
-//   fe_wred           in: L = 1, V < 32                       out: L = 1, V <= 2
-//   fe_canon          in: L = 1, V < 32                       out: canonical (0 <= x < p)
+//   fe_wred           in: L = 1, a < 2^261                    out: L = 1, a' < 2p
+//   fe_canon          in: L = 1, a < 2^261                    out: canonical (0 <= x < p)
+//                     (a < 2^261 is V < 32 for the 256-bit moduli and V < 64 for the 255-bit ones; the same holds for fe_is_zero_mod /
+//                     fe_maybe_zero_mod.  fe_wred's output is STRICTLY below 2p in all four fields: with p = 2^B - delta it takes off
+//                     floor(a / 2^B) * p and leaves less than 2^B + 32 * delta, with p = 2^B + delta it takes off one multiple less
+//                     and leaves less than 2^(B+1) < 2p; the pseudo-Mersenne fold leaves less than 2^BITS + 2^40.)
 #pragma once
 #include <cstdint>
 #if defined(__HIPCC__)
@@ -115,7 +125,8 @@ ARKBP_HD Fe fe_add(const Fe& a, const Fe& b) {
 }
 ARKBP_HD Fe fe_dbl(const Fe& a) { return fe_add(a, a); }
 
-// a - b + K*p with K in {2,4,8,16}; borrow-free: the K*p limbs are pre-spread to be >= 2^31 - 4
+// a - b + K*p with K in {2,4,8,16}; borrow-free: the K*p limbs are pre-spread to be >= 2^31 - 4 (limbs 0..7; limb 8 gives up 4 units:
+// b must stay limb-wise below the spread offset, see the contract table above)
 template <class P, int K> ARKBP_HD Fe fe_sub(const Fe& a, const Fe& b) {
     static_assert(K == 2 || K == 4 || K == 8 || K == 16, "K");
     Fe r;
@@ -300,11 +311,11 @@ template <class P> ARKBP_HD Fe fe_sqr(const Fe& a) {
     return t;
 }
 
-// weak reduction: subtract floor-estimate(a / 2^WR_BITS) * p; needs L = 1 and a < 2^261.  Result <= 2p.
+// weak reduction: subtract floor-estimate(a / 2^WR_BITS) * p; needs L = 1 and a < 2^261.  Result < 2p (contract table above).
 template <class P> ARKBP_HD Fe fe_wred(const Fe& a) {
     if constexpr (P::PM) {
         // pseudo-Mersenne: the bits above the modulus width come back multiplied by 2^BITS mod p (a 33-bit constant at most), one
-        // carry pass: ~30 cheap instructions instead of nine signed 64-bit multiply-subtracts.  Result < 2^BITS + 2^40 <= 2p.
+        // carry pass: ~30 cheap instructions instead of nine signed 64-bit multiply-subtracts.  Result < 2^BITS + 2^40 < 2p.
         constexpr int shp = P::BITS - 232;
         ARKBP_ASSERT(a.l[8] < (1u << 29) + 8u, "fe_wred: a >= 2^261");
         const u32 o = a.l[8] >> shp;                   // < 2^(29 - shp) + 1
@@ -334,9 +345,9 @@ template <class P> ARKBP_HD Fe fe_wred(const Fe& a) {
     return r;
 }
 
-// full reduction to the canonical representative; input L = 1, V < 32
+// full reduction to the canonical representative; input L = 1, a < 2^261
 template <class P> ARKBP_HD Fe fe_canon(const Fe& a) {
-    Fe w = fe_wred<P>(a);  // < 2p (+ tiny), so at most two subtractions of p
+    Fe w = fe_wred<P>(a);  // < 2p: ONE subtraction of p suffices for every legal input; the second pass is margin that none reaches
 #pragma unroll
     for (int rep = 0; rep < 2; rep++) {
         Fe d;
@@ -354,8 +365,9 @@ template <class P> ARKBP_HD Fe fe_canon(const Fe& a) {
     return w;
 }
 
-// a == 0 (mod p)?   Needs L = 1, V < 32.  Cheap filter on the low limb first: a = k*p forces
-// a_0 = k*p_0 mod 2^29 with k within one of the top-limb estimate; the exact test runs only then.
+// a == 0 (mod p)?   Needs L = 1, a < 2^261.  Cheap filter on the low limb first: a = k*p forces
+// a_0 = k*p_0 mod 2^29 with k within one of the top-limb estimate; the exact test runs only then.  (For these four moduli k is
+// the estimate itself (p = 2^B + delta, and k = 0) or the estimate + 1 (p = 2^B - delta): the d = -1 probe is margin as well.)
 template <class P> ARKBP_HD bool fe_maybe_zero_mod(const Fe& a) {   // the filter alone: false means a != 0 (mod p) for certain
     constexpr int sh = P::WR_BITS - 232;
     const u32 q = a.l[8] >> sh;

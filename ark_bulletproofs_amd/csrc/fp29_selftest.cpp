@@ -5,6 +5,7 @@
 #include "ec.cuh"
 #include "ecq.cuh"
 #include "glv.cuh"
+#include "dbg_raw.cuh"
 using namespace arkbp;
 
 template <class F> static void fe_op(int op, const u32* a, const u32* b, u32* out) {
@@ -83,7 +84,39 @@ template <class C> static int quad_op(int op, const u32* p, const u32* q, u32* o
     return bad;
 }
 
+// raw-representative ops (dbg_raw.cuh), the same bodies the k_dbg_*_raw kernels run; the quad ops go through QuadSim as above and
+// return all four lanes
+template <class C> static void raw_pt(int op, const u32* in, u32* out) {
+    if (op < RAW_P_QADD) { raw_point_op<C>(op, in, out); return; }
+    QuadSim& sim = quad_sim();
+    sim = QuadSim();
+    for (int round = 0; round < 16; round++)
+        for (int lane = 0; lane < 4; lane++) {
+            sim.site = 0; sim.lane = lane;
+            raw_store_jac(out + lane * RAW_P_OUT, raw_quad_op<C>(op, in, (u32)lane), 0);
+        }
+}
+
 extern "C" {
+void fp29_field_raw(int fid, int op, const u32* in, u32* out, int n) {
+    for (int i = 0; i < n; i++) {
+        const u32* a = in + (size_t)i * RAW_F_IN;
+        u32* o = out + (size_t)i * RAW_F_OUT;
+        switch (fid) {
+            case 0: raw_field_op<SecqFq>(op, a, o); break;
+            case 1: raw_field_op<SecqFr>(op, a, o); break;
+            case 2: raw_field_op<ZorroFq>(op, a, o); break;
+            default: raw_field_op<ZorroFr>(op, a, o); break;
+        }
+    }
+}
+void fp29_point_raw(int cid, int op, const u32* in, u32* out, int n) {
+    const int lanes = op < RAW_P_QADD ? 1 : 4;
+    for (int i = 0; i < n; i++) {
+        if (cid == 0) raw_pt<Secq>(op, in + (size_t)i * RAW_P_IN, out + (size_t)i * lanes * RAW_P_OUT);
+        else raw_pt<Zorro>(op, in + (size_t)i * RAW_P_IN, out + (size_t)i * lanes * RAW_P_OUT);
+    }
+}
 int fp29_quad_op(int cid, int op, const u32* p, const u32* q, u32* out) { return cid == 0 ? quad_op<Secq>(op, p, q, out) : quad_op<Zorro>(op, p, q, out); }
 // glv_split of a canonical secq256k1 scalar (8 words) -> mag1[4] | mag2[4] | signs; returns 1 when both halves fit 128 bits
 int fp29_glv_split(const u32* k, u32* out12) { return glv_split<Secq>(k, out12) ? 1 : 0; }

@@ -179,6 +179,20 @@ class Engine:
         check(lib().bp_debug_point_op(self.ctx, op, ptr(p), ptr(q), ptr(k), ptr(out), C.c_size_t(len(p))), "bp_debug_point_op")
         return out
 
+    def debug_field_raw(self, field, op, limbs):
+        """raw 9 x u32 limbs in and out (csrc/dbg_raw.cuh): limbs (n, 36) = a | b | c | d -> (n, 18)"""
+        a = np.ascontiguousarray(limbs, dtype=np.uint32).reshape(-1, 36)
+        out = np.zeros((len(a), 18), dtype=np.uint32)
+        check(lib().bp_debug_field_raw(self.ctx, field, op, ptr(a), ptr(out), C.c_size_t(len(a))), "bp_debug_field_raw")
+        return out
+
+    def debug_point_raw(self, op, limbs):
+        """limbs (n, 54) = P.X P.Y P.Z Q.X Q.Y Q.Z -> (n, lanes, 28) = X Y Z flag per lane; lanes = 4 for the quad ops 4..6"""
+        a = np.ascontiguousarray(limbs, dtype=np.uint32).reshape(-1, 54)
+        out = np.zeros((len(a), 1 if op < 4 else 4, 28), dtype=np.uint32)
+        check(lib().bp_debug_point_raw(self.ctx, op, ptr(a), ptr(out), C.c_size_t(len(a))), "bp_debug_point_raw")
+        return out
+
 
 # ---- InnerProductProof::create ---------------------------------------------------------------------
 _POINT_REDUCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64))

@@ -583,6 +583,15 @@ int bp_debug_verify_challenges(int curve, size_t count, const int* scenarios, co
                                size_t* nchal);
 /* op: 0 P+Q (general add), 1 P+Q (mixed add), 2 2P, 3 k*P (k canonical, one per element) */
 int bp_debug_point_op(bp_ctx* ctx, int op, const uint64_t* p_xy, const uint64_t* q_xy, const uint64_t* k, uint64_t* out_xy, size_t n);
+/* The same on RAW representatives: operands and results are the nine 32-bit limbs of the device's radix-2^29 form, no conversion
+ * either way, so a test can feed any legal representative (lazy limbs, values in [p, 2p) ..) and inspect the limbs that come back.
+ * csrc/dbg_raw.cuh lists the ops (RAW_F_*, RAW_P_*) and is what the CPU harness csrc/fp29_selftest.cpp runs as well.
+ * field_raw: in n x 36 words (a | b | c | d), out n x 18 words.  point_raw (the ctx's curve): in n x 54 words (P.X P.Y P.Z Q.X Q.Y
+ * Q.Z; the mixed additions read Q.X, Q.Y as the affine operand), out n x 28 words (X Y Z flag) for ops 0..3 (jac_add, jac_madd,
+ * jac_dbl, jac_madd_fast with flag = rare) and n x 4 x 28 for the quad-cooperative ops 4..6 (qjac_add, qjac_madd, qjac_dbl): one
+ * case runs in four adjacent lanes, 64 different cases per block, and every lane's result comes back. */
+int bp_debug_field_raw(bp_ctx* ctx, int field, int op, const uint32_t* in, uint32_t* out, size_t n);
+int bp_debug_point_raw(bp_ctx* ctx, int op, const uint32_t* in, uint32_t* out, size_t n);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import pymodel as M
+import rawcases as RC
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ark_bulletproofs_amd", "csrc")
 R = 1 << 256
@@ -18,7 +19,7 @@ R = 1 << 256
 @pytest.fixture(scope="module")
 def st():
     so = os.path.join(CSRC, "libfp29_selftest.so")
-    srcs = [os.path.join(CSRC, f) for f in ("fp29_selftest.cpp", "fp29.cuh", "ec.cuh", "ecq.cuh", "glv.cuh", "arkbp_params.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("fp29_selftest.cpp", "fp29.cuh", "ec.cuh", "ecq.cuh", "glv.cuh", "dbg_raw.cuh", "arkbp_params.h")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DARKBP_CHECK_BOUNDS", "-Wno-unknown-pragmas", "-o", so, srcs[0]])
     return C.CDLL(so)
@@ -143,6 +144,39 @@ def test_quad_cooperative_schedules(st, cv):
             exp = M.add(cv, P2, Q) if op < 2 else M.add(cv, P2, P2)
             got = None if not out.any() else (from_mont(out[:8], c["q"]), from_mont(out[8:], c["q"]))
             assert got == exp
+
+
+@pytest.mark.parametrize("fid", [0, 1, 2, 3])
+def test_raw_field_cases(st, fid):
+    """the raw-representative case list of tests/rawcases.py (products at the contract limit, every multiple of p and its neighbours,
+    fe_sub at its real limit ..) through the CPU build of csrc/dbg_raw.cuh: every contract is asserted, so a case that aborts here is
+    an illegal case; the GPU runs the same list (tests/test_gpu_group_law.py)"""
+    cases = RC.field_cases(fid)
+    assert {op for op, _, _ in cases} == set(range(13))
+    for op in sorted({op for op, _, _ in cases}):
+        sel = [c for c in cases if c[0] == op]
+        inp = np.array([sum(c[2], []) for c in sel], dtype=np.uint32)
+        out = np.full((len(sel), 18), 0xFFFFFFFF, dtype=np.uint32)
+        st.fp29_field_raw(fid, op, inp.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), len(sel))
+        for (_, name, ins), o in zip(sel, out):
+            RC.check_field(fid, op, name, ins, o)
+
+
+@pytest.mark.parametrize("cv", [0, 1])
+def test_raw_point_cases(st, cv):
+    """the group law on every representative and exception (tests/rawcases.py): Jacobian coordinates in [0, p) and [p, 2p), equal,
+    opposite, unrelated and identity operands, lazily negated affine operands — lane-per-operation forms and, through QuadSim, the
+    quad-cooperative forms with all four lanes returned"""
+    cases = RC.point_cases(cv)
+    assert {c[0] for c in cases} == set(range(7))
+    for op in range(7):
+        sel = [c for c in cases if c[0] == op]
+        inp = np.array([c[2] + c[3] for c in sel], dtype=np.uint32)
+        lanes = 4 if op >= RC.P_QADD else 1
+        out = np.full((len(sel), lanes, 28), 0xFFFFFFFF, dtype=np.uint32)
+        st.fp29_point_raw(cv, op, inp.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), len(sel))
+        for (_, name, _, _, kind, expect), o in zip(sel, out):
+            RC.check_point(cv, op, name, kind, expect, o)
 
 
 def test_glv_split_matches_big_integers(st):
