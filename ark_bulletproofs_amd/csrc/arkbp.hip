@@ -27,6 +27,7 @@
 #include "small.cuh"
 #include "small_batch.cuh"
 #include "small_batch_front.cuh"
+#include "vfy_each.cuh"
 #include "vfe.hpp"
 #include "vfe_sched.hpp"
 static_assert(arkbp::vfe::PB_WORDS == arkbp::VFY_PB_WORDS, "parameter block layout shared by vfe.hip and r1cs.cuh");
@@ -336,6 +337,10 @@ struct bp_ctx {
     void* h_pf = nullptr;            // pinned: witness staging, the aux block, results
     size_t h_pf_cap = 0;
     uint64_t pf_instances = 0, pf_groups = 0, pf_waits = 0;
+    // bp_verifier_verify_batch (verify_each.inc): its device arena and counters
+    size_t tune_verify_each = 0;     // BP_TUNE_VERIFY_EACH: most instances per group (0 = what VE_ARENA_BUDGET holds, at most VE_GROUP_MAX)
+    DevBuf ve_arena;
+    uint64_t ve_grouped = 0, ve_single = 0, ve_groups = 0, ve_waits = 0;
     uint64_t folds_deferred = 0, folds_tab2 = 0;   // first folds deferred / second folds that came straight from the tables (bp_ctx_fold_stats)
     IpaState ipa_step;         // bp_ipa_begin .. bp_ipa_finish
     bool ipa_step_active = false;
@@ -2793,6 +2798,7 @@ __attribute__((target("avx512f"))) static int dbg_challenge_x8(void* const* trs,
 #endif
 
 #include "prove_batch.inc"   // bp_prover_prove_batch, bp_prover_commit_batch (the C entry points are declared extern "C" by the header)
+#include "verify_each.inc"   // bp_verifier_verify_batch, bp_r1cs_verify_each_scenarios, bp_debug_msm_each
 
 extern "C" {
 
@@ -2828,7 +2834,7 @@ void bp_ctx_destroy(bp_ctx* c) {
     DevBuf* bufs[] = {&c->canon, &c->hist, &c->lvl_off, &c->totals, &c->cursor, &c->entries, &c->slots, &c->bin_cur, &c->boff, &c->lvA, &c->lvB, &c->Tbuf, &c->io_pts, &c->io_scal, &c->io_out,
                       &c->ipa_G, &c->ipa_H, &c->ipa_a, &c->ipa_b, &c->ipa_Gf, &c->ipa_Hf, &c->ipa_sL, &c->ipa_sR, &c->ipa_part, &c->ipa_Q, &c->ipa_jac, &c->ipa_pref, &c->ipa_cG, &c->ipa_cH,
                       &c->d_G, &c->d_H, &c->d_pc, &c->pc_table, &c->r_aL, &c->r_aR, &c->r_aO, &c->r_sL, &c->r_sR, &c->r_wL, &c->r_wR, &c->r_wO, &c->r_msmsc,
-                      &c->r_ypow, &c->r_part, &c->r_small, &c->r_g, &c->r_h, &c->r_chal, &c->r_tail, &c->v_params, &c->v_gpart, &c->v_hpart, &c->v_alpha, &c->v_tables, &c->v_dec, &c->cyc_a, &c->cyc_b, &c->cyc_Gf, &c->cyc_Hf, &c->ftab_G, &c->ftab_H, &c->fb_G, &c->fb_H, &c->fb_pc, &c->p_moff, &c->p_ment, &c->p_mc, &c->p_coefs, &c->p_ztab, &c->fs_bcnt, &c->fs_loff, &c->fs_binch, &c->fs_sums};
+                      &c->r_ypow, &c->r_part, &c->r_small, &c->r_g, &c->r_h, &c->r_chal, &c->r_tail, &c->v_params, &c->v_gpart, &c->v_hpart, &c->v_alpha, &c->v_tables, &c->v_dec, &c->ve_arena, &c->cyc_a, &c->cyc_b, &c->cyc_Gf, &c->cyc_Hf, &c->ftab_G, &c->ftab_H, &c->fb_G, &c->fb_H, &c->fb_pc, &c->p_moff, &c->p_ment, &c->p_mc, &c->p_coefs, &c->p_ztab, &c->fs_bcnt, &c->fs_loff, &c->fs_binch, &c->fs_sums};
     c->templates.clear();
     c->vfe_classes.clear();
     for (auto b : bufs) b->release();
@@ -2936,6 +2942,7 @@ int bp_ctx_set_tuning(bp_ctx* c, int knob, uint64_t value) {
         case BP_TUNE_MSM_CHUNK_CAP: if (value && (value < 8 || value > 64)) return BP_E_ARG; c->tune_msm_chunk_cap = (size_t)value; return BP_OK;
         case BP_TUNE_VFY_DEVICE: c->tune_vfy_device = value >= 2 ? 2 : (int)value; return BP_OK;
         case BP_TUNE_PROVE_BATCH: if (value > 65535) return BP_E_ARG; c->tune_prove_batch = (size_t)value; return BP_OK;
+        case BP_TUNE_VERIFY_EACH: c->tune_verify_each = (size_t)std::min<uint64_t>(value, 4096); return BP_OK;
         case BP_TUNE_PROVE_BATCH_FRONT: if (value > 1) return BP_E_ARG; c->tune_pb_front = (int)value; return BP_OK;
         case BP_TUNE_DIRECT_MAX: if (value > ((uint64_t)1 << 16)) return BP_E_ARG; c->tune_direct_max = (size_t)value; return BP_OK;
     }

@@ -2154,6 +2154,9 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
     return ok ? BP_OK : BP_E_VERIFICATION;
 }
 
+// what batch_verify_scenarios hands its provider to: batch_verify_core, or another core over the same instances (verify_each.inc)
+template <class C> using VfyCoreFn = std::function<int(const VfyProvider<C>&, const size_t* /* poff */, const F4* /* alphas */)>;
+
 // ---- scenario statements as callers of the core --------------------------------------------------------------------------
 // statement recording for one instance (Verifier::new + commits + gadget)
 template <class C> static int build_verifier_cs(host::ConstraintSystem<C>& cs, host::Transcript& tr, int scenario, const uint64_t* params,
@@ -2222,7 +2225,7 @@ __attribute__((target("avx512f"))) static void scenario_heads_x8(size_t k0, size
 template <class C>
 static int batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenarios, const uint64_t* params, const uint8_t* proofs, const size_t* proof_lens,
                                   const uint64_t* commit_xy, const size_t* ms, const uint64_t* publics, const size_t* npubs, const uint8_t* alpha_seed,
-                                  double* timing, size_t alpha_skip, uint64_t* point_out) {
+                                  double* timing, size_t alpha_skip, uint64_t* point_out, const VfyCoreFn<C>* other_core = nullptr) {
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
     if (point_out) memset(point_out, 0, 64);
@@ -2336,6 +2339,7 @@ static int batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenario
         db.commit_xy = [&](size_t k) { return commit_xy + 8 * coff[k]; };
         return true;
     };
+    if (other_core) return (*other_core)(prov, poff.data(), alphas.data());
     return batch_verify_core<C>(ctx, count, prov, proofs, poff.data(), alphas.data(), timing, point_out);
 }
 

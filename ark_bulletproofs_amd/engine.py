@@ -1124,3 +1124,101 @@ Engine.prove_batch = _prove_batch
 Engine.prover_commit_batch = _prover_commit_batch
 Engine.prove_batch_stats = _prove_batch_stats
 Engine.prove_batch_front_stats = _prove_batch_front_stats
+
+
+# ---- verification with a verdict per instance (bp_verifier_verify_batch) ----------------------------------------------------
+TUNE_VERIFY_EACH = 15                # include/arkbp.h BP_TUNE_VERIFY_EACH (Engine.set_tuning)
+VERIFY_EACH_WAITS_PER_GROUP = 1      # BP_VERIFY_EACH_WAITS_PER_GROUP
+
+
+def _verify_each(self, verifiers, proofs, want_points=False, timing=None):
+    """bp_verifier_verify_batch over VerifierCS objects (every one consumed): Verifier::verify for each instance, weight 1, in one
+    call.  Returns (rc, statuses) — rc = the first non-zero status in instance order — or (rc, statuses, points (count, 8)) with
+    want_points: the affine value of every instance's own mega-check, all-zero iff it is the identity.  Raises only when the
+    up-front checks refuse the whole batch (nothing consumed then)."""
+    n = len(verifiers)
+    if len(proofs) != n:
+        raise ValueError("verify_each: one proof per verifier")
+    hs = (C.c_void_p * max(n, 1))(*[v.h for v in verifiers])
+    blob = b"".join(bytes(p) for p in proofs)
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    st = (C.c_int * max(n, 1))(*([1] * max(n, 1)))   # (a status the library never returns: an instance it skipped would show)
+    pts = np.zeros((max(n, 1), 8), dtype=np.uint64)
+    tm = (C.c_double * 5)()
+    rc = lib().bp_verifier_verify_batch(self.ctx, C.c_size_t(n), hs, blob, lens, st, ptr(pts) if want_points else None, tm)
+    if timing is not None:
+        timing[:] = list(tm)
+    for v in verifiers:
+        if v._cb_errors:
+            raise v._cb_errors[0]
+        src = getattr(v, "_like", None)
+        if src is not None and src._cb_errors:
+            raise src._cb_errors[0]
+    if n and rc != 0 and all(s == 1 for s in st):   # refused as a whole
+        check(rc, "bp_verifier_verify_batch")
+    statuses = [st[k] for k in range(n)]
+    return (rc, statuses, pts[:n]) if want_points else (rc, statuses)
+
+
+def _verify_each_scenarios(self, instances, want_points=False, timing=None):
+    """bp_r1cs_verify_each_scenarios; instances: list of (scenario, params, proof_bytes, commitments, publics) or a PackedInstances.
+    Returns as verify_each."""
+    pk = instances if isinstance(instances, PackedInstances) else PackedInstances(instances)
+    n = pk.n
+    st = (C.c_int * max(n, 1))(*([1] * max(n, 1)))
+    pts = np.zeros((max(n, 1), 8), dtype=np.uint64)
+    tm = (C.c_double * 5)()
+    rc = lib().bp_r1cs_verify_each_scenarios(self.ctx, C.c_size_t(n), pk.scen, ptr(pk.prm), pk.proofs, pk.plens, ptr(pk.cms), pk.ms, ptr(pk.pubs), pk.npubs, st,
+                                             ptr(pts) if want_points else None, tm)
+    if timing is not None:
+        timing[:] = list(tm)
+    if n and rc != 0 and all(s == 1 for s in st):
+        check(rc, "bp_r1cs_verify_each_scenarios")
+    statuses = [st[k] for k in range(n)]
+    return (rc, statuses, pts[:n]) if want_points else (rc, statuses)
+
+
+def _verify_each_stats(self):
+    """(instances that took the grouped path, instances verified by the single route, groups launched, host waits of the groups)"""
+    a, b, g, w = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().bp_ctx_verify_each_stats(self.ctx, C.byref(a), C.byref(b), C.byref(g), C.byref(w)), "bp_ctx_verify_each_stats")
+    return a.value, b.value, g.value, w.value
+
+
+def _debug_msm_each(self, jobs, canonical=False):
+    """bp_debug_msm_each: jobs = list of (bases (n_j, 8), scalars (n_j, 4)); one variable-base MSM per job through k_ve_tail.
+    Returns the (len(jobs), 8) affine results."""
+    n = len(jobs)
+    bs = [u64arr(b, 8) if len(b) else np.zeros((0, 8), dtype=np.uint64) for b, _ in jobs]
+    ss = [u64arr(s, 4) if len(s) else np.zeros((0, 4), dtype=np.uint64) for _, s in jobs]
+    if any(len(b) != len(s) for b, s in zip(bs, ss)):
+        raise ValueError("msm_each: bases and scalars differ in length")
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(b) for b in bs])
+    off_c = (C.c_size_t * (n + 1))(*[int(o) for o in offs])
+    B = np.ascontiguousarray(np.concatenate(bs + [np.zeros((1, 8), dtype=np.uint64)]))
+    S = np.ascontiguousarray(np.concatenate(ss + [np.zeros((1, 4), dtype=np.uint64)]))
+    out = np.zeros((max(n, 1), 8), dtype=np.uint64)
+    check(lib().bp_debug_msm_each(self.ctx, C.c_size_t(n), off_c, ptr(B), ptr(S), int(canonical), ptr(out)), "bp_debug_msm_each")
+    return out[:n]
+
+
+def debug_ve_plan(offsets, scalars_canonical, job):
+    """host only (bp_debug_ve_plan): k_ve_tail's layout and digit functions for one job.  Returns (first term, terms,
+    digits (terms, 64) uint8, planes (terms, 64) uint8, lanes (64,) uint32, group slots (64,) uint32)."""
+    n = len(offsets) - 1
+    off_c = (C.c_size_t * (n + 1))(*[int(o) for o in offsets])
+    sc = u64arr(scalars_canonical, 4) if len(scalars_canonical) else np.zeros((1, 4), dtype=np.uint64)
+    nt = int(offsets[job + 1]) - int(offsets[job])
+    first, terms = C.c_uint32(0), C.c_uint32(0)
+    dg, pl = np.zeros((max(nt, 1), 64), dtype=np.uint8), np.zeros((max(nt, 1), 64), dtype=np.uint8)
+    lanes, groups = np.zeros(64, dtype=np.uint32), np.zeros(64, dtype=np.uint32)
+    check(lib().bp_debug_ve_plan(C.c_size_t(n), off_c, ptr(sc), C.c_size_t(job), C.byref(first), C.byref(terms), ptr(dg), ptr(pl), ptr(lanes), ptr(groups)),
+          "bp_debug_ve_plan")
+    return first.value, terms.value, dg[:nt], pl[:nt], lanes, groups
+
+
+Engine.verify_each = _verify_each
+Engine.verify_each_scenarios = _verify_each_scenarios
+Engine.verify_each_stats = _verify_each_stats
+Engine.debug_msm_each = _debug_msm_each

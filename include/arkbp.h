@@ -399,6 +399,53 @@ int bp_r1cs_batch_verify(bp_ctx* ctx, size_t count, bp_cs* const* verifiers, con
  * `of`, plus whatever the gadget appends through bp_cs_transcript.  The reference has no such call — every `Verifier` there records
  * its gadget anew (verifier.rs:69-224); with 4096 instances of a 2^14-multiplier circuit that recording is the whole cost. */
 int bp_verifier_new_like(bp_cs* of, void* transcript, bp_cs** out);
+/* Verification of many proofs with a verdict for EACH: `Verifier::verify` (verifier.rs:549-600) for `count` instances in one call —
+ * the loop `for (v, proof) in instances { v.verify(&proof, &pc_gens, &bp_gens) }` of a service that must tell its proofs apart.
+ * Instance k = (verifiers[k], the k-th of the concatenated compressed proofs).
+ *   status (count): status[k] is exactly what bp_verifier_verify(ctx, verifiers[k], proof_k, len_k) returns for that instance alone:
+ *   BP_OK, BP_E_VERIFICATION, BP_E_FORMAT, BP_E_GENS_LENGTH, or the non-zero return of the instance's randomized-phase callback.
+ *   Every instance is checked with weight 1: there are no alphas, and nothing one instance does changes another instance's status
+ *   or check point.  The call returns the first non-zero status in instance order.
+ *   check_points_xy (count x 8 words, may be NULL): the affine value of instance k's own mega-check (verifier.rs:574-595), all-zero
+ *   iff it is the identity — and all-zero for an instance that failed before its check ran.
+ *   timing (5 doubles, may be NULL; seconds): the whole call, host replay, waits for the GPU, the single-route instances, decoding.
+ * Up-front checks, before any work: every verifier live, of the ctx's curve and given once; generators installed.  A failed check
+ * returns BP_E_ARG (BP_E_GENS_LENGTH when no generators are installed) and consumes no verifier.  A host-only ctx returns
+ * BP_E_NO_DEVICE after the checks and consumes nothing.  Otherwise every verifier is consumed.  count == 0 returns BP_OK.  The
+ * transcript of an instance whose status is BP_OK is left in the state bp_verifier_verify leaves it in.  Randomized-phase callbacks
+ * of different instances may run concurrently on the ctx's host pool, as in batch verification.
+ * Grouping: an instance whose proof claims a padded size N of 2 .. BP_TUNE_DIRECT_MAX that the installed generators and the direct
+ * window tables cover (built on first use, as for proving), on a ctx that is not sharded, takes the GROUPED path: the host pool
+ * replays the transcripts (an instance that fails anywhere in decode or replay — a malformed or off-curve point, an identity under
+ * validate_and_append_point, an L_vec of the wrong length, a callback error — gets its own status and is left out of the launches;
+ * the batch goes on), the survivors are grouped by (circuit template, N), and a group — at most BP_TUNE_VERIFY_EACH instances, and
+ * what a 256 MB device arena holds for that N — is ONE sequence of launches on the ctx's stream: k_vfy_tables, k_vfy_batch with one
+ * chunk per proof (every proof keeps its own g / h rows), k_ve_heads, the table sums of the fixed bases (k_dt_accum_multi), k_ve_tail
+ * (the proofs' own points: P short variable-base MSMs), k_ve_check, one copy back of flags and points.  The host waits for the GPU
+ * ONCE per group (BP_VERIFY_EACH_WAITS_PER_GROUP), whatever the number of instances or N; the decompression of the call's points
+ * is one more wait per call, a circuit template that is not cached yet one per gadget.  Every other instance (N = 1, N beyond the
+ * tables' reach, a sharded ctx, a proof whose framing fails) is verified inside the same call by the single-instance route of
+ * bp_verifier_verify.  bp_verifier_verify, bp_r1cs_batch_verify and the scenario entry points keep their behaviour and code paths.
+ * bp_r1cs_verify_each_scenarios: the same for scenario statements; flat arrays as in bp_r1cs_batch_verify_scenarios, no alpha.
+ * bp_ctx_verify_each_stats: instances that took the grouped path / the single route, groups launched, host waits for the GPU made
+ * by the groups, since ctx creation. */
+#define BP_VERIFY_EACH_WAITS_PER_GROUP 1
+int bp_verifier_verify_batch(bp_ctx* ctx, size_t count, bp_cs* const* verifiers, const uint8_t* proofs, const size_t* proof_lens, int* status,
+                             uint64_t* check_points_xy, double* timing);
+int bp_r1cs_verify_each_scenarios(bp_ctx* ctx, size_t count, const int* scenarios, const uint64_t* params, const uint8_t* proofs, const size_t* proof_lens,
+                                  const uint64_t* commit_xy, const size_t* ms, const uint64_t* publics, const size_t* npubs, int* status,
+                                  uint64_t* check_points_xy, double* timing);
+int bp_ctx_verify_each_stats(bp_ctx* ctx, uint64_t* grouped_instances, uint64_t* single_instances, uint64_t* groups, uint64_t* host_waits);
+/* test hook: `count` independent variable-base MSMs through k_ve_tail alone; job j owns terms [offsets[j], offsets[j + 1]) of
+ * bases_xy (ark layout) and scalars (ark Montgomery words, or any 256-bit integers when scalars_canonical); out_xy: count affine
+ * points */
+int bp_debug_msm_each(bp_ctx* ctx, size_t count, const size_t* offsets, const uint64_t* bases_xy, const uint64_t* scalars, int scalars_canonical, uint64_t* out_xy);
+/* test hook, host only: k_ve_tail's own digit and layout functions (csrc/vfy_each.cuh) for job `job` of `count`: *first / *terms = the
+ * job's term range; for its term t (t < *terms, scalars: canonical words of ALL terms) and window w < 64: digits[64 t + w] = the 4-bit
+ * digit, planes[64 t + w] = its four bit-plane membership bits as the kernel tests them, lanes[w] = first lane of the window's quad,
+ * groups[w] = the LDS slot of the group sum the window folds into */
+int bp_debug_ve_plan(size_t count, const size_t* offsets, const uint64_t* scalars_canonical, size_t job, uint32_t* first, uint32_t* terms, uint8_t* digits,
+                     uint8_t* planes, uint32_t* lanes, uint32_t* groups);
 /* merlin::Transcript <-> bp_transcript handle: Strobe128 {state[200], pos, pos_begin, cur_flags} (merlin 3.0 src/strobe.rs) */
 int bp_transcript_export_state(const void* transcript, uint8_t out[203]);
 int bp_transcript_import_state(void* transcript, const uint8_t in[203]);
@@ -442,7 +489,8 @@ int bp_r1cs_batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenari
 #define BP_K_VFE_POINTS 12  /* k_vfe_points: decompression + serialization of a batch's points (device front end of batch verification) */
 #define BP_K_VFE_SPONGE 13  /* k_vfe_sponge: transcript replay + challenge derivation, one lane per proof */
 #define BP_K_VFE_PREPARE 14 /* k_vfe_consts + k_vfe_wv + k_vfe_sum2: challenge arithmetic, parameter blocks, tail scalars */
-#define BP_K_COUNT 15
+#define BP_K_VE_TAIL 15     /* k_ve_tail: the per-proof variable-base sums of bp_verifier_verify_batch */
+#define BP_K_COUNT 16
 int bp_ctx_set_profiling(bp_ctx* ctx, int enabled);
 /* accumulated milliseconds and launch count since the last reset */
 int bp_ctx_kernel_time(bp_ctx* ctx, int which, double* ms_total, uint64_t* launches);
@@ -487,6 +535,8 @@ int bp_ctx_reset_profiling(bp_ctx* ctx);
 #define BP_TUNE_PROVE_BATCH_FRONT 14   /* 1 (default): bp_prover_prove_batch runs the stages in front of the inner-product argument group-wide
                                   * too (see "Batch proving"); 0: those stages run one instance after the other on the single-proof
                                   * workspaces (A/B, tests).  Results never depend on it */
+#define BP_TUNE_VERIFY_EACH 15    /* most instances per group of bp_verifier_verify_batch (0 = default: what a 256 MB device arena holds, at most 4096;
+                                  * values above 4096 act as 4096) */
 int bp_ctx_set_tuning(bp_ctx* ctx, int knob, uint64_t value);
 
 /* The O(N) part of `Verifier::verification_scalars` (src/r1cs/verifier.rs:465-514, s from inner_product_proof.rs:279-311) for a
