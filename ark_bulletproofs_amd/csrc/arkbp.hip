@@ -28,6 +28,7 @@
 #include "small_batch.cuh"
 #include "small_batch_front.cuh"
 #include "vfy_each.cuh"
+#include "msm_batch.cuh"
 #include "vfe.hpp"
 #include "vfe_sched.hpp"
 static_assert(arkbp::vfe::PB_WORDS == arkbp::VFY_PB_WORDS, "parameter block layout shared by vfe.hip and r1cs.cuh");
@@ -341,6 +342,9 @@ struct bp_ctx {
     size_t tune_verify_each = 0;     // BP_TUNE_VERIFY_EACH: most instances per group (0 = what VE_ARENA_BUDGET holds, at most VE_GROUP_MAX)
     DevBuf ve_arena;
     uint64_t ve_grouped = 0, ve_single = 0, ve_groups = 0, ve_waits = 0;
+    // bp_msm_batch (msm_batch.inc): its knobs (0 = the default) and counters; it stages in ve_arena
+    uint64_t tune_msb_short = 0, tune_msb_slice = 0, tune_msb_max = 0, tune_msb_min_jobs = 0;   // BP_TUNE_MSM_BATCH_SHORT / _SLICE / _MAX / _MIN_JOBS
+    uint64_t mb_short = 0, mb_bucketed = 0, mb_single = 0, mb_groups = 0, mb_waits = 0;
     uint64_t folds_deferred = 0, folds_tab2 = 0;   // first folds deferred / second folds that came straight from the tables (bp_ctx_fold_stats)
     IpaState ipa_step;         // bp_ipa_begin .. bp_ipa_finish
     bool ipa_step_active = false;
@@ -2799,6 +2803,7 @@ __attribute__((target("avx512f"))) static int dbg_challenge_x8(void* const* trs,
 
 #include "prove_batch.inc"   // bp_prover_prove_batch, bp_prover_commit_batch (the C entry points are declared extern "C" by the header)
 #include "verify_each.inc"   // bp_verifier_verify_batch, bp_r1cs_verify_each_scenarios, bp_debug_msm_each
+#include "msm_batch.inc"     // bp_msm_batch, bp_msm_batch_dev, bp_ctx_msm_batch_stats, bp_debug_msm_batch_plan
 
 extern "C" {
 
@@ -2945,6 +2950,10 @@ int bp_ctx_set_tuning(bp_ctx* c, int knob, uint64_t value) {
         case BP_TUNE_VERIFY_EACH: c->tune_verify_each = (size_t)std::min<uint64_t>(value, 4096); return BP_OK;
         case BP_TUNE_PROVE_BATCH_FRONT: if (value > 1) return BP_E_ARG; c->tune_pb_front = (int)value; return BP_OK;
         case BP_TUNE_DIRECT_MAX: if (value > ((uint64_t)1 << 16)) return BP_E_ARG; c->tune_direct_max = (size_t)value; return BP_OK;
+        case BP_TUNE_MSM_BATCH_SHORT: c->tune_msb_short = value; return BP_OK;   // (the four take every value: 0 = the default)
+        case BP_TUNE_MSM_BATCH_MIN_JOBS: c->tune_msb_min_jobs = value; return BP_OK;
+        case BP_TUNE_MSM_BATCH_SLICE: c->tune_msb_slice = value; return BP_OK;
+        case BP_TUNE_MSM_BATCH_MAX: c->tune_msb_max = value; return BP_OK;
     }
     return BP_E_ARG;
 }

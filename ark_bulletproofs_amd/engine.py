@@ -1222,3 +1222,81 @@ Engine.verify_each = _verify_each
 Engine.verify_each_scenarios = _verify_each_scenarios
 Engine.verify_each_stats = _verify_each_stats
 Engine.debug_msm_each = _debug_msm_each
+
+
+# ---- many variable-base MSMs per call (bp_msm_batch) ---------------------------------------------------------------------------
+TUNE_MSM_BATCH_SHORT, TUNE_MSM_BATCH_SLICE, TUNE_MSM_BATCH_MAX, TUNE_MSM_BATCH_MIN_JOBS = 16, 17, 18, 19   # include/arkbp.h BP_TUNE_MSM_BATCH_* (Engine.set_tuning; 0 = default)
+MSM_BATCH_DEFAULTS = (8, None, 4096, 6)  # what 0 stands for: short, slice (None: msm_batch_default_slice), max, min jobs (csrc/msm_batch.inc MSB_DEFAULT_*)
+
+
+def msm_batch_default_slice(bucketed_terms):
+    """the slice cap in force when BP_TUNE_MSM_BATCH_SLICE is 0, for a call whose bucketed jobs hold this many terms (csrc/msm_batch.cuh msb_auto_slice)"""
+    return min(max(-(-int(bucketed_terms) // 128), 64), 512)
+
+MSM_BATCH_WAITS_PER_GROUP = 1            # BP_MSM_BATCH_WAITS_PER_GROUP
+K_MSM_BATCH = 16                         # BP_K_MSM_BATCH (Engine.kernel_time)
+
+
+def _job_offsets(lengths):
+    offs = [0]
+    for n in lengths:
+        offs.append(offs[-1] + int(n))
+    return offs, (C.c_size_t * len(offs))(*offs)
+
+
+def _msm_batch(self, jobs, canonical=False):
+    """bp_msm_batch: jobs = list of (bases (n_j, 8), scalars (n_j, 4)), as debug_msm_each takes them; one VariableBaseMSM::msm per job,
+    in one call.  Returns the (len(jobs), 8) affine results (the identity is all-zero)."""
+    n = len(jobs)
+    bs = [u64arr(b, 8) if len(b) else np.zeros((0, 8), dtype=np.uint64) for b, _ in jobs]
+    ss = [u64arr(s, 4) if len(s) else np.zeros((0, 4), dtype=np.uint64) for _, s in jobs]
+    if any(len(b) != len(s) for b, s in zip(bs, ss)):
+        raise ValueError("msm_batch: bases and scalars differ in length")
+    _, off_c = _job_offsets([len(b) for b in bs])
+    B = np.ascontiguousarray(np.concatenate(bs + [np.zeros((1, 8), dtype=np.uint64)]))
+    S = np.ascontiguousarray(np.concatenate(ss + [np.zeros((1, 4), dtype=np.uint64)]))
+    out = np.zeros((max(n, 1), 8), dtype=np.uint64)
+    check(lib().bp_msm_batch(self.ctx, C.c_size_t(n), off_c, ptr(B), ptr(S), int(canonical), ptr(out)), "bp_msm_batch")
+    return out[:n]
+
+
+def _msm_batch_dev(self, d_bases, d_scalars, lengths, canonical=False):
+    """bp_msm_batch_dev: resident operands (upload_points / upload_scalars), job j = the next lengths[j] terms.  Neither buffer is
+    modified.  Returns the (len(lengths), 8) affine results."""
+    n = len(lengths)
+    _, off_c = _job_offsets(lengths)
+    out = np.zeros((max(n, 1), 8), dtype=np.uint64)
+    check(lib().bp_msm_batch_dev(self.ctx, C.c_size_t(n), off_c, d_bases.ptr, d_scalars.ptr, int(canonical), ptr(out)), "bp_msm_batch_dev")
+    return out[:n]
+
+
+def _msm_batch_stats(self):
+    """(short jobs, bucketed jobs, single-route jobs, groups launched, host waits of the groups) since ctx creation"""
+    v = [C.c_uint64(0) for _ in range(5)]
+    check(lib().bp_ctx_msm_batch_stats(self.ctx, *[C.byref(x) for x in v]), "bp_ctx_msm_batch_stats")
+    return tuple(x.value for x in v)
+
+
+def debug_msm_batch_plan(lengths, scalars_canonical=None, job=0, short_max=0, slice_terms=0, batch_max=0):
+    """host only (bp_debug_msm_batch_plan): the plan bp_msm_batch makes for jobs of these lengths under the given knob values (0 =
+    default).  Returns (routes (count,) uint8, nslices (count,) uint32, slice_first, slice_len (nslices[job],) uint32,
+    digits (terms of `job`, 64) int8 or None without scalars)."""
+    n = len(lengths)
+    offs, off_c = _job_offsets(lengths)
+    route, nsl = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint32)
+    knobs = (C.c_uint64(int(short_max)), C.c_uint64(int(slice_terms)), C.c_uint64(int(batch_max)))
+    check(lib().bp_debug_msm_batch_plan(C.c_size_t(n), off_c, *knobs, None, C.c_size_t(job), ptr(route), ptr(nsl), None, None, None), "bp_debug_msm_batch_plan")
+    S, nt = int(nsl[job]), int(lengths[job])
+    first, length = np.zeros(max(S, 1), dtype=np.uint32), np.zeros(max(S, 1), dtype=np.uint32)
+    dg = np.zeros((max(nt, 1), 64), dtype=np.int8) if scalars_canonical is not None else None
+    sc = u64arr(scalars_canonical, 4) if scalars_canonical is not None and len(scalars_canonical) else np.zeros((1, 4), dtype=np.uint64)
+    if scalars_canonical is not None and len(sc) < offs[-1]:
+        raise ValueError("debug_msm_batch_plan: scalars of ALL terms are needed")
+    check(lib().bp_debug_msm_batch_plan(C.c_size_t(n), off_c, *knobs, ptr(sc), C.c_size_t(job), None, None, ptr(first), ptr(length), ptr(dg) if dg is not None else None),
+          "bp_debug_msm_batch_plan")
+    return route[:n], nsl[:n], first[:S], length[:S], (dg[:nt] if dg is not None else None)
+
+
+Engine.msm_batch = _msm_batch
+Engine.msm_batch_dev = _msm_batch_dev
+Engine.msm_batch_stats = _msm_batch_stats

@@ -63,6 +63,38 @@ int bp_msm(bp_ctx* ctx, const uint64_t* bases_xy, const uint64_t* scalars, size_
 /* Same with operands already resident: d_bases in the engine's layout (bp_points_import), d_scalars n x
  * 32 B.  This is the call the timed region of bench.py makes. */
 int bp_msm_dev(bp_ctx* ctx, const void* d_bases, const void* d_scalars, size_t n, int scalars_canonical, uint64_t out_xy[8]);
+/* `count` independent VariableBaseMSM::msm calls in one: job j owns terms [offsets[j], offsets[j + 1]) of bases_xy / scalars (count + 1
+ * offsets); out_xy[8 j ..] is exactly what bp_msm(ctx, bases_xy + 8 offsets[j], scalars + 4 offsets[j], n_j, scalars_canonical, ..)
+ * returns, whatever the other jobs of the call are.  The identity is all-zero; a job without terms gives the identity.  With
+ * scalars_canonical != 0 a scalar may be any 256-bit integer k (the term is k * P); Montgomery input is the ark form.
+ * Refused before any work with BP_E_ARG: a null ctx, offsets or out_xy, decreasing offsets, 2^31 terms or more in all, null bases or
+ * scalars with a non-zero total; then BP_E_NO_DEVICE on a host-only ctx.  count == 0 returns BP_OK at once (null pointers allowed).
+ * Routes, by job length n_j (results never depend on the route):
+ *   short     n_j <= BP_TUNE_MSM_BATCH_SHORT: one workgroup per job, bit-plane accumulators (k_ve_tail);
+ *   bucketed  up to BP_TUNE_MSM_BATCH_MAX: the job is cut into slices of at most BP_TUNE_MSM_BATCH_SLICE terms, one workgroup per
+ *             slice with 15 buckets per 4-bit window in LDS, then one workgroup per job combines the slices (k_msb_accum, k_msb_combine);
+ *   single    longer jobs, a job no staging arena could hold, EVERY job of a window-sharded ctx (the shard callbacks keep their
+ *             meaning) and EVERY job of a call with fewer than BP_TUNE_MSM_BATCH_MIN_JOBS short and bucketed jobs (a loop is the
+ *             faster path there): one after the other inside the call, exactly as bp_msm / bp_msm_dev.
+ * Consecutive short and bucketed jobs form a GROUP — what a 256 MB device arena holds; a single-route job in between also ends it —:
+ * one staging copy, one sequence of launches on the ctx's stream, BP_MSM_BATCH_WAITS_PER_GROUP host wait, one shared inversion for the
+ * affine results.
+ * The environment variable ARKBP_MSM_BATCH_ARENA=<bytes> (read per call; values from 1 to 256 MB) narrows the arena budget: it exists so
+ * that the cut into groups can be exercised with a few hundred terms; results never depend on it.
+ * bp_ctx_msm_batch_stats: jobs per route, groups, and host waits made by the groups (not those of single-route jobs), since ctx creation. */
+#define BP_MSM_BATCH_WAITS_PER_GROUP 1
+int bp_msm_batch(bp_ctx* ctx, size_t count, const size_t* offsets, const uint64_t* bases_xy, const uint64_t* scalars, int scalars_canonical, uint64_t* out_xy);
+/* operands resident: d_bases in the engine's layout (bp_points_import), d_scalars 32 B each; neither buffer is modified */
+int bp_msm_batch_dev(bp_ctx* ctx, size_t count, const size_t* offsets, const void* d_bases, const void* d_scalars, int scalars_canonical, uint64_t* out_xy);
+int bp_ctx_msm_batch_stats(bp_ctx* ctx, uint64_t* short_jobs, uint64_t* bucketed_jobs, uint64_t* single_jobs, uint64_t* groups, uint64_t* host_waits);
+/* test hook, host only: the plan bp_msm_batch makes for `count` jobs under the given knob values (0 = default), csrc/msm_batch.cuh's own
+ * functions: route[j] (0 short, 1 bucketed, 2 single: by the job's length alone, on a ctx that is not sharded and a call of enough
+ * jobs) and nslices[j] = the slices job j has on the bucketed route, for every job (the default slice cap follows from these jobs); for
+ * job `job`: slice_first[s] (a term index relative to offsets[0]) / slice_len[s] for s < nslices[job], and for its term t and window
+ * w < 64 digits[64 t + w] = the digit the kernel files the term under (unsigned 4-bit digits, 0 .. 15: no sign, no carry window;
+ * scalars_canonical: canonical words of ALL terms).  Every output may be null. */
+int bp_debug_msm_batch_plan(size_t count, const size_t* offsets, uint64_t short_max, uint64_t slice_terms, uint64_t batch_max, const uint64_t* scalars_canonical,
+                            size_t job, uint8_t* route, uint32_t* nslices, uint32_t* slice_first, uint32_t* slice_len, int8_t* digits);
 
 /* Window-sharded MSM for one large MSM across the GPUs of a node (every GPU holds all bases and scalars): the call
  * accumulates only Pippenger windows [w_lo, w_hi) of the bp_msm_window_count(curve, n) windows and returns that partial
@@ -490,7 +522,8 @@ int bp_r1cs_batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenari
 #define BP_K_VFE_SPONGE 13  /* k_vfe_sponge: transcript replay + challenge derivation, one lane per proof */
 #define BP_K_VFE_PREPARE 14 /* k_vfe_consts + k_vfe_wv + k_vfe_sum2: challenge arithmetic, parameter blocks, tail scalars */
 #define BP_K_VE_TAIL 15     /* k_ve_tail: the per-proof variable-base sums of bp_verifier_verify_batch */
-#define BP_K_COUNT 16
+#define BP_K_MSM_BATCH 16   /* k_msb_accum + k_msb_combine: the bucketed route of bp_msm_batch, one region per group */
+#define BP_K_COUNT 17
 int bp_ctx_set_profiling(bp_ctx* ctx, int enabled);
 /* accumulated milliseconds and launch count since the last reset */
 int bp_ctx_kernel_time(bp_ctx* ctx, int which, double* ms_total, uint64_t* launches);
@@ -537,6 +570,14 @@ int bp_ctx_reset_profiling(bp_ctx* ctx);
                                   * workspaces (A/B, tests).  Results never depend on it */
 #define BP_TUNE_VERIFY_EACH 15    /* most instances per group of bp_verifier_verify_batch (0 = default: what a 256 MB device arena holds, at most 4096;
                                   * values above 4096 act as 4096) */
+#define BP_TUNE_MSM_BATCH_SHORT 16 /* bp_msm_batch: jobs of at most this many terms take the short route (0 = default: 8) */
+#define BP_TUNE_MSM_BATCH_SLICE 17 /* bp_msm_batch: most terms per slice of a bucketed job.  0 = default: the call's bucketed terms / 128, at least 64 and at
+                                    * most 512 — many jobs: long slices, few jobs: enough slices to occupy the CUs.  Every value >= 1 is accepted, values
+                                    * above 2^30 act as 2^30 */
+#define BP_TUNE_MSM_BATCH_MAX 18   /* bp_msm_batch: jobs above the short route and of at most this many terms take the bucketed route, longer ones the single
+                                    * route (0 = default: 4096; a value at or below the short one leaves no bucketed route) */
+#define BP_TUNE_MSM_BATCH_MIN_JOBS 19 /* bp_msm_batch: a call with fewer short and bucketed jobs than this runs every job on the single route (0 = default: 6;
+                                    * 1 = never): a group costs the latency of one serial Horner chain whatever it holds.  Results never depend on the four */
 int bp_ctx_set_tuning(bp_ctx* ctx, int knob, uint64_t value);
 
 /* The O(N) part of `Verifier::verification_scalars` (src/r1cs/verifier.rs:465-514, s from inner_product_proof.rs:279-311) for a
