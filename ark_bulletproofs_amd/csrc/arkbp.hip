@@ -324,6 +324,7 @@ struct bp_ctx {
     size_t tune_direct_max = 8192;   // BP_TUNE_DIRECT_MAX: padded sizes up to this one prove over the direct tables (0 = never)
     u32* h_dt = nullptr;             // pinned: the results of one launch (or its partial points, see msm_direct_launch)
     u32 dt_pending_parts = 1;        // partial points per MSM on their way to h_dt
+    u32 dt_last_nblk = 0;            // workgroups per MSM of the last msm_direct_launch (bp_debug_msm_direct reports it)
     uint64_t dt_runs = 0;            // MSMs answered from the direct tables
     // bp_prover_prove_batch: its own device arena and pinned staging (never the single-proof workspaces above), and its counters
     size_t tune_prove_batch = 0;     // BP_TUNE_PROVE_BATCH: most instances per lockstep group (0 = as many as PB_ARENA_BUDGET allows)
@@ -1670,6 +1671,7 @@ template <class C> static int msm_direct_launch(bp_ctx* ctx, const DtJobs& jobs,
         if (nblk > 1 && !host_sum) hipLaunchKernelGGL(k_dt_finish<C>, dim3((u32)nout), dim3(256), 0, st, part, nblk, res);
     }
     ctx->dt_pending_parts = host_sum ? nblk : 1u;
+    ctx->dt_last_nblk = nblk;
     HIPCHK(hipMemcpyAsync(ctx->h_dt, host_sum ? part : res, (size_t)nout * ctx->dt_pending_parts * 96, hipMemcpyDeviceToHost, st));
     return BP_OK;
 }
@@ -2805,6 +2807,66 @@ __attribute__((target("avx512f"))) static int dbg_challenge_x8(void* const* trs,
 #include "verify_each.inc"   // bp_verifier_verify_batch, bp_r1cs_verify_each_scenarios, bp_debug_msm_each
 #include "msm_batch.inc"     // bp_msm_batch, bp_msm_batch_dev, bp_ctx_msm_batch_stats, bp_debug_msm_batch_plan
 
+// test hook: the production msm_direct on caller-chosen jobs (include/arkbp.h bp_debug_msm_direct).  Everything a job would read is
+// checked here on the host — k_dt_accum itself trusts its descriptors
+template <class C>
+static int dbg_msm_direct(bp_ctx* ctx, size_t njobs, const uint32_t* desc, const uint64_t* imm, const uint64_t* const* scalars, const size_t* scalar_lens,
+                          uint64_t* out_xy, uint32_t* workgroups) {
+    typedef typename C::Fr FrP;
+    hipStream_t st = ctx->stream;
+    const size_t nbases = 2 + 2 * ctx->dt_cap;
+    DtJobs jobs; memset(&jobs, 0, sizeof jobs);
+    size_t seg_off[DT_MAXOUT][DT_MAXSEG], seg_len[DT_MAXOUT][DT_MAXSEG], total = 0;
+    for (size_t j = 0; j < njobs; j++) {
+        const uint32_t* d = desc + j * BP_DEBUG_DT_DESC_WORDS;
+        DtJob& jb = jobs.job[j];
+        if (d[0] > (uint32_t)DT_MAXSEG || d[1] > 1) { g_err = "bp_debug_msm_direct: bad segment count or immediate flag"; return BP_E_ARG; }
+        jb.nseg = d[0]; jb.has_imm = d[1]; jb.imm_base = d[1] ? d[2] : 0;
+        if (jb.has_imm) {
+            if (!imm || jb.imm_base >= nbases) { g_err = "bp_debug_msm_direct: the immediate term's base is outside the tables"; return BP_E_ARG; }
+            memcpy(jb.imm, imm + 4 * j, 32);
+        }
+        size_t terms = jb.has_imm;
+        for (uint32_t s = 0; s < jb.nseg; s++) {
+            const uint32_t* sd = d + 3 + 5 * s;
+            const size_t base0 = sd[0], count = sd[1], fn = sd[3];
+            if (!count || sd[2] > 2 || sd[4] > 1) { g_err = "bp_debug_msm_direct: empty segment, or bad format / fold_hi"; return BP_E_ARG; }
+            // the last element term count - 1 stands for (small.cuh DtSeg::fold_n); the remapping is monotonic in the term
+            const size_t last = fn ? ((count - 1) / fn) * 2 * fn + (count - 1) % fn + (sd[4] ? fn : 0) : count - 1;
+            if (base0 >= nbases || last >= nbases - base0) { g_err = "bp_debug_msm_direct: a segment leaves the tables"; return BP_E_ARG; }
+            if (!scalars || !scalar_lens || !scalars[j * DT_MAXSEG + s] || scalar_lens[j * DT_MAXSEG + s] <= last) {
+                g_err = "bp_debug_msm_direct: a scalar array is shorter than the elements its segment visits"; return BP_E_ARG;
+            }
+            seg_off[j][s] = total; seg_len[j][s] = last + 1;
+            total += last + 1;
+            terms += count;
+            jb.seg[s].base0 = (u32)base0; jb.seg[s].count = (u32)count; jb.seg[s].resident = sd[2]; jb.seg[s].fold_n = (u32)fn; jb.seg[s].fold_hi = sd[4];
+        }
+        if (!terms) { g_err = "bp_debug_msm_direct: a job without terms"; return BP_E_ARG; }
+        jb.terms = (u32)terms;
+    }
+    BPCHK(ctx->io_scal.ensure(std::max<size_t>(total, 1) * 32));
+    u32* d_sc = ctx->io_scal.as<u32>();
+    for (size_t j = 0; j < njobs; j++) {
+        for (uint32_t s = 0; s < jobs.job[j].nseg; s++) {
+            DtSeg& sg = jobs.job[j].seg[s];
+            u32* dst = d_sc + seg_off[j][s] * 8;
+            const size_t n = seg_len[j][s];
+            HIPCHK(hipMemcpyAsync(dst, scalars[j * DT_MAXSEG + s], n * 32, hipMemcpyHostToDevice, st));
+            if (sg.resident == 1) hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, dst, dst, (u32)n);
+            sg.sc = dst;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    J4 r[DT_MAXOUT];
+    A4 a[DT_MAXOUT];
+    BPCHK(msm_direct<C>(ctx, jobs, (int)njobs, r));
+    if (workgroups) *workgroups = ctx->dt_last_nblk;
+    to_aff_batch<C>(r, (int)njobs, a);
+    for (size_t j = 0; j < njobs; j++) { memcpy(out_xy + 8 * j, a[j].x.v, 32); memcpy(out_xy + 8 * j + 4, a[j].y.v, 32); }
+    return BP_OK;
+}
+
 extern "C" {
 
 int bp_device_count(void) {
@@ -3160,11 +3222,27 @@ int bp_gens_tables_check(bp_ctx* c, uint64_t* bad_fold_entries, uint64_t* bad_ms
     return c->curve == 0 ? tables_check<Secq>(c, bad_fold_entries, bad_msm_rows) : tables_check<Zorro>(c, bad_fold_entries, bad_msm_rows);
 }
 int bp_debug_tables_ptr(bp_ctx* c, int which, void** dptr, size_t* nbytes) {
-    if (!c || !dptr || !nbytes || which < 0 || which > 3) return BP_E_ARG;
+    if (!c || !dptr || !nbytes || which < 0 || which > 6) return BP_E_ARG;
+    if (which >= 4) {   // the direct window tables (small.cuh) and the 8-bit Pedersen tables (pedersen.cuh)
+        DevBuf& t = which == 4 ? c->dt_tab : which == 5 ? c->pc_dt : c->pc_table;
+        const size_t size = which == 4 ? (c->dt_cap ? (2 + 2 * c->dt_cap) * DT_BASE_BYTES : 0) : which == 5 ? (size_t)2 * DT_BASE_BYTES : PC_TABLE_BYTES;
+        const bool built = t.p && size && t.cap >= size;
+        *dptr = built ? t.p : nullptr; *nbytes = built ? size : 0;
+        return BP_OK;
+    }
     DevBuf& b = which == 0 ? c->ftab_G : which == 1 ? c->ftab_H : which == 2 ? c->fb_G : c->fb_H;
     const size_t used = which < 2 ? (c->ftab_n ? (size_t)c->ftab_nwin * ((size_t)1 << (c->ftab_w - 1)) * c->ftab_n * 64 : 0) : (size_t)FB_ROWS * c->fb_cap * 64;
     *dptr = used ? b.p : nullptr; *nbytes = used;
     return BP_OK;
+}
+int bp_debug_msm_direct(bp_ctx* c, size_t njobs, const uint32_t* desc, const uint64_t* imm, const uint64_t* const* scalars, const size_t* scalar_lens,
+                        uint64_t* out_xy, uint32_t* workgroups) {
+    if (!c || !desc || !out_xy || njobs < 1 || njobs > (size_t)DT_MAXOUT) { g_err = "bp_debug_msm_direct: bad argument"; return BP_E_ARG; }
+    if (c->host_only) return BP_E_NO_DEVICE;
+    if (!c->dt_cap || !c->dt_tab.p) { g_err = "bp_debug_msm_direct: the direct tables are not built (bp_gens_direct_tables)"; return BP_E_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    return c->curve == 0 ? dbg_msm_direct<Secq>(c, njobs, desc, imm, scalars, scalar_lens, out_xy, workgroups)
+                         : dbg_msm_direct<Zorro>(c, njobs, desc, imm, scalars, scalar_lens, out_xy, workgroups);
 }
 int bp_gens_download(bp_ctx* c, uint64_t* G_xy, uint64_t* H_xy, size_t n) {
     if (!c || !G_xy || !H_xy || n > c->gens_cap) return BP_E_ARG;

@@ -891,8 +891,54 @@ def _debug_poke(self, dptr, data=None, nbytes=0):
     check(lib().bp_dev_upload(self.ctx, C.c_void_p(dptr), ptr(arr), C.c_size_t(arr.nbytes)), "bp_dev_upload")
 
 
+def _debug_table_points(self, which):
+    """every entry of table `which` (bp_debug_tables_ptr) as ark words, (entries, 8): bp_points_export into a buffer of its own, then
+    one download.  None when the table is not built."""
+    dptr, nbytes = self.debug_tables_ptr(which)
+    if not dptr:
+        return None
+    buf = DeviceBuffer(self, nbytes)
+    try:
+        check(lib().bp_points_export(self.ctx, C.c_void_p(dptr), buf.ptr, C.c_size_t(nbytes // 64)), "bp_points_export")
+        self.sync()
+        return buf.download().reshape(-1, 8)
+    finally:
+        buf.free()
+
+
+DT_MAXSEG, DT_MAXOUT, DT_DESC_WORDS = 3, 6, 18   # csrc/small.cuh; include/arkbp.h BP_DEBUG_DT_DESC_WORDS
+
+
+def _debug_msm_direct(self, jobs, with_workgroups=False):
+    """bp_debug_msm_direct: sums over the direct window tables through the prover's msm_direct.  jobs = 1 .. 6 of (segments, imm):
+    segments = up to three (base0, count, format, fold_n, fold_hi, scalars (n, 4) u64), imm = None or (base, 256-bit integer).
+    Returns the (len(jobs), 8) affine results (the identity is all-zero), with_workgroups: and k_dt_accum's workgroups per job."""
+    n = len(jobs)
+    desc = np.zeros((n, DT_DESC_WORDS), dtype=np.uint32)
+    imm = np.zeros((n, 4), dtype=np.uint64)
+    ptrs, lens, keep = (C.c_void_p * (DT_MAXSEG * n))(), (C.c_size_t * (DT_MAXSEG * n))(), []
+    for j, (segs, im) in enumerate(jobs):
+        if len(segs) > DT_MAXSEG:
+            raise ValueError("debug_msm_direct: more than %d segments" % DT_MAXSEG)
+        desc[j, 0] = len(segs)
+        if im is not None:
+            desc[j, 1], desc[j, 2] = 1, im[0]
+            imm[j] = [(int(im[1]) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+        for s, (base0, count, fmt, fold_n, fold_hi, sc) in enumerate(segs):
+            desc[j, 3 + 5 * s: 8 + 5 * s] = [base0, count, fmt, fold_n, fold_hi]
+            sc = u64arr(sc, 4)
+            keep.append(sc)
+            ptrs[DT_MAXSEG * j + s], lens[DT_MAXSEG * j + s] = sc.ctypes.data, len(sc)
+    out = np.zeros((n, 8), dtype=np.uint64)
+    nblk = C.c_uint32(0)
+    check(lib().bp_debug_msm_direct(self.ctx, C.c_size_t(n), ptr(desc), ptr(imm), ptrs, lens, ptr(out), C.byref(nblk)), "bp_debug_msm_direct")
+    return (out, nblk.value) if with_workgroups else out
+
+
 Engine.gens_tables_check = _gens_tables_check
 Engine.debug_tables_ptr = _debug_tables_ptr
+Engine.debug_table_points = _debug_table_points
+Engine.debug_msm_direct = _debug_msm_direct
 Engine.debug_poke = _debug_poke
 
 

@@ -226,9 +226,37 @@ int bp_gens_direct_tables(bp_ctx* ctx, size_t count, size_t* bytes_out);
  * corrupted entry (a bit flip in 150 GB of HBM, a bad build) cannot be found by proving; this finds it, in about the time of one
  * proof.  Tables that are not installed count as 0. */
 int bp_gens_tables_check(bp_ctx* ctx, uint64_t* bad_fold_entries, uint64_t* bad_msm_rows);
-/* test hook: device address and size in bytes of a table (which: 0 / 1 fold tables of G / H, layout [window][digit-1][i] x 64 B;
- * 2 / 3 MSM rows of G / H, layout [row][i] x 64 B); NULL / 0 when not installed */
+/* test hook: device address and size in bytes of a table; NULL / 0 when it is not built.  which:
+ *   0 / 1  fold tables of G / H, layout [window][digit-1][i] x 64 B;
+ *   2 / 3  MSM rows of G / H, layout [row][i] x 64 B;
+ *   4      the direct window tables of the small-statement path (bp_gens_direct_tables; cap = bp_ctx_direct_stats' bases per vector):
+ *          (2 + 2 cap) * 61440 bytes, bases [B, B_blinding | G[0..cap) | H[0..cap)], entry ((base * 64 + w) * 15 + d - 1) x 64 B
+ *          = d * 16^w * base for w < 64, 1 <= d <= 15 (no entry is the identity).  A ctx that shares generators (bp_gens_share)
+ *          reports the owner's address;
+ *   5      the direct window tables of B, B_blinding alone that batches of up to 4096 commitments read: 2 bases, layout as 4;
+ *   6      the 8-bit tables that larger commitment batches read: layout [b < 2][w < 32][d < 256] x 64 B = d * 256^w * base_b, b = 0
+ *          for B, 1 for B_blinding; d = 0 is the identity.
+ *   5 and 6 exist once the ctx has run its first bp_pedersen_commit_batch.
+ * Every entry is an affine point in the RESIDENT layout: bp_points_export turns entries into ark words (the identity: all zero). */
 int bp_debug_tables_ptr(bp_ctx* ctx, int which, void** dptr, size_t* nbytes);
+/* test hook: `njobs` (1 .. 6) sums over the direct window tables through the prover's own msm_direct (k_dt_accum, k_dt_finish, the
+ * host's sum of partial points), as commit_direct and the rounds of the inner-product argument launch them.
+ * desc: BP_DEBUG_DT_DESC_WORDS words per job = nseg (0 .. 3), has_imm (0 / 1), imm_base, then (base0, count, format, fold_n, fold_hi)
+ * for each of three segments (those past nseg are ignored).  Bases are indices into table 4 of bp_debug_tables_ptr: 0 = B,
+ * 1 = B_blinding, 2 + i = G[i], 2 + cap + i = H[i].  Term j of a segment is element t = j when fold_n = 0, else
+ * t = (j / fold_n) * 2 * fold_n + j % fold_n + (fold_hi ? fold_n : 0); it multiplies base base0 + t by scalar t of the segment's
+ * array scalars[3 * job + seg] (4 words each, scalar_lens[3 * job + seg] of them: at least the last visited element + 1).
+ * format 0: any 256-bit integers, used digit by digit as they are (an integer k >= r still gives (k mod r) * base);
+ * format 1: ark Montgomery words, which the hook turns into the resident form first (k_scalars_import); format 2: ark Montgomery
+ * words, read by the kernel as they are.  With has_imm the job's term 0 is imm[4 * job ..] (a 256-bit integer, as format 0) times
+ * base imm_base.  out_xy: one affine point per job, ark layout, all-zero words for the identity.  *workgroups (may be
+ * NULL): k_dt_accum's workgroups per job in this launch — 1: its points are the results; 2 .. 16: the host added the partial
+ * points; more: k_dt_finish did.
+ * BP_E_ARG — and nothing launched — when the tables are not built, a job has no terms, a used segment has count 0, a format is
+ * unknown, a scalar array is too short, or any element a job would visit lies outside [0, 2 + 2 cap). */
+#define BP_DEBUG_DT_DESC_WORDS 18
+int bp_debug_msm_direct(bp_ctx* ctx, size_t njobs, const uint32_t* desc, const uint64_t* imm, const uint64_t* const* scalars, const size_t* scalar_lens,
+                        uint64_t* out_xy, uint32_t* workgroups);
 /* PedersenGens::default() -> (B, B_blinding); host only */
 int bp_pedersen_gens(int curve, uint64_t B_xy[8], uint64_t B_blinding_xy[8]);
 /* GeneratorsChain for label 'G'|'H' || LE32(party) (src/generators.rs:71-121), first `count` points; host only */
