@@ -241,7 +241,9 @@ struct bp_ctx {
     std::vector<hipEvent_t> event_pool;
     // MSM workspaces
     DevBuf canon, hist, lvl_off, totals, cursor, entries, slots, bin_cur, boff, lvA, lvB, Tbuf, io_pts, io_scal, io_out;
-    DevBuf fs_bcnt, fs_loff, fs_binch, fs_sums;   // fixed-shape MSM pipeline (msm.cuh 7)
+    DevBuf fs_bcnt, fs_loff, fs_binch, fs_sums, fs_over;   // fixed-shape MSM pipeline (msm.cuh 7); fs_over: one overflow word per job
+    int tune_msm_pair = 1;                        // BP_TUNE_MSM_PAIR: L and R of an inner-product round as two jobs of one launch chain (msm_run_pair)
+    uint64_t pair_passes = 0, pair_redone = 0;    // paired passes completed / jobs of those redone on the general path (bp_ctx_msm_pair_stats)
     // IPA workspaces (resident layouts)
     DevBuf ipa_G, ipa_H, ipa_a, ipa_b, ipa_Gf, ipa_Hf, ipa_sL, ipa_sR, ipa_part, ipa_Q, ipa_jac, ipa_pref, ipa_cG, ipa_cH;
     // generator tables (BulletproofGens party 0, PedersenGens), resident layout
@@ -604,23 +606,23 @@ template <class C> static int msm_run_fs_glv(bp_ctx* ctx, const BaseSegs& segs_i
     const u32 gp = (u32)((n + (size_t)256 * bp.tpt - 1) / ((size_t)256 * bp.tpt));
     for (int wa = 0; wa < (int)bp.wb; wa += wg) {
         const int we = std::min<int>((int)bp.wb, wa + wg);
-        hipLaunchKernelGGL(k_msm_bin_partition<C>, dim3(gp), dim3(256), ((size_t)(we - wa) * bp.NBIN + (wa == 0 ? bp.top_nb : 0)) * 4, st, d_scalars, ctx->canon.as<u32>(),
-                           ctx->hist.as<u32>(), pl, scalars_mont, bp, sp, ctx->bin_cur.as<u32>(), ctx->slots.as<u32>(), d_over, wa, we, wa == 0 ? 1 : 0);
+        hipLaunchKernelGGL(k_msm_bin_partition<C>, dim3(gp), dim3(256), ((size_t)(we - wa) * bp.NBIN + (wa == 0 ? bp.top_nb : 0)) * 4, st, PerJob<ScalSegs>{{d_scalars}}, ctx->canon.as<u32>(),
+                           ctx->hist.as<u32>(), pl, scalars_mont, bp, sp, ctx->bin_cur.as<u32>(), ctx->slots.as<u32>(), d_over, wa, we, wa == 0 ? 1 : 0, FsJobs{});
     }
     hipLaunchKernelGGL(k_msm_bin_sort_fs, dim3(bp.NBIN, bp.wb + fp.has_top), dim3(256), (((size_t)1 << bp.LB) + 8 + bp.cap) * 4, st, ctx->slots.as<u32>(),
                        ctx->bin_cur.as<u32>(), ctx->hist.as<u32>(), ctx->boff.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(), ctx->fs_binch.as<u32>(),
-                       d_over, pl, bp, sp, chl_fs);
+                       d_over, pl, bp, sp, chl_fs, FsJobs{});
     {
         ScopedK acc(ctx, BP_K_MSM_ACCUM_FS);
-        hipLaunchKernelGGL(k_msm_accum_fs<C>, dim3((u32)((maxch + 255) / 256)), dim3(256), 0, st, segs, ctx->slots.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
-                           ctx->boff.as<u32>(), ctx->fs_binch.as<u32>(), ctx->lvA.as<u32>(), pl, bp, fp, chl_fs, d_info);
+        hipLaunchKernelGGL(k_msm_accum_fs<C>, dim3((u32)((maxch + 255) / 256)), dim3(256), 0, st, PerJob<BaseSegs>{{segs}}, ctx->slots.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
+                           ctx->boff.as<u32>(), ctx->fs_binch.as<u32>(), ctx->lvA.as<u32>(), pl, bp, fp, chl_fs, d_info, FsJobs{});
     }
     {
         ScopedK agg(ctx, BP_K_MSM_AGG);
         MSM_LAUNCH_REDUCE_FS(red_g, dim3((u32)(((size_t)bp.wb * pl.NB * red_g + 255) / 256)), ctx->lvA.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
-                           ctx->fs_binch.as<u32>(), ctx->fs_sums.as<u32>(), pl, bp, fp, chl_fs, red_g);
+                           ctx->fs_binch.as<u32>(), ctx->fs_sums.as<u32>(), pl, bp, fp, chl_fs, red_g, FsJobs{});
         MSM_LAUNCH_MARGINALS_FS(dim3((u32)tc), ctx->fs_sums.as<u32>(), ctx->lvA.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
-                           ctx->Tbuf.as<u32>(), pl, bp, fp, chl_fs, d_info, d_over);
+                           ctx->Tbuf.as<u32>(), pl, bp, fp, chl_fs, d_info, d_over, FsJobs{});
     }
     HIPCHK(hipMemcpyAsync(ctx->h_T, ctx->Tbuf.p, tb, hipMemcpyDeviceToHost, st));
     total.stop();
@@ -682,11 +684,186 @@ template <class C> static int shard_point_reduce(bp_ctx* ctx, J4& part) {
     return BP_OK;
 }
 
+// ---- plans shared by msm_run and msm_run_pair -----------------------------------------------------------------------------------
+static bool msm_use_marginals(const bp_ctx* ctx, const MsmPlan& pl) {
+    static const bool force_marginals = getenv("ARKBP_MSM_MARGINALS") != nullptr;   // A/B: the bit-marginal bucket aggregation everywhere
+    return force_marginals || pl.B < ctx->tune_msm_wsum_min;
+}
+// two-level (binned) sort for large MSMs: the full windows go to bin regions, the short top window keeps its slots behind them
+template <class C> static bool msm_bin_plan(const bp_ctx* ctx, size_t n, const MsmPlan& pl, BinPlan& bp) {
+    memset(&bp, 0, sizeof bp);
+    const int bits_last = C::Fr::BITS - pl.c * (pl.W - 1);
+    const int wbn = bits_last < pl.c - 1 ? pl.W - 1 : pl.W;
+    static const bool no_bins = getenv("ARKBP_MSM_NOBIN") != nullptr;
+    if (!(n >= ctx->tune_msm_bin_min && wbn > 0 && !no_bins)) return false;
+    u32 nbin = 1, lg = 0;
+    while ((size_t)nbin * 8192 < n && nbin < (u32)pl.NB) { nbin <<= 1; lg++; }
+    // bins of up to 12 K entries (43 KB of LDS in the bin sort) where that keeps the MSM inside the fixed-shape pipeline's bin
+    // limit: 2^20 < n <= 1.5 * 2^20, e.g. the 1.25 M-term MSM of a 4096-proof batch verification
+    if ((size_t)wbn * nbin + 1 > MSM_FS_MAXBINS && nbin >= 2 && (size_t)(nbin / 2) * 12288 >= n && (size_t)wbn * (nbin / 2) + 1 <= MSM_FS_MAXBINS) { nbin >>= 1; lg--; }
+    int LB = pl.c - 1 - (int)lg;
+    while (LB > 11) { nbin <<= 1; LB--; }
+    const double mu = (double)n / nbin;
+    const size_t cap = std::min<size_t>(n, (size_t)(mu + 8.0 * std::sqrt(mu) + 64.0));
+    const size_t lds_sort = (((size_t)1 << LB) + 4 + cap) * 4;
+    if (!(n < ((size_t)1 << (31 - LB)) && lds_sort <= 64 * 1024 && (size_t)wbn * nbin * cap < ((size_t)1 << 31))) return false;
+    bp.LB = (u32)LB; bp.NBIN = nbin; bp.cap = (u32)cap; bp.wb = (u32)wbn;
+    static const int tpt_env = getenv("ARKBP_MSM_TPT") ? atoi(getenv("ARKBP_MSM_TPT")) : 0;
+    bp.tpt = tpt_env > 0 ? (u32)tpt_env : (u32)std::min<size_t>(16, std::max<size_t>(1, n / (256 * 512)));
+    if (wbn < pl.W) {   // same-address device atomics serialise (~170 ns each): count a narrow top window per workgroup
+        const size_t nb_top = std::min<size_t>((size_t)pl.NB, ((size_t)1 << std::max(bits_last, 0)) + 1);
+        if (nb_top <= 2048) bp.top_nb = (u32)nb_top;
+    }
+    return true;
+}
+// slot plan of the one-pass sort for the windows from w_first on, behind first_slot entries; returns the entries in all
+template <class C> static size_t msm_make_slots(const MsmPlan& pl, size_t n, SlotPlan& sp, int w_first, size_t first_slot) {
+    memset(&sp, 0, sizeof sp);
+    size_t nslots = first_slot;
+    for (int w = w_first; w < pl.W; w++) {
+        const int bits_left = C::Fr::BITS - pl.c * w;  // scalar bits at or above this window's base
+        size_t nb_eff = (size_t)pl.NB;
+        if (bits_left < pl.c - 1) nb_eff = std::min<size_t>(nb_eff, ((size_t)1 << std::max(bits_left, 0)) + 1);
+        size_t cap = std::min<size_t>(n, 2 * ((n + nb_eff - 1) / nb_eff) + 32);
+        sp.base[w] = (u32)nslots; sp.cap[w] = (u32)cap;
+        nslots += nb_eff * cap;
+    }
+    return nslots;
+}
+// the MSM goes through the fixed-shape pipeline (msm.cuh 7)
+static bool msm_fs_fits(const bp_ctx* ctx, const MsmPlan& pl, const BinPlan& bp, bool binned, const BaseSegs& segs) {
+    static const bool no_fs = getenv("ARKBP_MSM_NOFS") != nullptr;
+    return binned && msm_use_marginals(ctx, pl) && !no_fs && (bp.wb == (u32)pl.W || bp.top_nb > 0) && (size_t)bp.wb * bp.NBIN + 1 <= MSM_FS_MAXBINS && !segs.fixed_c4;
+}
+// The fixed-shape pipeline for J <= MSM_JOBS MSMs of n terms each — same plan, own scalars and bases — as ONE chain of launches with
+// the job in grid.z: no host wait before the last kernel, one D2H copy of the J result blocks, one wait, the J host Horner tails.
+// Every job works in its own stride of the ctx's buffers (FsJobs), so each result is the sum it is alone.  ran = false: the shape
+// does not fit, nothing was launched.  over[j]: job j raised its overflow word (skewed scalars) and results[j] is not written; the
+// caller redoes that job on the general path.
+template <class C> static int msm_fs_jobs(bp_ctx* ctx, int J, const BaseSegs* segs, const ScalSegs* scalars, size_t n, int scalars_mont, const MsmPlan& pl,
+                                          const BinPlan& bp, J4* results, bool* over, bool& ran) {
+    typedef host::Grp<C> G;
+    static const bool mtrace = getenv("ARKBP_MSM_TRACE") != nullptr;
+    hipStream_t st = ctx->stream;
+    ran = false;
+    const auto tfs = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_f0 = mtrace ? tfs() : 0;
+    const u32 chl_fs = fs_chunk_cap(ctx, (double)n * bp.wb * (1.0 - std::ldexp(1.0, -pl.c)), (double)bp.wb * pl.NB, bp.wb < (u32)pl.W ? (double)n : 0.0, (double)bp.top_nb);   // (entries per chunk; any value from 8)
+    FsPlan fp; memset(&fp, 0, sizeof fp);
+    fp.has_top = bp.wb < (u32)pl.W ? 1u : 0u;
+    fp.nbins = bp.wb * bp.NBIN + fp.has_top;
+    if (fp.has_top) { u32 t = bp.top_nb; while (t) { fp.top_bits++; t >>= 1; } }
+    const size_t nwin = (size_t)(pl.w_hi - pl.w_lo);
+    const u32 red_g = (size_t)bp.wb * pl.NB > 49152 ? 1u : 4u;   // lanes per bucket of k_msm_reduce_fs: groups while the lanes fit the chip at once, one lane per bucket beyond
+    const size_t maxch = (n * nwin) / chl_fs + std::min<size_t>(n * nwin, nwin * (size_t)pl.NB) + 64;
+    fp.max_chunks = (u32)maxch;
+    SlotPlan sp;
+    const size_t nslots = msm_make_slots<C>(pl, n, sp, (int)bp.wb, (size_t)bp.wb * bp.NBIN * bp.cap);
+    fp.top_parts = (u32)std::min<size_t>(MSM_TOP_PARTS_MAX, std::max<size_t>(4, n >> 15));
+    const size_t tc = (size_t)bp.wb * pl.c + (size_t)fp.top_bits * fp.top_parts;
+    const size_t tb = tc * 96 + 64;
+    if (J < 1 || J > MSM_JOBS || !(nslots < ((size_t)1 << 32) && maxch < ((size_t)1 << 31))) return BP_OK;
+    const size_t nj = (size_t)J;
+    FsJobs jb; memset(&jb, 0, sizeof jb);
+    jb.canon = n * 8; jb.hist = pl.B; jb.bin_cur = (size_t)pl.W * bp.NBIN; jb.slots = nslots; jb.buckets = pl.B; jb.binch = MSM_FS_MAXBINS + 1;
+    jb.part = maxch * 24; jb.sums = (size_t)bp.wb * pl.NB * 24; jb.T = tb / 4; jb.over = 1;
+    BPCHK(ctx->canon.ensure(nj * jb.canon * 4));
+    // hist, the bin cursors and the overflow words are all-zero between MSMs in every job's region: their last readers restore that
+    BPCHK(ctx->hist.ensure_zeroed(nj * jb.hist * 4, st));
+    BPCHK(ctx->bin_cur.ensure_zeroed(nj * jb.bin_cur * 4, st));
+    BPCHK(ctx->fs_over.ensure_zeroed(MSM_JOBS * 4, st));
+    BPCHK(ctx->slots.ensure(nj * jb.slots * 4));
+    BPCHK(ctx->boff.ensure(nj * jb.buckets * 4));
+    BPCHK(ctx->fs_bcnt.ensure(nj * jb.buckets * 4));
+    BPCHK(ctx->fs_loff.ensure(nj * jb.buckets * 4));
+    BPCHK(ctx->fs_binch.ensure(nj * jb.binch * 4));
+    BPCHK(ctx->fs_sums.ensure(nj * jb.sums * 4));
+    BPCHK(ctx->lvA.ensure(nj * jb.part * 4));
+    BPCHK(ctx->Tbuf.ensure(nj * tb));
+    if (ctx->h_T_cap < nj * tb) {
+        if (ctx->h_T) HIPCHK(hipHostFree(ctx->h_T));
+        ctx->h_T = nullptr; ctx->h_T_cap = 0;
+        HIPCHK(hipHostMalloc((void**)&ctx->h_T, nj * tb + 4096));
+        ctx->h_T_cap = nj * tb + 4096;
+    }
+    PerJob<ScalSegs> sj; memset(&sj, 0, sizeof sj);
+    PerJob<BaseSegs> bj; memset(&bj, 0, sizeof bj);
+    for (int j = 0; j < J; j++) { sj.j[j] = scalars[j]; bj.j[j] = segs[j]; }
+    ran = true;
+    ScopedK total(ctx, BP_K_MSM_TOTAL);
+    u32* d_over = ctx->fs_over.as<u32>();
+    u32* d_info = ctx->Tbuf.as<u32>() + tc * 24;
+    const int wg = std::max(1, (int)(12288 / bp.NBIN));
+    const u32 gp = (u32)((n + (size_t)256 * bp.tpt - 1) / ((size_t)256 * bp.tpt));
+    const u32 gz = (u32)J;
+    for (int wa = 0; wa < (int)bp.wb; wa += wg) {
+        const int we = std::min<int>((int)bp.wb, wa + wg);
+        hipLaunchKernelGGL(k_msm_bin_partition<C>, dim3(gp, 1, gz), dim3(256), ((size_t)(we - wa) * bp.NBIN + (wa == 0 ? bp.top_nb : 0)) * 4, st, sj, ctx->canon.as<u32>(),
+                           ctx->hist.as<u32>(), pl, scalars_mont, bp, sp, ctx->bin_cur.as<u32>(), ctx->slots.as<u32>(), d_over, wa, we, wa == 0 ? 1 : 0, jb);
+    }
+    hipLaunchKernelGGL(k_msm_bin_sort_fs, dim3(bp.NBIN, bp.wb + fp.has_top, gz), dim3(256), (((size_t)1 << bp.LB) + 8 + bp.cap) * 4, st, ctx->slots.as<u32>(),
+                       ctx->bin_cur.as<u32>(), ctx->hist.as<u32>(), ctx->boff.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(), ctx->fs_binch.as<u32>(),
+                       d_over, pl, bp, sp, chl_fs, jb);
+    {
+        ScopedK acc(ctx, BP_K_MSM_ACCUM_FS);
+        hipLaunchKernelGGL(k_msm_accum_fs<C>, dim3((u32)((maxch + 255) / 256), 1, gz), dim3(256), 0, st, bj, ctx->slots.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
+                           ctx->boff.as<u32>(), ctx->fs_binch.as<u32>(), ctx->lvA.as<u32>(), pl, bp, fp, chl_fs, d_info, jb);
+    }
+    {
+        ScopedK agg(ctx, BP_K_MSM_AGG);
+        MSM_LAUNCH_REDUCE_FS(red_g, dim3((u32)(((size_t)bp.wb * pl.NB * red_g + 255) / 256), 1, gz), ctx->lvA.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
+                           ctx->fs_binch.as<u32>(), ctx->fs_sums.as<u32>(), pl, bp, fp, chl_fs, red_g, jb);
+        MSM_LAUNCH_MARGINALS_FS(dim3((u32)tc, 1, gz), ctx->fs_sums.as<u32>(), ctx->lvA.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
+                           ctx->Tbuf.as<u32>(), pl, bp, fp, chl_fs, d_info, d_over, jb);
+    }
+    HIPCHK(hipMemcpyAsync(ctx->h_T, ctx->Tbuf.p, nj * tb, hipMemcpyDeviceToHost, st));
+    total.stop();
+    const double t_f1 = mtrace ? tfs() : 0;
+    HIPCHK(ctx_stream_wait(ctx));
+    HIPCHK(hipGetLastError());
+    const double t_f2 = mtrace ? tfs() : 0;
+    for (int jn = 0; jn < J; jn++) {
+        const uint8_t* blk = (const uint8_t*)ctx->h_T + (size_t)jn * tb;
+        const u32* info = (const u32*)(blk + tc * 96);
+        over[jn] = info[2] != 0;
+        if (over[jn]) {
+            if (mtrace) fprintf(stderr, "[msm-fs] n=%zu job %d: overflow, the general path takes over\n", n, jn);
+            continue;
+        }
+        J4 acc = G::inf();
+        const u64* T = (const u64*)blk;
+        auto add_T = [&](size_t idx) {
+            const u64* t = T + idx * 12;
+            J4 p; memcpy(p.X.v, t, 32); memcpy(p.Y.v, t + 4, 32); memcpy(p.Z.v, t + 8, 32);
+            if (!p.Z.is_zero()) acc = G::add(acc, p);
+        };
+        const int ngen = (int)bp.wb * pl.c;
+        for (int j = ngen + (int)fp.top_bits - 1; j >= 0; j--) {
+            acc = G::dbl(acc);
+            if (j >= ngen) { for (u32 q = 0; q < fp.top_parts; q++) add_T((size_t)ngen + (size_t)(j - ngen) * fp.top_parts + q); }
+            else add_T((size_t)j);
+        }
+        results[jn] = acc;
+        if (mtrace) fprintf(stderr, "[msm-fs] n=%zu job %d/%d c=%d W=%d bins=%u chunks=%u/%u  enqueue %.1f us  wait %.1f us  host tails so far %.1f us\n", n, jn, J, pl.c, pl.W, fp.nbins,
+                            info[0], fp.max_chunks, (t_f1 - t_f0) * 1e6, (t_f2 - t_f1) * 1e6, (tfs() - t_f2) * 1e6);
+    }
+    return BP_OK;
+}
+// the mid-size MSM takes the GLV-split pipeline (msm_run_fs_glv) when it applies: callers that wait for one result
+template <class C> static bool msm_glv_route(const bp_ctx* ctx, const BaseSegs& segs, size_t n, bool sharded, int w_hi) {
+    if constexpr (!C::HAS_GLV) { (void)ctx; (void)segs; (void)n; (void)sharded; (void)w_hi; return false; }
+    else {
+        static const bool no_glv = getenv("ARKBP_MSM_NOGLV") != nullptr, no_fs0 = getenv("ARKBP_MSM_NOFS") != nullptr;
+        return !no_glv && !no_fs0 && msm_use_quad(ctx) && !sharded && w_hi < 0 && ctx->shard_world == 1 && !segs.fixed_c4 && n >= std::max<size_t>(ctx->tune_msm_bin_min, ctx->tune_msm_glv_min) && n < ((size_t)1 << 27);
+    }
+}
+
 template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u32* d_scalars_one, size_t n, int scalars_mont, J4& result,
                                       int w_lo = 0, int w_hi = -1 /* window range for multi-GPU window sharding; default all */,
                                       int shard_mode = -1 /* -1: the ctx's mode (window partition + reduce when world > 1); 0: none (replicated);
                                                              2: the terms are this rank's own share: all windows, then the point-reduce */,
-                                      const ScalSegs* sseg = nullptr /* the scalars as runs read in place (then d_scalars_one is unused) */) {
+                                      const ScalSegs* sseg = nullptr /* the scalars as runs read in place (then d_scalars_one is unused) */,
+                                      bool no_fixed_shape = false /* straight to the general path: a job of msm_run_pair whose fixed-shape pass overflowed */) {
     ScalSegs d_scalars; memset(&d_scalars, 0, sizeof d_scalars);
     if (sseg) d_scalars = *sseg; else { d_scalars.nseg = 1; d_scalars.ptr[0] = d_scalars_one; d_scalars.start[0] = 0; d_scalars.start[1] = (u32)n; }
     typedef host::Grp<C> G;
@@ -706,14 +883,11 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
         if (!sharded) return BP_OK;
         return shard_point_reduce<C>(ctx, part);
     };
-    if constexpr (C::HAS_GLV) {
+    if (!no_fixed_shape && msm_glv_route<C>(ctx, segs, n, sharded, w_hi)) {
         // mid-size MSMs on a curve with the endomorphism: the fixed-shape pipeline over GLV-split scalars (half the windows)
-        static const bool no_glv = getenv("ARKBP_MSM_NOGLV") != nullptr, no_fs0 = getenv("ARKBP_MSM_NOFS") != nullptr;
-        if (!no_glv && !no_fs0 && msm_use_quad(ctx) && !sharded && w_hi < 0 && ctx->shard_world == 1 && !segs.fixed_c4 && n >= std::max<size_t>(ctx->tune_msm_bin_min, ctx->tune_msm_glv_min) && n < ((size_t)1 << 27)) {
-            bool done = false;
-            BPCHK(msm_run_fs_glv<C>(ctx, segs, d_scalars, n, scalars_mont, result, done));
-            if (done) return BP_OK;
-        }
+        bool done = false;
+        BPCHK(msm_run_fs_glv<C>(ctx, segs, d_scalars, n, scalars_mont, result, done));
+        if (done) return BP_OK;
     }
     if (w_hi >= 0) { pl.w_lo = std::max(0, w_lo); pl.w_hi = std::min(pl.W, w_hi); }
     if (pl.w_lo >= pl.w_hi) return finish_sharded(result);  // this rank owns no window: the identity
@@ -731,8 +905,7 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
     BPCHK(ctx->lvl_off.ensure(Bp1 * NL * 4));
     BPCHK(ctx->totals.ensure_zeroed((NL + 2) * 4 + (size_t)ntiles * (NL + 1) * 4, st));
     BPCHK(ctx->cursor.ensure(pl.B * 4));
-    static const bool force_marginals = getenv("ARKBP_MSM_MARGINALS") != nullptr;   // A/B: the bit-marginal bucket aggregation everywhere
-    const bool use_marginals = force_marginals || pl.B < ctx->tune_msm_wsum_min;
+    const bool use_marginals = msm_use_marginals(ctx, pl);
     const u32 nblk_ws = (u32)((pl.NB + 256 * MSM_SEG - 1) / (256 * MSM_SEG));   // workgroups per window of k_msm_window_sums
     const size_t tcount = use_marginals ? (size_t)pl.W * pl.c : (size_t)pl.W * nblk_ws;
     BPCHK(ctx->Tbuf.ensure(tcount * 96));
@@ -743,51 +916,10 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
         HIPCHK(hipHostMalloc((void**)&ctx->h_T, tbytes + 4096));
         ctx->h_T_cap = tbytes + 4096;
     }
-    // slot plan of the one-pass sort; two-level (binned) sort for large MSMs: the full windows go to bin regions, the short
-    // top window keeps its slots behind them
     if (pl.W > MSM_MAXW) { g_err = "msm: too many windows"; return BP_E_ARG; }
-    BinPlan bp; memset(&bp, 0, sizeof bp);
-    bool binned = false;
-    {
-        const int bits_last = C::Fr::BITS - pl.c * (pl.W - 1);
-        const int wbn = bits_last < pl.c - 1 ? pl.W - 1 : pl.W;
-        static const bool no_bins = getenv("ARKBP_MSM_NOBIN") != nullptr;
-        if (n >= ctx->tune_msm_bin_min && wbn > 0 && !no_bins) {
-            u32 nbin = 1, lg = 0;
-            while ((size_t)nbin * 8192 < n && nbin < (u32)pl.NB) { nbin <<= 1; lg++; }
-            // bins of up to 12 K entries (43 KB of LDS in the bin sort) where that keeps the MSM inside the fixed-shape pipeline's bin
-            // limit: 2^20 < n <= 1.5 * 2^20, e.g. the 1.25 M-term MSM of a 4096-proof batch verification
-            if ((size_t)wbn * nbin + 1 > MSM_FS_MAXBINS && nbin >= 2 && (size_t)(nbin / 2) * 12288 >= n && (size_t)wbn * (nbin / 2) + 1 <= MSM_FS_MAXBINS) { nbin >>= 1; lg--; }
-            int LB = pl.c - 1 - (int)lg;
-            while (LB > 11) { nbin <<= 1; LB--; }
-            const double mu = (double)n / nbin;
-            const size_t cap = std::min<size_t>(n, (size_t)(mu + 8.0 * std::sqrt(mu) + 64.0));
-            const size_t lds_sort = (((size_t)1 << LB) + 4 + cap) * 4;
-            if (n < ((size_t)1 << (31 - LB)) && lds_sort <= 64 * 1024 && (size_t)wbn * nbin * cap < ((size_t)1 << 31)) {
-                bp.LB = (u32)LB; bp.NBIN = nbin; bp.cap = (u32)cap; bp.wb = (u32)wbn;
-                static const int tpt_env = getenv("ARKBP_MSM_TPT") ? atoi(getenv("ARKBP_MSM_TPT")) : 0;
-                bp.tpt = tpt_env > 0 ? (u32)tpt_env : (u32)std::min<size_t>(16, std::max<size_t>(1, n / (256 * 512)));
-                if (wbn < pl.W) {   // same-address device atomics serialise (~170 ns each): count a narrow top window per workgroup
-                    const size_t nb_top = std::min<size_t>((size_t)pl.NB, ((size_t)1 << std::max(bits_last, 0)) + 1);
-                    if (nb_top <= 2048) bp.top_nb = (u32)nb_top;
-                }
-                binned = true;
-            }
-        }
-    }
-    auto make_slots = [&](SlotPlan& sp, int w_first, size_t first_slot) -> size_t {
-        memset(&sp, 0, sizeof sp);
-        size_t nslots = first_slot;
-        for (int w = w_first; w < pl.W; w++) {
-            const int bits_left = C::Fr::BITS - pl.c * w;  // scalar bits at or above this window's base
-            size_t nb_eff = (size_t)pl.NB;
-            if (bits_left < pl.c - 1) nb_eff = std::min<size_t>(nb_eff, ((size_t)1 << std::max(bits_left, 0)) + 1);
-            size_t cap = std::min<size_t>(n, 2 * ((n + nb_eff - 1) / nb_eff) + 32);
-            sp.base[w] = (u32)nslots; sp.cap[w] = (u32)cap;
-            nslots += nb_eff * cap;
-        }
-        return nslots;
-    };
+    BinPlan bp;
+    bool binned = msm_bin_plan<C>(ctx, n, pl, bp);
+    auto make_slots = [&](SlotPlan& sp, int w_first, size_t first_slot) -> size_t { return msm_make_slots<C>(pl, n, sp, w_first, first_slot); };
     SlotPlan sp;
     u32* lvl = ctx->lvl_off.as<u32>();
     u32* d_tot = ctx->totals.as<u32>();
@@ -813,8 +945,8 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
             const u32 gp = (u32)((n + (size_t)256 * bp.tpt - 1) / ((size_t)256 * bp.tpt));
             for (int wa = 0; wa < (int)bp.wb; wa += wg) {
                 const int we = std::min<int>((int)bp.wb, wa + wg);
-                hipLaunchKernelGGL(k_msm_bin_partition<C>, dim3(gp), dim3(256), ((size_t)(we - wa) * bp.NBIN + (wa == 0 ? bp.top_nb : 0)) * 4, st, d_scalars, ctx->canon.as<u32>(),
-                                   ctx->hist.as<u32>(), pl, scalars_mont, bp, sp, ctx->bin_cur.as<u32>(), ctx->slots.as<u32>(), d_over, wa, we, wa == 0 ? 1 : 0);
+                hipLaunchKernelGGL(k_msm_bin_partition<C>, dim3(gp), dim3(256), ((size_t)(we - wa) * bp.NBIN + (wa == 0 ? bp.top_nb : 0)) * 4, st, PerJob<ScalSegs>{{d_scalars}}, ctx->canon.as<u32>(),
+                                   ctx->hist.as<u32>(), pl, scalars_mont, bp, sp, ctx->bin_cur.as<u32>(), ctx->slots.as<u32>(), d_over, wa, we, wa == 0 ? 1 : 0, FsJobs{});
             }
             hipLaunchKernelGGL(k_msm_bin_sort, dim3(bp.NBIN, pl.W), dim3(256), (((size_t)1 << bp.LB) + 4 + bp.cap) * 4, st, ctx->slots.as<u32>(),
                                ctx->bin_cur.as<u32>(), ctx->hist.as<u32>(), ctx->boff.as<u32>(), pl, bp, sp);
@@ -834,91 +966,10 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
     };
     static const bool mtrace = getenv("ARKBP_MSM_TRACE") != nullptr;   // host-side phase times of every MSM on stderr
     // ---- the fixed-shape pipeline (msm.cuh 7): no host wait before the last kernel; falls through to the general path on overflow ----
-    static const bool no_fs = getenv("ARKBP_MSM_NOFS") != nullptr;
-    if (binned && use_marginals && !no_fs && (bp.wb == (u32)pl.W || bp.top_nb > 0) && (size_t)bp.wb * bp.NBIN + 1 <= MSM_FS_MAXBINS && !segs.fixed_c4) {
-        const auto tfs = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        const double t_f0 = mtrace ? tfs() : 0;
-        const u32 chl_fs = fs_chunk_cap(ctx, (double)n * bp.wb * (1.0 - std::ldexp(1.0, -pl.c)), (double)bp.wb * pl.NB, bp.wb < (u32)pl.W ? (double)n : 0.0, (double)bp.top_nb);   // (entries per chunk; any value from 8)
-        FsPlan fp; memset(&fp, 0, sizeof fp);
-        fp.has_top = bp.wb < (u32)pl.W ? 1u : 0u;
-        fp.nbins = bp.wb * bp.NBIN + fp.has_top;
-        if (fp.has_top) { u32 t = bp.top_nb; while (t) { fp.top_bits++; t >>= 1; } }
-        const size_t nwin = (size_t)(pl.w_hi - pl.w_lo);
-        const u32 red_g = (size_t)bp.wb * pl.NB > 49152 ? 1u : 4u;   // lanes per bucket of k_msm_reduce_fs: groups while the lanes fit the chip at once, one lane per bucket beyond
-        const size_t maxch = (n * nwin) / chl_fs + std::min<size_t>(n * nwin, nwin * (size_t)pl.NB) + 64;
-        fp.max_chunks = (u32)maxch;
-        const size_t nslots = make_slots(sp, (int)bp.wb, (size_t)bp.wb * bp.NBIN * bp.cap);
-        fp.top_parts = (u32)std::min<size_t>(MSM_TOP_PARTS_MAX, std::max<size_t>(4, n >> 15));
-        const size_t tc = (size_t)bp.wb * pl.c + (size_t)fp.top_bits * fp.top_parts;
-        const size_t tb = tc * 96 + 64;
-        if (nslots < ((size_t)1 << 32) && maxch < ((size_t)1 << 31)) {
-            BPCHK(ctx->slots.ensure(nslots * 4));
-            BPCHK(ctx->bin_cur.ensure_zeroed((size_t)pl.W * bp.NBIN * 4, st));
-            BPCHK(ctx->boff.ensure((size_t)pl.B * 4));
-            BPCHK(ctx->fs_bcnt.ensure((size_t)pl.B * 4));
-            BPCHK(ctx->fs_loff.ensure((size_t)pl.B * 4));
-            BPCHK(ctx->fs_binch.ensure((MSM_FS_MAXBINS + 1) * 4));
-            BPCHK(ctx->fs_sums.ensure((size_t)bp.wb * pl.NB * 96));
-            BPCHK(ctx->lvA.ensure(maxch * 96));
-            BPCHK(ctx->Tbuf.ensure(tb));
-            if (ctx->h_T_cap < tb) {
-                if (ctx->h_T) HIPCHK(hipHostFree(ctx->h_T));
-                HIPCHK(hipHostMalloc((void**)&ctx->h_T, tb + 4096));
-                ctx->h_T_cap = tb + 4096;
-            }
-            ScopedK total(ctx, BP_K_MSM_TOTAL);
-            u32* d_over = ctx->totals.as<u32>() + (MSM_NLMAX + 1);
-            u32* d_info = ctx->Tbuf.as<u32>() + tc * 24;
-            const int wg = std::max(1, (int)(12288 / bp.NBIN));
-            const u32 gp = (u32)((n + (size_t)256 * bp.tpt - 1) / ((size_t)256 * bp.tpt));
-            for (int wa = 0; wa < (int)bp.wb; wa += wg) {
-                const int we = std::min<int>((int)bp.wb, wa + wg);
-                hipLaunchKernelGGL(k_msm_bin_partition<C>, dim3(gp), dim3(256), ((size_t)(we - wa) * bp.NBIN + (wa == 0 ? bp.top_nb : 0)) * 4, st, d_scalars, ctx->canon.as<u32>(),
-                                   ctx->hist.as<u32>(), pl, scalars_mont, bp, sp, ctx->bin_cur.as<u32>(), ctx->slots.as<u32>(), d_over, wa, we, wa == 0 ? 1 : 0);
-            }
-            hipLaunchKernelGGL(k_msm_bin_sort_fs, dim3(bp.NBIN, bp.wb + fp.has_top), dim3(256), (((size_t)1 << bp.LB) + 8 + bp.cap) * 4, st, ctx->slots.as<u32>(),
-                               ctx->bin_cur.as<u32>(), ctx->hist.as<u32>(), ctx->boff.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(), ctx->fs_binch.as<u32>(),
-                               d_over, pl, bp, sp, chl_fs);
-            {
-                ScopedK acc(ctx, BP_K_MSM_ACCUM_FS);
-                hipLaunchKernelGGL(k_msm_accum_fs<C>, dim3((u32)((maxch + 255) / 256)), dim3(256), 0, st, segs, ctx->slots.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
-                                   ctx->boff.as<u32>(), ctx->fs_binch.as<u32>(), ctx->lvA.as<u32>(), pl, bp, fp, chl_fs, d_info);
-            }
-            {
-            ScopedK agg(ctx, BP_K_MSM_AGG);
-            MSM_LAUNCH_REDUCE_FS(red_g, dim3((u32)(((size_t)bp.wb * pl.NB * red_g + 255) / 256)), ctx->lvA.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
-                               ctx->fs_binch.as<u32>(), ctx->fs_sums.as<u32>(), pl, bp, fp, chl_fs, red_g);
-            MSM_LAUNCH_MARGINALS_FS(dim3((u32)tc), ctx->fs_sums.as<u32>(), ctx->lvA.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
-                           ctx->Tbuf.as<u32>(), pl, bp, fp, chl_fs, d_info, d_over);
-            }
-            HIPCHK(hipMemcpyAsync(ctx->h_T, ctx->Tbuf.p, tb, hipMemcpyDeviceToHost, st));
-            total.stop();
-            const double t_f1 = mtrace ? tfs() : 0;
-            HIPCHK(ctx_stream_wait(ctx));
-            HIPCHK(hipGetLastError());
-            const double t_f2 = mtrace ? tfs() : 0;
-            const u32* info = (const u32*)((const uint8_t*)ctx->h_T + tc * 96);
-            if (info[2] == 0) {
-                J4 acc = G::inf();
-                const u64* T = (const u64*)ctx->h_T;
-                auto add_T = [&](size_t idx) {
-                    const u64* t = T + idx * 12;
-                    J4 p; memcpy(p.X.v, t, 32); memcpy(p.Y.v, t + 4, 32); memcpy(p.Z.v, t + 8, 32);
-                    if (!p.Z.is_zero()) acc = G::add(acc, p);
-                };
-                const int ngen = (int)bp.wb * pl.c;
-                for (int j = ngen + (int)fp.top_bits - 1; j >= 0; j--) {
-                    acc = G::dbl(acc);
-                    if (j >= ngen) { for (u32 q = 0; q < fp.top_parts; q++) add_T((size_t)ngen + (size_t)(j - ngen) * fp.top_parts + q); }
-                    else add_T((size_t)j);
-                }
-                result = acc;
-                if (mtrace) fprintf(stderr, "[msm-fs] n=%zu c=%d W=%d bins=%u chunks=%u/%u  enqueue %.1f us  wait %.1f us  host tail %.1f us\n", n, pl.c, pl.W, fp.nbins, info[0],
-                                    fp.max_chunks, (t_f1 - t_f0) * 1e6, (t_f2 - t_f1) * 1e6, (tfs() - t_f2) * 1e6);
-                return finish_sharded(result);
-            }
-            if (mtrace) fprintf(stderr, "[msm-fs] n=%zu: overflow, the general path takes over\n", n);
-        }
+    if (!no_fixed_shape && msm_fs_fits(ctx, pl, bp, binned, segs)) {
+        bool ran = false, over = false;
+        BPCHK(msm_fs_jobs<C>(ctx, 1, &segs, &d_scalars, n, scalars_mont, pl, bp, &result, &over, ran));
+        if (ran && !over) return finish_sharded(result);
     }
     ScopedK total(ctx, BP_K_MSM_TOTAL);
     const auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1714,6 +1765,70 @@ template <class C> static void to_aff_batch(const J4* in, int count, A4* out) {
     }
 }
 
+// Two MSMs of n terms each that do not depend on each other — L and R of an inner-product round — as two jobs of ONE fixed-shape
+// launch chain (msm_fs_jobs): half the launches and one host wait instead of two, and the two latency-bound trees run side by side.
+// Where the pair does not go through that pipeline alone on this ctx, the two msm_run calls run as they always did, in order: a
+// sharded ctx or instance (the order of the collectives must not change), fixed-base rows, the GLV route of the latency-first
+// entry points, a shape outside the pipeline, BP_TUNE_MSM_PAIR = 0.  A job whose scalars overflow the fixed shape is redone alone on
+// the general path; the other job's result stands.
+template <class C> static int msm_run_pair(bp_ctx* ctx, const BaseSegs segs[2], const u32* const d_scalars[2], size_t n, int scalars_mont, J4 results[2], int shard_mode = -1) {
+    typedef host::Grp<C> G;
+    auto two_calls = [&]() -> int {
+        for (int j = 0; j < 2; j++) BPCHK(msm_run<C>(ctx, segs[j], d_scalars[j], n, scalars_mont, results[j], 0, -1, shard_mode));
+        return BP_OK;
+    };
+    if (!ctx->tune_msm_pair || n == 0 || n >= (1u << 31) || ctx->shard_world > 1 || shard_mode != -1) return two_calls();
+    MsmPlan pl = msm_plan(n, C::Fr::BITS);
+    if (pl.W > MSM_MAXW) return two_calls();
+    BinPlan bp;
+    const bool binned = msm_bin_plan<C>(ctx, n, pl, bp);   // (false below tune_msm_bin_min)
+    for (int j = 0; j < 2; j++)
+        if (msm_glv_route<C>(ctx, segs[j], n, false, -1) || !msm_fs_fits(ctx, pl, bp, binned, segs[j])) return two_calls();
+    ScalSegs ss[2]; memset(ss, 0, sizeof ss);
+    for (int j = 0; j < 2; j++) { ss[j].nseg = 1; ss[j].ptr[0] = d_scalars[j]; ss[j].start[0] = 0; ss[j].start[1] = (u32)n; results[j] = G::inf(); }
+    bool over[2] = {false, false}, ran = false;
+    BPCHK(msm_fs_jobs<C>(ctx, 2, segs, ss, n, scalars_mont, pl, bp, results, over, ran));
+    if (!ran) return two_calls();
+    ctx->pair_passes++;
+    for (int j = 0; j < 2; j++) {
+        if (!over[j]) continue;
+        ctx->pair_redone++;
+        BPCHK(msm_run<C>(ctx, segs[j], d_scalars[j], n, scalars_mont, results[j], 0, -1, shard_mode, nullptr, true));
+    }
+    return BP_OK;
+}
+// ... and their affine forms in ark words (one shared inversion)
+template <class C> static int msm_run_pair_aff(bp_ctx* ctx, const BaseSegs segs[2], const u32* const d_scalars[2], size_t n, int scalars_mont, uint64_t out0[8], uint64_t out1[8],
+                                               int shard_mode = -1) {
+    J4 r[2]; A4 a[2];
+    BPCHK(msm_run_pair<C>(ctx, segs, d_scalars, n, scalars_mont, r, shard_mode));
+    to_aff_batch<C>(r, 2, a);
+    memcpy(out0, a[0].x.v, 32); memcpy(out0 + 4, a[0].y.v, 32);
+    memcpy(out1, a[1].x.v, 32); memcpy(out1 + 4, a[1].y.v, 32);
+    return BP_OK;
+}
+
+// test hook: msm_run_pair on caller-chosen device arrays (include/arkbp.h bp_debug_msm_pair)
+template <class C> static int dbg_msm_pair(bp_ctx* c, const void* const* base_ptrs, const size_t* base_counts, const void* const* d_scalars, size_t n, int canonical,
+                                           int latency_first, uint64_t* out_xy) {
+    BaseSegs segs[2]; memset(segs, 0, sizeof segs);
+    for (int j = 0; j < 2; j++) {
+        size_t at = 0; int k = 0;
+        for (int r = 0; r < MSM_MAXSEG && base_counts[j * MSM_MAXSEG + r]; r++, k++) {
+            if (!base_ptrs[j * MSM_MAXSEG + r]) { g_err = "bp_debug_msm_pair: a run without a pointer"; return BP_E_ARG; }
+            segs[j].ptr[k] = (const u32*)base_ptrs[j * MSM_MAXSEG + r]; segs[j].start[k] = (u32)at; at += base_counts[j * MSM_MAXSEG + r];
+        }
+        segs[j].start[k] = (u32)at; segs[j].nseg = k;
+        if (at != n) { g_err = "bp_debug_msm_pair: a job's runs do not add up to n"; return BP_E_ARG; }
+    }
+    const u32* const scs[2] = {(const u32*)d_scalars[0], (const u32*)d_scalars[1]};
+    const bool prev = c->msm_latency_first;
+    c->msm_latency_first = latency_first != 0;
+    const int rc = msm_run_pair_aff<C>(c, segs, scs, n, canonical ? 0 : 1, out_xy, out_xy + 8);
+    c->msm_latency_first = prev;
+    return rc;
+}
+
 // State of one InnerProductProof::create in flight (the loop body of src/inner_product_proof.rs:70-237 cut at the Fiat-Shamir
 // step): ipa_round_lr computes L, R of the current round, ipa_round_fold consumes the challenge.  ipa_create_dev drives it with a
 // callback; bp_ipa_begin / bp_ipa_round_LR / bp_ipa_round_fold / bp_ipa_finish expose the same steps for hosts that keep the
@@ -1787,12 +1902,9 @@ template <class C> static int ipa_round_lr(bp_ctx* ctx, IpaState& s, uint64_t Lw
         BaseSegs sg; memset(&sg, 0, sizeof sg);
         sg.nseg = 3; sg.start[0] = 0; sg.start[1] = (u32)n0; sg.start[2] = (u32)(2 * n0); sg.start[3] = (u32)(2 * n0 + 1);
         sg.ptr[0] = s.d_G; sg.ptr[1] = s.d_H; sg.ptr[2] = s.d_Q;
-        J4 Lj, Rj;
-        BPCHK(msm_run<C>(ctx, sg, sL, 2 * n0 + 1, 0, Lj, 0, -1, s.msm_mode));
-        BPCHK(msm_run<C>(ctx, sg, sR, 2 * n0 + 1, 0, Rj, 0, -1, s.msm_mode));
-        A4 La = G::to_aff(Lj), Ra = G::to_aff(Rj);
-        memcpy(Lw, La.x.v, 32); memcpy(Lw + 4, La.y.v, 32);
-        memcpy(Rw, Ra.x.v, 32); memcpy(Rw + 4, Ra.y.v, 32);
+        const BaseSegs sgs[2] = {sg, sg};
+        const u32* const scs[2] = {sL, sR};
+        BPCHK(msm_run_pair_aff<C>(ctx, sgs, scs, 2 * n0 + 1, 0, Lw, Rw, s.msm_mode));
         s.lr_done = true;
         return BP_OK;
     }
@@ -1914,6 +2026,14 @@ template <class C> static int ipa_round_lr(bp_ctx* ctx, IpaState& s, uint64_t Lw
         const size_t f0 = s.gens_first, sd = s.gens_stride;
         FbRun rl[3] = {{0, f0 + n * sd, n, sd}, {1, f0, n, sd}, {2, 0, 1}};
         BPCHK(msm_fixed_run<C>(ctx, rl, 3, ss, 2 * n + 1, 0, Lj, dl, 2));
+    }
+    if (!cyc_fixed) {   // neither side goes through the fixed-base rows: L over [G_hi | H_lo | Q] and R over [G_lo | H_hi | Q] as one pair
+        BaseSegs sgs[2] = {sg, sg};
+        sgs[1].ptr[0] = Gb; sgs[1].ptr[1] = Hb + n * 16;
+        const u32* const scs[2] = {sL, sR};
+        BPCHK(msm_run_pair_aff<C>(ctx, sgs, scs, 2 * n + 1, 0, Lw, Rw, s.msm_mode));
+        s.lr_done = true;
+        return BP_OK;
     }
     if (!dl) BPCHK(msm_run<C>(ctx, sg, sL, 2 * n + 1, 0, Lj, 0, -1, s.msm_mode));
     sg.ptr[0] = Gb; sg.ptr[1] = Hb + n * 16;
@@ -2898,7 +3018,7 @@ void bp_ctx_destroy(bp_ctx* c) {
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->sync_ev) (void)hipEventDestroy(c->sync_ev);
     if (c->sync_ev_aux) (void)hipEventDestroy(c->sync_ev_aux);
-    DevBuf* bufs[] = {&c->canon, &c->hist, &c->lvl_off, &c->totals, &c->cursor, &c->entries, &c->slots, &c->bin_cur, &c->boff, &c->lvA, &c->lvB, &c->Tbuf, &c->io_pts, &c->io_scal, &c->io_out,
+    DevBuf* bufs[] = {&c->fs_over, &c->canon, &c->hist, &c->lvl_off, &c->totals, &c->cursor, &c->entries, &c->slots, &c->bin_cur, &c->boff, &c->lvA, &c->lvB, &c->Tbuf, &c->io_pts, &c->io_scal, &c->io_out,
                       &c->ipa_G, &c->ipa_H, &c->ipa_a, &c->ipa_b, &c->ipa_Gf, &c->ipa_Hf, &c->ipa_sL, &c->ipa_sR, &c->ipa_part, &c->ipa_Q, &c->ipa_jac, &c->ipa_pref, &c->ipa_cG, &c->ipa_cH,
                       &c->d_G, &c->d_H, &c->d_pc, &c->pc_table, &c->r_aL, &c->r_aR, &c->r_aO, &c->r_sL, &c->r_sR, &c->r_wL, &c->r_wR, &c->r_wO, &c->r_msmsc,
                       &c->r_ypow, &c->r_part, &c->r_small, &c->r_g, &c->r_h, &c->r_chal, &c->r_tail, &c->v_params, &c->v_gpart, &c->v_hpart, &c->v_alpha, &c->v_tables, &c->v_dec, &c->ve_arena, &c->cyc_a, &c->cyc_b, &c->cyc_Gf, &c->cyc_Hf, &c->ftab_G, &c->ftab_H, &c->fb_G, &c->fb_H, &c->fb_pc, &c->p_moff, &c->p_ment, &c->p_mc, &c->p_coefs, &c->p_ztab, &c->fs_bcnt, &c->fs_loff, &c->fs_binch, &c->fs_sums};
@@ -3016,6 +3136,7 @@ int bp_ctx_set_tuning(bp_ctx* c, int knob, uint64_t value) {
         case BP_TUNE_MSM_BATCH_MIN_JOBS: c->tune_msb_min_jobs = value; return BP_OK;
         case BP_TUNE_MSM_BATCH_SLICE: c->tune_msb_slice = value; return BP_OK;
         case BP_TUNE_MSM_BATCH_MAX: c->tune_msb_max = value; return BP_OK;
+        case BP_TUNE_MSM_PAIR: if (value > 1) return BP_E_ARG; c->tune_msm_pair = (int)value; return BP_OK;
     }
     return BP_E_ARG;
 }
@@ -3072,6 +3193,13 @@ int bp_msm_dev(bp_ctx* c, const void* d_bases, const void* d_scalars, size_t n, 
     if (!c || !out_xy || ((!d_bases || !d_scalars) && n)) { g_err = "bp_msm_dev: bad argument"; return BP_E_ARG; }
     HIPCHK(hipSetDevice(c->device));
     return c->curve == 0 ? msm_dev_entry<Secq>(c, d_bases, d_scalars, n, canonical, out_xy) : msm_dev_entry<Zorro>(c, d_bases, d_scalars, n, canonical, out_xy);
+}
+int bp_debug_msm_pair(bp_ctx* c, const void* const* base_ptrs, const size_t* base_counts, const void* const* d_scalars, size_t n, int canonical, int latency_first,
+                      uint64_t* out_xy) {
+    if (!c || !base_ptrs || !base_counts || !d_scalars || !d_scalars[0] || !d_scalars[1] || !out_xy || n == 0 || n >= ((size_t)1 << 31)) { g_err = "bp_debug_msm_pair: bad argument"; return BP_E_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    return c->curve == 0 ? dbg_msm_pair<Secq>(c, base_ptrs, base_counts, d_scalars, n, canonical, latency_first, out_xy)
+                         : dbg_msm_pair<Zorro>(c, base_ptrs, base_counts, d_scalars, n, canonical, latency_first, out_xy);
 }
 int bp_msm_gens(bp_ctx* c, int use_G, int use_H, size_t off, size_t n, const uint64_t* extra_bases_xy, size_t n_extra, const uint64_t* scalars,
                 int canonical, uint64_t out_xy[8]) {
@@ -3727,6 +3855,12 @@ int bp_ctx_fold_stats(bp_ctx* c, uint64_t* deferred_first_folds, uint64_t* secon
     if (!c) return BP_E_ARG;
     if (deferred_first_folds) *deferred_first_folds = c->folds_deferred;
     if (second_folds_from_tables) *second_folds_from_tables = c->folds_tab2;
+    return BP_OK;
+}
+int bp_ctx_msm_pair_stats(bp_ctx* c, uint64_t* paired_passes, uint64_t* jobs_redone) {
+    if (!c) return BP_E_ARG;
+    if (paired_passes) *paired_passes = c->pair_passes;
+    if (jobs_redone) *jobs_redone = c->pair_redone;
     return BP_OK;
 }
 int bp_ctx_direct_stats(bp_ctx* c, uint64_t* direct_msms, size_t* bases_per_vector) {

@@ -85,6 +85,16 @@ __device__ __forceinline__ const u32* seg_scalar_ptr(const ScalSegs& s, u32 idx)
     return s.ptr[k] + (size_t)(idx - s.start[k]) * 8;
 }
 
+// Jobs of the fixed-shape pipeline (section 7): blockIdx.z of its five kernels is the job.  The jobs of one launch have the same
+// term count, hence the same plans; each has its own scalars and bases and its own copy of every buffer the kernels read or write,
+// FsJobs words further per job.  Nothing is shared between jobs, so a job computes exactly what it computes alone; a launch with
+// gridDim.z == 1 needs no strides (FsJobs{}).
+static constexpr int MSM_JOBS = 2;   // (L and R of an inner-product round)
+template <class T> struct PerJob { T j[MSM_JOBS]; };
+struct FsJobs {   // per-job strides in 32-bit words
+    u64 canon, hist, bin_cur, slots, buckets /* boff, bcnt, loff */, binch, part, sums, T /* the marginals with the info words behind */, over;
+};
+
 struct MsmPlan {
     int c, W, NB;        // window bits, windows, buckets per window (2^(c-1))
     u32 B;               // W * NB
@@ -259,9 +269,12 @@ struct BinPlan {
 // entry in a bin region: (term << (LB+1)) | (fine bucket << 1) | sign; with bp.glv the term field is 2 * i + half and `canon` holds
 // MSM_GLV_WORDS words per scalar (the split magnitudes and signs) instead of the 8 canonical words
 template <class C> __global__ void __launch_bounds__(256)
-k_msm_bin_partition(ScalSegs scalars, u32* __restrict__ canon, u32* __restrict__ hist, MsmPlan pl, int scalars_mont, BinPlan bp,
-                    SlotPlan sp, u32* __restrict__ bin_cur, u32* __restrict__ ent, u32* __restrict__ overflow, int wa, int we, int first) {
+k_msm_bin_partition(PerJob<ScalSegs> sjobs, u32* __restrict__ canon, u32* __restrict__ hist, MsmPlan pl, int scalars_mont, BinPlan bp,
+                    SlotPlan sp, u32* __restrict__ bin_cur, u32* __restrict__ ent, u32* __restrict__ overflow, int wa, int we, int first, FsJobs jb) {
     typedef typename C::Fr Fr;
+    const u32 job = blockIdx.z;
+    const ScalSegs& scalars = sjobs.j[job];
+    canon += job * jb.canon; hist += job * jb.hist; bin_cur += job * jb.bin_cur; ent += job * jb.slots; overflow += job * jb.over;
     extern __shared__ u32 lds_cnt[];   // (we - wa) * NBIN bin counters, then top_nb bucket counters of the slot window
     const u32 nbinc = (u32)(we - wa) * bp.NBIN;
     const bool top = first && bp.top_nb;           // this launch also places the slot window, aggregated per workgroup
@@ -887,6 +900,8 @@ k_msm_sum_partials(const u32* __restrict__ T_in, u32 count, u32* __restrict__ T_
 //                        stretching a tree for its sake; copies and clears the overflow flag into the result block
 // One D2H copy, one wait, the host Horner tail.  A bucket above 256 entries or a full bin raises the flag: the MSM is then redone by
 // the general path (skew-tolerant).  Results are identical either way (a sum of the same group elements).
+// blockIdx.z of the five kernels is the JOB (FsJobs above): up to MSM_JOBS MSMs of the same term count share one chain of launches, each
+// in its own stride of every buffer and with its own flag; gridDim.z == 1 with FsJobs{} is the single MSM.
 static constexpr u32 MSM_FS_MAXBINS = 4096;
 static constexpr u32 MSM_FS_BUCKET_MAX = 256;   // entries of a binned bucket; with chcap >= 8 at most 32 partials reach k_msm_reduce_fs
 static constexpr u32 MSM_TOP_PARTS_MAX = 32;   // (a bit of the slot window collects ~n/32 partials: 4 .. 32 workgroups share them)
@@ -917,8 +932,11 @@ __device__ __forceinline__ void fs_block_scan(const u32* __restrict__ src, u32 n
 // grid (NBIN, wb + has_top).  Row wb (bin 0 only) is the slot window: hist -> bcnt / loff / boff, hist restored to zero.
 __global__ void __launch_bounds__(256)
 k_msm_bin_sort_fs(u32* __restrict__ ent, u32* __restrict__ bin_cur, u32* __restrict__ hist, u32* __restrict__ boff, u32* __restrict__ bcnt,
-                  u32* __restrict__ loff, u32* __restrict__ bin_chunks, u32* __restrict__ overflow, MsmPlan pl, BinPlan bp, SlotPlan sp, u32 chcap) {
+                  u32* __restrict__ loff, u32* __restrict__ bin_chunks, u32* __restrict__ overflow, MsmPlan pl, BinPlan bp, SlotPlan sp, u32 chcap, FsJobs jb) {
     extern __shared__ u32 lds[];
+    const u32 job = blockIdx.z;
+    ent += job * jb.slots; bin_cur += job * jb.bin_cur; hist += job * jb.hist; boff += job * jb.buckets; bcnt += job * jb.buckets; loff += job * jb.buckets;
+    bin_chunks += job * jb.binch; overflow += job * jb.over;
     const u32 w = blockIdx.y, bin = blockIdx.x, tid = threadIdx.x;
     const u32 lane = tid & 63u, wv = tid >> 6;
     const u32 chm = chcap - 1u;   // chunks of a bucket: ceil(population / chcap) (chcap: 8 .. 64, any value — the host picks it per MSM)
@@ -1001,10 +1019,14 @@ __device__ __forceinline__ void fs_bin_range(u32 x, const MsmPlan& pl, const Bin
     else { b0 = ((u32)pl.W - 1u) * (u32)pl.NB; nb = bp.top_nb; }
 }
 template <class C> __global__ void __launch_bounds__(256)
-k_msm_accum_fs(BaseSegs segs, const u32* __restrict__ entries, const u32* __restrict__ bcnt, const u32* __restrict__ loff, const u32* __restrict__ boff,
-               const u32* __restrict__ bin_chunks, u32* __restrict__ out, MsmPlan pl, BinPlan bp, FsPlan fp, u32 chcap, u32* __restrict__ info) {
+k_msm_accum_fs(PerJob<BaseSegs> bjobs, const u32* __restrict__ entries, const u32* __restrict__ bcnt, const u32* __restrict__ loff, const u32* __restrict__ boff,
+               const u32* __restrict__ bin_chunks, u32* __restrict__ out, MsmPlan pl, BinPlan bp, FsPlan fp, u32 chcap, u32* __restrict__ info, FsJobs jb) {
     __shared__ u32 base[MSM_FS_MAXBINS + 1];
     __shared__ u32 ws[4];
+    const u32 job = blockIdx.z;
+    const BaseSegs& segs = bjobs.j[job];
+    entries += job * jb.slots; bcnt += job * jb.buckets; loff += job * jb.buckets; boff += job * jb.buckets; bin_chunks += job * jb.binch;
+    out += job * jb.part; info += job * jb.T;
     fs_block_scan(bin_chunks, fp.nbins, base, ws);
     const u32 total = min(base[fp.nbins], fp.max_chunks);
     if (blockIdx.x == 0 && threadIdx.x == 0) { info[0] = base[fp.nbins]; info[1] = base[fp.nbins - 1]; }   // chunks; first chunk of the last bin
@@ -1063,9 +1085,11 @@ k_msm_accum_fs(BaseSegs segs, const u32* __restrict__ entries, const u32* __rest
 // q, q + G, .. (<= 32 in all), lg G shuffle levels join them -> sums[b] (the identity when the bucket is empty)
 template <class C, bool QUAD = false> __global__ void __launch_bounds__(256)
 k_msm_reduce_fs(const u32* __restrict__ part, const u32* __restrict__ bcnt, const u32* __restrict__ loff, const u32* __restrict__ bin_chunks,
-                u32* __restrict__ sums, MsmPlan pl, BinPlan bp, FsPlan fp, u32 chcap, u32 G) {
+                u32* __restrict__ sums, MsmPlan pl, BinPlan bp, FsPlan fp, u32 chcap, u32 G, FsJobs jb) {
     __shared__ u32 base[MSM_FS_MAXBINS + 1];
     __shared__ u32 ws[4];
+    const u32 job = blockIdx.z;
+    part += job * jb.part; bcnt += job * jb.buckets; loff += job * jb.buckets; bin_chunks += job * jb.binch; sums += job * jb.sums;
     fs_block_scan(bin_chunks, fp.nbins, base, ws);
     const u32 g = blockIdx.x * 256u + threadIdx.x;
     const u32 nbk = bp.wb * (u32)pl.NB;
@@ -1120,7 +1144,10 @@ template <class C> __device__ __forceinline__ void store_T_ark(u32* __restrict__
 // the level-1 partials of the buckets whose value has bit k.  T_out[wb * c + k * top_parts + part]; info[2] = overflow flag (then cleared).
 template <class C, u32 NT, bool QUAD = false> __global__ void __launch_bounds__(NT)
 k_msm_marginals_fs(const u32* __restrict__ sums, const u32* __restrict__ part, const u32* __restrict__ bcnt, const u32* __restrict__ loff,
-                   u32* __restrict__ T_out, MsmPlan pl, BinPlan bp, FsPlan fp, u32 chcap, u32* __restrict__ info, u32* __restrict__ overflow) {
+                   u32* __restrict__ T_out, MsmPlan pl, BinPlan bp, FsPlan fp, u32 chcap, u32* __restrict__ info, u32* __restrict__ overflow, FsJobs jb) {
+    const u32 job = blockIdx.z;
+    sums += job * jb.sums; part += job * jb.part; bcnt += job * jb.buckets; loff += job * jb.buckets; T_out += job * jb.T; info += job * jb.T;
+    overflow += job * jb.over;
     __shared__ u32 pre[2052];      // slot window: prefix counts of the partials of the buckets with bit k (top_nb <= 2048)
     __shared__ u32 wsum[NT / 64];
     __shared__ u32 tree[NT * 27];

@@ -1090,6 +1090,38 @@ def _fold_stats(self):
 
 Engine.fold_stats = _fold_stats
 
+TUNE_MSM_PAIR = 21                   # include/arkbp.h BP_TUNE_MSM_PAIR (Engine.set_tuning)
+MSM_PAIR_RUNS = 6                    # BP_DEBUG_MSM_PAIR_RUNS
+
+
+def _msm_pair_stats(self):
+    """(passes in which the L and R MSMs of an inner-product round ran as two jobs of one launch chain, jobs of those redone alone)"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    check(lib().bp_ctx_msm_pair_stats(self.ctx, C.byref(a), C.byref(b)), "bp_ctx_msm_pair_stats")
+    return a.value, b.value
+
+
+def _debug_msm_pair(self, runs, d_scalars, n, canonical=False, latency_first=False):
+    """bp_debug_msm_pair: two MSMs of n terms through the prover's msm_run_pair.  runs: per job a list of up to MSM_PAIR_RUNS
+    (DeviceBuffer of resident points, first point, count); d_scalars: two DeviceBuffers of n scalars.  Returns the two affine sums
+    as a (2, 8) uint64 array (ark words)."""
+    if len(runs) != 2 or len(d_scalars) != 2 or any(len(r) > MSM_PAIR_RUNS for r in runs):
+        raise ValueError("debug_msm_pair: two jobs of at most %d runs" % MSM_PAIR_RUNS)
+    ptrs = (C.c_void_p * (2 * MSM_PAIR_RUNS))()
+    counts = (C.c_size_t * (2 * MSM_PAIR_RUNS))()
+    for j, job in enumerate(runs):
+        for r, (buf, first, count) in enumerate(job):
+            ptrs[j * MSM_PAIR_RUNS + r] = buf.ptr.value + 64 * int(first)
+            counts[j * MSM_PAIR_RUNS + r] = int(count)
+    sc = (C.c_void_p * 2)(d_scalars[0].ptr.value, d_scalars[1].ptr.value)
+    out = np.zeros((2, 8), dtype=np.uint64)
+    check(lib().bp_debug_msm_pair(self.ctx, ptrs, counts, sc, C.c_size_t(n), int(canonical), int(latency_first), ptr(out)), "bp_debug_msm_pair")
+    return out
+
+
+Engine.msm_pair_stats = _msm_pair_stats
+Engine.debug_msm_pair = _debug_msm_pair
+
 
 def _prover_handle(p):
     """bp_cs* of a ProverCS or a scenario Statement (bp_stmt_as_prover)"""

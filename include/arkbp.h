@@ -257,6 +257,16 @@ int bp_debug_tables_ptr(bp_ctx* ctx, int which, void** dptr, size_t* nbytes);
 #define BP_DEBUG_DT_DESC_WORDS 18
 int bp_debug_msm_direct(bp_ctx* ctx, size_t njobs, const uint32_t* desc, const uint64_t* imm, const uint64_t* const* scalars, const size_t* scalar_lens,
                         uint64_t* out_xy, uint32_t* workgroups);
+/* test hook: two variable-base MSMs of n terms each through the prover's own msm_run_pair, as the rounds of the inner-product argument
+ * call it.  Job j (0, 1) reads its bases as up to BP_DEBUG_MSM_PAIR_RUNS runs: run r is base_counts[j * RUNS + r] points (resident layout,
+ * bp_points_import) at device pointer base_ptrs[j * RUNS + r]; the first count of 0 ends the job's runs, and they must add up to n.
+ * d_scalars[j]: n device scalars of 4 words (ark Montgomery words, or integers below r with canonical = 1).  latency_first = 0
+ * runs exactly the schedule the prover gets; 1 sets what the bp_msm* entry points set for the duration of the call (the
+ * latency-first schedule, which on secq256k1 takes mid-size MSMs through the GLV split and therefore declines the pairing).
+ * out_xy: the two affine sums, 8 ark words each, all zero for the identity.  bp_ctx_msm_pair_stats tells whether the call paired. */
+#define BP_DEBUG_MSM_PAIR_RUNS 6
+int bp_debug_msm_pair(bp_ctx* ctx, const void* const* base_ptrs, const size_t* base_counts, const void* const* d_scalars, size_t n, int canonical, int latency_first,
+                      uint64_t* out_xy);
 /* PedersenGens::default() -> (B, B_blinding); host only */
 int bp_pedersen_gens(int curve, uint64_t B_xy[8], uint64_t B_blinding_xy[8]);
 /* GeneratorsChain for label 'G'|'H' || LE32(party) (src/generators.rs:71-121), first `count` points; host only */
@@ -606,6 +616,9 @@ int bp_ctx_reset_profiling(bp_ctx* ctx);
                                     * route (0 = default: 4096; a value at or below the short one leaves no bucketed route) */
 #define BP_TUNE_MSM_BATCH_MIN_JOBS 19 /* bp_msm_batch: a call with fewer short and bucketed jobs than this runs every job on the single route (0 = default: 6;
                                     * 1 = never): a group costs the latency of one serial Horner chain whatever it holds.  Results never depend on the four */
+#define BP_TUNE_MSM_PAIR 21        /* (20 stays unassigned: tests/test_msm_batch_cpu.py pins it as the first knob that is refused.)  1 (default): L and R of a round of the inner-product argument — two mid-size MSMs of the same length that do not
+                                    * depend on each other — run as two jobs of ONE chain of launches with one host wait (see bp_ctx_msm_pair_stats);
+                                    * 0: one MSM after the other (A/B, tests).  Results never depend on it */
 int bp_ctx_set_tuning(bp_ctx* ctx, int knob, uint64_t value);
 
 /* The O(N) part of `Verifier::verification_scalars` (src/r1cs/verifier.rs:465-514, s from inner_product_proof.rs:279-311) for a
@@ -684,6 +697,11 @@ int bp_ctx_direct_stats(bp_ctx* ctx, uint64_t* direct_msms, size_t* bases_per_ve
  * ctx deferred, and second folds it then produced straight from the tables — on one GPU and, since round 4, on the index-cyclic slice
  * of a sharded prover */
 int bp_ctx_fold_stats(bp_ctx* ctx, uint64_t* deferred_first_folds, uint64_t* second_folds_from_tables);
+/* Paired MSMs (BP_TUNE_MSM_PAIR): passes in which the L and R MSMs of an inner-product round ran as two jobs of one launch chain on
+ * this ctx, and the jobs of those passes that were redone alone on the general path because their scalars overflowed the fixed
+ * shape (skewed scalars; the other job's result stands).  A round that does not qualify — sharded ctx, fixed-base rows, direct
+ * tables, fewer terms than BP_TUNE_MSM_BIN_MIN, the knob off — runs its two MSMs one after the other and counts nothing */
+int bp_ctx_msm_pair_stats(bp_ctx* ctx, uint64_t* paired_passes, uint64_t* jobs_redone);
 /* A ctx WITHOUT a device for sanitizer runs of the host layer on machines with no GPU (tools/sanitize/): only bp_r1cs_batch_verify,
  * bp_r1cs_batch_verify_scenarios, bp_ctx_set_tuning and bp_ctx_destroy accept it.  They run the complete host side of batch
  * verification — framing, square roots (on the host here), thread pools, shared recordings, transcript replay (live and lockstep),

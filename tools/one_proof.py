@@ -1,6 +1,6 @@
 """Profiling helper (not part of the product or the tests): proves `count` 2^logn square-chain statements one at a time with the
 bench's tables installed, so that per-proof kernel statistics / PMC counters / latencies can be read off a run directly.
-usage: python tools/one_proof.py [logn=20] [count=1] [--quad-max POINTS] [--table-rounds 1|2] [--curve 0|1] [--freeze-len N]"""
+usage: python tools/one_proof.py [logn=20] [count=1] [--quad-max POINTS] [--table-rounds 1|2] [--curve 0|1] [--freeze-len N] [--msm-pair 0|1]"""
 import argparse
 import sys
 import time
@@ -16,6 +16,7 @@ ap.add_argument("--quad-max", type=int, default=0, help="BP_TUNE_FOLD_QUAD_MAX: 
 ap.add_argument("--table-rounds", type=int, default=2, help="fold rounds served by the fixed-base tables (2: tables over 3N/4 bases)")
 ap.add_argument("--curve", type=int, default=0)
 ap.add_argument("--freeze-len", type=int, default=0, help="BP_TUNE_IPA_FREEZE_LEN: vector length from which G and H are no longer folded (0 = the library's default)")
+ap.add_argument("--msm-pair", type=int, choices=(0, 1), default=None, help="BP_TUNE_MSM_PAIR: L and R of a round as two jobs of one launch chain (default: the library's, 1)")
 args = ap.parse_args()
 N = 1 << args.logn
 eng = A.Engine(curve=args.curve)
@@ -26,6 +27,8 @@ if args.quad_max:
     eng.set_tuning(8, args.quad_max)
 if args.freeze_len:
     eng.set_tuning(2, args.freeze_len)
+if args.msm_pair is not None:
+    eng.set_tuning(E.TUNE_MSM_PAIR, args.msm_pair)
 eng.set_profiling(True)
 lat = []
 for k in range(args.count):
@@ -42,4 +45,5 @@ print("proved %d x 2^%d (curve %d, table rounds %d, quad max %d, freeze length %
 print("prove() wall after the TranscriptRng head: %s ms;  inner-product argument alone: %s ms;  host CPU time of the process in prove(): %s ms"
       % (", ".join("%.1f" % (a * 1e3) for a, _, _ in lat), ", ".join("%.1f" % (b * 1e3) for _, b, _ in lat), ", ".join("%.1f" % (c * 1e3) for _, _, c in lat)))
 print("last proof, HIP-event times: " + "; ".join("%s %.2f ms / %d launches" % (names[k], kt[k][0], kt[k][1]) for k in names))
+print("paired L/R passes, jobs redone alone (all proofs): %d, %d" % eng.msm_pair_stats())
 eng.close()
