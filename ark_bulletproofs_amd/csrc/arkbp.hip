@@ -349,6 +349,8 @@ struct bp_ctx {
     uint64_t tune_msb_short = 0, tune_msb_slice = 0, tune_msb_max = 0, tune_msb_min_jobs = 0;   // BP_TUNE_MSM_BATCH_SHORT / _SLICE / _MAX / _MIN_JOBS
     uint64_t mb_short = 0, mb_bucketed = 0, mb_single = 0, mb_groups = 0, mb_waits = 0;
     uint64_t folds_deferred = 0, folds_tab2 = 0;   // first folds deferred / second folds that came straight from the tables (bp_ctx_fold_stats)
+    u32 fold_took = 0;         // which fold kernels the launchers enqueued since the last reset (FOLD_TOOK_*; bp_debug_fold reports it)
+    bool gens_derived = false; // the resident generators are a prefix of party 0's derived chain (bp_gens_derive), not caller-installed points
     IpaState ipa_step;         // bp_ipa_begin .. bp_ipa_finish
     bool ipa_step_active = false;
     u32* h_totals = nullptr;  // pinned
@@ -1436,6 +1438,8 @@ template <class C> static bool glv_pair(const F4& tG, const F4& tH, Naf2& g, Naf
 // Rounds with at least 2^16 output points convert to affine through k_ipa_fold_finish (one inversion per m points); smaller
 // rounds are launch/latency bound and keep the in-lane inversion.
 struct FoldFinish { u32* jac = nullptr; u32* pref = nullptr; u32 m = 0; };
+// what a fold launcher enqueued (bp_ctx::fold_took; include/arkbp.h bp_debug_fold)
+enum : u32 { FOLD_TOOK_GLV = 1, FOLD_TOOK_NAF = 2, FOLD_TOOK_QUAD = 4, FOLD_TOOK_FINISH = 8, FOLD_TOOK_TAB = 16, FOLD_TOOK_TAB2 = 32 };
 static int fold_finish_plan(bp_ctx* ctx, size_t lanes, FoldFinish& ff) {
     static const bool off = getenv("ARKBP_FOLD_NOBATCH") != nullptr;
     ff = FoldFinish();
@@ -1448,12 +1452,14 @@ static int fold_finish_plan(bp_ctx* ctx, size_t lanes, FoldFinish& ff) {
 }
 template <class C> static void fold_finish_launch(bp_ctx* ctx, const FoldFinish& ff, u32* d_G, u32* d_H, size_t n, int which, size_t lanes) {
     if (!ff.jac) return;
+    ctx->fold_took |= FOLD_TOOK_FINISH;
     ScopedK tk(ctx, BP_K_FOLD_FINISH);
     const u32 threads = (u32)((lanes + ff.m - 1) / ff.m);
     hipLaunchKernelGGL(k_ipa_fold_finish<C>, dim3((threads + 255) / 256), dim3(256), 0, ctx->stream, ff.jac, ff.pref, d_G, d_H, (u32)n, which, (u32)lanes, ff.m);
 }
 // launches the uniform fold for multipliers (tG, tH): GLV ladder where the curve has the endomorphism, plain NAF ladder otherwise
-template <class C> static int launch_uniform_fold(bp_ctx* ctx, u32* d_G, u32* d_H, size_t n, const F4& tG, const F4& tH, int which) {
+// (force_naf: the NAF ladder there too — the route a multiplier without a short GLV split takes; bp_debug_fold)
+template <class C> static int launch_uniform_fold(bp_ctx* ctx, u32* d_G, u32* d_H, size_t n, const F4& tG, const F4& tH, int which, bool force_naf = false) {
     typedef host::Fld<typename C::Fr> S;
     hipStream_t st = ctx->stream;
     const u32 lanes = (u32)(which == 3 ? 2 * n : n);
@@ -1468,17 +1474,20 @@ template <class C> static int launch_uniform_fold(bp_ctx* ctx, u32* d_G, u32* d_
     ScopedK tk(ctx, BP_K_FOLD_LADDER);
     if constexpr (C::HAS_GLV) {
         Naf2 g, h;
-        if (glv_pair<C>(tG, tH, g, h)) {
+        if (!force_naf && glv_pair<C>(tG, tH, g, h)) {
             if (quad) hipLaunchKernelGGL((k_ipa_fold_glv<C, true>), dim3(grid), dim3(256), 0, st, d_G, d_H, (u32)n, g, h, which, ff.jac);
             else hipLaunchKernelGGL((k_ipa_fold_glv<C, false>), dim3(grid), dim3(256), 0, st, d_G, d_H, (u32)n, g, h, which, ff.jac);
             done = true;
+            ctx->fold_took |= FOLD_TOOK_GLV;
         }
     }
     if (!done) {
+        ctx->fold_took |= FOLD_TOOK_NAF;
         Naf a = naf_of<S>(tG), b = naf_of<S>(tH);
         if (quad) hipLaunchKernelGGL((k_ipa_fold_uniform<C, true>), dim3(grid), dim3(256), 0, st, d_G, d_H, (u32)n, a, b, which, ff.jac);
         else hipLaunchKernelGGL((k_ipa_fold_uniform<C, false>), dim3(grid), dim3(256), 0, st, d_G, d_H, (u32)n, a, b, which, ff.jac);
     }
+    if (quad) ctx->fold_took |= FOLD_TOOK_QUAD;
     }
     fold_finish_launch<C>(ctx, ff, d_G, d_H, n, which, lanes);
     return BP_OK;
@@ -1620,6 +1629,7 @@ template <class C> static int launch_tab_fold(bp_ctx* ctx, const IpaState& s, u3
     hipLaunchKernelGGL(k_ipa_fold_tab<C>, dim3((lanes + 255) / 256), dim3(256), 0, ctx->stream, ctx->ftab_G.as<u32>(), ctx->ftab_H.as<u32>(), (u32)ctx->ftab_n,
                        1u << (ctx->ftab_w - 1), d_G, d_H, (u32)n, dG, dH, 3, c0, cs, ff.jac, s.d_G_in, s.d_H_in);
     }
+    ctx->fold_took |= FOLD_TOOK_TAB;
     fold_finish_launch<C>(ctx, ff, d_G, d_H, n, 3, lanes);
     done = true;
     return BP_OK;
@@ -1660,9 +1670,66 @@ template <class C> static int launch_tab_fold2(bp_ctx* ctx, const IpaState& s, u
         hipLaunchKernelGGL(k_ipa_fold_tab2<C>, dim3((lanes + 255) / 256), dim3(256), 0, ctx->stream, ctx->ftab_G.as<u32>(), ctx->ftab_H.as<u32>(), (u32)ctx->ftab_n,
                            1u << (ctx->ftab_w - 1), d_G, d_H, (u32)m, dG, dH, ff.jac, s.d_G_in, s.d_H_in, c0, cs);
     }
+    ctx->fold_took |= FOLD_TOOK_TAB2;
     fold_finish_launch<C>(ctx, ff, d_G, d_H, m, 3, lanes);
     done = true;
     return BP_OK;
+}
+// test hook: one fold through the launchers above with caller-chosen multipliers (include/arkbp.h bp_debug_fold).  Everything a
+// kernel would read is checked here first: the launchers themselves rely on the prover's rounds for that.
+template <class C> static int dbg_fold(bp_ctx* ctx, int route, size_t n, const uint64_t* tGw, const uint64_t* tHw, const uint64_t* t2Gw, const uint64_t* t2Hw, u32 first,
+                                       u32 stride, const uint64_t* G_xy, const uint64_t* H_xy, uint64_t* G_out, uint64_t* H_out, u32* took) {
+    hipStream_t st = ctx->stream;
+    *took = 0;
+    const bool ladder = route == BP_DEBUG_FOLD_LADDER || route == BP_DEBUG_FOLD_LADDER_NAF, tab2 = route == BP_DEBUG_FOLD_TAB2;
+    const size_t in_pts = tab2 ? 4 * n : 2 * n;   // elements of each vector the fold reads
+    const bool whole = first == 0 && stride == 1;
+    F4 tG, tH, t2G, t2H;
+    memcpy(tG.v, tGw, 32); memcpy(tH.v, tHw, 32);
+    if (tab2) { memcpy(t2G.v, t2Gw, 32); memcpy(t2H.v, t2Hw, 32); }
+    IpaState s;
+    if (!ladder) {
+        if (!ctx->ftab_n || !ctx->ftab_G.p || !ctx->ftab_H.p) { g_err = "bp_debug_fold: the fold tables are not built (bp_gens_fold_tables)"; return BP_E_ARG; }
+        if (!stride || (size_t)first + (in_pts - 1) * (size_t)stride >= ctx->gens_cap) { g_err = "bp_debug_fold: an element lies outside the installed generators"; return BP_E_ARG; }
+        s.gens_first = first; s.gens_stride = stride;
+        u32 c0 = 0, cs = 1;
+        const size_t tabled = tab2 ? 3 * n : n;   // the elements that are looked up: [0, n), or [0, n + n/2) of the 2n a deferred fold spans
+        if (!ftab_cols(ctx, s, c0, cs) || (size_t)c0 + (tabled - 1) * (size_t)cs >= ctx->ftab_n) { g_err = "bp_debug_fold: an element lies outside the fold tables"; return BP_E_ARG; }
+    }
+    DevBuf wG, wH, out;
+    auto done = [&](int rc) { wG.release(); wH.release(); out.release(); return rc; };
+#define DFCHK(x) do { int rc__ = (x); if (rc__ != BP_OK) return done(rc__); } while (0)
+#define DFHIP(x) do { if ((x) != hipSuccess) { g_err = "bp_debug_fold: HIP error"; return done(BP_E_HIP); } } while (0)
+    DFCHK(wG.ensure_exact(in_pts * 64)); DFCHK(wH.ensure_exact(in_pts * 64)); DFCHK(out.ensure_exact(2 * n * 64));
+    u32 *d_G = wG.as<u32>(), *d_H = wH.as<u32>();
+    if (ladder) {
+        DFHIP(hipMemcpyAsync(d_G, G_xy, 2 * n * 64, hipMemcpyHostToDevice, st));
+        DFHIP(hipMemcpyAsync(d_H, H_xy, 2 * n * 64, hipMemcpyHostToDevice, st));
+        DFCHK(bp_points_import(ctx, d_G, d_G, 2 * n)); DFCHK(bp_points_import(ctx, d_H, d_H, 2 * n));
+    } else if (whole) {   // the resident tables read in place; the working vectors only receive
+        s.d_G_in = ctx->d_G.as<u32>(); s.d_H_in = ctx->d_H.as<u32>();
+    } else {              // the slice as a compact copy, which is also where the results go (ipa_create_cyclic)
+        const u32 gb = (u32)((in_pts + 255) / 256);
+        hipLaunchKernelGGL(k_cyclic_gather<Blk64>, dim3(gb), dim3(256), 0, st, ctx->d_G.as<u32>(), d_G, (u32)in_pts, first, stride);
+        hipLaunchKernelGGL(k_cyclic_gather<Blk64>, dim3(gb), dim3(256), 0, st, ctx->d_H.as<u32>(), d_H, (u32)in_pts, first, stride);
+        s.d_G_in = d_G; s.d_H_in = d_H;
+    }
+    ctx->fold_took = 0;
+    bool ran = true;
+    if (ladder) DFCHK(launch_uniform_fold<C>(ctx, d_G, d_H, n, tG, tH, 3, route == BP_DEBUG_FOLD_LADDER_NAF));
+    else if (!tab2) DFCHK(launch_tab_fold<C>(ctx, s, d_G, d_H, n, tG, tH, ran));
+    else { s.def_tG = tG; s.def_tH = tH; DFCHK(launch_tab_fold2<C>(ctx, s, d_G, d_H, n, t2G, t2H, ran)); }
+    DFHIP(hipGetLastError());
+    *took = ran ? ctx->fold_took : 0;
+    if (ran) {
+        DFCHK(bp_points_export(ctx, d_G, out.p, n)); DFCHK(bp_points_export(ctx, d_H, out.as<u32>() + n * 16, n));
+        DFHIP(hipMemcpyAsync(G_out, out.p, n * 64, hipMemcpyDeviceToHost, st));
+        DFHIP(hipMemcpyAsync(H_out, out.as<u32>() + n * 16, n * 64, hipMemcpyDeviceToHost, st));
+    }
+    DFHIP(ctx_stream_wait(ctx));
+#undef DFCHK
+#undef DFHIP
+    return done(BP_OK);
 }
 
 // ---- direct window tables of the first generators (small.cuh): the small-statement path --------------------------------------------
@@ -3363,6 +3430,18 @@ int bp_debug_tables_ptr(bp_ctx* c, int which, void** dptr, size_t* nbytes) {
     *dptr = used ? b.p : nullptr; *nbytes = used;
     return BP_OK;
 }
+int bp_debug_fold(bp_ctx* c, int route, size_t n, const uint64_t tG[4], const uint64_t tH[4], const uint64_t t2G[4], const uint64_t t2H[4], uint32_t gens_first,
+                  uint32_t gens_stride, const uint64_t* G_xy, const uint64_t* H_xy, uint64_t* G_out_xy, uint64_t* H_out_xy, uint32_t* took) {
+    if (!c || route < BP_DEBUG_FOLD_LADDER || route > BP_DEBUG_FOLD_TAB2 || !n || n >= ((size_t)1 << 28) || !tG || !tH || !G_out_xy || !H_out_xy || !took) {
+        g_err = "bp_debug_fold: bad argument"; return BP_E_ARG;
+    }
+    if (route == BP_DEBUG_FOLD_TAB2 && (!t2G || !t2H)) { g_err = "bp_debug_fold: the second multipliers are missing"; return BP_E_ARG; }
+    if (route <= BP_DEBUG_FOLD_LADDER_NAF && (!G_xy || !H_xy)) { g_err = "bp_debug_fold: the ladder routes fold the caller's points"; return BP_E_ARG; }
+    if (c->host_only) return BP_E_NO_DEVICE;
+    HIPCHK(hipSetDevice(c->device));
+    return c->curve == 0 ? dbg_fold<Secq>(c, route, n, tG, tH, t2G, t2H, gens_first, gens_stride, G_xy, H_xy, G_out_xy, H_out_xy, took)
+                         : dbg_fold<Zorro>(c, route, n, tG, tH, t2G, t2H, gens_first, gens_stride, G_xy, H_xy, G_out_xy, H_out_xy, took);
+}
 int bp_debug_msm_direct(bp_ctx* c, size_t njobs, const uint32_t* desc, const uint64_t* imm, const uint64_t* const* scalars, const size_t* scalar_lens,
                         uint64_t* out_xy, uint32_t* workgroups) {
     if (!c || !desc || !out_xy || njobs < 1 || njobs > (size_t)DT_MAXOUT) { g_err = "bp_debug_msm_direct: bad argument"; return BP_E_ARG; }
@@ -3710,7 +3789,7 @@ int bp_gens_share(bp_ctx* dst, bp_ctx* src) {
     DevBuf* d[] = {&dst->d_G, &dst->d_H, &dst->d_pc};
     DevBuf* sr[] = {&src->d_G, &src->d_H, &src->d_pc};
     for (int i = 0; i < 3; i++) { d[i]->release(); d[i]->p = sr[i]->p; d[i]->cap = sr[i]->cap; d[i]->owned = false; }
-    dst->gens_cap = src->gens_cap; dst->pc_B = src->pc_B; dst->pc_Bb = src->pc_Bb;
+    dst->gens_cap = src->gens_cap; dst->gens_derived = src->gens_derived; dst->pc_B = src->pc_B; dst->pc_Bb = src->pc_Bb;
     DevBuf* dt[] = {&dst->ftab_G, &dst->ftab_H, &dst->fb_G, &dst->fb_H, &dst->fb_pc};
     DevBuf* stb[] = {&src->ftab_G, &src->ftab_H, &src->fb_G, &src->fb_H, &src->fb_pc};
     for (int i = 0; i < 5; i++) { dt[i]->release(); dt[i]->p = stb[i]->p; dt[i]->cap = stb[i]->cap; dt[i]->owned = false; }

@@ -65,7 +65,17 @@ template <class C> static int upload_witness5(bp_ctx* ctx, u32* const dst[5], co
     return BP_OK;
 }
 
+// The precomputed tables are multiples of the resident generators: whatever puts OTHER points there releases them (a shared view is
+// let go, not freed).  They come back when asked for again (bp_gens_fold_tables, bp_gens_msm_tables; the direct tables on first use).
+static void gens_tables_drop(bp_ctx* ctx) {
+    for (DevBuf* b : {&ctx->ftab_G, &ctx->ftab_H, &ctx->fb_G, &ctx->fb_H, &ctx->fb_pc}) b->release();
+    ctx->ftab_n = 0; ctx->ftab_first = 0; ctx->ftab_stride = 1;
+    ctx->fb_cap = 0;
+    ctx->dt_cap = 0;
+}
 template <class C> static int gens_install(bp_ctx* ctx, const uint64_t* G_xy, const uint64_t* H_xy, size_t cap) {
+    gens_tables_drop(ctx);   // (before the first byte changes)
+    ctx->gens_derived = false;
     BPCHK(ctx->d_G.ensure(cap * 64 + 64)); BPCHK(ctx->d_H.ensure(cap * 64 + 64));
     HIPCHK(hipMemcpyAsync(ctx->d_G.p, G_xy, cap * 64, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_H.p, H_xy, cap * 64, hipMemcpyHostToDevice, ctx->stream));
@@ -80,7 +90,6 @@ template <class C> static int gens_install(bp_ctx* ctx, const uint64_t* G_xy, co
     BPCHK(bp_points_import(ctx, ctx->d_pc.p, ctx->d_pc.p, 2));
     HIPCHK(ctx_stream_wait(ctx));
     ctx->gens_cap = cap;
-    ctx->dt_cap = 0;   // (direct window tables of other generators)
     return BP_OK;
 }
 // BulletproofGens::new(cap, 1) (src/generators.rs:174-221) with the square roots on the GPU.  GeneratorsChain draws, per
@@ -125,6 +134,10 @@ template <class C> static int derive_table_gpu(bp_ctx* ctx, char which, DevBuf& 
     return BP_OK;
 }
 template <class C> static int gens_derive(bp_ctx* ctx, size_t cap) {
+    // deriving to a larger capacity extends the same chain: G[i], H[i] stay what they were for every i the fold tables and the MSM rows
+    // cover, and those stay.  After caller-installed points, or down to fewer generators than before, they go.
+    if (!ctx->gens_derived || cap < ctx->gens_cap) gens_tables_drop(ctx);
+    ctx->gens_derived = false;
     BPCHK(derive_table_gpu<C>(ctx, 'G', ctx->d_G, cap));
     BPCHK(derive_table_gpu<C>(ctx, 'H', ctx->d_H, cap));
     host::PedersenGens<C> pc = host::PedersenGens<C>::make_default();
@@ -136,7 +149,8 @@ template <class C> static int gens_derive(bp_ctx* ctx, size_t cap) {
     BPCHK(bp_points_import(ctx, ctx->d_pc.p, ctx->d_pc.p, 2));
     HIPCHK(ctx_stream_wait(ctx));
     ctx->gens_cap = cap;
-    ctx->dt_cap = 0;   // (direct window tables of other generators)
+    ctx->gens_derived = true;
+    ctx->dt_cap = 0;   // (the direct window tables are sized by the capacity: built again on first use)
     return BP_OK;
 }
 

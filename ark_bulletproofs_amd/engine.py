@@ -1123,6 +1123,29 @@ Engine.msm_pair_stats = _msm_pair_stats
 Engine.debug_msm_pair = _debug_msm_pair
 
 
+FOLD_LADDER, FOLD_LADDER_NAF, FOLD_TAB, FOLD_TAB2 = 0, 1, 2, 3   # include/arkbp.h BP_DEBUG_FOLD_*
+FOLD_TOOK_GLV, FOLD_TOOK_NAF, FOLD_TOOK_QUAD, FOLD_TOOK_FINISH, FOLD_TOOK_TAB, FOLD_TOOK_TAB2 = 1, 2, 4, 8, 16, 32   # bits of its *took
+
+
+def _debug_fold(self, route, n, tG, tH, t2G=None, t2H=None, gens_first=0, gens_stride=1, G=None, H=None):
+    """bp_debug_fold: one fold of n outputs per vector through the prover's launchers.  tG, tH (and t2G, t2H for FOLD_TAB2): the
+    multipliers as ark words; G, H: the caller's 2n points each for the ladder routes.  Returns (G_out (n, 8), H_out (n, 8), took) —
+    took = 0: the launcher declined and the outputs are all zero."""
+    def words(t):
+        return None if t is None else ptr(np.ascontiguousarray(t, dtype=np.uint64).reshape(4))
+    keep = [None if v is None else u64arr(v, 8) for v in (G, H)]
+    if any(v is not None and len(v) != 2 * n for v in keep):
+        raise ValueError("debug_fold: the ladder routes take 2n points per vector")
+    Go, Ho = np.zeros((n, 8), dtype=np.uint64), np.zeros((n, 8), dtype=np.uint64)
+    took = C.c_uint32(0)
+    check(lib().bp_debug_fold(self.ctx, int(route), C.c_size_t(n), words(tG), words(tH), words(t2G), words(t2H), C.c_uint32(gens_first), C.c_uint32(gens_stride),
+                              None if keep[0] is None else ptr(keep[0]), None if keep[1] is None else ptr(keep[1]), ptr(Go), ptr(Ho), C.byref(took)), "bp_debug_fold")
+    return Go, Ho, took.value
+
+
+Engine.debug_fold = _debug_fold
+
+
 def _prover_handle(p):
     """bp_cs* of a ProverCS or a scenario Statement (bp_stmt_as_prover)"""
     if isinstance(p, Statement):

@@ -198,7 +198,13 @@ int bp_gens_download(bp_ctx* ctx, uint64_t* G_xy, uint64_t* H_xy, size_t n);
  * ~34 look-ups + mixed adds per point (w = 8) instead of a 130-step double-and-add ladder.  count = the left half of the largest
  * proof: N/2.  window_bits 2..8, or 0 = the widest whose tables fit in budget_bytes (0 = 3/4 of the free device memory); the
  * choice and the table size come back in *window_bits_out / *bytes_out (2^19 bases, w = 8: 146 GB for both vectors on secq256k1).
- * Built on the ctx that owns the generators; bp_gens_share hands them on.  count = 0 frees them.  Results never depend on it. */
+ * Built on the ctx that owns the generators; bp_gens_share hands them on.  count = 0 frees them.  Results never depend on it.
+ * WHICH WIDTHS ARE USED: a table has nwin = 130 / w + 1 windows on secq256k1 (the GLV halves) and 256 / w + 1 on zorro, the last one
+ * for the carry of the signed digits, and the fold kernels take a multiplier's digits only when nwin <= 44.  So w = 3 .. 8 serve on
+ * secq256k1 and w = 6, 7, 8 on zorro; w = 2 there, and w = 2 .. 5 on zorro, are built (and pass bp_gens_tables_check) but every fold
+ * goes through the ladder kernels as if there were no tables.
+ * The tables are multiples of the resident generators: bp_gens_upload releases them, the MSM rows and the direct tables below (views of
+ * another ctx's tables are let go); bp_gens_derive to the same or a larger capacity extends the same chain and keeps them. */
 int bp_gens_fold_tables(bp_ctx* ctx, size_t count, int window_bits, size_t budget_bytes, int* window_bits_out, size_t* bytes_out);
 /* The same for ONE RANK of a sharded prover (bp_ctx_set_shard, index-cyclic inner-product argument): only the generators
  * rank + i * world, i < count / world — 1/world of the memory (count = 3N/4 of a 2^22 proof on 8 GPUs at w = 8: 110 GB per rank instead of
@@ -206,8 +212,8 @@ int bp_gens_fold_tables(bp_ctx* ctx, size_t count, int window_bits, size_t budge
  * (bp_gens_share first, then this); bp_gens_tables_check and bp_gens_fold_tables(.., 0, ..) treat them like the whole ones.
  * count must be a multiple of world.  Results never depend on it. */
 int bp_gens_fold_tables_slice(bp_ctx* ctx, size_t count, int window_bits, size_t budget_bytes, int rank, int world, int* window_bits_out, size_t* bytes_out);
-/* Optional: fixed-base rows 2^(4r) * G[i], 2^(4r) * H[i] (r < 64, i < count) and the same for PedersenGens, 4 KiB per generator
- * (count = 2^20: 8.6 GB).  With them every MSM the prover runs over the generator tables themselves — the commitments A_I, A_O, S
+/* Optional: fixed-base rows 2^(4r) * G[i], 2^(4r) * H[i] (r <= 64: 65 rows, the last one — 2^256 * P — for the carry out of the top
+ * window; i < count) and the same for PedersenGens, 65 * 64 B = 4160 bytes per generator and vector (count = 2^20: 8.7 GB).  With them every MSM the prover runs over the generator tables themselves — the commitments A_I, A_O, S
  * (src/r1cs/prover.rs:516-559, 604-649) and the first round's L, R (src/inner_product_proof.rs:83-131), 7/9 of a proof's MSM
  * terms — sorts the digits of ALL Pippenger windows into ONE bucket set (the row supplies the power of two): the per-window costs
  * are paid once, the window is wider (c = 20 at 2^21 terms: 13 mixed adds per term instead of 17-18) and the result needs no
@@ -267,6 +273,28 @@ int bp_debug_msm_direct(bp_ctx* ctx, size_t njobs, const uint32_t* desc, const u
 #define BP_DEBUG_MSM_PAIR_RUNS 6
 int bp_debug_msm_pair(bp_ctx* ctx, const void* const* base_ptrs, const size_t* base_counts, const void* const* d_scalars, size_t n, int canonical, int latency_first,
                       uint64_t* out_xy);
+/* test hook: ONE fold of the inner-product argument through the prover's own launchers (launch_uniform_fold, launch_tab_fold,
+ * launch_tab_fold2 and the shared-inversion epilogue) with caller-chosen multipliers — the multipliers themselves (ark Montgomery
+ * words), not the challenge u.  n outputs per vector.  route:
+ *   BP_DEBUG_FOLD_LADDER      out[i] = V[n+i] + t_V * V[i] over the caller's points G_xy, H_xy (2n each, ark layout): the GLV ladder on
+ *                             secq256k1, the NAF ladder on zorro; BP_TUNE_FOLD_QUAD_MAX and BP_TUNE_FOLD_BATCH_MIN apply as in the prover;
+ *   BP_DEBUG_FOLD_LADDER_NAF  the same with the NAF ladder on secq256k1 as well (what a multiplier without a short GLV split takes);
+ *   BP_DEBUG_FOLD_TAB         out[i] = Gen[n+i] + t_V * Gen[i] from the fold tables and the resident generators (G_xy, H_xy unused);
+ *   BP_DEBUG_FOLD_TAB2        out[i] = Gen[3n+i] + tV * Gen[n+i] + t2V * Gen[2n+i] + tV*t2V * Gen[i]: two rounds from the tables.
+ * Gen[j] is generator gens_first + j * gens_stride.  gens_first = 0, gens_stride = 1: the whole vectors, whose upper halves are read
+ * in place; anything else: an index-cyclic slice, gathered into a compact copy first, as the sharded prover does.  t2G, t2H: TAB2 only.
+ * G_out_xy, H_out_xy: n affine points each, ark layout, all-zero words for the identity.
+ * *took: bit 0 a GLV ladder ran, 1 a NAF ladder, 2 in the quad form, 3 the shared-inversion epilogue (k_ipa_fold_finish), 4
+ * k_ipa_fold_tab, 5 k_ipa_fold_tab2; 0: the launcher declined (a table width whose digits do not fit, see bp_gens_fold_tables; n < 64
+ * for TAB) and nothing was written.
+ * BP_E_ARG — and nothing launched — when a table route finds no tables, or an element would lie outside the tables' columns or the
+ * installed generators. */
+#define BP_DEBUG_FOLD_LADDER 0
+#define BP_DEBUG_FOLD_LADDER_NAF 1
+#define BP_DEBUG_FOLD_TAB 2
+#define BP_DEBUG_FOLD_TAB2 3
+int bp_debug_fold(bp_ctx* ctx, int route, size_t n, const uint64_t tG[4], const uint64_t tH[4], const uint64_t t2G[4], const uint64_t t2H[4], uint32_t gens_first,
+                  uint32_t gens_stride, const uint64_t* G_xy, const uint64_t* H_xy, uint64_t* G_out_xy, uint64_t* H_out_xy, uint32_t* took);
 /* PedersenGens::default() -> (B, B_blinding); host only */
 int bp_pedersen_gens(int curve, uint64_t B_xy[8], uint64_t B_blinding_xy[8]);
 /* GeneratorsChain for label 'G'|'H' || LE32(party) (src/generators.rs:71-121), first `count` points; host only */
