@@ -1604,6 +1604,57 @@ template <class C> static int tables_check(bp_ctx* ctx, uint64_t* bad_fold, uint
     if (bad_rows) *bad_rows = h[1];
     return BP_OK;
 }
+// The same for the tables of the small-statement path and of the commitments, and for the resident points they are anchored at
+// (small.cuh k_dt_check, pedersen.cuh k_pc_table_check, msm.cuh k_points_on_curve): every launch first, then one copy back and one
+// wait.  Reads what is there — a view of another ctx's generators and direct tables included — and builds nothing.
+template <class C> static int direct_tables_check(bp_ctx* ctx, uint64_t* bad, uint64_t* first_bad, uint64_t* checked) {
+    hipStream_t st = ctx->stream;
+    BPCHK(ctx->io_out.ensure(2 * BP_TABLES_KINDS * 8));
+    unsigned long long* d_bad = ctx->io_out.as<unsigned long long>();
+    unsigned long long* d_first = d_bad + BP_TABLES_KINDS;
+    HIPCHK(hipMemsetAsync(d_bad, 0, BP_TABLES_KINDS * 8, st));
+    HIPCHK(hipMemsetAsync(d_first, 0xff, BP_TABLES_KINDS * 8, st));
+    uint64_t seen[BP_TABLES_KINDS] = {0, 0, 0, 0};
+    const u32* pc = ctx->d_pc.as<u32>();
+    const size_t cap = ctx->dt_cap, nb = 2 + 2 * cap;
+    if (cap && pc && cap <= ctx->gens_cap && ctx->dt_tab.p && ctx->dt_tab.cap >= nb * DT_BASE_BYTES) {
+        const size_t entries = nb * DT_PER_BASE;
+        ScopedK tk(ctx, BP_K_DT_CHECK);
+        hipLaunchKernelGGL(k_dt_check<C>, dim3((u32)((entries + 255) / 256)), dim3(256), 0, st, pc, ctx->d_G.as<u32>(), ctx->d_H.as<u32>(), (u32)cap, ctx->dt_tab.as<u32>(),
+                           (u32)nb, d_bad + BP_TABLES_DIRECT, d_first + BP_TABLES_DIRECT);
+        seen[BP_TABLES_DIRECT] = entries;
+    }
+    if (pc && ctx->pc_dt.p && ctx->pc_dt.cap >= (size_t)2 * DT_BASE_BYTES) {
+        hipLaunchKernelGGL(k_dt_check<C>, dim3((2 * DT_PER_BASE + 255) / 256), dim3(256), 0, st, pc, (const u32*)nullptr, (const u32*)nullptr, 0u, ctx->pc_dt.as<u32>(), 2u,
+                           d_bad + BP_TABLES_PC_DIRECT, d_first + BP_TABLES_PC_DIRECT);
+        seen[BP_TABLES_PC_DIRECT] = 2 * DT_PER_BASE;
+    }
+    if (pc && ctx->pc_table.p && ctx->pc_table.cap >= PC_TABLE_BYTES) {
+        hipLaunchKernelGGL(k_pc_table_check<C>, dim3(2 * PC_WINDOWS * PC_DIGITS / 256), dim3(256), 0, st, pc, ctx->pc_table.as<u32>(), d_bad + BP_TABLES_PC_WIDE,
+                           d_first + BP_TABLES_PC_WIDE);
+        seen[BP_TABLES_PC_WIDE] = 2 * PC_WINDOWS * PC_DIGITS;
+    }
+    if (pc) {
+        hipLaunchKernelGGL(k_points_on_curve<C>, dim3(1), dim3(256), 0, st, pc, 2u, 0u, d_bad + BP_TABLES_RESIDENT, d_first + BP_TABLES_RESIDENT);
+        seen[BP_TABLES_RESIDENT] = 2;
+        if (const u32 n = (u32)ctx->gens_cap) {
+            const u32 gb = (n + 255) / 256;
+            hipLaunchKernelGGL(k_points_on_curve<C>, dim3(gb), dim3(256), 0, st, ctx->d_G.as<u32>(), n, 2u, d_bad + BP_TABLES_RESIDENT, d_first + BP_TABLES_RESIDENT);
+            hipLaunchKernelGGL(k_points_on_curve<C>, dim3(gb), dim3(256), 0, st, ctx->d_H.as<u32>(), n, 2u + n, d_bad + BP_TABLES_RESIDENT, d_first + BP_TABLES_RESIDENT);
+            seen[BP_TABLES_RESIDENT] += 2 * (uint64_t)n;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    unsigned long long h[2 * BP_TABLES_KINDS];
+    HIPCHK(hipMemcpyAsync(h, d_bad, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx_stream_wait(ctx));
+    for (int k = 0; k < BP_TABLES_KINDS; k++) {
+        if (bad) bad[k] = h[k];
+        if (first_bad) first_bad[k] = h[BP_TABLES_KINDS + k];
+        if (checked) checked[k] = seen[k];
+    }
+    return BP_OK;
+}
 // Table columns of a state's local elements: element j (generator gens_first + j * gens_stride) is column c0 + j * cs of the ctx's
 // fold tables — whole tables (column = generator index) or a rank's slice of them; false when the elements do not lie on the columns
 static bool ftab_cols(const bp_ctx* ctx, const IpaState& s, u32& c0, u32& cs) {
@@ -3416,8 +3467,21 @@ int bp_gens_tables_check(bp_ctx* c, uint64_t* bad_fold_entries, uint64_t* bad_ms
     if (!c->gens_cap) { g_err = "tables_check: generators not installed"; return BP_E_GENS_LENGTH; }
     return c->curve == 0 ? tables_check<Secq>(c, bad_fold_entries, bad_msm_rows) : tables_check<Zorro>(c, bad_fold_entries, bad_msm_rows);
 }
+int bp_gens_direct_tables_check(bp_ctx* c, uint64_t bad[BP_TABLES_KINDS], uint64_t first_bad[BP_TABLES_KINDS], uint64_t checked[BP_TABLES_KINDS]) {
+    if (!c) { g_err = "bp_gens_direct_tables_check: null ctx"; return BP_E_ARG; }
+    if (c->host_only) return BP_E_NO_DEVICE;
+    HIPCHK(hipSetDevice(c->device));
+    return c->curve == 0 ? direct_tables_check<Secq>(c, bad, first_bad, checked) : direct_tables_check<Zorro>(c, bad, first_bad, checked);
+}
 int bp_debug_tables_ptr(bp_ctx* c, int which, void** dptr, size_t* nbytes) {
-    if (!c || !dptr || !nbytes || which < 0 || which > 6) return BP_E_ARG;
+    if (!c || !dptr || !nbytes || which < 0 || which > 9) return BP_E_ARG;
+    if (which >= 7) {   // the resident points themselves
+        DevBuf& t = which == 7 ? c->d_pc : which == 8 ? c->d_G : c->d_H;
+        const size_t size = which == 7 ? (size_t)128 : c->gens_cap * 64;
+        const bool there = t.p && size && t.cap >= size;
+        *dptr = there ? t.p : nullptr; *nbytes = there ? size : 0;
+        return BP_OK;
+    }
     if (which >= 4) {   // the direct window tables (small.cuh) and the 8-bit Pedersen tables (pedersen.cuh)
         DevBuf& t = which == 4 ? c->dt_tab : which == 5 ? c->pc_dt : c->pc_table;
         const size_t size = which == 4 ? (c->dt_cap ? (2 + 2 * c->dt_cap) * DT_BASE_BYTES : 0) : which == 5 ? (size_t)2 * DT_BASE_BYTES : PC_TABLE_BYTES;

@@ -563,6 +563,22 @@ template <class C> __device__ __forceinline__ bool jac_equals_aff(const Jac& J, 
     if (!fe_eq_mod<F>(fe_wred<F>(J.X), fe_mul<F>(A.x, zz))) return false;
     return fe_eq_mod<F>(fe_wred<F>(J.Y), fe_mul<F>(A.y, fe_mul<F>(zz, J.Z)));
 }
+// One entry of a window table against its own rule, from its STORED neighbours (bp_gens_direct_tables_check; the kernels are next to
+// the tables' builders, small.cuh and pedersen.cuh): cur == p + q, or cur == p for an anchor (q = nullptr).  The mixed addition is the
+// complete one — the d = 2 rule adds an entry to itself.  Whatever the 64 bytes at cur hold, the answer is a verdict: words that are
+// no canonical coordinates, a point off the curve, the identity where identity_ok is false all come out false; a neighbour's words are
+// taken modulo p, so a wrong neighbour fails the entries that are derived from it and nothing else.
+template <class C> __device__ __forceinline__ bool chain_entry_ok(const u32* __restrict__ cur, const u32* __restrict__ p, const u32* __restrict__ q, bool identity_ok) {
+    typedef typename C::Fq F;
+    bool canon, unused;
+    const Aff A = load_aff_checked<C>(cur, canon);
+    const Aff P = load_aff_checked<C>(p, unused);
+    Aff Q;
+    Q.x = fe_zero<F>(); Q.y = fe_zero<F>();
+    if (q) Q = load_aff_checked<C>(q, unused);
+    if (!canon || (!identity_ok && aff_is_inf(A))) return false;
+    return jac_equals_aff<C>(jac_madd<C>(jac_from_aff<C>(P), Q), A);
+}
 template <class C> __global__ void __launch_bounds__(256)
 k_ftab_check(const u32* __restrict__ gens, const u32* __restrict__ T, u32 n, u32 E, u32 nwin, unsigned long long* __restrict__ bad,
              u32 g_first = 0, u32 g_stride = 1 /* column i of the table stands for generator g_first + i * g_stride (a rank's slice) */) {

@@ -1271,4 +1271,47 @@ template <class C> __global__ void k_points_dev_to_ark(const u32* __restrict__ i
     store_words8(out + (size_t)i * 16 + 8, o + 8);
 }
 
+// ---- integrity of resident points (bp_gens_direct_tables_check) ---------------------------------------------------------------------
+// 64 bytes of a resident table as a point, WHATEVER they hold.  canon: both coordinates are the canonical representatives, as every
+// kernel of the engine stores them (fe_pack of fe_canon).  The coordinates that come back are reduced, so the contracts of the field
+// and group operations hold for arbitrary words (a raw 256-bit value can reach V = 2 on zorro).
+template <class C> __device__ __forceinline__ Aff load_aff_checked(const u32* p, bool& canon) {
+    typedef typename C::Fq F;
+    const Aff raw = load_aff_dev(p);
+    Aff r;
+    r.x = fe_canon<F>(raw.x);
+    r.y = fe_canon<F>(raw.y);
+    canon = fe_eq_exact(r.x, raw.x) && fe_eq_exact(r.y, raw.y);
+    return r;
+}
+// A workgroup's verdicts -> the counters of the call.  Every lane of the workgroup calls it (it holds barriers); `index` grows with
+// threadIdx.x.  A clean workgroup issues no atomic; one with wrong entries issues one addition and one minimum, from its lowest wrong lane.
+__device__ __forceinline__ void check_tally(bool wrong, unsigned long long index, unsigned long long* __restrict__ bad, unsigned long long* __restrict__ first) {
+    __shared__ u32 lowest;
+    if (threadIdx.x == 0) lowest = 0xffffffffu;
+    __syncthreads();
+    if (wrong) atomicMin(&lowest, threadIdx.x);
+    const int n = __syncthreads_count(wrong ? 1 : 0);
+    if (n && threadIdx.x == lowest) {
+        atomicAdd(bad, (unsigned long long)n);
+        atomicMin(first, index);
+    }
+}
+// point i is wrong unless it is a canonical, finite solution of y^2 = x^3 + a x + b
+template <class C> __global__ void __launch_bounds__(256)
+k_points_on_curve(const u32* __restrict__ pts, u32 n, u32 index0, unsigned long long* __restrict__ bad, unsigned long long* __restrict__ first) {
+    typedef typename C::Fq F;
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool wrong = false;
+    if (i < n) {
+        bool canon;
+        const Aff P = load_aff_checked<C>(pts + (size_t)i * 16, canon);
+        Fe rhs = fe_mul<F>(fe_sqr<F>(P.x), P.x);
+        if (!C::A_ZERO) rhs = fe_norm(fe_add(rhs, fe_times<(C::A_ZERO ? 1 : C::A_SMALL)>(P.x)));
+        rhs = fe_norm(fe_add(rhs, fe_load_ark<F>(C::B)));   // V < 2 + 6 + 2
+        wrong = !canon || aff_is_inf(P) || !fe_eq_mod<F>(fe_sqr<F>(P.y), rhs);
+    }
+    check_tally(wrong, (unsigned long long)index0 + i, bad, first);
+}
+
 }  // namespace arkbp

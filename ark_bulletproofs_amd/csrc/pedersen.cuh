@@ -33,6 +33,30 @@ k_pc_table_build(const u32* __restrict__ pc /* B, B_blinding: resident affine la
     store_words8(table + (size_t)t * 16 + 8, wd + 8);
 }
 
+// the table's integrity (bp_gens_direct_tables_check), one thread per entry against its own rule with the stored affine neighbours
+// (ipa.cuh chain_entry_ok: a mixed addition and a projective comparison, where the builder has a ladder and doublings):
+//   T[b][w][0] == identity (all-zero words)      T[b][0][1] == base b      T[b][w][1] == T[b][w-1][255] + T[b][w-1][1]
+//   T[b][w][d] == T[b][w][d-1] + T[b][w][1]  for d >= 2
+template <class C> __global__ void __launch_bounds__(256)
+k_pc_table_check(const u32* __restrict__ pc, const u32* __restrict__ table, unsigned long long* __restrict__ bad, unsigned long long* __restrict__ first) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    bool wrong = false;
+    if (t < 2 * PC_WINDOWS * PC_DIGITS) {
+        const u32 b = t / (PC_WINDOWS * PC_DIGITS), w = (t / PC_DIGITS) % PC_WINDOWS, d = t % PC_DIGITS;
+        const u32* cur = table + (size_t)t * 16;
+        if (d == 0) wrong = !aff_is_inf(load_aff_dev(cur));
+        else {
+            const u32 *p = cur - 16, *q = cur - (size_t)(d - 1) * 16;               // d >= 2: the digit before + the window's unit
+            if (d == 1) {
+                if (w) { p = cur - (size_t)2 * 16; q = cur - (size_t)PC_DIGITS * 16; }   // the window before: its d = 255 + its unit
+                else { p = pc + (size_t)b * 16; q = nullptr; }
+            }
+            wrong = !chain_entry_ok<C>(cur, p, q, true);
+        }
+    }
+    check_tally(wrong, (unsigned long long)t, bad, first);
+}
+
 // one thread per commitment.  v, blind: ark layout (Montgomery words, as the caller's Fr values lie in memory);
 // out: affine points in ark layout (x || y Montgomery words, identity = zeros)
 template <class C> __global__ void __launch_bounds__(256)

@@ -57,6 +57,32 @@ k_dt_entries(const u32* __restrict__ ws, u32 nb, u32* __restrict__ tab) {
     store_words8(tab + t * 16, wd);
     store_words8(tab + t * 16 + 8, wd + 8);
 }
+// ---- checking them (bp_gens_direct_tables_check) --------------------------------------------------------------------------------------
+// One lane per entry, each against its OWN rule with the stored affine neighbours (ipa.cuh chain_entry_ok: one mixed addition, one
+// projective comparison, no inversion — not the builders' doublings and ladder):
+//   E[b][0][1] == resident base b        E[b][w][1] == E[b][w-1][15] + E[b][w-1][1]        E[b][w][d] == E[b][w][d-1] + E[b][w][1]
+// and no entry is the identity.  Every entry is some other entry's neighbour except d = 15 of the last window.  Bases as in the
+// builder: [pc[0], pc[1] | G[0..cap) | H[0..cap)]; the tables of B, B_blinding alone are cap = 0.  Three 64-byte reads at addresses
+// that depend on the lane index only.
+template <class C> __global__ void __launch_bounds__(256)
+k_dt_check(const u32* __restrict__ pc, const u32* __restrict__ G, const u32* __restrict__ H, u32 cap, const u32* __restrict__ tab, u32 nb,
+           unsigned long long* __restrict__ bad, unsigned long long* __restrict__ first) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool wrong = false;
+    if (t < (size_t)nb * DT_PER_BASE) {
+        const u32 d = (u32)(t % DT_ENT) + 1u;
+        const size_t bw = t / DT_ENT;   // base * 64 + w
+        const u32 w = (u32)(bw % DT_WINDOWS), b = (u32)(bw / DT_WINDOWS);
+        const u32* cur = tab + t * 16;
+        const u32 *p = cur - 16, *q = cur - (size_t)(d - 1) * 16;                   // d >= 2: the digit before + the window's unit
+        if (d == 1) {
+            if (w) q = cur - (size_t)DT_ENT * 16;                                   // the window before: its d = 15 + its unit
+            else { p = b < 2 ? pc + (size_t)b * 16 : b < 2 + cap ? G + (size_t)(b - 2) * 16 : H + (size_t)(b - 2 - cap) * 16; q = nullptr; }
+        }
+        wrong = !chain_entry_ok<C>(cur, p, q, false);
+    }
+    check_tally(wrong, (unsigned long long)t, bad, first);
+}
 
 // ---- sums over the tables --------------------------------------------------------------------------------------------------------
 // One MSM = up to DT_MAXSEG runs of (scalars, consecutive bases) + one immediate term whose scalar comes with the launch (a

@@ -875,6 +875,19 @@ def _gens_tables_check(self):
     return a.value, b.value
 
 
+TABLES_DIRECT, TABLES_PC_DIRECT, TABLES_PC_WIDE, TABLES_RESIDENT, TABLES_KINDS = 0, 1, 2, 3, 4   # include/arkbp.h BP_TABLES_*
+K_DT_CHECK = 17                          # BP_K_DT_CHECK (Engine.kernel_time)
+
+
+def _gens_direct_tables_check(self):
+    """bp_gens_direct_tables_check: (bad, first_bad, checked), three lists of TABLES_KINDS integers — per kind of table (the direct
+    window tables, those of B and B_blinding alone, the 8-bit commitment tables, the resident points) the entries that fail their
+    own rule, the smallest index of one (2**64 - 1: none) and the entries examined (0: the table is not built)"""
+    arrs = [(C.c_uint64 * TABLES_KINDS)() for _ in range(3)]
+    check(lib().bp_gens_direct_tables_check(self.ctx, *arrs), "bp_gens_direct_tables_check")
+    return tuple([int(v) for v in a] for a in arrs)
+
+
 def _debug_tables_ptr(self, which):
     p, n = C.c_void_p(), C.c_size_t(0)
     check(lib().bp_debug_tables_ptr(self.ctx, int(which), C.byref(p), C.byref(n)), "bp_debug_tables_ptr")
@@ -936,6 +949,7 @@ def _debug_msm_direct(self, jobs, with_workgroups=False):
 
 
 Engine.gens_tables_check = _gens_tables_check
+Engine.gens_direct_tables_check = _gens_direct_tables_check
 Engine.debug_tables_ptr = _debug_tables_ptr
 Engine.debug_table_points = _debug_table_points
 Engine.debug_msm_direct = _debug_msm_direct

@@ -225,13 +225,47 @@ int bp_gens_msm_tables(bp_ctx* ctx, size_t count, size_t* bytes_out);
  * BP_TUNE_DIRECT_MAX and the installed generators allow; count = 0 frees them.  As with the other tables: rebuilding them (a larger
  * count, other generators) on a ctx whose tables are shared is the owner's responsibility.  Results never depend on it. */
 int bp_gens_direct_tables(bp_ctx* ctx, size_t count, size_t* bytes_out);
-/* Integrity check of both kinds of precomputed tables: every entry is re-derived from its stored neighbours by the chain rule
+/* Integrity check of both kinds of precomputed tables of the LARGE-statement path (the fold tables and the MSM rows; the direct window
+ * tables, the commitment tables and the resident points themselves: bp_gens_direct_tables_check below): every entry is re-derived from its stored neighbours by the chain rule
  * (e * 2^(w*j) * P = (e-1) * 2^(w*j) * P + 2^(w*j) * P, next window = the doubled last entry; MSM rows: next row = 16 * row) with
  * mixed additions / doublings compared projectively, anchored at the resident generators; *bad_fold_entries / *bad_msm_rows (either
  * may be NULL) receive the number of entries that do not fit.  A proof touches only the few rows its challenges select, so a
  * corrupted entry (a bit flip in 150 GB of HBM, a bad build) cannot be found by proving; this finds it, in about the time of one
  * proof.  Tables that are not installed count as 0. */
 int bp_gens_tables_check(bp_ctx* ctx, uint64_t* bad_fold_entries, uint64_t* bad_msm_rows);
+/* Integrity check of the tables that every small-statement proof, every group of bp_prover_prove_batch, every verdict of
+ * bp_verifier_verify_batch and every bp_pedersen_commit_batch read, and of the resident points they are multiples of.  Four kinds:
+ *   BP_TABLES_DIRECT     table 4 of bp_debug_tables_ptr: entry E[b][w][d] (w < 64, 1 <= d <= 15) at index (b * 64 + w) * 15 + d - 1,
+ *                        bases b = [B, B_blinding | G[0..cap) | H[0..cap)];
+ *   BP_TABLES_PC_DIRECT  table 5: the same layout for B and B_blinding alone;
+ *   BP_TABLES_PC_WIDE    table 6: entry T[b][w][d] (b < 2, w < 32, d < 256) at index (b * 32 + w) * 256 + d;
+ *   BP_TABLES_RESIDENT   the resident points: index 0 = B, 1 = B_blinding, 2 + i = G[i], 2 + gens_capacity + i = H[i].
+ * Each entry has ONE rule, evaluated from its STORED affine neighbours with a complete mixed addition and a projective comparison
+ * (no inversion; the builders use doublings and ladders):
+ *   tables 4, 5:  E[b][0][1] == resident base b;   E[b][w][1] == E[b][w-1][15] + E[b][w-1][1] for w >= 1;
+ *                 E[b][w][d] == E[b][w][d-1] + E[b][w][1] for d >= 2;   and no entry is the identity (all-zero words fail);
+ *   table 6:      T[b][w][0] is the identity (all-zero words);   T[b][0][1] == base b;
+ *                 T[b][w][1] == T[b][w-1][255] + T[b][w-1][1] for w >= 1;   T[b][w][d] == T[b][w][d-1] + T[b][w][1] for d >= 2;
+ *   resident:     the point satisfies the equation of the ctx's curve and is not the identity.
+ * In all four an entry must also hold the canonical representatives of its coordinates (values below the modulus), as every kernel
+ * stores them.  Every table entry is some other entry's neighbour except the last digit of a base's last window, so ONE wrong entry
+ * usually counts several times: itself and the entries derived from it (a unit entry d = 1: the 14 other digits of its window and the
+ * next window's unit).  Off-curve words, the identity and arbitrary bit patterns all come out as "bad" and nothing else.
+ * bad[k]: the entries of kind k that fail their own rule; first_bad[k]: the smallest index of one, UINT64_MAX when there is none;
+ * checked[k]: the entries examined — 0 for a table that is not built, so that "0 bad" and "nothing looked at" differ.  Each of the
+ * three arrays may be NULL.  Nothing is built or rebuilt: the call reads what is there, on the ctx's stream, with one copy back and
+ * one wait after the last launch.  A ctx that shares generators (bp_gens_share) checks the owner's points and direct tables through
+ * its view (tables 5 and 6 are each ctx's own).
+ * WHAT IT CANNOT SEE: BP_TABLES_RESIDENT knows a point only as a point of the curve — two on-curve generators swapped in the
+ * resident table, or any other valid point in a generator's place, pass it; the anchors of table 4 then fail (for generators within
+ * the tables' reach), and generators beyond the reach are not pinned by anything here.  B and B_blinding are pinned by three anchors.
+ * BP_E_ARG for a null ctx, BP_E_NO_DEVICE for a host-only ctx. */
+#define BP_TABLES_DIRECT 0      /* bp_debug_tables_ptr which = 4 */
+#define BP_TABLES_PC_DIRECT 1   /* which = 5 */
+#define BP_TABLES_PC_WIDE 2     /* which = 6 */
+#define BP_TABLES_RESIDENT 3    /* the resident points themselves: B, B_blinding, G[0..gens_cap), H[0..gens_cap) */
+#define BP_TABLES_KINDS 4
+int bp_gens_direct_tables_check(bp_ctx* ctx, uint64_t bad[BP_TABLES_KINDS], uint64_t first_bad[BP_TABLES_KINDS], uint64_t checked[BP_TABLES_KINDS]);
 /* test hook: device address and size in bytes of a table; NULL / 0 when it is not built.  which:
  *   0 / 1  fold tables of G / H, layout [window][digit-1][i] x 64 B;
  *   2 / 3  MSM rows of G / H, layout [row][i] x 64 B;
@@ -243,6 +277,8 @@ int bp_gens_tables_check(bp_ctx* ctx, uint64_t* bad_fold_entries, uint64_t* bad_
  *   6      the 8-bit tables that larger commitment batches read: layout [b < 2][w < 32][d < 256] x 64 B = d * 256^w * base_b, b = 0
  *          for B, 1 for B_blinding; d = 0 is the identity.
  *   5 and 6 exist once the ctx has run its first bp_pedersen_commit_batch.
+ *   7      the resident points B, B_blinding (128 bytes); 8 / 9: the resident generators G / H, gens_capacity x 64 B — what the tables
+ *          are anchored at and BP_TABLES_RESIDENT of bp_gens_direct_tables_check examines (the owner's, on a ctx that shares them).
  * Every entry is an affine point in the RESIDENT layout: bp_points_export turns entries into ark words (the identity: all zero). */
 int bp_debug_tables_ptr(bp_ctx* ctx, int which, void** dptr, size_t* nbytes);
 /* test hook: `njobs` (1 .. 6) sums over the direct window tables through the prover's own msm_direct (k_dt_accum, k_dt_finish, the
@@ -589,7 +625,8 @@ int bp_r1cs_batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenari
 #define BP_K_VFE_PREPARE 14 /* k_vfe_consts + k_vfe_wv + k_vfe_sum2: challenge arithmetic, parameter blocks, tail scalars */
 #define BP_K_VE_TAIL 15     /* k_ve_tail: the per-proof variable-base sums of bp_verifier_verify_batch */
 #define BP_K_MSM_BATCH 16   /* k_msb_accum + k_msb_combine: the bucketed route of bp_msm_batch, one region per group */
-#define BP_K_COUNT 17
+#define BP_K_DT_CHECK 17    /* k_dt_check over table 4: the direct window tables' part of bp_gens_direct_tables_check */
+#define BP_K_COUNT 18
 int bp_ctx_set_profiling(bp_ctx* ctx, int enabled);
 /* accumulated milliseconds and launch count since the last reset */
 int bp_ctx_kernel_time(bp_ctx* ctx, int which, double* ms_total, uint64_t* launches);
