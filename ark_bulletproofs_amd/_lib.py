@@ -24,6 +24,7 @@ EXPORTS = [
     "bp_cs_multiply", "bp_cs_allocate", "bp_cs_allocate_multiplier", "bp_cs_constrain", "bp_cs_allocate_multipliers", "bp_cs_constrain_many",
     "bp_cs_specify_randomized_constraints", "bp_cs_challenge_scalar", "bp_prover_set_rng", "bp_prover_precompute", "bp_prover_precompute_batch", "bp_prover_prove", "bp_prover_prove_batch", "bp_prover_commit_batch", "bp_ctx_prove_batch_stats", "bp_ctx_prove_batch_front_stats",
     "bp_verifier_verify_batch", "bp_r1cs_verify_each_scenarios", "bp_ctx_verify_each_stats", "bp_debug_msm_each", "bp_debug_ve_plan",
+    "bp_r1cs_batch_verify_locate", "bp_r1cs_batch_verify_locate_scenarios", "bp_ctx_verify_locate_stats", "bp_debug_locate_plan",
     "bp_msm_batch", "bp_msm_batch_dev", "bp_ctx_msm_batch_stats", "bp_debug_msm_batch_plan",
     "bp_ctx_set_shard_allgather", "bp_gens_fold_tables", "bp_gens_msm_tables", "bp_debug_exp_iter", "bp_debug_inner_product", "bp_verifier_verify", "bp_r1cs_batch_verify", "bp_stmt_as_prover", "bp_transcript_export_state", "bp_transcript_import_state", "bp_transcript_clone",
     "bp_gens_tables_check", "bp_debug_tables_ptr", "bp_debug_msm_direct", "bp_rccl_unique_id", "bp_ctx_rccl_init", "bp_ctx_rccl_shutdown", "bp_ctx_collective_stats", "bp_debug_rccl_allgather",

@@ -345,6 +345,9 @@ struct bp_ctx {
     size_t tune_verify_each = 0;     // BP_TUNE_VERIFY_EACH: most instances per group (0 = what VE_ARENA_BUDGET holds, at most VE_GROUP_MAX)
     DevBuf ve_arena;
     uint64_t ve_grouped = 0, ve_single = 0, ve_groups = 0, ve_waits = 0;
+    // bp_r1cs_batch_verify_locate: its knob and counters (calls, passes of the core, instances in them, instances decided exactly)
+    size_t tune_verify_locate_leaf = 0;   // BP_TUNE_VERIFY_LOCATE_LEAF (0 = 1: pure bisection)
+    uint64_t vl_calls = 0, vl_passes = 0, vl_instances = 0, vl_exact = 0;
     // bp_msm_batch (msm_batch.inc): its knobs (0 = the default) and counters; it stages in ve_arena
     uint64_t tune_msb_short = 0, tune_msb_slice = 0, tune_msb_max = 0, tune_msb_min_jobs = 0;   // BP_TUNE_MSM_BATCH_SHORT / _SLICE / _MAX / _MIN_JOBS
     uint64_t mb_short = 0, mb_bucketed = 0, mb_single = 0, mb_groups = 0, mb_waits = 0;
@@ -3045,6 +3048,241 @@ __attribute__((target("avx512f"))) static int dbg_challenge_x8(void* const* trs,
 #include "verify_each.inc"   // bp_verifier_verify_batch, bp_r1cs_verify_each_scenarios, bp_debug_msm_each
 #include "msm_batch.inc"     // bp_msm_batch, bp_msm_batch_dev, bp_ctx_msm_batch_stats, bp_debug_msm_batch_plan
 
+// ---- bp_r1cs_batch_verify_locate: batch verification that names the failing instances --------------------------------------------
+// The planner (verify_locate.inc) asks for passes over subsets of the batch; a pass is ONE call of batch_verify_core over the
+// subset's own provider, proofs and weights, gathered through an index map.  Instance k keeps weight k in every pass.
+#include "verify_locate.inc"
+// sub(idx, n, out): the provider of instances idx[0 .. n) of the batch.  restore(idx, n): puts those instances back into the state
+// they had on entry to the call (recorded handles; scenario providers build their recordings anew in every pass).
+template <class C> using LocateSubFn = std::function<void(const uint32_t*, size_t, VfyProvider<C>&)>;
+template <class C>
+static int locate_core(bp_ctx* ctx, size_t count, const LocateSubFn<C>& sub, const std::function<void(const uint32_t*, size_t)>& restore, const uint8_t* proofs,
+                       const size_t* poff /* count + 1 */, const F4* alphas, int* status, double* timing, double snap_s) {
+    const double t_entry = now_s(), snap0 = snap_s;
+    double t_first = 0, t_later = 0;
+    const size_t leaf = ctx->tune_verify_locate_leaf ? ctx->tune_verify_locate_leaf : 1;
+    LocatePlanner plan(count, leaf, status);
+    std::vector<uint8_t> buf;
+    std::vector<size_t> spoff;
+    std::vector<F4> sal;
+    // the subset's proofs in one contiguous buffer with its own offsets, its weights likewise; the whole batch is used in place
+    auto gather = [&](const uint32_t* idx, size_t n, const uint8_t*& pr, const size_t*& po, const F4*& al) {
+        if (n == count) { pr = proofs; po = poff; al = alphas; return; }   // (a contiguous range of the survivors that holds every instance)
+        spoff.assign(n + 1, 0);
+        for (size_t j = 0; j < n; j++) spoff[j + 1] = spoff[j] + (poff[idx[j] + 1] - poff[idx[j]]);
+        buf.resize(spoff[n] ? spoff[n] : 1);
+        sal.resize(n);
+        for (size_t j = 0; j < n; j++) { memcpy(buf.data() + spoff[j], proofs + poff[idx[j]], spoff[j + 1] - spoff[j]); sal[j] = alphas[idx[j]]; }
+        pr = buf.data(); po = spoff.data(); al = sal.data();
+    };
+    bool first = true;
+    auto enter = [&](const uint32_t* idx, size_t n) {   // every pass but the first starts its members from their entry state
+        if (first) { first = false; return; }
+        const double t0 = now_s();
+        restore(idx, n);
+        snap_s += now_s() - t0;
+    };
+    const LocatePlanner::RunFn run = [&](size_t lo, size_t n, LocateOutcome& out) -> int {
+        const double t0 = now_s();
+        const bool was_first = first;
+        const uint32_t* idx = plan.survivors().data() + lo;
+        enter(idx, n);
+        const uint8_t* pr; const size_t* po; const F4* al;
+        gather(idx, n, pr, po, al);
+        VfyProvider<C> prov;
+        sub(idx, n, prov);
+        std::vector<int> st(n, BP_OK);
+        const int rc = batch_verify_core<C>(ctx, n, prov, pr, po, al, nullptr, nullptr, st.data());
+        ctx->vl_passes++; ctx->vl_instances += n;
+        (was_first ? t_first : t_later) += now_s() - t0;
+        for (size_t j = 0; j < n; j++) if (st[j]) out.before.emplace_back(j, st[j]);
+        if (!out.before.empty()) { out.kind = LocateOutcome::FAILED_BEFORE; return BP_OK; }
+        if (rc == BP_OK) { out.kind = LocateOutcome::PASSED; return BP_OK; }
+        if (rc == BP_E_VERIFICATION) { out.kind = LocateOutcome::FAILED_CHECK; return BP_OK; }
+        return rc;   // (a HIP error, a structure digest collision: the call cannot go on)
+    };
+    // a failing range of at most BP_TUNE_VERIFY_LOCATE_LEAF members: the machinery of bp_verifier_verify_batch, a verdict for each
+    const LocatePlanner::ExactFn exact = [&](size_t lo, size_t n, int* st) -> int {
+        const double t0 = now_s();
+        const uint32_t* idx = plan.survivors().data() + lo;
+        enter(idx, n);
+        const uint8_t* pr; const size_t* po; const F4* al;
+        gather(idx, n, pr, po, al);
+        VfyProvider<C> prov;
+        sub(idx, n, prov);
+        prov.dev_batch = nullptr;
+        std::fill(st, st + n, BP_OK);
+        const int rc = verify_each_core<C>(ctx, n, prov, pr, po, st, nullptr, nullptr);
+        t_later += now_s() - t0;
+        int want = BP_OK;
+        for (size_t j = 0; j < n && !want; j++) want = st[j];
+        return rc == want ? BP_OK : rc;   // (it returns the first status; anything else is an error of the call itself)
+    };
+    const int prc = plan.plan(run, exact, BP_E_VERIFICATION);
+    ctx->vl_calls++; ctx->vl_exact += plan.exact_leaves();
+    if (timing) { timing[0] = now_s() - t_entry + snap0; timing[1] = t_first; timing[2] = t_later; timing[3] = snap_s; }
+    if (prc) return prc > 0 ? BP_E_ARG : prc;
+    for (size_t k = 0; k < count; k++) if (status[k]) return status[k];
+    return BP_OK;
+}
+// over recorded verifier handles (each consumed, like `verify(self)`)
+template <class C>
+static int cs_batch_verify_locate(bp_ctx* c, size_t count, bp_cs* const* vs, const uint8_t* proofs, const size_t* proof_lens, const uint64_t* alphas, int* status,
+                                  double* timing) {
+    typedef host::Fld<typename C::Fr> S;
+    typedef host::ConstraintSystem<C> CS;
+    std::vector<size_t> poff(count + 1, 0);
+    for (size_t k = 0; k < count; k++) poff[k + 1] = poff[k] + proof_lens[k];
+    std::vector<F4> al(count);
+    for (size_t k = 0; k < count; k++) { if (alphas) memcpy(al[k].v, alphas + 4 * k, 32); else al[k] = S::one(); }
+    // entry states: the transcript (the host replay advances it) and what the randomized phase changes in the recorder
+    const double t_snap = now_s();
+    std::vector<host::Strobe> tr0(count);
+    std::vector<typename CS::RandSnap> cs0(count);
+    for (size_t k = 0; k < count; k++) { CS* ck = vs[k]->cs<C>(); if (ck->tr) tr0[k] = ck->tr->s; ck->snapshot(cs0[k]); }
+    const double snap_s = now_s() - t_snap;
+    const std::function<void(const uint32_t*, size_t)> restore = [&](const uint32_t* idx, size_t n) {
+        for (size_t j = 0; j < n; j++) { CS* ck = vs[idx[j]]->cs<C>(); if (ck->tr) ck->tr->s = tr0[idx[j]]; ck->restore(cs0[idx[j]]); }
+    };
+    const bool two_ok = c->tune_vfy_device >= 2;
+    const LocateSubFn<C> sub = [&](const uint32_t* idx, size_t n, VfyProvider<C>& prov) {
+        prov.m_of = [vs, idx](size_t j) { return vs[idx[j]]->cs<C>()->V.size(); };
+        prov.get = [vs, idx](size_t j, VfyInstance<C>& out) -> int { out.cs = vs[idx[j]]->cs<C>(); return BP_OK; };
+        // like-instances of one recording: as in cs_batch_verify, over the subset
+        prov.dev_batch = [vs, idx, n, two_ok](VfyDevBatch<C>& db) -> bool {
+            const CS* c0 = vs[idx[0]]->cs<C>();
+            if (!c0->base || !c0->tr || (!c0->deferred.empty() && !two_ok)) return false;
+            for (size_t j = 0; j < n; j++) {
+                const CS* ck = vs[idx[j]]->cs<C>();
+                if (ck->base != c0->base || ck->cs_off.size() != 1 || ck->deferred.size() != c0->deferred.size() || ck->phase2 || ck->num_vars != c0->num_vars || ck->V.size() != c0->V.size() ||
+                    !ck->tr)
+                    return false;
+            }
+            db.src = c0; db.m = c0->V.size(); db.absorb_commitments = false; db.shared_state = false;
+            db.state_of = [vs, idx](size_t j) { return (const host::Strobe*)&vs[idx[j]]->cs<C>()->tr->s; };
+            db.commit_xy = [vs, idx](size_t j) { return (const uint64_t*)vs[idx[j]]->cs<C>()->V.data(); };
+            if (!c0->deferred.empty()) db.cs_of = [vs, idx](size_t j) { return vs[idx[j]]->cs<C>(); };
+            return true;
+        };
+    };
+    for (size_t k = 0; k < count; k++) { vs[k]->consumed = true; vs[k]->running = true; }
+    const int rc = locate_core<C>(c, count, sub, restore, proofs, poff.data(), al.data(), status, timing, snap_s);
+    for (size_t k = 0; k < count; k++) vs[k]->running = false;
+    return rc;
+}
+// scenario statements: batch_verify_scenarios' sources, recorders and weights; a subset's provider goes through the index map
+template <class C>
+static int scenarios_batch_verify_locate(bp_ctx* c, size_t count, const int* scenarios, const uint64_t* params, const uint8_t* proofs, const size_t* proof_lens,
+                                         const uint64_t* commit_xy, const size_t* ms, const uint64_t* publics, const size_t* npubs, const uint8_t* alpha_seed, int* status,
+                                         double* timing) {
+    const VfyCoreFn<C> core = [&](const VfyProvider<C>& full, const size_t* poff, const F4* alphas) -> int {
+        for (size_t k = 0; k < count; k++) if (alphas[k].is_zero()) { g_err = "batch_verify_locate: a weight is zero"; return BP_E_ARG; }
+        const LocateSubFn<C> sub = [&](const uint32_t* idx, size_t n, VfyProvider<C>& prov) {
+            if (n == count) { prov = full; return; }   // (the lockstep heads need consecutive instances: the whole batch only)
+            prov.m_of = [&full, idx](size_t j) { return full.m_of(idx[j]); };
+            prov.get = [&full, idx](size_t j, VfyInstance<C>& out) -> int { return full.get(idx[j], out); };
+            if (full.dev_batch) prov.dev_batch = [&full, idx](VfyDevBatch<C>& db) -> bool {
+                VfyDevBatch<C> all;
+                if (!full.dev_batch(all)) return false;   // one statement shape for the whole batch, so for every subset of it
+                db = all;
+                db.state_of = [s = all.state_of, idx](size_t j) { return s(idx[j]); };
+                db.commit_xy = [x = all.commit_xy, idx](size_t j) { return x(idx[j]); };
+                if (all.cs_of) db.cs_of = [f = all.cs_of, idx](size_t j) { return f(idx[j]); };
+                return true;
+            };
+        };
+        const std::function<void(const uint32_t*, size_t)> restore = [](const uint32_t*, size_t) {};
+        return locate_core<C>(c, count, sub, restore, proofs, poff, alphas, status, timing, 0.0);
+    };
+    return batch_verify_scenarios<C>(c, count, scenarios, params, proofs, proof_lens, commit_xy, ms, publics, npubs, alpha_seed, nullptr, 0, nullptr, &core);
+}
+
+int bp_r1cs_batch_verify_locate(bp_ctx* c, size_t count, bp_cs* const* verifiers, const uint8_t* proofs, const size_t* proof_lens, const uint64_t* alphas, int* status,
+                                double* timing) {
+    if (!c) return BP_E_ARG;
+    if (count == 0) return BP_OK;
+    if (!verifiers || !proofs || !proof_lens || !status) return BP_E_ARG;
+    if (count > 1 && !alphas) { g_err = "batch_verify_locate: per-instance weights (alphas) are required for more than one instance"; return BP_E_ARG; }
+    if (alphas) for (size_t k = 0; k < count; k++) {   // (zero is zero in Montgomery form too)
+        if (!(alphas[4 * k] | alphas[4 * k + 1] | alphas[4 * k + 2] | alphas[4 * k + 3])) { g_err = "batch_verify_locate: a zero weight hides its instance from every sum"; return BP_E_ARG; }
+    }
+    for (size_t k = 0; k < count; k++) {
+        if (!verifiers[k] || verifiers[k]->consumed || verifiers[k]->proving || verifiers[k]->curve != c->curve) { g_err = "batch_verify_locate: every instance needs a live verifier of the ctx's curve"; return BP_E_ARG; }
+    }
+    if (count > 1) {
+        std::vector<const bp_cs*> sorted(verifiers, verifiers + count);
+        std::sort(sorted.begin(), sorted.end(), std::less<const bp_cs*>());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { g_err = "batch_verify_locate: a verifier is consumed by ONE instance"; return BP_E_ARG; }
+    }
+    {   // a like-instance must hold every commitment the shared constraints name (verify_prepare would refuse it mid-pass)
+        const host::FrozenRecording* seen = nullptr;
+        size_t need = 0;
+        for (size_t k = 0; k < count; k++) {
+            const host::FrozenRecording* b = c->curve == 0 ? verifiers[k]->cs0->base.get() : verifiers[k]->cs1->base.get();
+            if (!b) continue;
+            if (b != seen) { seen = b; need = 0; for (const auto& vt : b->vterms) need = std::max(need, (size_t)vt.j + 1); }
+            const size_t have = c->curve == 0 ? verifiers[k]->cs0->V.size() : verifiers[k]->cs1->V.size();
+            if (have < need) { g_err = "batch_verify_locate: the constraints refer to more commitments than a verifier holds (bp_verifier_commit)"; return BP_E_ARG; }
+        }
+    }
+    if (!c->gens_cap) { g_err = "batch_verify_locate: generators not installed"; return BP_E_GENS_LENGTH; }
+    if (c->host_only) { g_err = "batch_verify_locate: a host-only ctx has no device to verify on"; return BP_E_NO_DEVICE; }
+    HIPCHK(hipSetDevice(c->device));
+    return c->curve == 0 ? cs_batch_verify_locate<Secq>(c, count, verifiers, proofs, proof_lens, alphas, status, timing)
+                         : cs_batch_verify_locate<Zorro>(c, count, verifiers, proofs, proof_lens, alphas, status, timing);
+}
+int bp_r1cs_batch_verify_locate_scenarios(bp_ctx* c, size_t count, const int* scenarios, const uint64_t* params, const uint8_t* proofs, const size_t* proof_lens,
+                                          const uint64_t* commit_xy, const size_t* ms, const uint64_t* publics, const size_t* npubs, const uint8_t alpha_seed[32],
+                                          int* status, double* timing) {
+    if (!c) return BP_E_ARG;
+    if (count == 0) return BP_OK;
+    if (!scenarios || !params || !proofs || !proof_lens || !ms || !npubs || !status) return BP_E_ARG;
+    if (count > 1 && !alpha_seed) { g_err = "batch_verify_locate: the weights' seed is required for more than one instance"; return BP_E_ARG; }
+    size_t tm = 0, tp = 0;
+    for (size_t k = 0; k < count; k++) { tm += ms[k]; tp += npubs[k]; }
+    if ((tm && !commit_xy) || (tp && !publics)) return BP_E_ARG;
+    if (!c->gens_cap) { g_err = "batch_verify_locate: generators not installed"; return BP_E_GENS_LENGTH; }
+    if (c->host_only) { g_err = "batch_verify_locate: a host-only ctx has no device to verify on"; return BP_E_NO_DEVICE; }
+    HIPCHK(hipSetDevice(c->device));
+    return c->curve == 0 ? scenarios_batch_verify_locate<Secq>(c, count, scenarios, params, proofs, proof_lens, commit_xy, ms, publics, npubs, alpha_seed, status, timing)
+                         : scenarios_batch_verify_locate<Zorro>(c, count, scenarios, params, proofs, proof_lens, commit_xy, ms, publics, npubs, alpha_seed, status, timing);
+}
+int bp_ctx_verify_locate_stats(bp_ctx* c, uint64_t* calls, uint64_t* passes, uint64_t* instances_in_passes, uint64_t* exact_leaves) {
+    if (!c) return BP_E_ARG;
+    if (calls) *calls = c->vl_calls;
+    if (passes) *passes = c->vl_passes;
+    if (instances_in_passes) *instances_in_passes = c->vl_instances;
+    if (exact_leaves) *exact_leaves = c->vl_exact;
+    return BP_OK;
+}
+// test hook, host only: the planner over a simulated core
+int bp_debug_locate_plan(size_t count, const uint8_t* fails_check, const uint8_t* fails_before, uint32_t* npasses, uint32_t* pass_lo, uint32_t* pass_n,
+                         uint8_t* pass_failed, uint64_t* instances_in_passes, int* status) {
+    if (!status || (count && !fails_check) || count >= ((size_t)1 << 31)) return BP_E_ARG;
+    LocatePlanner plan(count, 1, status);
+    uint32_t np = 0;
+    const LocatePlanner::RunFn run = [&](size_t lo, size_t n, LocateOutcome& out) -> int {
+        const uint32_t* idx = plan.survivors().data() + lo;
+        for (size_t j = 0; j < n; j++) if (fails_before && fails_before[idx[j]]) out.before.emplace_back(j, BP_E_FORMAT);
+        if (!out.before.empty()) out.kind = LocateOutcome::FAILED_BEFORE;
+        else { out.kind = LocateOutcome::PASSED; for (size_t j = 0; j < n; j++) if (fails_check[idx[j]]) out.kind = LocateOutcome::FAILED_CHECK; }
+        if (pass_lo) pass_lo[np] = (uint32_t)lo;
+        if (pass_n) pass_n[np] = (uint32_t)n;
+        if (pass_failed) pass_failed[np] = (uint8_t)out.kind;
+        np++;
+        return BP_OK;
+    };
+    const LocatePlanner::ExactFn exact = [&](size_t lo, size_t n, int* st) -> int {   // (not reached with leaf 1 and this simulator)
+        const uint32_t* idx = plan.survivors().data() + lo;
+        for (size_t j = 0; j < n; j++) st[j] = fails_before && fails_before[idx[j]] ? BP_E_FORMAT : fails_check[idx[j]] ? BP_E_VERIFICATION : BP_OK;
+        return BP_OK;
+    };
+    const int rc = plan.plan(run, exact, BP_E_VERIFICATION);
+    if (npasses) *npasses = np;
+    if (instances_in_passes) *instances_in_passes = plan.instances_in_passes();
+    return rc ? BP_E_ARG : BP_OK;
+}
+
 // test hook: the production msm_direct on caller-chosen jobs (include/arkbp.h bp_debug_msm_direct).  Everything a job would read is
 // checked here on the host — k_dt_accum itself trusts its descriptors
 template <class C>
@@ -3255,6 +3493,7 @@ int bp_ctx_set_tuning(bp_ctx* c, int knob, uint64_t value) {
         case BP_TUNE_MSM_BATCH_SLICE: c->tune_msb_slice = value; return BP_OK;
         case BP_TUNE_MSM_BATCH_MAX: c->tune_msb_max = value; return BP_OK;
         case BP_TUNE_MSM_PAIR: if (value > 1) return BP_E_ARG; c->tune_msm_pair = (int)value; return BP_OK;
+        case BP_TUNE_VERIFY_LOCATE_LEAF: if (value > 4096) return BP_E_ARG; c->tune_verify_locate_leaf = (size_t)value; return BP_OK;
     }
     return BP_E_ARG;
 }

@@ -1782,14 +1782,20 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
 // circuit template, the 2N g/h scalars of every proof, alpha-weighted accumulation).  Instances are grouped by the template their
 // recording canonicalises to — single-phase and randomized statements alike; one launch per (template, block).  The alpha-scaling
 // of the tails and the canonical forms are GPU work; the host keeps only the two head scalars.  One MSM at the end.
+//
+// inst_status (count ints, optional; bp_r1cs_batch_verify_locate): the call then does not stop at the first instance that fails
+// before the mega-check (framing, decompression, verify_prepare).  EVERY such instance of the batch gets its own status — what a
+// batch of that instance alone returns — the others stay BP_OK, and the call returns the first of them in instance order without
+// a mega-check verdict.  When no instance fails that way the statuses are all BP_OK and the return value is the mega-check's.
 template <class C>
 static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& prov, const uint8_t* proofs, const size_t* poff /* count + 1 */, const F4* alphas,
-                             double* timing, uint64_t* point_out) {
+                             double* timing, uint64_t* point_out, int* inst_status = nullptr) {
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
     hipStream_t st = ctx->stream;
     const double t_entry = now_s();
     if (point_out) memset(point_out, 0, 64);   // every early exit leaves a defined (identity) check point
+    if (inst_status) std::fill(inst_status, inst_status + count, BP_OK);
     static const bool vtrace = getenv("ARKBP_VFY_TRACE") != nullptr;
     double t_last = t_entry;
     auto mark = [&](const char* what) { if (vtrace) { double t = now_s(); fprintf(stderr, "[vfy] %-28s %8.3f ms\n", what, (t - t_last) * 1e3); t_last = t; } };
@@ -1813,7 +1819,10 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
     std::vector<int> rcs(count, BP_OK);
     std::vector<host::LazyProof> lps(count);
     parallel_range(0, count, [&](size_t k) { rcs[k] = host::proof_parse_lazy<C>(lps[k], proofs + poff[k], poff[k + 1] - poff[k]); });
-    for (size_t k = 0; k < count; k++) if (rcs[k]) return rcs[k];
+    for (size_t k = 0; k < count; k++) if (rcs[k]) {
+        if (!inst_status) return rcs[k];
+        lps[k].xs.clear(); lps[k].flags.clear(); lps[k].k = (size_t)-1;   // no points of its own; it dooms the batch below
+    }
     std::vector<size_t> xoff(count + 1, 0);
     for (size_t k = 0; k < count; k++) xoff[k + 1] = xoff[k] + lps[k].xs.size();
     // compressed points: x words and flag bytes gathered in pinned memory; the square roots run on a second stream, block by
@@ -1887,7 +1896,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
         const size_t first_hi = doomed ? count : std::min(count, VFY_BLOCK);
         BPCHK(issue_decode(first_hi, 0));
         HIPCHK(event_wait(ctx, ctx->dec_ev[0]));
-        BPCHK(check_decoded(0, first_hi));
+        if (!inst_status) BPCHK(check_decoded(0, first_hi));
     }
     mark("gpu decompress (first block)");
     if (timing) timing[4] = now_s() - t_entry;
@@ -1898,6 +1907,25 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
         if (rc) return rc;
         return verify_prepare<C>(*r.inst.cs, r.pf, ctx->gens_cap, r.vp);
     };
+    // inst_status: instances [from, count) each on their own — framing, its points, its replay — with no GPU work but the decode
+    auto report_each = [&](size_t from) -> int {
+        if (decoded_upto < count) BPCHK(issue_decode(count, 0));
+        HIPCHK(hipStreamSynchronize(ctx->aux_stream));
+        std::vector<int> erc(count, BP_OK);
+        std::vector<const char*> emsg(count, nullptr);
+        parallel_range(from, count, [&](size_t k) {
+            if (rcs[k]) { erc[k] = rcs[k]; return; }
+            for (size_t j = xoff[k]; j < xoff[k + 1]; j++) if (!all_ok[j]) { erc[k] = BP_E_FORMAT; return; }
+            Replayed r;
+            erc[k] = replay(k, r); emsg[k] = r.vp.err;
+            const size_t kk = lps[k].k;
+            if (!erc[k] && (kk == (size_t)-1 || kk >= 32 || ((size_t)1 << kk) > ctx->gens_cap)) erc[k] = BP_E_VERIFICATION;   // (not reached, as below)
+        });
+        for (size_t k = from; k < count; k++) inst_status[k] = erc[k];
+        for (size_t k = 0; k < count; k++) if (inst_status[k]) { if (k >= from && emsg[k]) g_err = emsg[k]; return inst_status[k]; }
+        return BP_OK;
+    };
+    if (inst_status && (doomed || check_decoded(0, std::min(count, VFY_BLOCK)))) return report_each(0);
     if (doomed) {
         std::vector<int> erc(count, BP_OK);
         std::vector<const char*> emsg(count, nullptr);
@@ -1926,6 +1954,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
     mark("layout + alphas");
     double host_busy = 0;
     int first_err = BP_OK;
+    size_t err_from = 0;   // inst_status: the instances from here on have no status yet when first_err stops the blocks
     uint64_t dry_sum = 0xcbf29ce484222325ULL;
     for (size_t blk = 0; blk < nblocks && !first_err; blk++) {
         const size_t lo = blk * VFY_BLOCK, hi = std::min(count, lo + VFY_BLOCK), nb = hi - lo;
@@ -1934,7 +1963,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
         if (blk > 0) {
             HIPCHK(event_wait(ctx, ctx->dec_ev[half]));              // this block's points are in host memory
             const int frc = check_decoded(lo, hi);
-            if (frc) { first_err = frc; break; }
+            if (frc) { first_err = frc; err_from = lo; break; }
         }
         if (decoded_upto < count) BPCHK(issue_decode(std::min(count, decoded_upto + VFY_BLOCK), half ^ 1));   // next block's decode runs beside this block
         // staging layout of this block: [parameter blocks (block order) | tail scalars | tail points | perm | coefficient tables]
@@ -2027,6 +2056,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
             if (all_ok_blk) { fold(st_pb, bytes_pb); fold(st_ts, bytes_ts); fold(st_tp, bytes_tp); fold(part_sB.data(), nb * 32); fold(part_sBb.data(), nb * 32); }
         }
         for (size_t p = 0; p < nb; p++) if (rep[p].rc) { first_err = rep[p].rc; if (rep[p].vp.err) g_err = rep[p].vp.err; break; }   // the first error in instance order (`?` at :619)
+        if (first_err && inst_status) { for (size_t p = 0; p < nb; p++) inst_status[lo + p] = rep[p].rc; err_from = hi; }
         if (first_err) break;
         for (size_t p = 0; p < nb; p++) { sB = S::add(sB, part_sB[p]); sBb = S::add(sBb, part_sBb[p]); }
         // templates: look up by structure digest; a miss records the matrices from this instance (upload + sync, once per gadget)
@@ -2122,6 +2152,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
     }
     if (first_err) {
         (void)hipStreamSynchronize(st);
+        if (inst_status) return report_each(err_from);   // the blocks before passed their replay; the rest is decided one by one
         if (first_err != BP_E_FORMAT) {   // the reference decodes every proof before batch_verify runs: a malformed later proof wins
             if (decoded_upto < count) BPCHK(issue_decode(count, 0));
             HIPCHK(hipStreamSynchronize(ctx->aux_stream));

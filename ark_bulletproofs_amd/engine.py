@@ -1339,6 +1339,83 @@ Engine.verify_each_stats = _verify_each_stats
 Engine.debug_msm_each = _debug_msm_each
 
 
+# ---- batch verification that names the failing instances (bp_r1cs_batch_verify_locate) ----------------------------------------
+TUNE_VERIFY_LOCATE_LEAF = 22         # include/arkbp.h BP_TUNE_VERIFY_LOCATE_LEAF (Engine.set_tuning; 0 = default: 1)
+
+
+def batch_verify_locate_cs(engine, verifiers, proofs, alphas, timing=None):
+    """bp_r1cs_batch_verify_locate over VerifierCS objects (every one consumed); alphas: (count, 4) words, non-zero, required for
+    more than one instance.  Returns (rc, statuses): statuses[k] is what Verifier::verify returns for instance k alone — exact for
+    a valid proof and for every instance decided on its own, with batch_verify's soundness over the weights for an invalid proof
+    inside a subset that passed — and rc the first non-zero status in instance order.  Raises only when the up-front checks refuse
+    the whole batch (nothing consumed then)."""
+    n = len(verifiers)
+    if len(proofs) != n:
+        raise ValueError("batch_verify_locate_cs: one proof per verifier")
+    hs = (C.c_void_p * max(n, 1))(*[v.h for v in verifiers])
+    blob = b"".join(bytes(p) for p in proofs)
+    lens = (C.c_size_t * max(n, 1))(*[len(p) for p in proofs])
+    al = None if alphas is None else u64arr(alphas, 4)
+    st = (C.c_int * max(n, 1))(*([1] * max(n, 1)))   # (a status the library never returns: an instance it skipped would show)
+    tm = (C.c_double * 4)()
+    rc = lib().bp_r1cs_batch_verify_locate(engine.ctx, C.c_size_t(n), hs, blob, lens, ptr(al) if al is not None else None, st, tm)
+    if timing is not None:
+        timing[:] = list(tm)
+    for v in verifiers:
+        if v._cb_errors:
+            raise v._cb_errors[0]
+        src = getattr(v, "_like", None)
+        if src is not None and src._cb_errors:
+            raise src._cb_errors[0]
+    if n and rc != 0 and all(s == 1 for s in st):   # refused as a whole
+        check(rc, "bp_r1cs_batch_verify_locate")
+    return rc, [st[k] for k in range(n)]
+
+
+def _batch_verify_locate(self, instances, alpha_seed, timing=None):
+    """bp_r1cs_batch_verify_locate_scenarios; instances: list of (scenario, params, proof_bytes, commitments, publics) or a
+    PackedInstances; the weights are batch_verify's (alpha_seed, instance order).  Returns as batch_verify_locate_cs."""
+    pk = instances if isinstance(instances, PackedInstances) else PackedInstances(instances)
+    n = pk.n
+    st = (C.c_int * max(n, 1))(*([1] * max(n, 1)))
+    tm = (C.c_double * 4)()
+    rc = lib().bp_r1cs_batch_verify_locate_scenarios(self.ctx, C.c_size_t(n), pk.scen, ptr(pk.prm), pk.proofs, pk.plens, ptr(pk.cms), pk.ms, ptr(pk.pubs), pk.npubs,
+                                                     bytes(alpha_seed) if alpha_seed is not None else None, st, tm)
+    if timing is not None:
+        timing[:] = list(tm)
+    if n and rc != 0 and all(s == 1 for s in st):
+        check(rc, "bp_r1cs_batch_verify_locate_scenarios")
+    return rc, [st[k] for k in range(n)]
+
+
+def _verify_locate_stats(self):
+    """(calls, passes of the batch verifier's core, instances in those passes, instances decided exactly) since ctx creation"""
+    a, b, g, w = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().bp_ctx_verify_locate_stats(self.ctx, C.byref(a), C.byref(b), C.byref(g), C.byref(w)), "bp_ctx_verify_locate_stats")
+    return a.value, b.value, g.value, w.value
+
+
+def debug_locate_plan(fails_check, fails_before=None):
+    """host only (bp_debug_locate_plan): the planner of batch_verify_locate over a simulated core.  fails_check / fails_before:
+    one truth value per instance.  Returns (statuses, passes, instances_in_passes) with passes = [(lo, n, outcome)] over the list of
+    instances still in the batch at that time; outcome 0 passed, 1 failed its check, 2 reported members failing before it."""
+    n = len(fails_check)
+    fc = np.ascontiguousarray([1 if x else 0 for x in fails_check] + [0], dtype=np.uint8)
+    fb = None if fails_before is None else np.ascontiguousarray([1 if x else 0 for x in fails_before] + [0], dtype=np.uint8)
+    cap = 2 * n + 2
+    lo, cnt, failed = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint8)
+    st = (C.c_int * max(n, 1))()
+    npasses, inst = C.c_uint32(0), C.c_uint64(0)
+    check(lib().bp_debug_locate_plan(C.c_size_t(n), ptr(fc), ptr(fb) if fb is not None else None, C.byref(npasses), ptr(lo), ptr(cnt), ptr(failed), C.byref(inst), st),
+          "bp_debug_locate_plan")
+    p = npasses.value
+    return [st[k] for k in range(n)], [(int(lo[i]), int(cnt[i]), int(failed[i])) for i in range(p)], inst.value
+
+
+Engine.batch_verify_locate = _batch_verify_locate
+Engine.verify_locate_stats = _verify_locate_stats
+
+
 # ---- many variable-base MSMs per call (bp_msm_batch) ---------------------------------------------------------------------------
 TUNE_MSM_BATCH_SHORT, TUNE_MSM_BATCH_SLICE, TUNE_MSM_BATCH_MAX, TUNE_MSM_BATCH_MIN_JOBS = 16, 17, 18, 19   # include/arkbp.h BP_TUNE_MSM_BATCH_* (Engine.set_tuning; 0 = default)
 MSM_BATCH_DEFAULTS = (8, None, 4096, 6)  # what 0 stands for: short, slice (None: msm_batch_default_slice), max, min jobs (csrc/msm_batch.inc MSB_DEFAULT_*)

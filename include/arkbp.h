@@ -580,6 +580,57 @@ int bp_debug_msm_each(bp_ctx* ctx, size_t count, const size_t* offsets, const ui
  * groups[w] = the LDS slot of the group sum the window folds into */
 int bp_debug_ve_plan(size_t count, const size_t* offsets, const uint64_t* scalars_canonical, size_t job, uint32_t* first, uint32_t* terms, uint8_t* digits,
                      uint8_t* planes, uint32_t* lanes, uint32_t* groups);
+/* Batch verification that NAMES the failing instances: `batch_verify` (verifier.rs:604-691) at its own speed while the batch is
+ * valid, and a verdict for each instance when it is not — the loop `for (v, proof) in instances { v.verify(..) }` of a service with
+ * large statements, for which bp_verifier_verify_batch falls back to one MSM per proof.  The reference has no such call.
+ * Instance k = (verifiers[k], the k-th of the concatenated compressed proofs) with weight alphas[k] (count x 4 words, ark Montgomery
+ * form); framing and weights as in bp_r1cs_batch_verify.  Instance k keeps its weight in every pass.
+ *   status (count): status[k] is what bp_verifier_verify(ctx, verifiers[k], proof_k, len_k) returns for that instance alone: BP_OK,
+ *   BP_E_VERIFICATION, BP_E_FORMAT, BP_E_GENS_LENGTH, or the non-zero return of its randomized-phase callback — with ONE caveat: an
+ *   invalid proof is reported BP_OK only if a weighted sum that contains it is the identity, which is the failure probability of
+ *   `batch_verify` itself over the caller's weights.  A valid proof is never reported invalid (a subset of valid proofs sums to the
+ *   identity whatever the weights), and a subset of one is decided exactly (alpha * C is the identity iff C is, alpha != 0).
+ *   The call returns the first non-zero status in instance order; when it returns BP_OK the batch is accepted exactly as
+ *   bp_r1cs_batch_verify accepts it.
+ *   timing (4 doubles, may be NULL; seconds): the whole call, pass 1, all later passes, snapshot / restore of the instances' states.
+ * How: a PASS is one run of the batch verifier's core (the launch chains of bp_r1cs_batch_verify: the device front end for
+ * like-instances of one recording, the host replay otherwise) over a subset, gathered through an index map.  Pass 1 covers the
+ * batch; a valid batch costs that one pass.  An instance that fails BEFORE its check — a malformed or off-curve point, an identity
+ * under validate_and_append_point, an L_vec of the wrong length, too few generators, a callback error — keeps its own status and
+ * leaves the batch, the rest go on (bp_verifier_verify_batch's rule, not bp_r1cs_batch_verify's "first error rejects the call"):
+ * pass 1 names all of them at once, pass 2 covers the survivors.  A subset whose check fails is halved, lower half floor(n / 2): the
+ * lower half is tested; if it passes, the upper half is known to fail and is split without a pass of its own; if it fails, it is
+ * searched and the upper half tested after it.  With f >= 1 invalid proofs among n survivors: at most 1 + 2 f ceil(log2 n) passes,
+ * and for f = 1 at most 3 n instances in all passes.  Every pass runs its members from the state they had on entry to the call
+ * (transcript and recorder are snapshotted before pass 1 and restored before each later pass).
+ * BP_TUNE_VERIFY_LOCATE_LEAF: a failing subset of at most this many instances is not split further but decided by the machinery of
+ * bp_verifier_verify_batch (exact; grouped where the direct tables reach, the single route elsewhere).  Results never depend on it.
+ * Up-front checks, before any work: every verifier live, of the ctx's curve and given once; status non-null; alphas non-null for
+ * count > 1 (NULL = weight 1 for count == 1); NO WEIGHT ZERO (a zero weight hides its instance from every sum — a refusal that
+ * bp_r1cs_batch_verify does not make); a bp_verifier_new_like handle that holds fewer commitments than the shared constraints name;
+ * generators installed.  A failed check returns BP_E_ARG (BP_E_GENS_LENGTH when no generators are installed) and consumes no
+ * verifier.  A host-only ctx returns BP_E_NO_DEVICE after the checks and consumes nothing.  count == 0 returns BP_OK.  Otherwise
+ * every verifier is consumed.  The transcripts' states after the call are UNSPECIFIED, as after bp_r1cs_batch_verify: a pass that
+ * completes on the device front end does not advance the host transcripts, the host replay does, and later passes restart their
+ * members from the entry state.  Callbacks of an instance run once per pass that holds it, possibly concurrently with other
+ * instances' on the ctx's host pool.  On a sharded ctx every pass works as bp_r1cs_batch_verify does there.
+ * bp_r1cs_batch_verify_locate_scenarios: the same for scenario statements; flat arrays and weights (alpha_seed, drawn in instance
+ * order; required for count > 1) as in bp_r1cs_batch_verify_scenarios; the recordings are rebuilt in every pass.
+ * bp_ctx_verify_locate_stats, since ctx creation: calls; passes; the sum of the passes' subset sizes; instances decided exactly (as a
+ * subset of one, or by the leaf machinery). */
+int bp_r1cs_batch_verify_locate(bp_ctx* ctx, size_t count, bp_cs* const* verifiers, const uint8_t* proofs, const size_t* proof_lens,
+                                const uint64_t* alphas, int* status, double* timing);
+int bp_r1cs_batch_verify_locate_scenarios(bp_ctx* ctx, size_t count, const int* scenarios, const uint64_t* params, const uint8_t* proofs,
+                                          const size_t* proof_lens, const uint64_t* commit_xy, const size_t* ms, const uint64_t* publics,
+                                          const size_t* npubs, const uint8_t alpha_seed[32], int* status, double* timing);
+int bp_ctx_verify_locate_stats(bp_ctx* ctx, uint64_t* calls, uint64_t* passes, uint64_t* instances_in_passes, uint64_t* exact_leaves);
+/* test hook, host only: the planner of bp_r1cs_batch_verify_locate (leaf 1) over a simulated core — a range fails its check iff it
+ * holds a fails_check member (count bytes); fails_before members (count bytes, may be NULL) are reported, with BP_E_FORMAT, and
+ * dropped by the first pass that holds them.  Pass i covered survivors [pass_lo[i], pass_lo[i] + pass_n[i]) of the list of instances
+ * still in the batch at that time, in instance order; pass_failed[i]: 0 passed, 1 failed its check, 2 reported members failing before
+ * it.  The pass arrays need room for 2 * count + 2 entries and may be NULL; status: count ints. */
+int bp_debug_locate_plan(size_t count, const uint8_t* fails_check, const uint8_t* fails_before, uint32_t* npasses, uint32_t* pass_lo, uint32_t* pass_n,
+                         uint8_t* pass_failed, uint64_t* instances_in_passes, int* status);
 /* merlin::Transcript <-> bp_transcript handle: Strobe128 {state[200], pos, pos_begin, cur_flags} (merlin 3.0 src/strobe.rs) */
 int bp_transcript_export_state(const void* transcript, uint8_t out[203]);
 int bp_transcript_import_state(void* transcript, const uint8_t in[203]);
@@ -684,6 +735,8 @@ int bp_ctx_reset_profiling(bp_ctx* ctx);
 #define BP_TUNE_MSM_PAIR 21        /* (20 stays unassigned: tests/test_msm_batch_cpu.py pins it as the first knob that is refused.)  1 (default): L and R of a round of the inner-product argument — two mid-size MSMs of the same length that do not
                                     * depend on each other — run as two jobs of ONE chain of launches with one host wait (see bp_ctx_msm_pair_stats);
                                     * 0: one MSM after the other (A/B, tests).  Results never depend on it */
+#define BP_TUNE_VERIFY_LOCATE_LEAF 22 /* bp_r1cs_batch_verify_locate: a failing subset of at most this many instances is decided by the machinery of
+                                      * bp_verifier_verify_batch instead of being split further (0 = default: 1, pure bisection; at most 4096) */
 int bp_ctx_set_tuning(bp_ctx* ctx, int knob, uint64_t value);
 
 /* The O(N) part of `Verifier::verification_scalars` (src/r1cs/verifier.rs:465-514, s from inner_product_proof.rs:279-311) for a
