@@ -268,6 +268,7 @@ struct bp_ctx {
     int tune_vfy_device = 1;                  // BP_TUNE_VFY_DEVICE: 0 host replay, 1 single-phase like-instances on the device, 2 two-phase ones too
     uint64_t fb_runs = 0, fb_runs_sharded = 0; // fixed-base MSMs completed on this ctx / of those, on a rank's share of the terms of a sharded proof
     uint64_t vfe_batches = 0, vfe_fallbacks = 0;                 // batches the device front end completed / handed to the host replay
+    uint64_t cw_front_end = 0, cw_prologue_gpu = 0, cw_host = 0;  // wire commitments decoded by k_vfe_points / by k_points_decompress / by host roots
     void* h_vstage[2] = {nullptr, nullptr};   // pinned staging halves of the batch-verify pipeline
     size_t h_vstage_cap[2] = {0, 0};
     hipEvent_t vstage_ev[2] = {nullptr, nullptr};
@@ -2663,6 +2664,9 @@ struct bp_cs {
     bool consumed = false;                          // prove(self) / verify(self)
     bool running = false;                           // inside prove / verify: the randomized-phase callbacks may still record
     std::vector<A4> commitments;                    // V points in commit order (both modes)
+    std::vector<uint8_t> wire;                      // verifier: pending wire commitments, 33 bytes each (bp_verifier_commit_compressed_batch, defer)
+    host::Strobe wire_state;                        // the transcript's state when the first of them was stored
+    size_t wire_count() const { return wire.size() / 33; }
     virtual ~bp_cs() {}
     template <class C> host::ConstraintSystem<C>* cs();
     size_t num_vars() const { return curve == 0 ? cs0->num_vars : cs1->num_vars; }
@@ -2727,6 +2731,130 @@ template <class C> static int cs_precompute_batch(bp_cs** hs, size_t count) {
     }
     return BP_OK;
 }
+// ---- verifier commitments from the wire (include/arkbp.h: bp_verifier_commit_compressed_batch) ---------------------------------
+// A verifier handle may hold its commitments as the 33-byte encodings it received (bp_cs::wire) next to the transcript state of
+// that moment.  They become Verifier::commit calls either here (wire_materialize: one decode for all instances of a call, then the
+// appends on the pool) or never: k_vfe_points decodes them for a batch the device front end takes (VfyDevBatch::commit_wire).
+template <class C> static int verifier_commit(bp_cs* h, const uint64_t* V_xy, size_t count, bp_var* vars);
+static bool strobe_eq(const host::Strobe& a, const host::Strobe& b) { return !memcmp(a.st.b, b.st.b, 200) && a.pos == b.pos && a.pos_begin == b.pos_begin && a.cur == b.cur; }
+static void wire_pool_range(bp_ctx* ctx, size_t n, const std::function<void(size_t)>& fn) {
+    if (ctx && n > 1 && !ctx->pool) ctx->pool.reset(new host::HostPool(std::max(1u, ctx->tune_host_threads ? (unsigned)ctx->tune_host_threads : host::host_pool_threads()) - 1));
+    if (!ctx || !ctx->pool || n <= 1) { for (size_t i = 0; i < n; i++) fn(i); return; }
+    ctx->pool->run(0, n, fn);
+}
+// n encodings -> affine ark words; a rejected one gives zero words and ok = 0 (ark-serialize's rules, host_math.hpp deser_compressed).
+// With a device: framing on the pool, the roots in ONE k_points_decompress launch.  Without (null or host-only ctx): host roots.
+template <class C> static int wire_decode(bp_ctx* ctx, const uint8_t* c33, size_t n, A4* out, uint8_t* ok) {
+    typedef host::Fld<typename C::Fq> Fq;
+    if (!n) return BP_OK;
+    if (!ctx || ctx->host_only) {
+        wire_pool_range(ctx, n, [&](size_t i) { A4 p; const bool good = host::Grp<C>::deser_compressed(p, c33 + 33 * i); out[i] = good ? p : A4{}; ok[i] = good ? 1 : 0; });
+        return BP_OK;
+    }
+    std::vector<F4> xs(n); std::vector<u32> fl(n);
+    wire_pool_range(ctx, (n + 255) / 256, [&](size_t c) {
+        for (size_t i = c * 256, hi = std::min(n, i + 256); i < hi; i++) {
+            const uint8_t* d = c33 + 33 * i;
+            fl[i] = d[32];
+            bool good = !(fl[i] & 0x3f) && (fl[i] & 0xc0) != 0xc0 && Fq::from_bytes(xs[i], d);
+            if (good && (fl[i] & 0x40) && !xs[i].is_zero()) good = false;
+            if (!good) { xs[i] = F4{{0, 0, 0, 0}}; fl[i] = 0xFFu; }   // malformed framing: not ok below, whatever the kernel makes of it
+        }
+    });
+    std::vector<A4> pts; std::vector<u32> okv;
+    BPCHK(decompress_points<C>(ctx, xs.data(), fl.data(), n, pts, okv));
+    for (size_t i = 0; i < n; i++) { ok[i] = fl[i] != 0xFFu && okv[i]; out[i] = ok[i] ? pts[i] : A4{}; }
+    return BP_OK;
+}
+// every use of pending commitments: the borrowed transcript must still be where it was when they were stored
+static int wire_check_states(const char* who, size_t count, bp_cs* const* vs) {
+    for (size_t k = 0; k < count; k++) {
+        const bp_cs* h = vs[k];
+        if (h->wire.empty()) continue;
+        if (!h->tr || !strobe_eq(h->tr->s, h->wire_state)) {
+            g_err = std::string(who) + ": instance " + std::to_string(k) + ": the transcript changed while wire commitments were pending (bp_verifier_materialize before binding more data)";
+            return BP_E_ARG;
+        }
+    }
+    return BP_OK;
+}
+// the pending commitments of instances at(0 .. count): decoded together, then Verifier::commit per instance on the pool.  st[k] =
+// BP_E_FORMAT for an instance with a rejected encoding: it keeps its pending bytes, handle and transcript untouched.
+template <class C> static int wire_materialize(bp_ctx* ctx, size_t count, const std::function<bp_cs*(size_t)>& at, int* st) {
+    std::vector<size_t> off(count + 1, 0);
+    for (size_t k = 0; k < count; k++) { st[k] = BP_OK; off[k + 1] = off[k] + at(k)->wire_count(); }
+    const size_t tot = off[count];
+    if (!tot) return BP_OK;
+    std::vector<uint8_t> all(tot * 33), ok(tot);
+    std::vector<A4> pts(tot);
+    wire_pool_range(ctx, count, [&](size_t k) { const bp_cs* h = at(k); if (!h->wire.empty()) memcpy(all.data() + off[k] * 33, h->wire.data(), h->wire.size()); });
+    BPCHK(wire_decode<C>(ctx, all.data(), tot, pts.data(), ok.data()));
+    if (ctx) (ctx->host_only ? ctx->cw_host : ctx->cw_prologue_gpu) += tot;
+    wire_pool_range(ctx, count, [&](size_t k) {
+        bp_cs* h = at(k);
+        const size_t mk = off[k + 1] - off[k];
+        if (!mk) return;
+        for (size_t j = 0; j < mk; j++) if (!ok[off[k] + j]) { st[k] = BP_E_FORMAT; return; }
+        h->wire.clear();
+        st[k] = verifier_commit<C>(h, (const uint64_t*)(pts.data() + off[k]), mk, nullptr);
+    });
+    return BP_OK;
+}
+// the device front end's view of a batch of like-instances: all commitments pending (same count), or none
+template <class C> static bool wire_dev_form(size_t n, const std::function<bp_cs*(size_t)>& at, bool& wire, size_t& m) {
+    bp_cs* h0 = at(0);
+    wire =!h0->wire.empty();
+    m = wire ? h0->wire_count() : h0->cs<C>()->V.size();
+    for (size_t k = 0; k < n; k++) {
+        bp_cs* h = at(k);
+        if (wire ? (h->wire_count() != m || !h->cs<C>()->V.empty()) : !h->wire.empty()) return false;
+    }
+    return true;
+}
+
+template <class C> static int points_compress_t(const uint64_t* xy, size_t n, uint8_t* out) {
+    for (size_t i = 0; i < n; i++) {
+        A4 p; memcpy(&p, xy + 8 * i, 64);
+        if (!host::Grp<C>::on_curve(p)) { g_err = "bp_points_compress: point " + std::to_string(i) + " is not on the curve"; return BP_E_ARG; }
+        host::Grp<C>::ser_compressed(out + 33 * i, p);
+    }
+    return BP_OK;
+}
+template <class C>
+static int verifier_commit_wire_batch(bp_ctx* c, size_t count, bp_cs* const* vs, const size_t* m_each, const uint8_t* c33, int defer, bp_var* vars_out, int* status) {
+    std::vector<size_t> off(count + 1, 0);
+    for (size_t k = 0; k < count; k++) off[k + 1] = off[k] + m_each[k];
+    for (size_t k = 0; k < count; k++) {   // the variables are known before anything is decoded: Committed(i) in commit order
+        if (status) status[k] = BP_OK;
+        const size_t first = vs[k]->cs<C>()->V.size() + vs[k]->wire_count();
+        if (vars_out) for (size_t j = 0; j < m_each[k]; j++) { vars_out[off[k] + j].kind = BP_VAR_COMMITTED; vars_out[off[k] + j].index = (uint32_t)(first + j); }
+    }
+    if (defer) {
+        for (size_t k = 0; k < count; k++) {
+            bp_cs* h = vs[k];
+            if (!m_each[k]) continue;
+            if (h->wire.empty()) h->wire_state = h->tr->s;   // (a later deferred call keeps the first snapshot: checked equal on entry)
+            h->wire.insert(h->wire.end(), c33 + 33 * off[k], c33 + 33 * off[k + 1]);
+        }
+        return BP_OK;
+    }
+    // immediate: one decode for the whole call, then Verifier::commit per verifier on the pool
+    const size_t tot = off[count];
+    std::vector<A4> pts(tot);
+    std::vector<uint8_t> ok(tot);
+    BPCHK(wire_decode<C>(c, c33, tot, pts.data(), ok.data()));
+    (c->host_only ? c->cw_host : c->cw_prologue_gpu) += tot;
+    std::vector<int> st(count, BP_OK);
+    wire_pool_range(c, count, [&](size_t k) {
+        for (size_t j = off[k]; j < off[k + 1]; j++) if (!ok[j]) { st[k] = BP_E_FORMAT; return; }
+        if (m_each[k]) st[k] = verifier_commit<C>(vs[k], (const uint64_t*)(pts.data() + off[k]), m_each[k], nullptr);
+    });
+    int first = BP_OK;
+    for (size_t k = 0; k < count; k++) { if (status) status[k] = st[k]; if (st[k] && !first) first = st[k]; }
+    if (first == BP_E_FORMAT) g_err = "bp_verifier_commit_compressed_batch: a commitment's encoding was rejected";
+    return first;
+}
+
 // batch_verify over recorded verifier handles (each consumed, like `verify(self)`)
 template <class C>
 static int cs_batch_verify(bp_ctx* c, size_t count, bp_cs* const* vs, const uint8_t* proofs, const size_t* proof_lens, const uint64_t* alphas, double* timing,
@@ -2752,12 +2880,16 @@ static int cs_batch_verify(bp_ctx* c, size_t count, bp_cs* const* vs, const uint
                 !ck->tr)
                 return false;
         }
-        db.src = c0; db.m = c0->V.size(); db.absorb_commitments = false; db.shared_state = false;
-        db.state_of = [&](size_t k) { return (const host::Strobe*)&vs[k]->cs<C>()->tr->s; };
-        db.commit_xy = [&](size_t k) { return (const uint64_t*)vs[k]->cs<C>()->V.data(); };
+        bool wire; size_t m;
+        if (!wire_dev_form<C>(count, [&](size_t k) { return vs[k]; }, wire, m)) return false;
+        db.src = c0; db.m = m; db.absorb_commitments = wire; db.shared_state = false;
+        db.state_of = [&](size_t k) { return (const host::Strobe*)&vs[k]->cs<C>()->tr->s; };   // (pending commitments: the pre-commit state, checked on entry)
+        if (wire) db.commit_wire = [&](size_t k) { return (const uint8_t*)vs[k]->wire.data(); };
+        else db.commit_xy = [&](size_t k) { return (const uint64_t*)vs[k]->cs<C>()->V.data(); };
         if (!c0->deferred.empty()) db.cs_of = [&](size_t k) { return vs[k]->cs<C>(); };
         return true;
     };
+    prov.prologue = [&](int* st) -> int { return wire_materialize<C>(c, count, [&](size_t k) { return vs[k]; }, st); };
     for (size_t k = 0; k < count; k++) { vs[k]->consumed = true; vs[k]->running = true; }
     const int rc = batch_verify_core<C>(c, count, prov, proofs, poff.data(), al.data(), timing, point_out);
     for (size_t k = 0; k < count; k++) vs[k]->running = false;
@@ -2887,7 +3019,7 @@ static inline void terms_in(std::vector<host::Term>& out, const bp_var* vars, co
 }
 template <class C> static bool terms_valid(bp_cs* h, const bp_var* vars, size_t n) {
     const host::ConstraintSystem<C>& cs = *h->cs<C>();
-    const size_t m = cs.proving ? cs.v.size() : cs.V.size();
+    const size_t m = cs.proving ? cs.v.size() : cs.V.size() + h->wire_count();   // (pending wire commitments are variables already)
     for (size_t i = 0; i < n; i++) {
         if (vars[i].kind > BP_VAR_ONE) return false;
         if (vars[i].kind == BP_VAR_COMMITTED ? vars[i].index >= m : vars[i].kind != BP_VAR_ONE && vars[i].index >= cs.num_vars) return false;
@@ -3158,11 +3290,22 @@ static int cs_batch_verify_locate(bp_ctx* c, size_t count, bp_cs* const* vs, con
                     !ck->tr)
                     return false;
             }
-            db.src = c0; db.m = c0->V.size(); db.absorb_commitments = false; db.shared_state = false;
+            bool wire; size_t m;
+            if (!wire_dev_form<C>(n, [vs, idx](size_t j) { return vs[idx[j]]; }, wire, m)) return false;
+            db.src = c0; db.m = m; db.absorb_commitments = wire; db.shared_state = false;
             db.state_of = [vs, idx](size_t j) { return (const host::Strobe*)&vs[idx[j]]->cs<C>()->tr->s; };
-            db.commit_xy = [vs, idx](size_t j) { return (const uint64_t*)vs[idx[j]]->cs<C>()->V.data(); };
+            if (wire) db.commit_wire = [vs, idx](size_t j) { return (const uint8_t*)vs[idx[j]]->wire.data(); };   // (the bytes stay pending: every pass reuses them)
+            else db.commit_xy = [vs, idx](size_t j) { return (const uint64_t*)vs[idx[j]]->cs<C>()->V.data(); };
             if (!c0->deferred.empty()) db.cs_of = [vs, idx](size_t j) { return vs[idx[j]]->cs<C>(); };
             return true;
+        };
+        // a pass the device front end declines commits the members' pending commitments: from then on THAT is their entry state
+        prov.prologue = [c, vs, idx, n, &tr0](int* st) -> int {
+            std::vector<char> had(n);
+            for (size_t j = 0; j < n; j++) had[j] = !vs[idx[j]]->wire.empty();
+            BPCHK(wire_materialize<C>(c, n, [vs, idx](size_t j) { return vs[idx[j]]; }, st));
+            for (size_t j = 0; j < n; j++) if (had[j] && !st[j]) tr0[idx[j]] = vs[idx[j]]->tr->s;
+            return BP_OK;
         };
     };
     for (size_t k = 0; k < count; k++) { vs[k]->consumed = true; vs[k]->running = true; }
@@ -3221,12 +3364,13 @@ int bp_r1cs_batch_verify_locate(bp_ctx* c, size_t count, bp_cs* const* verifiers
             const host::FrozenRecording* b = c->curve == 0 ? verifiers[k]->cs0->base.get() : verifiers[k]->cs1->base.get();
             if (!b) continue;
             if (b != seen) { seen = b; need = 0; for (const auto& vt : b->vterms) need = std::max(need, (size_t)vt.j + 1); }
-            const size_t have = c->curve == 0 ? verifiers[k]->cs0->V.size() : verifiers[k]->cs1->V.size();
+            const size_t have = (c->curve == 0 ? verifiers[k]->cs0->V.size() : verifiers[k]->cs1->V.size()) + verifiers[k]->wire_count();
             if (have < need) { g_err = "batch_verify_locate: the constraints refer to more commitments than a verifier holds (bp_verifier_commit)"; return BP_E_ARG; }
         }
     }
     if (!c->gens_cap) { g_err = "batch_verify_locate: generators not installed"; return BP_E_GENS_LENGTH; }
     if (c->host_only) { g_err = "batch_verify_locate: a host-only ctx has no device to verify on"; return BP_E_NO_DEVICE; }
+    BPCHK(wire_check_states("batch_verify_locate", count, verifiers));
     HIPCHK(hipSetDevice(c->device));
     return c->curve == 0 ? cs_batch_verify_locate<Secq>(c, count, verifiers, proofs, proof_lens, alphas, status, timing)
                          : cs_batch_verify_locate<Zorro>(c, count, verifiers, proofs, proof_lens, alphas, status, timing);
@@ -3965,7 +4109,64 @@ int bp_prover_commit(bp_cs* h, bp_ctx* ctx, const uint64_t* v, const uint64_t* v
 }
 int bp_verifier_commit(bp_cs* h, const uint64_t* V_xy, size_t count, bp_var* vars_out) {
     if (!cs_live(h) || h->proving || (count && !V_xy)) return BP_E_ARG;
+    if (!h->wire.empty()) { g_err = "bp_verifier_commit: wire commitments are pending on this verifier (bp_verifier_materialize first)"; return BP_E_ARG; }
     return CS_DISPATCH(h, verifier_commit<Secq>(h, V_xy, count, vars_out), verifier_commit<Zorro>(h, V_xy, count, vars_out));
+}
+// ---- the wire codec and verifier commitments from compressed bytes ----
+int bp_points_decompress(bp_ctx* c, const uint8_t* c33, size_t n, uint64_t* out_xy, uint8_t* ok) {
+    if (!c || (n && (!c33 || !out_xy || !ok))) return BP_E_ARG;
+    if (!c->host_only) HIPCHK(hipSetDevice(c->device));
+    static_assert(sizeof(A4) == 64, "affine points are x || y, 4 + 4 words");
+    return c->curve == 0 ? wire_decode<Secq>(c, c33, n, (A4*)out_xy, ok) : wire_decode<Zorro>(c, c33, n, (A4*)out_xy, ok);
+}
+int bp_points_compress(int curve, const uint64_t* xy, size_t n, uint8_t* c33_out) {
+    if ((curve != 0 && curve != 1) || (n && (!xy || !c33_out))) return BP_E_ARG;
+    return curve == 0 ? points_compress_t<Secq>(xy, n, c33_out) : points_compress_t<Zorro>(xy, n, c33_out);
+}
+int bp_verifier_commit_compressed_batch(bp_ctx* c, size_t count, bp_cs* const* verifiers, const size_t* m_each, const uint8_t* c33, int defer, bp_var* vars_out, int* status) {
+    if (!c && !defer) return BP_E_ARG;   // (the deferred form decodes nothing: it may go without a ctx, the handles then agree among themselves)
+    if (count == 0) return BP_OK;
+    if (!verifiers || !m_each || !verifiers[0]) return BP_E_ARG;
+    const int curve = c ? c->curve : verifiers[0]->curve;
+    size_t tot = 0;
+    for (size_t k = 0; k < count; k++) {
+        bp_cs* h = verifiers[k];
+        if (!cs_live(h) || h->proving || h->curve != curve || !h->tr) { g_err = "bp_verifier_commit_compressed_batch: every handle must be a live verifier of the ctx's curve"; return BP_E_ARG; }
+        if (CS_DISPATCH(h, h->cs0->phase2, h->cs1->phase2)) { g_err = "bp_verifier_commit_compressed_batch: commit inside the randomized phase"; return BP_E_ARG; }
+        tot += m_each[k];
+    }
+    if (count > 1) {
+        std::vector<const bp_cs*> sorted(verifiers, verifiers + count);
+        std::sort(sorted.begin(), sorted.end(), std::less<const bp_cs*>());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { g_err = "bp_verifier_commit_compressed_batch: a handle is given twice"; return BP_E_ARG; }
+    }
+    if (tot && !c33) return BP_E_ARG;
+    // commitments already pending: more may join them (or be committed behind them) only while the transcript stands where it stood
+    BPCHK(wire_check_states("bp_verifier_commit_compressed_batch", count, verifiers));
+    if (!defer) for (size_t k = 0; k < count; k++) if (!verifiers[k]->wire.empty()) {
+        g_err = "bp_verifier_commit_compressed_batch: instance " + std::to_string(k) + " has pending wire commitments (bp_verifier_materialize first)"; return BP_E_ARG;
+    }
+    if (!defer && !c->host_only) HIPCHK(hipSetDevice(c->device));
+    return curve == 0 ? verifier_commit_wire_batch<Secq>(c, count, verifiers, m_each, c33, defer, vars_out, status)
+                         : verifier_commit_wire_batch<Zorro>(c, count, verifiers, m_each, c33, defer, vars_out, status);
+}
+int bp_verifier_materialize(bp_ctx* c, bp_cs* h) {
+    if (!cs_live(h) || h->proving || (c && c->curve != h->curve)) return BP_E_ARG;
+    if (h->wire.empty()) return BP_OK;
+    BPCHK(wire_check_states("bp_verifier_materialize", 1, &h));
+    if (c && !c->host_only) HIPCHK(hipSetDevice(c->device));
+    int st = BP_OK;
+    const std::function<bp_cs*(size_t)> at = [h](size_t) { return h; };
+    BPCHK(CS_DISPATCH(h, wire_materialize<Secq>(c, 1, at, &st), wire_materialize<Zorro>(c, 1, at, &st)));
+    if (st == BP_E_FORMAT) g_err = "bp_verifier_materialize: a commitment's encoding was rejected";
+    return st;
+}
+int bp_ctx_commit_wire_stats(bp_ctx* c, uint64_t* by_front_end, uint64_t* by_prologue_gpu, uint64_t* on_host) {
+    if (!c) return BP_E_ARG;
+    if (by_front_end) *by_front_end = c->cw_front_end;
+    if (by_prologue_gpu) *by_prologue_gpu = c->cw_prologue_gpu;
+    if (on_host) *on_host = c->cw_host;
+    return BP_OK;
 }
 int bp_cs_multiply(bp_cs* h, const bp_var* lv, const uint64_t* lc, size_t nl, const bp_var* rv, const uint64_t* rc, size_t nr, bp_var out[3]) {
     CS_RECORD_GUARD(h);
@@ -4060,6 +4261,7 @@ int bp_r1cs_batch_verify(bp_ctx* c, size_t count, bp_cs* const* verifiers, const
         std::sort(sorted.begin(), sorted.end(), std::less<const bp_cs*>());
         if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { g_err = "batch_verify: a verifier is consumed by ONE instance"; return BP_E_ARG; }
     }
+    BPCHK(wire_check_states("batch_verify", count, verifiers));
     g_dry = c->host_only;
     HIPCHK(hipSetDevice(c->device));
     if (!c->gens_cap) { g_err = "batch_verify: generators not installed"; g_dry = false; return BP_E_GENS_LENGTH; }
@@ -4134,24 +4336,11 @@ int bp_debug_glv_decompose(int curve, const uint64_t t[4], uint32_t masks[20], u
     return BP_OK;
 }
 
-int bp_debug_decompress(bp_ctx* c, const uint8_t* compressed33, size_t n, uint64_t* out_xy, uint32_t* out_ok) {
+int bp_debug_decompress(bp_ctx* c, const uint8_t* compressed33, size_t n, uint64_t* out_xy, uint32_t* out_ok) {   // (the test hook's name for bp_points_decompress)
     if (!c || (n && (!compressed33 || !out_xy || !out_ok))) return BP_E_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<F4> xs(n); std::vector<u32> fl(n);
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t* d = compressed33 + 33 * i;
-        fl[i] = d[32];
-        bool ok = !(fl[i] & 0x3f) && (fl[i] & 0xc0) != 0xc0 &&
-                  (c->curve == 0 ? host::Fld<Secq::Fq>::from_bytes(xs[i], d) : host::Fld<Zorro::Fq>::from_bytes(xs[i], d));
-        if (ok && (fl[i] & 0x40) && !xs[i].is_zero()) ok = false;
-        if (!ok) { xs[i] = F4{{0, 0, 0, 0}}; fl[i] = 0xFFu; }   // malformed framing: reported as not ok below
-    }
-    std::vector<A4> pts; std::vector<u32> okv;
-    BPCHK(c->curve == 0 ? decompress_points<Secq>(c, xs.data(), fl.data(), n, pts, okv) : decompress_points<Zorro>(c, xs.data(), fl.data(), n, pts, okv));
-    for (size_t i = 0; i < n; i++) {
-        out_ok[i] = fl[i] == 0xFFu ? 0 : okv[i];
-        if (out_ok[i]) { memcpy(out_xy + 8 * i, pts[i].x.v, 32); memcpy(out_xy + 8 * i + 4, pts[i].y.v, 32); } else memset(out_xy + 8 * i, 0, 64);
-    }
+    std::vector<uint8_t> ok(n);
+    BPCHK(bp_points_decompress(c, compressed33, n, out_xy, ok.data()));
+    for (size_t i = 0; i < n; i++) out_ok[i] = ok[i];
     return BP_OK;
 }
 

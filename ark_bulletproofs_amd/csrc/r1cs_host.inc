@@ -1325,6 +1325,9 @@ template <class C> struct VfyDevBatch {
     bool shared_state = false;                               // state_of(k) is one object for every k
     std::function<const host::Strobe*(size_t)> state_of;     // the transcript of instance k
     std::function<const uint64_t*(size_t)> commit_xy;        // its m commitments, ark layout (x || y: 8 words per point)
+    // or, with absorb_commitments: its m commitments as 33-byte encodings (pending wire commitments, bp_verifier_commit_compressed_batch):
+    // k_vfe_points decodes them, they never reach the host in affine form.  Exactly one of commit_xy / commit_wire is set.
+    std::function<const uint8_t*(size_t)> commit_wire;
     // two-phase (src->deferred non-empty): the recorder on which instance k's randomized phase runs — needed when its callbacks
     // record through a handle (bp_cs); absent: a like-instance of src made for the purpose (the closures record into the recorder
     // they receive)
@@ -1338,6 +1341,10 @@ template <class C> struct VfyProvider {
     std::function<void(size_t, size_t, std::unique_ptr<host::Transcript>*)> head8;
     // optional: the whole batch as like-instances of ONE single-phase recording (the device front end, batch_verify_device)
     std::function<bool(VfyDevBatch<C>&)> dev_batch;
+    // optional: instances may still hold their commitments as wire bytes.  Called once, when the device front end did not take the
+    // batch and before anything else looks at the instances: decodes and commits them (Verifier::commit).  st: one status per
+    // instance, BP_E_FORMAT for an instance with a rejected encoding (it received none); the return value is an error of the call.
+    std::function<int(int*)> prologue;
 };
 
 // ---- batch_verify with the per-proof front end on the GPU -------------------------------------------------------------------
@@ -1405,6 +1412,9 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     for (size_t i = 0; i < count; i++) if (poff[i + 1] - poff[i] != plen) return BP_OK;
     for (const auto& vt : src.base->vterms) if (vt.j >= m) return BP_OK;                // (a weaker statement than the recorded one: BP_E_ARG there)
     const size_t tail = 6 + m + 5 + 2 * k, nV = db.absorb_commitments ? m : 0;
+    const bool wire = (bool)db.commit_wire;
+    if (wire && (!db.absorb_commitments || db.commit_xy)) return BP_OK;
+    const size_t vbytes = wire ? 33 : 64;   // per commitment in the staging area
     const size_t nitems = nV + 11 + 2 * k + 3;
     if (count > 65535 || m > 65535 || count * tail >= ((size_t)1 << 31) || nitems * vfe::ITEM_WORDS * count >= ((size_t)1 << 32)) return BP_OK;
     const size_t nblocks = (count + VFY_BLOCK - 1) / VFY_BLOCK;
@@ -1453,7 +1463,15 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
         // the reference instance: instance 0's randomized phase for real, on a copy of its transcript through S1 (verifier.rs:403-415)
         host::Transcript t0;
         t0.s = *s0;
-        if (db.absorb_commitments) for (size_t j = 0; j < m; j++) { A4 v; memcpy(&v, db.commit_xy(0) + 8 * j, 64); host::TP<C>::append_point(t0, "V", v); }
+        if (db.absorb_commitments) for (size_t j = 0; j < m; j++) {
+            A4 v;
+            if (!wire) memcpy(&v, db.commit_xy(0) + 8 * j, 64);
+            else {   // instance 0's own m roots on the host: the rehearsal needs them in affine form (m per batch, not m x count)
+                ctx->cw_host++;
+                if (!host::Grp<C>::deser_compressed(v, db.commit_wire(0) + 33 * j)) { ctx->vfe_fallbacks++; return BP_OK; }   // the prologue names the instance
+            }
+            host::TP<C>::append_point(t0, "V", v);
+        }
         t0.append_u64("m", m);
         A4 p3[3];
         static const char* const lab3[3] = {"A_I1", "A_O1", "S1"};
@@ -1583,7 +1601,7 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     }
     // staging: [proof bytes | commitments | transcript states], 256-byte aligned parts
     auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_proofs = up256(count * plen), b_V = up256(count * m * 64), b_st = up256((db.shared_state ? 1 : count) * 200), b_al = up256(count * 32);
+    const size_t b_proofs = up256(count * plen), b_V = up256(count * m * vbytes), b_st = up256((db.shared_state ? 1 : count) * 200), b_al = up256(count * 32);
     const size_t b_in = b_proofs + b_V + b_st + b_al;
     if (ctx->h_vfe_cap < b_in + 4096) {
         if (ctx->h_vfe) { HIPCHK(ctx_stream_wait(ctx)); HIPCHK(hipHostFree(ctx->h_vfe)); }
@@ -1609,7 +1627,7 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
             const size_t lo = c * chunk, hi = std::min(count, lo + chunk);
             memcpy(hs + lo * plen, proofs + poff[lo], (hi - lo) * plen);
             for (size_t i = lo; i < hi; i++) {
-                if (m) memcpy(hs + b_proofs + i * m * 64, db.commit_xy(i), m * 64);
+                if (m) memcpy(hs + b_proofs + i * m * vbytes, wire ? (const void*)db.commit_wire(i) : (const void*)db.commit_xy(i), m * vbytes);
                 if (!db.shared_state) memcpy(hs + b_proofs + b_V + i * 200, db.state_of(i)->st.b, 200);
             }
         });
@@ -1645,7 +1663,7 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((count + 255) / 256)), dim3(256), 0, st, (const u32*)(d_in + b_proofs + b_V + b_st), d_alpha, (u32)count);
     vfe::Shape sh;
     sh.P = (uint32_t)count; sh.m = (uint32_t)m; sh.nV = (uint32_t)nV; sh.k = (uint32_t)k; sh.plen = (uint32_t)plen; sh.tail = (uint32_t)tail; sh.nitems = (uint32_t)nitems;
-    sh.G = (uint32_t)G;
+    sh.G = (uint32_t)G; sh.vwire = wire ? 1u : 0u;
     {
         ScopedK tk(ctx, BP_K_VFE_POINTS);
         if (vfe::launch_points(C::ID, st, sh, d_in, (const u32*)(d_in + b_proofs), (uint64_t*)ctx->vfe_msg.p, ctx->r_tail.as<u32>(), d_status)) { g_err = "k_vfe_points: launch failed"; return BP_E_HIP; }
@@ -1769,6 +1787,7 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     if (timing) { timing[0] = t_end - t_entry; timing[1] = 0; timing[2] = t_msm - t_drain; timing[3] = t_end - t_msm; }
     if (ctx->profiling) collect_timers(ctx);
     ctx->vfe_batches++;
+    if (wire) ctx->cw_front_end += count * m;
     handled = true;
     return ok ? BP_OK : BP_E_VERIFICATION;
 }
@@ -1813,6 +1832,17 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
             bool handled = false;
             const int rc = batch_verify_device<C>(ctx, count, db, proofs, poff, alphas, timing, point_out, handled);
             if (handled || rc) return rc;
+        }
+    }
+    if (prov.prologue) {   // pending wire commitments: a rejected encoding is reported before anything the proof bytes would give
+        std::vector<int> pst(count, BP_OK);
+        BPCHK(prov.prologue(pst.data()));
+        int first = BP_OK;
+        for (size_t k = 0; k < count && !first; k++) first = pst[k];
+        if (first) {
+            if (inst_status) std::copy(pst.begin(), pst.end(), inst_status);
+            g_err = "batch_verify: a commitment's encoding was rejected";
+            return first;
         }
     }
     // decode: framing + x coordinates on the host, the square roots of all compressed points on the GPU

@@ -189,6 +189,9 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
         if (!ctx->pool || hi - lo == 1) { for (size_t k = lo; k < hi; k++) fn(k); return; }
         ctx->pool->run(lo, hi, fn);
     };
+    // 0. pending wire commitments: decoded and committed first; an instance with a rejected encoding is left out with BP_E_FORMAT
+    std::vector<int> pst(count, BP_OK);
+    if (prov.prologue) BPCHK(prov.prologue(pst.data()));
     // 1. framing; the proof's claim decides the route
     std::vector<host::LazyProof> lps(count);
     std::vector<int> prc(count, BP_OK);
@@ -207,7 +210,11 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
         if (ready) reach = std::min(ctx->dt_cap, reach_max);
     }
     std::vector<size_t> gl, sl;
-    for (size_t k = 0; k < count; k++) { const size_t Nk = claim(k); if (Nk && Nk <= reach) gl.push_back(k); else sl.push_back(k); }
+    for (size_t k = 0; k < count; k++) {
+        if (pst[k]) { stv[k] = pst[k]; continue; }
+        const size_t Nk = claim(k);
+        if (Nk && Nk <= reach) gl.push_back(k); else sl.push_back(k);
+    }
     const size_t ng = gl.size();
     ctx->ve_grouped += ng;
     mark("parse + route");
@@ -333,6 +340,7 @@ static int cs_verify_each(bp_ctx* c, size_t count, bp_cs* const* vs, const uint8
     VfyProvider<C> prov;
     prov.m_of = [&](size_t k) { return vs[k]->cs<C>()->V.size(); };
     prov.get = [&](size_t k, VfyInstance<C>& out) -> int { out.cs = vs[k]->cs<C>(); return BP_OK; };
+    prov.prologue = [&](int* st) -> int { return wire_materialize<C>(c, count, [&](size_t k) { return vs[k]; }, st); };
     for (size_t k = 0; k < count; k++) { vs[k]->consumed = true; vs[k]->running = true; }
     const int rc = verify_each_core<C>(c, count, prov, proofs, poff.data(), status, points, timing);
     for (size_t k = 0; k < count; k++) vs[k]->running = false;
@@ -354,6 +362,7 @@ int bp_verifier_verify_batch(bp_ctx* c, size_t count, bp_cs* const* verifiers, c
     }
     if (!c->gens_cap) { g_err = "verify_batch: generators not installed"; return BP_E_GENS_LENGTH; }
     if (c->host_only) { g_err = "verify_batch: a host-only ctx has no device to verify on"; return BP_E_NO_DEVICE; }
+    BPCHK(wire_check_states("verify_batch", count, verifiers));
     HIPCHK(hipSetDevice(c->device));
     return c->curve == 0 ? cs_verify_each<Secq>(c, count, verifiers, proofs, proof_lens, status, check_points_xy, timing)
                          : cs_verify_each<Zorro>(c, count, verifiers, proofs, proof_lens, status, check_points_xy, timing);

@@ -4,7 +4,8 @@
 // src/r1cs/verifier.rs:279-287 (commit), :403-541 (verification_scalars), :604-691 (batch_verify), src/inner_product_proof.rs:
 // 244-314, src/transcript.rs:45-102.  The host (r1cs_host.inc: batch_verify_device) only stages bytes and launches.
 //
-//   k_vfe_points   one lane per point: compressed proof points -> (x, y) by a device square root, commitments from ark layout;
+//   k_vfe_points   one lane per point: compressed proof points -> (x, y) by a device square root, commitments from ark layout or,
+//                  with Shape::vwire, from the same 33-byte encoding (a verifier's pending wire commitments: one more root each);
 //                  every point is written twice: as its 65-byte uncompressed serialization for the sponge ("items", laid out
 //                  word-major across proofs so that the sponge's lane-per-proof reads coalesce) and in the resident layout as a
 //                  base of the mega-check MSM.  Anything the reference rejects raises a status bit instead.
@@ -68,26 +69,41 @@ k_vfe_points(Shape sh, const u8* __restrict__ proofs, const u32* __restrict__ V,
     const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u64 n_pp = (u64)(11 + 2 * k) * P, n_v = (u64)m * P, n_s = (u64)5 * P;
     u32 bad = 0;
-    if (gid < n_pp) {
-        const u32 j = (u32)(gid / P), p = (u32)(gid % P);
-        const u8* pr = proofs + (size_t)p * sh.plen;
-        const u32 off = j < 11 ? 33u * j : j < 11 + k ? 467u + 33u * (j - 11) : 475u + 33u * k + 33u * (j - 11 - k);
-        const u32 slot = j < 6 ? j : j < 11 ? 6u + m + (j - 6) : 11u + m + (j - 11);   // A_I1..S2 | V | T_1..T_6 | L | R  (verifier.rs:378-393)
-        if (j == 0) {   // framing: both vectors announce k points (proof.rs: Vec<G> = u64 length || items)
-            u32 l[8];
+    const bool wire_v = sh.vwire && gid >= n_pp && gid < n_pp + n_v;   // a commitment in its 33-byte wire form: decoded as the proof points are
+    if (gid < n_pp || wire_v) {
+        u32 j, p, slot, item;
+        const u8* enc;
+        bool identity_ok;
+        if (!wire_v) {
+            j = (u32)(gid / P); p = (u32)(gid % P);
+            const u8* pr = proofs + (size_t)p * sh.plen;
+            const u32 off = j < 11 ? 33u * j : j < 11 + k ? 467u + 33u * (j - 11) : 475u + 33u * k + 33u * (j - 11 - k);
+            slot = j < 6 ? j : j < 11 ? 6u + m + (j - 6) : 11u + m + (j - 11);   // A_I1..S2 | V | T_1..T_6 | L | R  (verifier.rs:378-393)
+            if (j == 0) {   // framing: both vectors announce k points (proof.rs: Vec<G> = u64 length || items)
+                u32 l[8];
 #pragma unroll
-            for (int i = 0; i < 8; i++) l[i] = pr[459 + i];
-            u32 r[8];
+                for (int i = 0; i < 8; i++) l[i] = pr[459 + i];
+                u32 r[8];
 #pragma unroll
-            for (int i = 0; i < 8; i++) r[i] = pr[467 + 33 * k + i];
-            bool okl = l[0] == k, okr = r[0] == k;
+                for (int i = 0; i < 8; i++) r[i] = pr[467 + 33 * k + i];
+                bool okl = l[0] == k, okr = r[0] == k;
 #pragma unroll
-            for (int i = 1; i < 8; i++) { okl = okl && l[i] == 0; okr = okr && r[i] == 0; }
-            if (!okl || !okr) bad |= ST_FRAMING;
+                for (int i = 1; i < 8; i++) { okl = okl && l[i] == 0; okr = okr && r[i] == 0; }
+                if (!okl || !okr) bad |= ST_FRAMING;
+            }
+            enc = pr + off; item = sh.nV + j;
+            // the identity: fine on the wire; validate_and_append_point rejects it for all but A_I2, A_O2, S2 (verifier.rs:420-470)
+            identity_ok = j >= 3 && j <= 5;
+        } else {
+            const u64 g = gid - n_pp;
+            j = (u32)(g / P); p = (u32)(g % P);
+            enc = reinterpret_cast<const u8*>(V) + ((size_t)p * m + j) * 33;
+            slot = 6u + j; item = j;
+            identity_ok = true;   // Verifier::commit appends without validation (verifier.rs:279-287): as all-zero ark words below
         }
         u32 xw[8], yw[8];
-        load_le_words8(xw, pr + off);
-        const u32 fl = pr[off + 32];
+        load_le_words8(xw, enc);
+        const u32 fl = enc[32];
         u32 o[16];
         u32 flag_out = 0;
 #pragma unroll
@@ -100,8 +116,7 @@ k_vfe_points(Shape sh, const u8* __restrict__ proofs, const u32* __restrict__ V,
         if ((fl & 0x3f) || (fl & 0xc0) == 0xc0 || !words_lt_p<F>(xw) || ((fl & 0x40) && !x_zero)) {
             bad |= ST_FORMAT;
         } else if (fl & 0x40) {
-            // the identity: fine on the wire; validate_and_append_point rejects it for all but A_I2, A_O2, S2 (verifier.rs:420-470)
-            if (j < 3 || j > 5) bad |= ST_IDENTITY;
+            if (!identity_ok) bad |= ST_IDENTITY;
             flag_out = 0x40;
         } else {
             Aff a;
@@ -115,7 +130,7 @@ k_vfe_points(Shape sh, const u8* __restrict__ proofs, const u32* __restrict__ V,
                 flag_out = y_sign_flag<F>(a.y);
             }
         }
-        store_item(msg, P, sh.nV + j, p, xw, yw, flag_out);
+        if (!wire_v || sh.nV) store_item(msg, P, item, p, xw, yw, flag_out);
         u32* tp = tail_pts + ((size_t)p * sh.tail + slot) * 16;
         store_words8(tp, o);
         store_words8(tp + 8, o + 8);

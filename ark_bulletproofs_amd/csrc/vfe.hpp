@@ -19,6 +19,7 @@ struct Shape {
     uint32_t tail;     // tail terms per proof in the mega-check: 6 + m + 5 + 2 k
     uint32_t nitems;   // ItemMap::count()
     uint32_t G = 0;    // gadget challenges per proof (two-phase statements): challenges per proof = 6 + k + G
+    uint32_t vwire = 0;   // d_V holds P x m x 33 bytes (serialize_compressed) instead of ark words; k_vfe_points decodes them
 };
 
 // status bits raised by the kernels (any bit: the batch goes through the host replay instead, which reports the reference's error)
@@ -28,7 +29,8 @@ static constexpr uint32_t ST_FRAMING = 4;       // L_vec / R_vec length fields d
 
 // k_vfe_points: decompression, validation and serialization of every point of the batch.
 //   d_proofs   P x plen bytes (R1CSProof::to_bytes)
-//   d_V        P x m x 16 words, ark layout
+//   d_V        P x m x 16 words, ark layout; with sh.vwire P x m x 33 bytes, ark-serialize's compressed form (a rejected one raises
+//              ST_FORMAT, the identity is taken as all-zero words are)
 //   d_msg      nitems x 9 x P 64-bit words: word w of item `it` of proof p at [(it * 9 + w) * P + p]
 //   d_tail_pts P x tail x 16 words, resident layout, the mega-check's per-proof bases in verification_scalars' order
 //   d_status   one word, OR of ST_*

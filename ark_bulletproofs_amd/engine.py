@@ -784,9 +784,69 @@ class VerifierCS(_ConstraintSystem):
         check(lib().bp_verifier_commit(self.h, ptr(V), C.c_size_t(len(V)), ptr(vars_)), "bp_verifier_commit")
         return _vars_out(vars_)
 
+    def commit_compressed(self, blob, defer=True, engine=None):
+        """`commit(G::deserialize_compressed(..)?)` for the len(blob) / 33 encodings of blob, in order.  defer=True: stored as
+        pending wire commitments (decoded by whatever verifies, or by materialize()); defer=False: decoded and committed now,
+        which needs an engine.  Returns the variables."""
+        return _verifier_commit_compressed_batch(engine, [self], [blob], defer=defer)[0]
+
+    def materialize(self, engine=None):
+        """decodes and commits the pending wire commitments (GPU with an engine, host square roots without); returns the C status"""
+        return lib().bp_verifier_materialize(engine.ctx if engine is not None else None, self.h)
+
     def verify(self, engine, proof):
         """Verifier::verify(&proof, &pc_gens, &bp_gens): returns the C status (0 = Ok(()))"""
         return lib().bp_verifier_verify(engine.ctx, self.h, bytes(proof), C.c_size_t(len(proof)))
+
+
+def points_compress(curve, xy):
+    """affine ark words (n, 8) -> n x 33 bytes of ark-serialize's compressed encoding (all-zero words: the identity)"""
+    xy = u64arr(xy, 8)
+    out = C.create_string_buffer(max(33 * len(xy), 1))
+    check(lib().bp_points_compress(int(curve), ptr(xy), C.c_size_t(len(xy)), out), "bp_points_compress")
+    return out.raw[: 33 * len(xy)]
+
+
+def _points_decompress(self, compressed):
+    """compressed: bytes of n x 33; returns (points (n, 8) u64, ok (n,) u8): a rejected encoding gives zero words and ok = 0"""
+    n = len(compressed) // 33
+    out = np.zeros((n, 8), dtype=np.uint64)
+    ok = np.zeros(n, dtype=np.uint8)
+    check(lib().bp_points_decompress(self.ctx, bytes(compressed), C.c_size_t(n), ptr(out), ptr(ok)), "bp_points_decompress")
+    return out, ok
+
+
+def _verifier_commit_compressed_batch(self, verifiers, blobs, defer=False, want_status=False):
+    """bp_verifier_commit_compressed_batch: verifier k receives the len(blobs[k]) / 33 encodings of blobs[k].  Returns the
+    variables per verifier; with want_status (rc, per-verifier statuses, variables) instead of raising on a rejected encoding."""
+    n = len(verifiers)
+    hs = (C.c_void_p * max(n, 1))(*[v.h for v in verifiers])
+    ms = [len(b) // 33 for b in blobs]
+    m_each = (C.c_size_t * max(n, 1))(*ms)
+    blob = b"".join(bytes(b) for b in blobs)
+    vars_ = np.zeros((max(sum(ms), 1), 2), dtype=np.uint32)
+    st = np.zeros(max(n, 1), dtype=np.int32)
+    rc = lib().bp_verifier_commit_compressed_batch(self.ctx if self is not None else None, C.c_size_t(n), hs, m_each, blob if blob else None, int(bool(defer)), ptr(vars_), ptr(st))
+    out, at = [], 0
+    for m in ms:
+        out.append(_vars_out(vars_[at:at + m]))
+        at += m
+    if want_status:
+        return rc, st[:n].copy(), out
+    check(rc, "bp_verifier_commit_compressed_batch")
+    return out
+
+
+def _commit_wire_stats(self):
+    """wire commitments decoded since ctx creation: (by the device front end, by the GPU codec launch, by host square roots)"""
+    a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    check(lib().bp_ctx_commit_wire_stats(self.ctx, C.byref(a), C.byref(b), C.byref(c)), "bp_ctx_commit_wire_stats")
+    return a.value, b.value, c.value
+
+
+Engine.points_decompress = _points_decompress
+Engine.verifier_commit_compressed_batch = _verifier_commit_compressed_batch
+Engine.commit_wire_stats = _commit_wire_stats
 
 
 def batch_verify_cs(engine, verifiers, proofs, alphas, want_point=False):

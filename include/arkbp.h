@@ -448,6 +448,51 @@ void* bp_cs_transcript(bp_cs* cs);
 int bp_prover_commit(bp_cs* prover, bp_ctx* ctx_or_null, const uint64_t* v, const uint64_t* v_blinding, size_t count, uint64_t* V_xy_out, bp_var* vars_out);
 /* `Verifier::commit(V) -> Variable` (verifier.rs:279-287) for `count` commitments in order */
 int bp_verifier_commit(bp_cs* verifier, const uint64_t* V_xy, size_t count, bp_var* vars_out);
+
+/* ---- Commitments from the wire ----------------------------------------------------------------------------------------------
+ * The 33-byte encoding is ark-serialize's `serialize_compressed` of a short-Weierstrass affine point: x as 32 little-endian bytes,
+ * then a flag byte (0x80: y is the larger root, 0x40: the identity, then x = 0).  A decoder rejects: flag bits 0..5 set, both flags
+ * set, x >= p, the identity flag with x != 0, x not on the curve.
+ *
+ * bp_points_decompress: n encodings -> affine ark words (x || y, 8 words per point), the square roots on the GPU in one launch; on
+ * a host-only ctx (bp_debug_ctx_create_hostonly) on the host pool.  A rejected entry gives all-zero words and ok = 0; the identity
+ * gives all-zero words and ok = 1.
+ * bp_points_compress (host only): affine ark words -> encodings; all-zero words are the identity.  BP_E_ARG for a point off the curve. */
+int bp_points_decompress(bp_ctx* ctx, const uint8_t* c33, size_t n, uint64_t* out_xy, uint8_t* ok);
+int bp_points_compress(int curve, const uint64_t* xy, size_t n, uint8_t* c33_out);
+/* `V = G::deserialize_compressed(bytes)?; verifier.commit(V)` for many verifiers in one call: verifier k receives the next
+ * m_each[k] encodings of c33, in order.  vars_out (sum of m_each entries) and status (count entries) may be NULL.  BP_E_ARG, with
+ * nothing changed: a handle that is not a live verifier of the ctx's curve, a handle given twice, c33 NULL with encodings to read.
+ *
+ * defer == 0: all encodings are decoded in one launch (one copy back), then every verifier commits its points in order on the
+ * ctx's host pool: the state bp_verifier_commit leaves.  A verifier with a rejected encoding gets status[k] = BP_E_FORMAT and
+ * receives none of its commitments from this call (handle and transcript untouched); the others proceed.  Returns the first
+ * non-zero status in instance order.
+ *
+ * defer != 0: nothing is decoded, no transcript is touched.  The handle stores the bytes as PENDING wire commitments (vars_out
+ * still receives Committed(i) in order) with a copy of its transcript's state.  While commitments are pending bp_verifier_commit
+ * and the immediate form are BP_E_ARG; a further deferred call is allowed while the transcript is unchanged; recording calls
+ * (bp_cs_multiply, bp_cs_constrain*, bp_cs_allocate*, bp_cs_specify_randomized_constraints) and bp_verifier_new_like (the new handle
+ * starts with none) are allowed.  The transcript is borrowed: whoever appends to it while commitments are pending changes the order
+ * the reference would see, so every use of pending commitments first compares the transcript with the stored state and a difference
+ * is BP_E_ARG (the message names the instance).  A gadget that binds extra data through bp_cs_transcript calls
+ * bp_verifier_materialize first.
+ *
+ * Every verifying entry point (bp_verifier_verify, bp_r1cs_batch_verify, bp_verifier_verify_batch, bp_r1cs_batch_verify_locate)
+ * accepts handles with pending commitments: after its up-front checks it decodes the pending commitments of all instances in one
+ * launch and commits them on the pool.  A rejected encoding is that instance's BP_E_FORMAT, reported before any error of the proof
+ * bytes.  A batch of like-instances (bp_verifier_new_like) that the device front end takes, where every instance holds only pending
+ * commitments and the same number of them, never decodes them on the host at all: k_vfe_points reads the encodings.
+ *
+ * bp_verifier_materialize: decodes and commits the handle's pending commitments now (GPU with a ctx, host roots with NULL or a
+ * host-only ctx).  BP_E_FORMAT for a rejected encoding (the bytes stay pending); BP_OK when nothing is pending.
+ * bp_ctx_commit_wire_stats: wire commitments decoded since ctx creation by k_vfe_points (the device front end) / by
+ * k_points_decompress (the immediate form, materialize, the verify prologue) / by host square roots (host-only ctx, and the m
+ * commitments of instance 0 a two-phase device batch rehearses). */
+int bp_verifier_commit_compressed_batch(bp_ctx* ctx, size_t count, bp_cs* const* verifiers, const size_t* m_each, const uint8_t* c33, int defer, bp_var* vars_out,
+                                        int* status);
+int bp_verifier_materialize(bp_ctx* ctx_or_null, bp_cs* verifier);
+int bp_ctx_commit_wire_stats(bp_ctx* ctx, uint64_t* by_front_end, uint64_t* by_prologue_gpu, uint64_t* on_host);
 /* `multiply(left, right) -> (l, r, o)` (constraint_system.rs:30-41; prover.rs:103-133, verifier.rs:74-98) */
 int bp_cs_multiply(bp_cs* cs, const bp_var* left_vars, const uint64_t* left_coefs, size_t n_left, const bp_var* right_vars, const uint64_t* right_coefs,
                    size_t n_right, bp_var out[3]);
