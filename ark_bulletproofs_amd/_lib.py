@@ -32,6 +32,8 @@ EXPORTS = [
     "bp_ctx_msm_pair_stats", "bp_debug_msm_pair", "bp_debug_fold", "bp_gens_direct_tables_check",
     # verifier commitments from the wire
     "bp_points_decompress", "bp_points_compress", "bp_verifier_commit_compressed_batch", "bp_verifier_materialize", "bp_ctx_commit_wire_stats",
+    # PedersenGens of the caller's choice
+    "bp_pedersen_gens_install", "bp_ctx_pedersen_gens", "bp_prover_new_gens",
 ]
 
 

@@ -252,6 +252,7 @@ struct bp_ctx {
     DevBuf pc_dt;      // direct window tables of B, B_blinding (small.cuh k_dt_commit)
     size_t gens_cap = 0;
     A4 pc_B, pc_Bb;
+    bool pc_set = false, pc_custom = false;   // pc_B / pc_Bb hold a pair / one that bp_pedersen_gens_install put there (default() otherwise)
     // R1CS prover / verifier vectors (resident scalar layout)
     DevBuf r_aL, r_aR, r_aO, r_sL, r_sR, r_wL, r_wR, r_wO, r_msmsc, r_ypow, r_part, r_small, r_g, r_h, r_chal, r_tail;
     // batch verification: per-proof parameter blocks, chunk partials; cached circuit templates (VTemplate<C>)
@@ -1069,6 +1070,19 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
 static constexpr u32 FB_ROWS = 65;   // rows at bit positions 0, 4, 8, .., 256: any window width c that is a multiple of 4 finds its rows (the last one serves the carry window)
 // A run of generator-table bases of a fixed-base MSM: which table (0 = G, 1 = H, 2 = PedersenGens {B, B_blinding}), first index, count
 struct FbRun { int table; size_t first, count; size_t stride = 1; };   // stride: base j of the run is table[first + j * stride] (an index-cyclic slice)
+// the rows of `count` bases, slab by slab through the caller's scratch (tmp: 96 B, pref: 32 B, outb: 64 B per row and slab base)
+template <class C> static int fb_rows_build(hipStream_t st, const u32* gens, u32* table, size_t count, size_t table_cap, size_t slab, DevBuf& tmp, DevBuf& pref, DevBuf& outb) {
+    for (size_t lo = 0; lo < count; lo += slab) {
+        const size_t m = std::min(slab, count - lo);
+        const u32 gb = (u32)((m + 255) / 256);
+        hipLaunchKernelGGL(k_msm_fb_rows<C>, dim3(gb), dim3(256), 0, st, gens + lo * 16, tmp.as<u32>(), (u32)m, FB_ROWS);
+        hipLaunchKernelGGL(k_ftab_normalize<C>, dim3(gb), dim3(256), 0, st, tmp.as<u32>(), pref.as<u32>(), outb.as<u32>(), (u32)m, FB_ROWS);
+        HIPCHK(hipGetLastError());
+        for (u32 r = 0; r < FB_ROWS; r++)   // [r][i] of the slab -> [r][lo + i] of the table
+            HIPCHK(hipMemcpyAsync(table + ((size_t)r * table_cap + lo) * 16, outb.as<u32>() + (size_t)r * m * 16, m * 64, hipMemcpyDeviceToDevice, st));
+    }
+    return BP_OK;
+}
 template <class C> static int fb_tables_build(bp_ctx* ctx, size_t cap) {
     hipStream_t st = ctx->stream;
     if (cap == 0 || cap > ctx->gens_cap) { g_err = "msm tables: more bases than installed generators"; return BP_E_GENS_LENGTH; }
@@ -1078,18 +1092,7 @@ template <class C> static int fb_tables_build(bp_ctx* ctx, size_t cap) {
     const size_t slab = std::min<size_t>(cap, (size_t)1 << 18);   // bounds the Jacobian scratch: 65 rows x 2^18 x 96 B = 1.6 GB
     DevBuf tmp, pref, outb;
     BPCHK(tmp.ensure(FB_ROWS * slab * 96)); BPCHK(pref.ensure(FB_ROWS * slab * 32)); BPCHK(outb.ensure(FB_ROWS * slab * 64));
-    auto build = [&](const u32* gens, u32* table, size_t count, size_t table_cap) -> int {
-        for (size_t lo = 0; lo < count; lo += slab) {
-            const size_t m = std::min(slab, count - lo);
-            const u32 gb = (u32)((m + 255) / 256);
-            hipLaunchKernelGGL(k_msm_fb_rows<C>, dim3(gb), dim3(256), 0, st, gens + lo * 16, tmp.as<u32>(), (u32)m, FB_ROWS);
-            hipLaunchKernelGGL(k_ftab_normalize<C>, dim3(gb), dim3(256), 0, st, tmp.as<u32>(), pref.as<u32>(), outb.as<u32>(), (u32)m, FB_ROWS);
-            HIPCHK(hipGetLastError());
-            for (u32 r = 0; r < FB_ROWS; r++)   // [r][i] of the slab -> [r][lo + i] of the table
-                HIPCHK(hipMemcpyAsync(table + ((size_t)r * table_cap + lo) * 16, outb.as<u32>() + (size_t)r * m * 16, m * 64, hipMemcpyDeviceToDevice, st));
-        }
-        return BP_OK;
-    };
+    auto build = [&](const u32* gens, u32* table, size_t count, size_t table_cap) -> int { return fb_rows_build<C>(st, gens, table, count, table_cap, slab, tmp, pref, outb); };
     BPCHK(build(ctx->d_G.as<u32>(), ctx->fb_G.as<u32>(), cap, cap));
     BPCHK(build(ctx->d_H.as<u32>(), ctx->fb_H.as<u32>(), cap, cap));
     BPCHK(build(ctx->d_pc.as<u32>(), ctx->fb_pc.as<u32>(), 2, 2));
@@ -2664,6 +2667,8 @@ struct bp_cs {
     bool consumed = false;                          // prove(self) / verify(self)
     bool running = false;                           // inside prove / verify: the randomized-phase callbacks may still record
     std::vector<A4> commitments;                    // V points in commit order (both modes)
+    A4 pc_B, pc_Bb;                                 // prover: the pc_gens of Prover::new when they are not PedersenGens::default() (bp_prover_new_gens)
+    bool pc_custom = false;
     std::vector<uint8_t> wire;                      // verifier: pending wire commitments, 33 bytes each (bp_verifier_commit_compressed_batch, defer)
     host::Strobe wire_state;                        // the transcript's state when the first of them was stored
     size_t wire_count() const { return wire.size() / 33; }
@@ -2687,12 +2692,34 @@ template <class C> static void cs_handle_init(bp_cs* h, bool proving, host::Tran
     if (C::ID == 0) h->cs0.reset((host::ConstraintSystem<Secq>*)cs); else h->cs1.reset((host::ConstraintSystem<Zorro>*)cs);
     host::TP<C>::r1cs_domain_sep(*tr);   // Prover::new (prover.rs:291-308) / Verifier::new (verifier.rs:252-263)
 }
+// the pair a prover handle commits under: Prover::new(&pc_gens, ..) keeps a reference to it (prover.rs:291-308)
+template <class C> static host::PedersenGens<C> cs_pair(const bp_cs* h) {
+    if (!h->pc_custom) return host::PedersenGens<C>::default_ref();
+    host::PedersenGens<C> pc; pc.B = h->pc_B; pc.B_blinding = h->pc_Bb;
+    return pc;
+}
+template <class C> static void cs_pair_set(bp_cs* h, const A4& B, const A4& Bb) {
+    const auto& d = host::PedersenGens<C>::default_ref();
+    h->pc_custom = !(B == d.B && Bb == d.B_blinding);
+    h->pc_B = B; h->pc_Bb = Bb;
+}
+// a prover and the ctx it commits or proves on must hold the same pair: the reference's Prover has ONE pc_gens for both
+template <class C> static bool cs_pair_matches_t(const bp_cs* h, bp_ctx* c) {
+    host::PedersenGens<C> cp; pc_pair<C>(c, cp);
+    const host::PedersenGens<C> hp = cs_pair<C>(h);
+    return hp.B == cp.B && hp.B_blinding == cp.B_blinding;
+}
+static int cs_pair_check(const char* who, bp_ctx* c, const bp_cs* h, size_t instance) {
+    if (h->curve == 0 ? cs_pair_matches_t<Secq>(h, c) : cs_pair_matches_t<Zorro>(h, c)) return BP_OK;
+    g_err = std::string(who) + ": the Pedersen generators of prover " + std::to_string(instance) + " are not the ctx's (bp_prover_new_gens / bp_pedersen_gens_install)";
+    return BP_E_ARG;
+}
 template <class C> static int stmt_build(bp_stmt* s, const uint64_t* params, const uint8_t* seed, bp_ctx* ctx = nullptr) {
     s->owned_tr.reset(new host::Transcript(host::scenario_label(s->scenario)));
     cs_handle_init<C>(s, true, s->owned_tr.get());
     host::ChaChaRng prng(seed);
-    host::PedersenGens<C> pc = host::PedersenGens<C>::make_default();
-    if (ctx) pedersen_attach<C>(ctx, pc);
+    host::PedersenGens<C> pc = host::PedersenGens<C>::default_ref();
+    if (ctx) { pc_pair<C>(ctx, pc); cs_pair_set<C>(s, pc.B, pc.B_blinding); pedersen_attach<C>(ctx, pc); }   // (the host-only form stays on the default pair)
     int rc = host::scenario_prover<C>(*s->cs<C>(), pc, prng, s->scenario, params, s->io);
     if (rc) return rc;
     s->commitments = s->io.commitments;
@@ -3040,8 +3067,8 @@ template <class C> static int verifier_new_like(bp_cs* of, host::Transcript* tr,
 template <class C> static int prover_commit(bp_cs* h, bp_ctx* ctx, const uint64_t* v, const uint64_t* blind, size_t count, uint64_t* V_xy, bp_var* vars) {
     host::ConstraintSystem<C>& cs = *h->cs<C>();
     if (cs.phase2) return BP_E_ARG;
-    host::PedersenGens<C> pc = host::PedersenGens<C>::make_default();
-    if (ctx) pedersen_attach<C>(ctx, pc);
+    host::PedersenGens<C> pc = cs_pair<C>(h);
+    if (ctx) pedersen_attach<C>(ctx, pc);   // (the entry point has checked that the ctx's tables are multiples of this pair)
     std::vector<A4> pts(count);
     BPCHK(pc.commit_many((const F4*)v, (const F4*)blind, count, pts.data()));
     for (size_t i = 0; i < count; i++) {   // Prover::commit (prover.rs:327-341), in order
@@ -3918,6 +3945,35 @@ int bp_pedersen_gens(int curve, uint64_t B_xy[8], uint64_t B_blinding_xy[8]) {
     memcpy(B_xy, B.x.v, 32); memcpy(B_xy + 4, B.y.v, 32); memcpy(B_blinding_xy, Bb.x.v, 32); memcpy(B_blinding_xy + 4, Bb.y.v, 32);
     return BP_OK;
 }
+int bp_pedersen_gens_install(bp_ctx* c, const uint64_t B_xy[8], const uint64_t B_blinding_xy[8]) {
+    if (!c) { g_err = "bp_pedersen_gens_install: null ctx"; return BP_E_ARG; }
+    if (!B_xy != !B_blinding_xy) { g_err = "bp_pedersen_gens_install: both points, or neither for PedersenGens::default()"; return BP_E_ARG; }
+    if (c->host_only) return BP_E_NO_DEVICE;
+    if (c->d_pc.p && !c->d_pc.owned) { g_err = "bp_pedersen_gens_install: this ctx holds another ctx's generators (bp_gens_share): install on the owner"; return BP_E_ARG; }
+    A4 B, Bb;
+    if (B_xy) {
+        const bool ok = c->curve == 0 ? pc_point_ok<Secq>(B_xy, B) && pc_point_ok<Secq>(B_blinding_xy, Bb) : pc_point_ok<Zorro>(B_xy, B) && pc_point_ok<Zorro>(B_blinding_xy, Bb);
+        if (!ok) { g_err = "bp_pedersen_gens_install: B and B_blinding must be points of the curve other than the identity, coordinates below p"; return BP_E_ARG; }
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const int rc = c->curve == 0 ? pedersen_install<Secq>(c, B_xy ? &B : nullptr, &Bb) : pedersen_install<Zorro>(c, B_xy ? &B : nullptr, &Bb);
+    if (rc) return rc;
+    A4 dB, dBb;
+    if (c->curve == 0) { const auto& d = host::PedersenGens<Secq>::default_ref(); dB = d.B; dBb = d.B_blinding; }
+    else { const auto& d = host::PedersenGens<Zorro>::default_ref(); dB = d.B; dBb = d.B_blinding; }
+    c->pc_custom = !(c->pc_B == dB && c->pc_Bb == dBb);
+    return BP_OK;
+}
+int bp_ctx_pedersen_gens(bp_ctx* c, uint64_t B_xy[8], uint64_t B_blinding_xy[8], int* is_default) {
+    if (!c) { g_err = "bp_ctx_pedersen_gens: null ctx"; return BP_E_ARG; }
+    A4 B, Bb;
+    if (c->curve == 0) { host::PedersenGens<Secq> pc; pc_pair<Secq>(c, pc); B = pc.B; Bb = pc.B_blinding; }
+    else { host::PedersenGens<Zorro> pc; pc_pair<Zorro>(c, pc); B = pc.B; Bb = pc.B_blinding; }
+    if (B_xy) { memcpy(B_xy, B.x.v, 32); memcpy(B_xy + 4, B.y.v, 32); }
+    if (B_blinding_xy) { memcpy(B_blinding_xy, Bb.x.v, 32); memcpy(B_blinding_xy + 4, Bb.y.v, 32); }
+    if (is_default) *is_default = c->pc_custom ? 0 : 1;
+    return BP_OK;
+}
 int bp_host_derive_generators(int curve, int which_H, uint32_t party, size_t count, uint64_t* out_xy) {
     if (!out_xy) return BP_E_ARG;
     std::vector<A4> v;
@@ -4082,6 +4138,16 @@ int bp_prover_new(int curve, void* transcript, bp_cs** out) {
     *out = h;
     return BP_OK;
 }
+int bp_prover_new_gens(int curve, void* transcript, const uint64_t B_xy[8], const uint64_t B_blinding_xy[8], bp_cs** out) {
+    if (!transcript || !out || !B_xy || !B_blinding_xy || (curve != 0 && curve != 1)) { g_err = "bp_prover_new_gens: bad argument"; return BP_E_ARG; }
+    A4 B, Bb;
+    const bool ok = curve == 0 ? pc_point_ok<Secq>(B_xy, B) && pc_point_ok<Secq>(B_blinding_xy, Bb) : pc_point_ok<Zorro>(B_xy, B) && pc_point_ok<Zorro>(B_blinding_xy, Bb);
+    if (!ok) { g_err = "bp_prover_new_gens: B and B_blinding must be points of the curve other than the identity, coordinates below p"; return BP_E_ARG; }
+    const int rc = bp_prover_new(curve, transcript, out);
+    if (rc) return rc;
+    if (curve == 0) cs_pair_set<Secq>(*out, B, Bb); else cs_pair_set<Zorro>(*out, B, Bb);
+    return BP_OK;
+}
 int bp_verifier_new(int curve, void* transcript, bp_cs** out) {
     if (!transcript || !out || (curve != 0 && curve != 1)) return BP_E_ARG;
     bp_cs* h = new bp_cs();
@@ -4104,7 +4170,7 @@ int bp_cs_metrics(bp_cs* h, size_t* multipliers, size_t* constraints, size_t* co
 }
 int bp_prover_commit(bp_cs* h, bp_ctx* ctx, const uint64_t* v, const uint64_t* v_blinding, size_t count, uint64_t* V_xy_out, bp_var* vars_out) {
     if (!cs_live(h) || !h->proving || (count && (!v || !v_blinding))) return BP_E_ARG;
-    if (ctx) { if (ctx->curve != h->curve) return BP_E_ARG; HIPCHK(hipSetDevice(ctx->device)); }
+    if (ctx) { if (ctx->curve != h->curve) return BP_E_ARG; BPCHK(cs_pair_check("prover_commit", ctx, h, 0)); HIPCHK(hipSetDevice(ctx->device)); }
     return CS_DISPATCH(h, prover_commit<Secq>(h, ctx, v, v_blinding, count, V_xy_out, vars_out), prover_commit<Zorro>(h, ctx, v, v_blinding, count, V_xy_out, vars_out));
 }
 int bp_verifier_commit(bp_cs* h, const uint64_t* V_xy, size_t count, bp_var* vars_out) {
@@ -4238,6 +4304,7 @@ int bp_prover_prove(bp_ctx* c, bp_cs* h, const uint8_t rng_bytes[32], uint8_t* p
         memcpy(h->rng32, rng_bytes, 32); h->have_rng = true;
     }
     if (!h->have_rng) { g_err = "prove: the external rng bytes are missing"; return BP_E_ARG; }
+    BPCHK(cs_pair_check("prove", c, h, 0));   // (before the prover is consumed)
     HIPCHK(hipSetDevice(c->device));
     if (!c->gens_cap) { g_err = "prove: generators not installed (bp_gens_derive / bp_gens_upload / bp_gens_share)"; return BP_E_GENS_LENGTH; }
     h->consumed = true; h->running = true;
@@ -4295,6 +4362,8 @@ int bp_gens_share(bp_ctx* dst, bp_ctx* src) {
     DevBuf* sr[] = {&src->d_G, &src->d_H, &src->d_pc};
     for (int i = 0; i < 3; i++) { d[i]->release(); d[i]->p = sr[i]->p; d[i]->cap = sr[i]->cap; d[i]->owned = false; }
     dst->gens_cap = src->gens_cap; dst->gens_derived = src->gens_derived; dst->pc_B = src->pc_B; dst->pc_Bb = src->pc_Bb;
+    if (dst->pc_custom || src->pc_custom) { dst->pc_table.release(); dst->pc_dt.release(); }   // the view's own tables 5 and 6 were multiples of another pair
+    dst->pc_set = src->pc_set; dst->pc_custom = src->pc_custom;
     DevBuf* dt[] = {&dst->ftab_G, &dst->ftab_H, &dst->fb_G, &dst->fb_H, &dst->fb_pc};
     DevBuf* stb[] = {&src->ftab_G, &src->ftab_H, &src->fb_G, &src->fb_H, &src->fb_pc};
     for (int i = 0; i < 5; i++) { dt[i]->release(); dt[i]->p = stb[i]->p; dt[i]->cap = stb[i]->cap; dt[i]->owned = false; }

@@ -404,42 +404,58 @@ template <class C> struct PedersenGens {
         g.B_blinding = rand_point<C>(prng);
         return g;
     }
-    // Host fixed-base tables of the DEFAULT generators: d * 16^w * B for w < 64, d = 1..15 (affine).  A commitment of single scalars —
-    // the T_1..T_6 of every proof, the inputs of small statements — is then 2 x 64 additions instead of two 256-step double-and-add
-    // ladders (0.24 ms -> ~0.06 ms on one core; at the reference's own benchmark sizes, k-shuffles of 2 .. 1024 inputs, these
-    // commitments were a third of a proof's wall time).  Built once per curve, on first use (~1 ms).
+    static const PedersenGens& default_ref() {   // make_default() costs a SHA3 and a square root: once per curve
+        static const PedersenGens d = make_default();
+        return d;
+    }
+    // Host fixed-base tables of a pair: d * 16^w * base for w < 64, d = 1..15 (affine), for B and for B_blinding.  A commitment of
+    // single scalars — the T_1..T_6 of every proof, the inputs of small statements — is then 2 x 64 additions instead of two 256-step
+    // double-and-add ladders (0.24 ms -> ~0.06 ms on one core; at the reference's own benchmark sizes, k-shuffles of 2 .. 1024 inputs,
+    // these commitments were a third of a proof's wall time).  Built once per distinct pair, on first use (~1 ms), and kept in a small
+    // cache keyed by the four coordinates: the default pair and a caller's own (bp_pedersen_gens_install, bp_prover_new_gens) cost
+    // the same.  A thread remembers the set it used last, so the cache's lock is taken only when a thread changes pairs.
     struct FixedTables { A4 B, Bb; std::vector<A4> tB, tBb; };
-    static const FixedTables& fixed_tables() {
-        static FixedTables ft;
-        static std::once_flag once;
-        std::call_once(once, [] {
-            typedef Grp<C> G; typedef Fld<typename C::Fq> F;
-            const PedersenGens d = make_default();
-            ft.B = d.B; ft.Bb = d.B_blinding;
-            auto build = [](const A4& base, std::vector<A4>& out) {
-                std::vector<J4> jac(64 * 15);
-                J4 pw = G::from_aff(base);
-                for (int w = 0; w < 64; w++) {
-                    J4 acc = pw;
-                    for (int dgt = 1; dgt <= 15; dgt++) { jac[w * 15 + dgt - 1] = acc; acc = G::add(acc, pw); }
-                    pw = acc;            // 16 * pw
-                }
-                // to affine with one inversion (Montgomery's trick); no entry is the identity (the order is prime and > 2^250)
-                std::vector<F4> pref(jac.size());
-                F4 run = F::one();
-                for (size_t i = 0; i < jac.size(); i++) { pref[i] = run; run = F::mul(run, jac[i].Z); }
-                F4 inv = F::inv(run);
-                out.resize(jac.size());
-                for (size_t i = jac.size(); i-- > 0;) {
-                    const F4 zi = F::mul(inv, pref[i]);
-                    inv = F::mul(inv, jac[i].Z);
-                    const F4 zi2 = F::sqr(zi);
-                    out[i] = A4{F::mul(jac[i].X, zi2), F::mul(jac[i].Y, F::mul(zi2, zi))};
-                }
-            };
-            build(ft.B, ft.tB); build(ft.Bb, ft.tBb);
-        });
+    static constexpr size_t FIXED_CACHE_MAX = 8;   // distinct pairs kept; the oldest goes first (a set in use stays alive through its shared_ptr)
+    static std::shared_ptr<const FixedTables> build_fixed_tables(const A4& B, const A4& Bb) {
+        typedef Grp<C> G; typedef Fld<typename C::Fq> F;
+        auto ft = std::make_shared<FixedTables>();
+        ft->B = B; ft->Bb = Bb;
+        auto build = [](const A4& base, std::vector<A4>& out) {
+            std::vector<J4> jac(64 * 15);
+            J4 pw = G::from_aff(base);
+            for (int w = 0; w < 64; w++) {
+                J4 acc = pw;
+                for (int dgt = 1; dgt <= 15; dgt++) { jac[w * 15 + dgt - 1] = acc; acc = G::add(acc, pw); }
+                pw = acc;            // 16 * pw
+            }
+            // to affine with one inversion (Montgomery's trick); no entry is the identity (the order is prime and > 2^250, the base is not the identity)
+            std::vector<F4> pref(jac.size());
+            F4 run = F::one();
+            for (size_t i = 0; i < jac.size(); i++) { pref[i] = run; run = F::mul(run, jac[i].Z); }
+            F4 inv = F::inv(run);
+            out.resize(jac.size());
+            for (size_t i = jac.size(); i-- > 0;) {
+                const F4 zi = F::mul(inv, pref[i]);
+                inv = F::mul(inv, jac[i].Z);
+                const F4 zi2 = F::sqr(zi);
+                out[i] = A4{F::mul(jac[i].X, zi2), F::mul(jac[i].Y, F::mul(zi2, zi))};
+            }
+        };
+        build(B, ft->tB);
+        if (Bb == B) ft->tBb = ft->tB; else build(Bb, ft->tBb);
         return ft;
+    }
+    const FixedTables& fixed_tables() const {
+        static thread_local std::shared_ptr<const FixedTables> last;
+        if (last && last->B == B && last->Bb == B_blinding) return *last;
+        static std::mutex mu;
+        static std::vector<std::shared_ptr<const FixedTables>> cache;
+        std::lock_guard<std::mutex> lk(mu);   // (a first use builds under the lock: a second thread with the same pair waits instead of building it twice)
+        for (auto& e : cache) if (e->B == B && e->Bb == B_blinding) { last = e; return *last; }
+        if (cache.size() >= FIXED_CACHE_MAX) cache.erase(cache.begin());
+        cache.push_back(build_fixed_tables(B, B_blinding));
+        last = cache.back();
+        return *last;
     }
     static J4 fixed_mul_acc(J4 acc, const std::vector<A4>& tab, const F4& s) {
         u64 k[4]; Fld<typename C::Fr>::to_canon(k, s);
@@ -452,14 +468,10 @@ template <class C> struct PedersenGens {
     // the same before the final inversion (several commitments share one: Montgomery's trick at the caller)
     J4 commit_jac(const F4& v, const F4& blind) const {
         const FixedTables& ft = fixed_tables();
-        if (B == ft.B && B_blinding == ft.Bb) return fixed_mul_acc(fixed_mul_acc(Grp<C>::inf(), ft.tB, v), ft.tBb, blind);
-        return Grp<C>::add(Grp<C>::mul(B, v), Grp<C>::mul(B_blinding, blind));
+        return fixed_mul_acc(fixed_mul_acc(Grp<C>::inf(), ft.tB, v), ft.tBb, blind);
     }
-    A4 commit(const F4& v, const F4& blind) const {  // src/generators.rs:39-44
-        const FixedTables& ft = fixed_tables();
-        if (B == ft.B && B_blinding == ft.Bb) return Grp<C>::to_aff(fixed_mul_acc(fixed_mul_acc(Grp<C>::inf(), ft.tB, v), ft.tBb, blind));
-        return Grp<C>::to_aff(Grp<C>::add(Grp<C>::mul(B, v), Grp<C>::mul(B_blinding, blind)));
-    }
+    A4 commit(const F4& v, const F4& blind) const { return Grp<C>::to_aff(commit_jac(v, blind)); }  // src/generators.rs:39-44
+    J4 mul_B_jac(const F4& s) const { return fixed_mul_acc(Grp<C>::inf(), fixed_tables().tB, s); }   // s * B (the inner-product argument's Q = w * B)
     // optional: all commitments of a statement in one call (the engine installs its GPU fixed-base kernel here)
     std::function<int(const F4* v, const F4* blind, size_t m, A4* out)> batch;
     int commit_many(const F4* v, const F4* blind, size_t m, A4* out) const {

@@ -799,6 +799,7 @@ int bp_prover_prove_batch(bp_ctx* c, size_t count, bp_cs* const* provers, const 
         if (rng_bytes) {
             if (h->have_rng && (h->pre0.rng || h->pre1.rng) && memcmp(h->rng32, rng_bytes + 32 * k, 32)) { g_err = "prove_batch: rng bytes differ from the precomputed ones"; return BP_E_ARG; }
         } else if (!h->have_rng) { g_err = "prove_batch: the external rng bytes are missing"; return BP_E_ARG; }
+        BPCHK(cs_pair_check("prove_batch", c, h, k));
     }
     {
         std::vector<const void*> hv(provers, provers + count), tv(count);
@@ -820,7 +821,7 @@ template <class C> static int prover_commit_batch_t(bp_ctx* ctx, size_t count, b
                                                     uint64_t* V_xy, bp_var* vars) {
     size_t total = 0;
     for (size_t k = 0; k < count; k++) total += m_each[k];
-    host::PedersenGens<C> pc = host::PedersenGens<C>::make_default();
+    host::PedersenGens<C> pc; pc_pair<C>(ctx, pc);   // (every prover of the batch holds this pair: checked by the entry point)
     pedersen_attach<C>(ctx, pc);
     std::vector<A4> pts(total);
     BPCHK(pc.commit_many((const F4*)v, (const F4*)blind, total, pts.data()));   // every commitment of the batch: one launch, one inversion
@@ -849,6 +850,7 @@ int bp_prover_commit_batch(bp_ctx* c, size_t count, bp_cs* const* provers, const
         bp_cs* h = provers[k];
         if (!cs_live(h) || !h->proving || h->curve != c->curve) { g_err = "prover_commit_batch: every instance needs a live prover of the ctx's curve"; return BP_E_ARG; }
         if (CS_DISPATCH(h, h->cs0->phase2, h->cs1->phase2)) return BP_E_ARG;
+        BPCHK(cs_pair_check("prover_commit_batch", c, h, k));
         total += m_each[k];
     }
     if (total && (!v || !v_blinding)) return BP_E_ARG;

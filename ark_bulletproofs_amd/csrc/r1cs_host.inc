@@ -73,6 +73,22 @@ static void gens_tables_drop(bp_ctx* ctx) {
     ctx->fb_cap = 0;
     ctx->dt_cap = 0;
 }
+// The ctx's PedersenGens { B, B_blinding } as the resident pair d_pc: every kernel and every table builder reads the two bases from
+// there.  The pair is PedersenGens::default() (src/generators.rs:47-66) until bp_pedersen_gens_install puts the caller's there.
+template <class C> static void pc_pair(bp_ctx* ctx, host::PedersenGens<C>& pc) {
+    if (!ctx->pc_set) { const auto& d = host::PedersenGens<C>::default_ref(); ctx->pc_B = d.B; ctx->pc_Bb = d.B_blinding; ctx->pc_set = true; ctx->pc_custom = false; }
+    pc.B = ctx->pc_B; pc.B_blinding = ctx->pc_Bb;
+}
+template <class C> static int pc_upload(bp_ctx* ctx) {
+    host::PedersenGens<C> pc;
+    pc_pair<C>(ctx, pc);
+    uint64_t two[16];
+    memcpy(two, pc.B.x.v, 32); memcpy(two + 4, pc.B.y.v, 32); memcpy(two + 8, pc.B_blinding.x.v, 32); memcpy(two + 12, pc.B_blinding.y.v, 32);
+    BPCHK(ctx->d_pc.ensure(128));
+    HIPCHK(hipMemcpyAsync(ctx->d_pc.p, two, 128, hipMemcpyHostToDevice, ctx->stream));   // (pageable: the copy has left `two` when the call returns)
+    BPCHK(bp_points_import(ctx, ctx->d_pc.p, ctx->d_pc.p, 2));
+    return BP_OK;
+}
 template <class C> static int gens_install(bp_ctx* ctx, const uint64_t* G_xy, const uint64_t* H_xy, size_t cap) {
     gens_tables_drop(ctx);   // (before the first byte changes)
     ctx->gens_derived = false;
@@ -81,13 +97,7 @@ template <class C> static int gens_install(bp_ctx* ctx, const uint64_t* G_xy, co
     HIPCHK(hipMemcpyAsync(ctx->d_H.p, H_xy, cap * 64, hipMemcpyHostToDevice, ctx->stream));
     BPCHK(bp_points_import(ctx, ctx->d_G.p, ctx->d_G.p, cap));
     BPCHK(bp_points_import(ctx, ctx->d_H.p, ctx->d_H.p, cap));
-    host::PedersenGens<C> pc = host::PedersenGens<C>::make_default();
-    ctx->pc_B = pc.B; ctx->pc_Bb = pc.B_blinding;
-    uint64_t two[16];
-    memcpy(two, pc.B.x.v, 32); memcpy(two + 4, pc.B.y.v, 32); memcpy(two + 8, pc.B_blinding.x.v, 32); memcpy(two + 12, pc.B_blinding.y.v, 32);
-    BPCHK(ctx->d_pc.ensure(128));
-    HIPCHK(hipMemcpyAsync(ctx->d_pc.p, two, 128, hipMemcpyHostToDevice, ctx->stream));
-    BPCHK(bp_points_import(ctx, ctx->d_pc.p, ctx->d_pc.p, 2));
+    BPCHK(pc_upload<C>(ctx));   // the ctx keeps its pair: PedersenGens::default() unless bp_pedersen_gens_install put another there
     HIPCHK(ctx_stream_wait(ctx));
     ctx->gens_cap = cap;
     return BP_OK;
@@ -140,13 +150,7 @@ template <class C> static int gens_derive(bp_ctx* ctx, size_t cap) {
     ctx->gens_derived = false;
     BPCHK(derive_table_gpu<C>(ctx, 'G', ctx->d_G, cap));
     BPCHK(derive_table_gpu<C>(ctx, 'H', ctx->d_H, cap));
-    host::PedersenGens<C> pc = host::PedersenGens<C>::make_default();
-    ctx->pc_B = pc.B; ctx->pc_Bb = pc.B_blinding;
-    uint64_t two[16];
-    memcpy(two, pc.B.x.v, 32); memcpy(two + 4, pc.B.y.v, 32); memcpy(two + 8, pc.B_blinding.x.v, 32); memcpy(two + 12, pc.B_blinding.y.v, 32);
-    BPCHK(ctx->d_pc.ensure(128));
-    HIPCHK(hipMemcpyAsync(ctx->d_pc.p, two, 128, hipMemcpyHostToDevice, ctx->stream));
-    BPCHK(bp_points_import(ctx, ctx->d_pc.p, ctx->d_pc.p, 2));
+    BPCHK(pc_upload<C>(ctx));   // the ctx keeps its pair: PedersenGens::default() unless bp_pedersen_gens_install put another there
     HIPCHK(ctx_stream_wait(ctx));
     ctx->gens_cap = cap;
     ctx->gens_derived = true;
@@ -699,7 +703,7 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
         HIPCHK(hipMemcpyAsync(ctx->ipa_H.p, ctx->d_H.p, N * 64, hipMemcpyDeviceToDevice, st));
     }
     if (!direct) {   // Q = w * B as a point (prover.rs:779); over the direct tables c * Q is (c * w) * B and Q itself is never formed
-        const A4 Q = G::to_aff(G::mul(pc.B, w));
+        const A4 Q = G::to_aff(pc.mul_B_jac(w));   // (the host's fixed-base tables of the ctx's pair)
         uint64_t Qw[8]; memcpy(Qw, Q.x.v, 32); memcpy(Qw + 4, Q.y.v, 32);
         HIPCHK(hipMemcpyAsync(ctx->ipa_Q.p, Qw, 64, hipMemcpyHostToDevice, st));
         BPCHK(bp_points_import(ctx, ctx->ipa_Q.p, ctx->ipa_Q.p, 1));
@@ -785,14 +789,8 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
 
 // ---- batched Pedersen commitments (PedersenGens::commit, src/generators.rs:39-44, for all inputs of a statement) -------
 template <class C> static int pedersen_ensure(bp_ctx* ctx) {
-    if (!ctx->d_pc.p) {   // a ctx without BulletproofGens still has PedersenGens::default()
-        host::PedersenGens<C> pc = host::PedersenGens<C>::make_default();
-        ctx->pc_B = pc.B; ctx->pc_Bb = pc.B_blinding;
-        uint64_t two[16];
-        memcpy(two, pc.B.x.v, 32); memcpy(two + 4, pc.B.y.v, 32); memcpy(two + 8, pc.B_blinding.x.v, 32); memcpy(two + 12, pc.B_blinding.y.v, 32);
-        BPCHK(ctx->d_pc.ensure(128));
-        HIPCHK(hipMemcpyAsync(ctx->d_pc.p, two, 128, hipMemcpyHostToDevice, ctx->stream));
-        BPCHK(bp_points_import(ctx, ctx->d_pc.p, ctx->d_pc.p, 2));
+    if (!ctx->d_pc.p) {   // a ctx without BulletproofGens still has its PedersenGens
+        BPCHK(pc_upload<C>(ctx));
     }
     if (!ctx->pc_table.p) {
         BPCHK(ctx->pc_table.ensure(PC_TABLE_BYTES));
@@ -811,7 +809,40 @@ template <class C> static int pedersen_ensure(bp_ctx* ctx) {
     }
     return BP_OK;
 }
-static constexpr size_t PC_LATENCY_MAX = 4096;   // commitments per call up to which the wave-per-commitment kernel runs (one wave each: 4096 fill the chip four times)
+// A pair of the caller's choice as two points of the curve: what the affine tables can hold (no identity), canonical coordinates
+template <class C> static bool pc_point_ok(const uint64_t* xy, A4& out) {
+    typedef host::Fld<typename C::Fq> F;
+    memcpy(out.x.v, xy, 32); memcpy(out.y.v, xy + 4, 32);
+    if (F::geq_p(out.x.v) || F::geq_p(out.y.v) || out.is_inf()) return false;
+    return host::Grp<C>::on_curve(out);
+}
+// bp_pedersen_gens_install: the pair changes, and with it exactly what was computed from it.  Bases 0 and 1 of the direct window
+// tables and the fb_pc rows are rebuilt in place by the builders that made them; tables 5 and 6 go and come back with
+// pedersen_ensure.  Nothing that holds multiples of G and H only is read or written.  One wait.
+template <class C> static int pedersen_install(bp_ctx* ctx, const A4* B, const A4* Bb) {
+    hipStream_t st = ctx->stream;
+    if (B) { ctx->pc_B = *B; ctx->pc_Bb = *Bb; ctx->pc_set = true; ctx->pc_custom = true; }
+    else ctx->pc_set = false;   // (pc_pair puts the default there)
+    BPCHK(pc_upload<C>(ctx));
+    DevBuf ws, tmp, pref, outb;
+    auto done = [&](int rc) { ws.release(); tmp.release(); pref.release(); outb.release(); return rc; };
+    if (ctx->dt_cap && ctx->dt_tab.p) {
+        if (int rc = ws.ensure((size_t)2 * DT_WINDOWS * 96)) return done(rc);
+        hipLaunchKernelGGL(k_dt_window_bases<C>, dim3(1), dim3(64), 0, st, ctx->d_pc.as<u32>(), 2u, ws.as<u32>());
+        hipLaunchKernelGGL(k_dt_entries<C>, dim3((2 * DT_PER_BASE + 255) / 256), dim3(256), 0, st, ws.as<u32>(), 2u, ctx->dt_tab.as<u32>());
+    }
+    if (ctx->fb_cap && ctx->fb_pc.p) {
+        int rc = tmp.ensure((size_t)FB_ROWS * 2 * 96);
+        if (!rc) rc = pref.ensure((size_t)FB_ROWS * 2 * 32);
+        if (!rc) rc = outb.ensure((size_t)FB_ROWS * 2 * 64);
+        if (!rc) rc = fb_rows_build<C>(st, ctx->d_pc.as<u32>(), ctx->fb_pc.as<u32>(), 2, 2, 2, tmp, pref, outb);
+        if (rc) return done(rc);
+    }
+    if (hipGetLastError() != hipSuccess || ctx_stream_wait(ctx) != hipSuccess) { g_err = "bp_pedersen_gens_install: HIP error"; return done(BP_E_HIP); }
+    ctx->pc_table.release(); ctx->pc_dt.release();
+    return done(BP_OK);
+}
+static constexpr size_t PC_LATENCY_MAX = 4096;  // commitments per call up to which the wave-per-commitment kernel runs (one wave each: 4096 fill the chip four times)
 // v, blind: m Fr values in ark layout (host); out: m affine points in ark layout (host)
 template <class C> static int pedersen_commit_batch(bp_ctx* ctx, const uint64_t* v, const uint64_t* blind, size_t m, uint64_t* out_xy) {
     if (!m) return BP_OK;

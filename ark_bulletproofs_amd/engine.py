@@ -287,7 +287,7 @@ SC_SHUFFLE, SC_RANGE, SC_EXAMPLE, SC_SQUARE_CHAIN, SC_MULTI_RANGE = 0, 1, 2, 3, 
 
 
 def _gens_derive(self, cap):
-    """BulletproofGens::new(cap, 1) + PedersenGens::default(), installed in HBM"""
+    """BulletproofGens::new(cap, 1) + the engine's PedersenGens (default() unless pedersen_gens_install put a pair there), installed in HBM"""
     check(lib().bp_gens_derive(self.ctx, C.c_size_t(cap)), "bp_gens_derive")
     self.gens_capacity = cap
 
@@ -567,6 +567,26 @@ def _share_gens_from(self, other):
     self._gens_owner = other  # keep the owner alive
 
 
+def _pedersen_gens_install(self, B=None, Bb=None):
+    """PedersenGens { B, B_blinding } of the caller's choice for everything this engine does; no arguments: PedersenGens::default()"""
+    if B is None and Bb is None:
+        check(lib().bp_pedersen_gens_install(self.ctx, None, None), "bp_pedersen_gens_install")
+        return
+    b = None if B is None else np.ascontiguousarray(B, dtype=np.uint64).reshape(8)
+    bb = None if Bb is None else np.ascontiguousarray(Bb, dtype=np.uint64).reshape(8)
+    check(lib().bp_pedersen_gens_install(self.ctx, ptr(b) if b is not None else None, ptr(bb) if bb is not None else None), "bp_pedersen_gens_install")
+
+
+def _engine_pedersen_gens(self):
+    """the pair this engine holds now: (B, B_blinding, is_default)"""
+    B, Bb = np.zeros(8, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+    dflt = C.c_int(0)
+    check(lib().bp_ctx_pedersen_gens(self.ctx, ptr(B), ptr(Bb), C.byref(dflt)), "bp_ctx_pedersen_gens")
+    return B, Bb, bool(dflt.value)
+
+
+Engine.pedersen_gens_install = _pedersen_gens_install
+Engine.pedersen_gens = _engine_pedersen_gens
 Engine.share_gens_from = _share_gens_from
 Engine.pedersen_commit_batch = _pedersen_commit_batch
 
@@ -741,11 +761,16 @@ class _ConstraintSystem:
 
 
 class ProverCS(_ConstraintSystem):
-    """r1cs::Prover (src/r1cs/prover.rs): `ProverCS(curve, transcript)` = Prover::new(&pc_gens, transcript)"""
+    """r1cs::Prover (src/r1cs/prover.rs): `ProverCS(curve, transcript)` = Prover::new(&pc_gens, transcript) with
+    PedersenGens::default(); pc_gens=(B, B_blinding) (8 ark words each) for a pair of the caller's choice"""
 
-    def __init__(self, curve, transcript):
+    def __init__(self, curve, transcript, pc_gens=None):
         super().__init__(curve, transcript)
-        check(lib().bp_prover_new(curve, transcript.h, C.byref(self.h)), "bp_prover_new")
+        if pc_gens is None:
+            check(lib().bp_prover_new(curve, transcript.h, C.byref(self.h)), "bp_prover_new")
+        else:
+            B, Bb = [np.ascontiguousarray(x, dtype=np.uint64).reshape(8) for x in pc_gens]
+            check(lib().bp_prover_new_gens(curve, transcript.h, ptr(B), ptr(Bb), C.byref(self.h)), "bp_prover_new_gens")
 
     def commit(self, v, v_blinding, engine=None):
         """Prover::commit for one value or for arrays of values: returns (V points (count, 8), variables)"""

@@ -333,6 +333,22 @@ int bp_debug_fold(bp_ctx* ctx, int route, size_t n, const uint64_t tG[4], const 
                   uint32_t gens_stride, const uint64_t* G_xy, const uint64_t* H_xy, uint64_t* G_out_xy, uint64_t* H_out_xy, uint32_t* took);
 /* PedersenGens::default() -> (B, B_blinding); host only */
 int bp_pedersen_gens(int curve, uint64_t B_xy[8], uint64_t B_blinding_xy[8]);
+/* `PedersenGens { pub B, pub B_blinding }` (src/generators.rs:27-36) of the caller's choice for everything this ctx does: the pc_gens
+ * argument of `verifier.verify(&proof, &pc_gens, &bp_gens)` (verifier.rs:549-557) and `batch_verify(prng, instances, pc_gens, bp_gens)`
+ * (:604-691), the bases of bp_pedersen_commit_batch, and the pair that provers committing or proving on this ctx must hold
+ * (bp_prover_new_gens).  Both pointers NULL: back to PedersenGens::default().  A ctx that never installs holds the default pair.
+ * The reference validates nothing here; the engine's affine tables cannot hold an identity entry, so BP_E_ARG — and nothing
+ * changed — for exactly one null pointer, a point off the ctx's curve, a coordinate at or above p, or the identity (all-zero
+ * words).  Any other pair is accepted, B == B_blinding included.  BP_E_NO_DEVICE on a host-only ctx; BP_E_ARG on a ctx that holds
+ * another ctx's generators (bp_gens_share): the owner installs BEFORE it shares and the view receives the owner's pair.  An install
+ * on an owner whose tables other ctxs already view is the owner's responsibility, as with the other tables: share again afterwards.
+ * The pair survives bp_gens_derive (to any capacity) and bp_gens_upload.  Only what was computed from the pair is touched: bases 0
+ * and 1 of the direct window tables and the Pedersen rows of bp_gens_msm_tables are rebuilt in place if built, the two commitment
+ * tables (BP_TABLES_PC_DIRECT, BP_TABLES_PC_WIDE) are dropped and come back on next use; the fold tables, the G/H rows and the G/H
+ * part of the direct tables are neither read nor written.  One host wait. */
+int bp_pedersen_gens_install(bp_ctx* ctx, const uint64_t B_xy[8], const uint64_t B_blinding_xy[8]);
+/* what the ctx holds now; is_default = 1 when that is PedersenGens::default().  Any output may be NULL.  Host only. */
+int bp_ctx_pedersen_gens(bp_ctx* ctx, uint64_t B_xy[8], uint64_t B_blinding_xy[8], int* is_default);
 /* GeneratorsChain for label 'G'|'H' || LE32(party) (src/generators.rs:71-121), first `count` points; host only */
 int bp_host_derive_generators(int curve, int which_H, uint32_t party, size_t count, uint64_t* out_xy);
 
@@ -375,7 +391,7 @@ int bp_r1cs_prove_scenario(bp_ctx* ctx, int scenario, const uint64_t* params, co
                            uint64_t* commit_xy, size_t m_cap, size_t* m_out, uint64_t* publics, size_t* npub, double* timing);
 
 /* `PedersenGens::commit` (src/generators.rs:39-44) for m (value, blinding) pairs at once: out[i] = v[i]*B + blind[i]*B_blinding
- * with PedersenGens::default()'s bases, by fixed-base window tables on the GPU.  v, blind: m x 4 words (ark layout);
+ * with the ctx's bases (PedersenGens::default() unless bp_pedersen_gens_install put others there), by fixed-base window tables on the GPU.  v, blind: m x 4 words (ark layout);
  * out_xy: m x 8 words (affine, ark layout; the identity is all-zero). */
 int bp_pedersen_commit_batch(bp_ctx* ctx, const uint64_t* v, const uint64_t* blind, size_t m, uint64_t* out_xy);
 
@@ -391,7 +407,8 @@ struct bp_cs;
 struct bp_cs* bp_stmt_as_prover(bp_stmt* stmt);
 int bp_stmt_prover_create(int curve, int scenario, const uint64_t* params, const uint8_t seed[32], bp_stmt** out);
 /* same, with the statement's Pedersen commitments (`Prover::commit`, src/r1cs/prover.rs:327-341) computed on ctx's GPU in one
- * batch; the curve is ctx's.  Identical statement (same transcript, same commitments) as the host-only constructor. */
+ * batch; the curve and the Pedersen pair are ctx's.  With the default pair: identical statement (same transcript, same commitments)
+ * as the host-only constructor, which stays on PedersenGens::default(). */
 int bp_stmt_prover_create_dev(bp_ctx* ctx, int scenario, const uint64_t* params, const uint8_t seed[32], bp_stmt** out);
 void bp_stmt_free(bp_stmt* stmt);
 int bp_stmt_info(bp_stmt* stmt, uint64_t* commit_xy, size_t m_cap, size_t* m_out, uint64_t* publics, size_t* npub, size_t* multipliers,
@@ -437,8 +454,15 @@ typedef struct bp_cs bp_cs;
 typedef struct bp_var { uint32_t kind; uint32_t index; } bp_var;
 
 /* `Prover::new(&pc_gens, transcript)` (prover.rs:291-308) / `Verifier::new(transcript)` (verifier.rs:252-263): appends the r1cs
- * domain separator.  pc_gens is PedersenGens::default() (bp_pedersen_gens). */
+ * domain separator.  pc_gens is PedersenGens::default() (bp_pedersen_gens).  A verifier holds no pair: `Verifier::new` takes none,
+ * and every verifying entry point uses the ctx's (bp_pedersen_gens_install). */
 int bp_prover_new(int curve, void* transcript, bp_cs** out);
+/* `Prover::new(&pc_gens, transcript)` (prover.rs:291-308) with the caller's pc_gens, validated as in bp_pedersen_gens_install
+ * (BP_E_ARG for a null pointer, a point off the curve, a coordinate at or above p, the identity).  The handle keeps its pair:
+ * bp_prover_commit without a ctx commits under it on the host; with a ctx — and in bp_prover_commit_batch, bp_prover_prove and
+ * bp_prover_prove_batch — the ctx must hold the same pair, otherwise BP_E_ARG (the message names the instance), nothing is appended
+ * to a transcript and no prover is consumed. */
+int bp_prover_new_gens(int curve, void* transcript, const uint64_t B_xy[8], const uint64_t B_blinding_xy[8], bp_cs** out);
 int bp_verifier_new(int curve, void* transcript, bp_cs** out);
 void bp_cs_free(bp_cs* cs);
 /* `ConstraintSystem::transcript()` (constraint_system.rs:21): the recorder's transcript, for gadgets that bind extra data */

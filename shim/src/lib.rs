@@ -141,6 +141,18 @@ impl GpuContext {
         map_status(rc).expect("bp_gens_upload");
         self.gens_capacity = cap;
     }
+    /// makes `pc_gens` the pair this context works with (`bp_pedersen_gens_install`) unless it holds exactly that pair already
+    /// (`bp_ctx_pedersen_gens`): the `pc_gens` argument of `prove`'s Prover, of `verify` and of `batch_verify`.  The library refuses
+    /// what its affine tables cannot hold (the identity, a point off the curve), which the reference would accept silently.
+    pub fn ensure_pc_gens<G: GpuCurve>(&mut self, pc_gens: &PedersenGens<G>) {
+        let (b, bb) = (G::point_words(&pc_gens.B), G::point_words(&pc_gens.B_blinding));
+        let (mut hb, mut hbb, mut is_default) = ([0u64; 8], [0u64; 8], 0 as c_int);
+        map_status(unsafe { ffi::bp_ctx_pedersen_gens(self.raw, hb.as_mut_ptr(), hbb.as_mut_ptr(), &mut is_default) }).expect("bp_ctx_pedersen_gens");
+        if hb == b && hbb == bb {
+            return;
+        }
+        map_status(unsafe { ffi::bp_pedersen_gens_install(self.raw, b.as_ptr(), bb.as_ptr()) }).expect("bp_pedersen_gens_install");
+    }
 }
 
 thread_local! {
@@ -292,12 +304,19 @@ impl<G: GpuCurve, T: BorrowMut<Transcript>> Drop for Recorder<G, T> {
     }
 }
 impl<G: GpuCurve, T: BorrowMut<Transcript>> Recorder<G, T> {
-    fn new(proving: bool, mut transcript: T) -> Self {
+    /// pc_gens: Some(..) for a prover (`Prover::new(&pc_gens, ..)`), None for a verifier (`Verifier::new` takes none)
+    fn new(pc_gens: Option<&PedersenGens<G>>, mut transcript: T) -> Self {
         let bridge = TranscriptBridge::new(transcript.borrow_mut());
         let mut raw = null_mut();
         // Prover::new / Verifier::new append the "r1cs v1" domain separator (prover.rs:291-308, verifier.rs:252-263): the library does
-        let rc = unsafe { if proving { ffi::bp_prover_new(G::CURVE_ID, bridge.handle, &mut raw) } else { ffi::bp_verifier_new(G::CURVE_ID, bridge.handle, &mut raw) } };
-        map_status(rc).expect("bp_prover_new / bp_verifier_new");
+        let rc = match pc_gens {
+            Some(pc) => {
+                let (b, bb) = (G::point_words(&pc.B), G::point_words(&pc.B_blinding));
+                unsafe { ffi::bp_prover_new_gens(G::CURVE_ID, bridge.handle, b.as_ptr(), bb.as_ptr(), &mut raw) }
+            }
+            None => unsafe { ffi::bp_verifier_new(G::CURVE_ID, bridge.handle, &mut raw) },
+        };
+        map_status(rc).expect("bp_prover_new_gens / bp_verifier_new");
         Recorder { raw, bridge, transcript, callbacks: Vec::new(), drop_callbacks: Vec::new(), multipliers: 0, _g: PhantomData }
     }
     fn sync_to_engine(&mut self) {
@@ -433,26 +452,19 @@ where FF: 'static + Fn(&mut RandomizingCs<G>) -> Result<(), R1CSError> {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-/// The engine works with `PedersenGens::default()` (it derives B and B_blinding itself, `bp_pedersen_gens`): a caller with custom
-/// Pedersen generators must not be checked against the default ones silently.  Prover::new, Verifier::verify and batch_verify all
-/// assert it (the reference would use `pc_gens.B` / `pc_gens.B_blinding`, verifier.rs:574-576).
-fn assert_default_pc_gens<G: GpuCurve>(pc_gens: &PedersenGens<G>) {
-    let (mut b, mut bb) = ([0u64; 8], [0u64; 8]);
-    unsafe { ffi::bp_pedersen_gens(G::CURVE_ID, b.as_mut_ptr(), bb.as_mut_ptr()) };
-    assert!(G::point_words(&pc_gens.B) == b && G::point_words(&pc_gens.B_blinding) == bb, "the engine works with PedersenGens::default()");
-}
-
+/// The caller's `pc_gens` travel with every call, as in the reference: `Prover::new` hands them to the library's prover handle
+/// (`bp_prover_new_gens`), and `prove`, `verify` and `batch_verify` make them the context's pair first (`GpuContext::ensure_pc_gens`;
+/// the reference uses `pc_gens.B` / `pc_gens.B_blinding` there, verifier.rs:574-576).  Like the rest of this file: never compiled.
 // r1cs::Prover (src/r1cs/prover.rs)
 // ------------------------------------------------------------------------------------------------------------------------------
 pub struct Prover<'g, G: GpuCurve, T: BorrowMut<Transcript>> {
     rec: Recorder<G, T>,
-    _pc_gens: &'g PedersenGens<G>, // the engine derives PedersenGens::default() itself; kept for the signature (and checked below)
+    pc_gens: &'g PedersenGens<G>, // the handle holds the same pair (bp_prover_new_gens); prove() makes it the context's
 }
 impl<'g, G: GpuCurve, T: BorrowMut<Transcript>> Prover<'g, G, T> {
     /// `Prover::new(pc_gens, transcript)` (prover.rs:291-308)
     pub fn new(pc_gens: &'g PedersenGens<G>, transcript: T) -> Self {
-        assert_default_pc_gens::<G>(pc_gens);
-        Prover { rec: Recorder::new(true, transcript), _pc_gens: pc_gens }
+        Prover { rec: Recorder::new(Some(pc_gens), transcript), pc_gens }
     }
     /// `commit(v, v_blinding) -> (V, Variable)` (prover.rs:327-341)
     pub fn commit(&mut self, v: G::ScalarField, v_blinding: G::ScalarField) -> (G, Variable<G::ScalarField>) {
@@ -472,6 +484,7 @@ impl<'g, G: GpuCurve, T: BorrowMut<Transcript>> Prover<'g, G, T> {
         let mut len = buf.len();
         let rc = with_ctx::<G, _>(|ctx| {
             ctx.ensure_gens(bp_gens);
+            ctx.ensure_pc_gens(self.pc_gens);
             unsafe { ffi::bp_prover_prove(ctx.raw, self.rec.raw, rng32.as_ptr(), buf.as_mut_ptr(), &mut len, null_mut()) }
         });
         if rc == GADGET_FAILED {
@@ -507,7 +520,7 @@ pub struct Verifier<G: GpuCurve, T: BorrowMut<Transcript>> {
 }
 impl<G: GpuCurve, T: BorrowMut<Transcript>> Verifier<G, T> {
     /// `Verifier::new(transcript)` (verifier.rs:252-263)
-    pub fn new(transcript: T) -> Self { Verifier { rec: Recorder::new(false, transcript) } }
+    pub fn new(transcript: T) -> Self { Verifier { rec: Recorder::new(None, transcript) } }
     /// `commit(V) -> Variable` (verifier.rs:279-287)
     pub fn commit(&mut self, commitment: G) -> Variable<G::ScalarField> {
         self.rec.sync_to_engine();
@@ -518,11 +531,11 @@ impl<G: GpuCurve, T: BorrowMut<Transcript>> Verifier<G, T> {
     }
     /// `verify(self, proof, pc_gens, bp_gens)` (verifier.rs:549-557)
     pub fn verify(mut self, proof: &R1CSProof<G>, pc_gens: &PedersenGens<G>, bp_gens: &BulletproofGens<G>) -> Result<(), R1CSError> {
-        assert_default_pc_gens::<G>(pc_gens);
         self.rec.sync_to_engine();
         let bytes = proof.to_bytes().map_err(|_| R1CSError::FormatError)?;
         let rc = with_ctx::<G, _>(|ctx| {
             ctx.ensure_gens(bp_gens);
+            ctx.ensure_pc_gens(pc_gens);
             unsafe { ffi::bp_verifier_verify(ctx.raw, self.rec.raw, bytes.as_ptr(), bytes.len()) }
         });
         if rc == GADGET_FAILED {
@@ -559,7 +572,6 @@ where
     T: BorrowMut<Transcript>,
     I: IntoIterator<Item = (Verifier<G, T>, &'a R1CSProof<G>)>,
 {
-    assert_default_pc_gens::<G>(pc_gens);
     let mut verifiers: Vec<Verifier<G, T>> = Vec::new();
     let mut bytes: Vec<u8> = Vec::new();
     let mut lens: Vec<usize> = Vec::new();
@@ -580,6 +592,7 @@ where
     let raws: Vec<*mut ffi::BpCs> = verifiers.iter().map(|v| v.rec.raw).collect();
     let rc = with_ctx::<G, _>(|ctx| {
         ctx.ensure_gens(bp_gens);
+        ctx.ensure_pc_gens(pc_gens);
         unsafe { ffi::bp_r1cs_batch_verify(ctx.raw, raws.len(), raws.as_ptr(), bytes.as_ptr(), lens.as_ptr(), alphas.as_ptr(), null_mut(), null_mut()) }
     });
     if rc == GADGET_FAILED {
