@@ -34,6 +34,8 @@ EXPORTS = [
     "bp_points_decompress", "bp_points_compress", "bp_verifier_commit_compressed_batch", "bp_verifier_materialize", "bp_ctx_commit_wire_stats",
     # PedersenGens of the caller's choice
     "bp_pedersen_gens_install", "bp_ctx_pedersen_gens", "bp_prover_new_gens",
+    # blinding vectors from a key
+    "bp_prover_set_blinding", "bp_prover_blinding", "bp_host_blind_expand", "bp_debug_blind_expand", "bp_ctx_blinding_stats",
 ]
 
 

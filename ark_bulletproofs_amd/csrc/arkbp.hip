@@ -343,6 +343,7 @@ struct bp_ctx {
     void* h_pf = nullptr;            // pinned: witness staging, the aux block, results
     size_t h_pf_cap = 0;
     uint64_t pf_instances = 0, pf_groups = 0, pf_waits = 0;
+    uint64_t bx_scalars = 0, bx_launches = 0;   // BP_BLINDING_EXPANDED: scalars the expansion kernels wrote / their launches (bp_ctx_blinding_stats)
     // bp_verifier_verify_batch (verify_each.inc): its device arena and counters
     size_t tune_verify_each = 0;     // BP_TUNE_VERIFY_EACH: most instances per group (0 = what VE_ARENA_BUDGET holds, at most VE_GROUP_MAX)
     DevBuf ve_arena;
@@ -4290,6 +4291,40 @@ int bp_prover_precompute_batch(bp_cs** hs, size_t count) {
     for (size_t i = 0; i < count; i++) if (!cs_live(hs[i]) || !hs[i]->proving || !hs[i]->have_rng || hs[i]->curve != hs[0]->curve) return BP_E_ARG;
     if (!count) return BP_OK;
     return hs[0]->curve == 0 ? cs_precompute_batch<Secq>(hs, count) : cs_precompute_batch<Zorro>(hs, count);
+}
+// how prove() obtains s_L, s_R (include/arkbp.h): fixed once the head of prove() has drawn from the TranscriptRng
+int bp_prover_set_blinding(bp_cs* h, int mode) {
+    if (!h || !h->proving) { g_err = "set_blinding: not a prover handle"; return BP_E_ARG; }
+    if (mode != BP_BLINDING_TRANSCRIPT && mode != BP_BLINDING_EXPANDED) { g_err = "set_blinding: unknown mode"; return BP_E_ARG; }
+    if (h->consumed || h->pre0.rng || h->pre1.rng) { g_err = "set_blinding: the head of prove() has run on this prover"; return BP_E_ARG; }
+    h->pre0.mode = h->pre1.mode = mode;
+    return BP_OK;
+}
+int bp_prover_blinding(bp_cs* h, int* mode_out) {
+    if (!h || !h->proving || !mode_out) return BP_E_ARG;
+    *mode_out = h->pre0.mode;
+    return BP_OK;
+}
+int bp_host_blind_expand(int curve, const uint64_t kappa[4], uint64_t j0, size_t count, uint64_t* sL, uint64_t* sR) {
+    if ((curve != 0 && curve != 1) || !kappa || (count && (!sL || !sR)) || j0 > ((uint64_t)1 << 31) || count > ((uint64_t)1 << 31) - j0) return BP_E_ARG;
+    F4 k; memcpy(k.v, kappa, 32);
+    if (curve == 0 ? host::Fld<SecqFr>::geq_p(k.v) : host::Fld<ZorroFr>::geq_p(k.v)) { g_err = "blind_expand: kappa is not a reduced scalar"; return BP_E_ARG; }
+    if (curve == 0) host_blind_expand<Secq>(k, j0, count, (F4*)sL, (F4*)sR); else host_blind_expand<Zorro>(k, j0, count, (F4*)sL, (F4*)sR);
+    return BP_OK;
+}
+int bp_debug_blind_expand(bp_ctx* c, const uint64_t kappa[4], uint64_t j0, size_t count, uint64_t* sL, uint64_t* sR) {
+    if (!c || !kappa || !sL || !sR || !count || count > ((size_t)1 << 24) || j0 > ((uint64_t)1 << 31) || count > ((uint64_t)1 << 31) - j0) return BP_E_ARG;
+    if (c->host_only) return BP_E_NO_DEVICE;
+    F4 k; memcpy(k.v, kappa, 32);
+    if (c->curve == 0 ? host::Fld<SecqFr>::geq_p(k.v) : host::Fld<ZorroFr>::geq_p(k.v)) { g_err = "blind_expand: kappa is not a reduced scalar"; return BP_E_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    return c->curve == 0 ? dbg_blind_expand<Secq>(c, k, j0, count, sL, sR) : dbg_blind_expand<Zorro>(c, k, j0, count, sL, sR);
+}
+int bp_ctx_blinding_stats(bp_ctx* c, uint64_t* expanded_scalars, uint64_t* launches) {
+    if (!c) return BP_E_ARG;
+    if (expanded_scalars) *expanded_scalars = c->bx_scalars;
+    if (launches) *launches = c->bx_launches;
+    return BP_OK;
 }
 int bp_prover_set_rng(bp_cs* h, const uint8_t rng_bytes[32]) {
     if (!cs_live(h) || !h->proving || !rng_bytes) return BP_E_ARG;

@@ -33,6 +33,7 @@ struct PbLayout {
     // pair and s_R, w_L, w_R, w_O in the rounds' scalar vectors — those are first written by round 1 / round 0, after l(x), r(x) are out
     size_t o_waL = 0, o_waR = 0, o_waO = 0, o_wsL = 0, o_wsR = 0, o_wwL = 0, o_wwR = 0, o_wwO = 0, o_tp = 0;
     size_t ts_off = 0, bl_off = 0;   // the group's t(x) sums (6 x 32 bytes per proof) and blinding factors (8 x 32): inside the wiped range
+    size_t bd_off = 0;               // ... and the expansion jobs of BP_BLINDING_EXPANDED members (2 x BlindDesc per proof: they hold the keys)
     size_t vec_end = 0, cnt_off = 0, desc_off = 0, jobs_off = 0, acc_off = 0, res_off = 0, ab_off = 0, total = 0;   // the arena
     size_t stage_bytes = 0, stage_res = 0, stage_ab = 0;   // the pinned staging: [descriptors | jobs], results, a / b
     void make(size_t N_, size_t cap_) {
@@ -48,7 +49,8 @@ struct PbLayout {
         per_vec = o_tp + pb_align(gf * 6 * 32);
         o_wsL = o_a2; o_wsR = o_sL; o_wwL = o_sL + N * 32; o_wwR = o_sL + 2 * N * 32; o_wwO = o_sL + 3 * N * 32;   // (a2 | b2: >= 32 N bytes, sL | sR: >= 128 N)
         ts_off = per_vec * cap; bl_off = ts_off + pb_align(cap * 192);
-        vec_end = bl_off + cap * 256;
+        bd_off = bl_off + cap * 256;
+        vec_end = bd_off + pb_align(cap * 2 * sizeof(BlindDesc));
         cnt_off = vec_end; desc_off = cnt_off + pb_align(cap * 64);   // (counters: 64 bytes = 16 words per proof, DtRoundGeom)
         jobs_off = desc_off + cap * sizeof(DtRoundDesc);
         acc_off = pb_align(jobs_off + 2 * cap * sizeof(DtJob));
@@ -221,6 +223,7 @@ template <class C> struct PfMember {
     A4 c1[3];                           // A_I1, A_O1, S1
     F4 bl2[3], tb[5];                   // i_b2, o_b2, s_b2; the blinding factors of T_1, T_3 .. T_6
     F4 y, z, ztab[32];
+    F4 kappa2 = F4{{0, 0, 0, 0}};       // BP_BLINDING_EXPANDED: phase 2's key
     std::vector<F4> wV;
     F4 w;
     bool csc_ok = true;
@@ -273,6 +276,8 @@ template <class C> static int pf_phase1(bp_ctx* ctx, std::vector<PfMember<C>>& m
     typedef host::Fld<FrP> S;
     typedef host::TP<C> TP;
     const size_t B = mem.size(), n1 = mem[0].n1;
+    const bool expanded = mem[0].pre->mode == BP_BLINDING_EXPANDED;   // (a front group holds members of ONE mode: cs_prove_batch)
+    const size_t nv = expanded ? 3 : 5;                              // vectors that come through the staging
     hipStream_t st = ctx->stream;
     pb_pool_ensure(ctx, B);
     std::vector<J4> pts(3 * B);
@@ -284,11 +289,12 @@ template <class C> static int pf_phase1(bp_ctx* ctx, std::vector<PfMember<C>>& m
             pts[3 * j] = pc.commit_jac(S::zero(), pre.i_b1); pts[3 * j + 1] = pc.commit_jac(S::zero(), pre.o_b1); pts[3 * j + 2] = pc.commit_jac(S::zero(), pre.s_b1);
         });
     } else {
-        const size_t vb = pb_align(n1 * 32), p1 = 5 * vb, bl_off = p1 * B;             // the arena, for this phase: [B x 5 vectors | blinding factors]
+        const size_t vb = pb_align(n1 * 32), p1 = 5 * vb, bl_off = p1 * B;             // the arena, for this phase: [B x 5 vectors | blinding factors | expansion jobs]
+        const size_t bd_off = bl_off + pb_align(B * 96), ar_end = bd_off + (expanded ? pb_align(B * sizeof(BlindDesc)) : 0);
         const size_t nblk = pf_nblk(2 * n1 + 1, 3 * B);
-        const size_t s_bl = B * 5 * n1 * 32, s_jobs = s_bl + pb_align(B * 96), s_res = s_jobs + pb_align(3 * B * sizeof(DtJob)), s_end = s_res + 3 * B * 96;
+        const size_t s_bl = B * nv * n1 * 32, s_bd = s_bl + pb_align(B * 96), s_jobs = s_bd + (expanded ? pb_align(B * sizeof(BlindDesc)) : 0), s_res = s_jobs + pb_align(3 * B * sizeof(DtJob)), s_end = s_res + 3 * B * 96;
         const size_t a_acc = pb_align(3 * B * sizeof(DtJob)), a_res = a_acc + pb_align(3 * B * nblk * 96), a_end = a_res + 3 * B * 96;
-        BPCHK(ctx->pb_arena.ensure(bl_off + pb_align(B * 96)));
+        BPCHK(ctx->pb_arena.ensure(ar_end));
         BPCHK(ctx->pf_aux.ensure(a_end));
         BPCHK(pf_stage_ensure(ctx, s_end));
         char* hs = (char*)ctx->h_pf;
@@ -298,9 +304,15 @@ template <class C> static int pf_phase1(bp_ctx* ctx, std::vector<PfMember<C>>& m
         pb_on_pool(ctx, B, [&](size_t j) {
             const host::ConstraintSystem<C>& cs = *mem[j].cs;
             const ProvePre<C>& pre = *mem[j].pre;
-            char* w = hs + j * 5 * n1 * 32;
+            char* w = hs + j * nv * n1 * 32;
             const F4* src[5] = {cs.a_L.data(), cs.a_R.data(), cs.a_O.data(), pre.s_L.data(), pre.s_R.data()};
-            for (int v = 0; v < 5; v++) memcpy(w + (size_t)v * n1 * 32, src[v], n1 * 32);
+            for (size_t v = 0; v < nv; v++) memcpy(w + v * n1 * 32, src[v], n1 * 32);
+            if (expanded) {
+                BlindDesc& bd = ((BlindDesc*)(hs + s_bd))[j];
+                memset(&bd, 0, sizeof bd);
+                S::to_bytes((host::u8*)bd.key, pre.kappa1);
+                bd.slot = (u32)j; bd.first = 0; bd.count = (u32)n1;
+            }
             const F4 bl[3] = {pre.i_b1, pre.o_b1, pre.s_b1};
             memcpy(hs + s_bl + j * 96, bl, 96);
             const u32* base = (const u32*)(ar + j * p1);
@@ -320,17 +332,22 @@ template <class C> static int pf_phase1(bp_ctx* ctx, std::vector<PfMember<C>>& m
         tm.upload += now_s() - t0; t0 = now_s();
         PfGeom geo; memset(&geo, 0, sizeof geo);
         geo.arena = ar; geo.per_proof = p1; geo.aL = 0; geo.aR = (u32)vb; geo.aO = (u32)(2 * vb); geo.sL = (u32)(3 * vb); geo.sR = (u32)(4 * vb);
-        hipLaunchKernelGGL(k_pf_import<FrP>, dim3((u32)((5 * n1 + 255) / 256), (u32)B), dim3(256), 0, st, (const u32*)hs, (const PfDesc*)nullptr, (u32)n1, geo);
+        hipLaunchKernelGGL(k_pf_import<FrP>, dim3((u32)((nv * n1 + 255) / 256), (u32)B), dim3(256), 0, st, (const u32*)hs, (const PfDesc*)nullptr, (u32)n1, (u32)nv, geo);
+        if (expanded) {   // s_L, s_R of every member from its key: one launch for the group
+            HIPCHK(hipMemcpyAsync(ar + bd_off, hs + s_bd, B * sizeof(BlindDesc), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_blind_expand_multi<FrP>, dim3((u32)((2 * n1 + 255) / 256), (u32)B), dim3(256), 0, st, (const BlindDesc*)(ar + bd_off), ar, (unsigned long long)p1, geo.sL, geo.sR);
+            ctx->bx_scalars += 2 * n1 * B; ctx->bx_launches++;
+        }
         HIPCHK(hipMemcpyAsync(ar + bl_off, hs + s_bl, B * 96, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ax, hs + s_jobs, 3 * B * sizeof(DtJob), hipMemcpyHostToDevice, st));
         BPCHK((pf_accum<C>(ctx, (const DtJob*)ax, 3 * B, nblk, (u32*)(ax + a_acc), (u32*)(ax + a_res))));
         HIPCHK(hipMemcpyAsync(hs + s_res, ax + a_res, 3 * B * 96, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemsetAsync(ar, 0, bl_off + pb_align(B * 96), st));   // secret hygiene: this phase's copy of the witness
+        HIPCHK(hipMemsetAsync(ar, 0, ar_end, st));   // secret hygiene: this phase's copy of the witness (and the keys)
         HIPCHK(ctx_stream_wait(ctx));
         HIPCHK(hipGetLastError());
         ctx->pf_waits++;
         pf_points_in(hs + s_res, 3 * B, pts.data());
-        memset(hs, 0, s_jobs);   // the staged witness and blinding factors
+        memset(hs, 0, s_jobs);   // the staged witness, blinding factors and keys
     }
     const size_t chunk = 64, nchunks = (B + chunk - 1) / chunk;
     std::vector<A4> aff(3 * B);
@@ -380,6 +397,8 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     BPCHK(pb_stage_ensure(ctx, L.stage_bytes));
     // the aux buffer (32-bit words) and the pinned staging
     std::vector<PfDesc> descs(B);
+    const bool expanded = part[0]->pre->mode == BP_BLINDING_EXPANDED;   // (all members alike: they come from one front group)
+    const size_t nv = expanded ? 3 : 5;
     size_t nmax = 0, nzmax = 0, B2 = 0, in_words = 0;
     const size_t a_jobs2 = pb_align(B * sizeof(PfDesc));
     for (size_t j = 0; j < B; j++) if (part[j]->n > part[j]->n1) B2++;
@@ -391,7 +410,7 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
         memset(&d, 0, sizeof d);
         const size_t nnz = m.csc->ment.size(), nc = m.csc->coefs.size();
         d.n = (u32)m.n; d.n1 = (u32)m.n1; d.nzhi = (u32)((m.csc->q + 1) >> 8) + 1;
-        d.in_off = in_words; in_words += 5 * m.n * 8;
+        d.in_off = in_words; in_words += nv * m.n * 8;
         d.moff = (u32)(at / 4); at += pb_align((m.n + 1) * 4);
         d.ment = (u32)(at / 4); at += pb_align(std::max<size_t>(nnz, 1) * 4);
         d.mc = (u32)(at / 4); at += pb_align(std::max<size_t>(nnz, 1) * 4);
@@ -409,10 +428,10 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     const size_t a_acc2 = pb_align(at), a_res2 = a_acc2 + pb_align(3 * B2 * nblk2 * 96), a_resT = a_res2 + pb_align(3 * B2 * 96), a_end = a_resT + 5 * B * 96;
     if (a_end >= ((size_t)1 << 34)) { g_err = "prove_batch: a front group's tables exceed 16 GB"; return BP_E_ARG; }
     BPCHK(ctx->pf_aux.ensure(a_end));
-    const size_t s_bl = in_words * 4, s_u1 = s_bl + B * 256, s_u2 = s_u1 + a_u2, s_xu = s_u2 + B * 96 * 32, s_res2 = s_xu + pb_align(B * sizeof(PfXu)),
+    const size_t s_bl = in_words * 4, s_bd = s_bl + B * 256, s_u1 = s_bd + (expanded ? pb_align(B * 2 * sizeof(BlindDesc)) : 0), s_u2 = s_u1 + a_u2, s_xu = s_u2 + B * 96 * 32, s_res2 = s_xu + pb_align(B * sizeof(PfXu)),
                  s_ts = s_res2 + pb_align(3 * B2 * 96), s_resT = s_ts + pb_align(B * 192), s_end = s_resT + 5 * B * 96;
     BPCHK(pf_stage_ensure(ctx, s_end));
-    secret_stage_bytes = s_u1;   // the witness and the blinding factors, in front of everything public
+    secret_stage_bytes = s_u1;   // the witness, the blinding factors and the keys, in front of everything public
     char* hs = (char*)ctx->h_pf;
     char* ar = (char*)ctx->pb_arena.p;
     char* ax = (char*)ctx->pf_aux.p;
@@ -437,9 +456,12 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
         for (auto& b : m.bl2) b = S::zero();
         const bool has2 = n > n1;
         if (has2) { m.bl2[0] = host::rand_fe<FrP>(rng); m.bl2[1] = host::rand_fe<FrP>(rng); m.bl2[2] = host::rand_fe<FrP>(rng); }
-        pre.s_L.resize(n); pre.s_R.resize(n);
-        for (size_t i = n1; i < n; i++) pre.s_L[i] = host::rand_fe<FrP>(rng);
-        for (size_t i = n1; i < n; i++) pre.s_R[i] = host::rand_fe<FrP>(rng);
+        if (expanded) { if (has2) m.kappa2 = host::rand_fe<FrP>(rng); }   // one draw where the 2 (n - n1) would begin
+        else {
+            pre.s_L.resize(n); pre.s_R.resize(n);
+            for (size_t i = n1; i < n; i++) pre.s_L[i] = host::rand_fe<FrP>(rng);
+            for (size_t i = n1; i < n; i++) pre.s_R[i] = host::rand_fe<FrP>(rng);
+        }
         for (auto& b : m.tb) b = host::rand_fe<FrP>(rng);   // T_1, T_3 .. T_6: the next draws whatever t(x) turns out to be (r1cs_prove)
     });
     tm.rng += now_s() - t0; t0 = now_s();
@@ -451,7 +473,13 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
         const bool has2 = n > n1;
         char* w = hs + descs[j].in_off * 4;
         const F4* src[5] = {m.cs->a_L.data(), m.cs->a_R.data(), m.cs->a_O.data(), pre.s_L.data(), pre.s_R.data()};
-        for (int v = 0; v < 5; v++) memcpy(w + (size_t)v * n * 32, src[v], n * 32);
+        for (size_t v = 0; v < nv; v++) memcpy(w + v * n * 32, src[v], n * 32);
+        if (expanded) {   // both phases' vectors again (phase 1's copy went with that phase's arena): two jobs, an empty phase has count 0
+            BlindDesc* bd = (BlindDesc*)(hs + s_bd) + 2 * j;
+            memset(bd, 0, 2 * sizeof(BlindDesc));
+            S::to_bytes((host::u8*)bd[0].key, pre.kappa1); bd[0].slot = (u32)j; bd[0].first = 0; bd[0].count = (u32)n1;
+            S::to_bytes((host::u8*)bd[1].key, m.kappa2); bd[1].slot = (u32)j; bd[1].first = (u32)n1; bd[1].count = (u32)(n - n1);
+        }
         F4 bl[8] = {m.bl2[0], m.bl2[1], m.bl2[2], m.tb[0], m.tb[1], m.tb[2], m.tb[3], m.tb[4]};
         memcpy(hs + s_bl + j * 256, bl, 256);
         const u32* blp = (const u32*)(ar + L.bl_off + j * 256);
@@ -488,7 +516,14 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     tm.upload += now_s() - t0; t0 = now_s();
     HIPCHK(hipMemcpyAsync(ax, hs + s_u1, a_u2, hipMemcpyHostToDevice, st));   // descriptors, jobs, constraint indices, coefficients: one copy
     HIPCHK(hipMemcpyAsync(ar + L.bl_off, hs + s_bl, B * 256, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_pf_import<FrP>, dim3((u32)((5 * nmax + 255) / 256), (u32)B), dim3(256), 0, st, (const u32*)hs, (const PfDesc*)ax, 0u, geo);
+    hipLaunchKernelGGL(k_pf_import<FrP>, dim3((u32)((nv * nmax + 255) / 256), (u32)B), dim3(256), 0, st, (const u32*)hs, (const PfDesc*)ax, 0u, (u32)nv, geo);
+    if (expanded) {
+        size_t total = 0;
+        for (size_t j = 0; j < B; j++) total += 2 * part[j]->n;
+        HIPCHK(hipMemcpyAsync(ar + L.bd_off, hs + s_bd, B * 2 * sizeof(BlindDesc), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_blind_expand_multi<FrP>, dim3((u32)((2 * nmax + 255) / 256), (u32)(2 * B)), dim3(256), 0, st, (const BlindDesc*)(ar + L.bd_off), ar, (unsigned long long)L.per_vec, geo.sL, geo.sR);
+        ctx->bx_scalars += total; ctx->bx_launches++;
+    }
     HIPCHK(hipGetLastError());
     std::vector<A4> aff2(3 * B2);
     if (B2) {
@@ -614,6 +649,7 @@ template <class C> static int pf_run_part(bp_ctx* ctx, std::vector<PfMember<C>*>
         if (std::find(leavers.begin(), leavers.end(), m) != leavers.end()) continue;   // (a leaver's vectors are r1cs_prove's to wipe)
         for (auto& x : m->pre->s_L) x = S::zero();
         for (auto& x : m->pre->s_R) x = S::zero();
+        m->pre->kappa1 = S::zero(); m->kappa2 = S::zero();
     }
     if (rc) {
         (void)hipStreamSynchronize(ctx->stream);   // (nothing reads the staging any more)
@@ -655,7 +691,11 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
     };
     std::vector<size_t> order(count);
     for (size_t k = 0; k < count; k++) order[k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return hs[a]->cs<C>()->a_L.size() < hs[b]->cs<C>()->a_L.size(); });
+    // (members of both blinding modes may arrive in one call; a front group holds one mode, so equal sizes are ordered by mode)
+    auto mode_of = [&](size_t k) { return C::ID == 0 ? hs[k]->pre0.mode : hs[k]->pre1.mode; };
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+        return std::make_pair(hs[a]->cs<C>()->a_L.size(), mode_of(a)) < std::make_pair(hs[b]->cs<C>()->a_L.size(), mode_of(b));
+    });
     // one instance through r1cs_prove (resume1: it left a front group after its randomized phase); `left`: instances still to come
     auto prove_single = [&](size_t k, size_t left, const A4* resume1) {
         bp_cs* s = hs[k];
@@ -725,9 +765,10 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
         if (!qualifies(order[oi])) { prove_single(order[oi], count - oi, nullptr); oi++; continue; }
         // a front group: the qualifying instances that follow with the same phase-1 multiplier count
         const size_t n1 = hs[order[oi]]->cs<C>()->a_L.size();
+        const int mode1 = mode_of(order[oi]);
         size_t cap1 = cap_knob ? cap_knob : std::min(PF_PHASE1_MAX, std::max<size_t>(1, PB_ARENA_BUDGET / (5 * pb_align(std::max<size_t>(n1, 1) * 32) + 256)));
         std::vector<PfMember<C>> mem;
-        while (oi < count && mem.size() < cap1 && hs[order[oi]]->cs<C>()->a_L.size() == n1 && qualifies(order[oi])) {
+        while (oi < count && mem.size() < cap1 && hs[order[oi]]->cs<C>()->a_L.size() == n1 && mode_of(order[oi]) == mode1 && qualifies(order[oi])) {
             PfMember<C> m;
             bp_cs* sk = hs[order[oi]];
             m.k = order[oi]; m.s = sk; m.cs = sk->cs<C>(); m.pre = C::ID == 0 ? (ProvePre<C>*)&sk->pre0 : (ProvePre<C>*)&sk->pre1; m.n1 = n1;

@@ -50,18 +50,73 @@ template <class C> static int upload_scalars_pinned(bp_ctx* ctx, u32* dst, const
 // the five witness vectors of a phase (a_L, a_R, a_O, s_L, s_R: cnt elements each) -> dst[0..4]: a small statement stages them in the
 // pinned slab and ONE kernel reads them from there (k_scalars_import5); a large one keeps the asynchronous copies
 static constexpr size_t UPLOAD_FUSED_MAX = 8192;
-template <class C> static int upload_witness5(bp_ctx* ctx, u32* const dst[5], const F4* const src[5], size_t cnt) {
+template <class C> static int upload_witness5(bp_ctx* ctx, u32* const dst[5], const F4* const src[5], size_t cnt, int nvec = 5 /* 3: a_L, a_R, a_O only (BP_BLINDING_EXPANDED) */) {
     if (!cnt) return BP_OK;
     if (cnt > UPLOAD_FUSED_MAX) {
-        for (int v = 0; v < 5; v++) BPCHK(upload_scalars_pinned<C>(ctx, dst[v], src[v], cnt, (size_t)v * cnt * 32));
+        for (int v = 0; v < nvec; v++) BPCHK(upload_scalars_pinned<C>(ctx, dst[v], src[v], cnt, (size_t)v * cnt * 32));
         return BP_OK;
     }
     char* stage = (char*)ctx->h_upload;
     ImportList il; memset(&il, 0, sizeof il);
-    il.nseg = 5;
-    for (int v = 0; v < 5; v++) { memcpy(stage + (size_t)v * cnt * 32, src[v], cnt * 32); il.dst[v] = dst[v]; il.cnt[v] = (u32)cnt; }
-    hipLaunchKernelGGL(k_scalars_import_multi<typename C::Fr>, dim3((u32)((5 * cnt + 255) / 256)), dim3(256), 0, ctx->stream, (const u32*)stage, il);
+    il.nseg = nvec;
+    for (int v = 0; v < nvec; v++) { memcpy(stage + (size_t)v * cnt * 32, src[v], cnt * 32); il.dst[v] = dst[v]; il.cnt[v] = (u32)cnt; }
+    hipLaunchKernelGGL(k_scalars_import_multi<typename C::Fr>, dim3((u32)(((size_t)nvec * cnt + 255) / 256)), dim3(256), 0, ctx->stream, (const u32*)stage, il);
     HIPCHK(hipGetLastError());
+    return BP_OK;
+}
+
+// ---- blinding vectors from a key (BP_BLINDING_EXPANDED; the construction: blind.cuh) ------------------------------------------------
+// W(key, t) on the host, as ark Montgomery words: the twin the device kernel is tested against (64-bit Montgomery arithmetic, nothing
+// shared with blind.cuh but the definition)
+template <class P> static F4 host_blind_scalar(const host::u8 key[32], u32 t) {
+    typedef host::Fld<P> S;
+    host::ChaChaRng prng(key);
+    prng.ctr = t;
+    prng.block();
+    F4 lo, hi;
+    memcpy(lo.v, prng.blk, 32); memcpy(hi.v, prng.blk + 8, 32);
+    const F4 r2 = {{P::R2_64[0], P::R2_64[1], P::R2_64[2], P::R2_64[3]}};
+    const F4 r = S::add(S::mul(lo, r2), S::mul(S::mul(hi, r2), r2));   // (lo + hi * 2^256) * 2^256 mod r; the products take any 256-bit operand
+    memset(prng.k, 0, sizeof prng.k); memset(prng.blk, 0, sizeof prng.blk);
+    return r;
+}
+template <class C> static void host_blind_expand(const F4& kappa, u64 j0, size_t count, F4* sL, F4* sR) {
+    typedef typename C::Fr FrP;
+    host::u8 key[32];
+    host::Fld<FrP>::to_bytes(key, kappa);
+    for (size_t i = 0; i < count; i++) {
+        sL[i] = host_blind_scalar<FrP>(key, (u32)(2 * (j0 + i)));
+        sR[i] = host_blind_scalar<FrP>(key, (u32)(2 * (j0 + i) + 1));
+    }
+    memset(key, 0, 32);
+}
+// s_L[0 .. count), s_R[0 .. count) at sL / sR (resident form) for the phase-local indices j0 .. j0 + count - 1: one launch, the key as
+// a kernel argument
+template <class C> static int blind_expand_launch(bp_ctx* ctx, const F4& kappa, u64 j0, size_t count, u32* sL, u32* sR) {
+    if (!count) return BP_OK;
+    if (j0 + count > ((u64)1 << 31)) { g_err = "blind_expand: indices reach 2^31"; return BP_E_ARG; }
+    BlindKey key;
+    host::Fld<typename C::Fr>::to_bytes((host::u8*)key.k, kappa);
+    hipLaunchKernelGGL(k_blind_expand<typename C::Fr>, dim3((u32)((2 * count + 255) / 256)), dim3(256), 0, ctx->stream, key, (u32)j0, (u32)count, sL, sR);
+    memset(&key, 0, sizeof key);
+    HIPCHK(hipGetLastError());
+    ctx->bx_scalars += 2 * count; ctx->bx_launches++;
+    return BP_OK;
+}
+// test hook (include/arkbp.h bp_debug_blind_expand): the production kernel on the ctx's stream, its output exported back to ark words
+template <class C> static int dbg_blind_expand(bp_ctx* c, const F4& k, uint64_t j0, size_t count, uint64_t* sL, uint64_t* sR) {
+    typedef typename C::Fr FrP;
+    BPCHK(c->io_scal.ensure(2 * count * 32)); BPCHK(c->io_out.ensure(2 * count * 32));
+    u32* res = c->io_scal.as<u32>();
+    u32* out = c->io_out.as<u32>();
+    BPCHK(blind_expand_launch<C>(c, k, j0, count, res, res + count * 8));
+    hipLaunchKernelGGL(k_scalars_export<FrP>, dim3((u32)((2 * count + 255) / 256)), dim3(256), 0, c->stream, (const u32*)res, out, (u32)(2 * count));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sL, out, count * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(sR, out + count * 8, count * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemsetAsync(res, 0, 2 * count * 32, c->stream));
+    HIPCHK(hipMemsetAsync(out, 0, 2 * count * 32, c->stream));
+    HIPCHK(ctx_stream_wait(c));
     return BP_OK;
 }
 
@@ -288,6 +343,8 @@ template <class C> struct ProvePre {
     F4 i_b1, o_b1, s_b1;
     std::vector<F4> s_L, s_R;
     double t_rng = 0;
+    int mode = BP_BLINDING_TRANSCRIPT;   // bp_prover_set_blinding
+    F4 kappa1 = F4{{0, 0, 0, 0}};        // BP_BLINDING_EXPANDED: phase 1's key, drawn where s_L[0] would be (n1 > 0); s_L, s_R stay empty
 };
 // rng_bytes: the 32 bytes `builder.finalize(prng)` draws from the caller's external rng (prover.rs:493; merlin's
 // TranscriptRngBuilder::finalize fills exactly one 32-byte array) — all the prover ever takes from it.
@@ -302,6 +359,11 @@ template <class C> static void prove_precompute(host::ConstraintSystem<C>& cs, c
     pre.rng->finalize_bytes(rng_bytes);
     const size_t n1 = cs.a_L.size();
     pre.i_b1 = host::rand_fe<FrP>(*pre.rng); pre.o_b1 = host::rand_fe<FrP>(*pre.rng); pre.s_b1 = host::rand_fe<FrP>(*pre.rng);
+    if (pre.mode == BP_BLINDING_EXPANDED) {   // one draw instead of 2 n1: the vectors come from it on the device
+        if (n1) pre.kappa1 = host::rand_fe<FrP>(*pre.rng);
+        pre.t_rng = now_s() - t0;
+        return;
+    }
     host::reserve_huge(pre.s_L, n1); host::reserve_huge(pre.s_R, n1);
     pre.s_L.resize(n1); pre.s_R.resize(n1);
     for (auto& x : pre.s_L) x = host::rand_fe<FrP>(*pre.rng);
@@ -317,7 +379,7 @@ template <class C> static void prove_precompute_batch(host::ConstraintSystem<C>*
     typedef host::Fld<FrP> S;
     bool ok = count == 8 && host::cpu_has_avx512();
     for (size_t j = 0; ok && j < count; j++)
-        ok = !pres[j]->rng && css[j]->a_L.size() == css[0]->a_L.size() && css[j]->v.size() == css[0]->v.size() && css[0]->a_L.size() >= 64;
+        ok = !pres[j]->rng && pres[j]->mode == BP_BLINDING_TRANSCRIPT /* (an expanded head is four draws: the scalar path) */ && css[j]->a_L.size() == css[0]->a_L.size() && css[j]->v.size() == css[0]->v.size() && css[0]->a_L.size() >= 64;
 #if !defined(__x86_64__)
     ok = false;
 #endif
@@ -408,6 +470,8 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     mark("begin");
     ProvePre<C> pre_local;
     ProvePre<C>& pre = pre_in && pre_in->rng ? *pre_in : pre_local;
+    if (pre_in) pre_local.mode = pre_in->mode;
+    const bool expanded = pre.mode == BP_BLINDING_EXPANDED;
     if (!pre.rng) prove_precompute<C>(cs, rng_bytes, pre);
     host::TranscriptRng& rng = *pre.rng;
     tm.rng += pre.t_rng;
@@ -436,7 +500,8 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     {
         u32* const dst[5] = {ctx->r_aL.as<u32>(), ctx->r_aR.as<u32>(), ctx->r_aO.as<u32>(), ctx->r_sL.as<u32>(), ctx->r_sR.as<u32>()};
         const F4* const src[5] = {cs.a_L.data(), cs.a_R.data(), cs.a_O.data(), s_L.data(), s_R.data()};
-        BPCHK(upload_witness5<C>(ctx, dst, src, n1));
+        BPCHK(upload_witness5<C>(ctx, dst, src, n1, expanded ? 3 : 5));
+        if (expanded) BPCHK(blind_expand_launch<C>(ctx, pre.kappa1, 0, n1, dst[3], dst[4]));
     }
     tm.upload += now_s() - t0;
     mark("head + upload");
@@ -477,9 +542,13 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     F4 i_b2 = S::zero(), o_b2 = S::zero(), s_b2 = S::zero();
     t0 = now_s();
     if (has2) { i_b2 = host::rand_fe<FrP>(rng); o_b2 = host::rand_fe<FrP>(rng); s_b2 = host::rand_fe<FrP>(rng); }
-    s_L.resize(n); s_R.resize(n);
-    for (size_t i = n1; i < n; i++) s_L[i] = host::rand_fe<FrP>(rng);
-    for (size_t i = n1; i < n; i++) s_R[i] = host::rand_fe<FrP>(rng);
+    F4 kappa2 = S::zero();
+    if (expanded) { if (has2) kappa2 = host::rand_fe<FrP>(rng); }
+    else {
+        s_L.resize(n); s_R.resize(n);
+        for (size_t i = n1; i < n; i++) s_L[i] = host::rand_fe<FrP>(rng);
+        for (size_t i = n1; i < n; i++) s_R[i] = host::rand_fe<FrP>(rng);
+    }
     tm.rng += now_s() - t0;
     A4 A_I2 = G::aff_inf(), A_O2 = G::aff_inf(), S2 = G::aff_inf();
     if (has2) {
@@ -489,8 +558,10 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
         BPCHK(upload_slab_ensure(ctx, 5 * std::max(n1, n2) * 32));
         {
             u32* const dst[5] = {ctx->r_aL.as<u32>() + n1 * 8, ctx->r_aR.as<u32>() + n1 * 8, ctx->r_aO.as<u32>() + n1 * 8, ctx->r_sL.as<u32>() + n1 * 8, ctx->r_sR.as<u32>() + n1 * 8};
-            const F4* const src[5] = {cs.a_L.data() + n1, cs.a_R.data() + n1, cs.a_O.data() + n1, s_L.data() + n1, s_R.data() + n1};
-            BPCHK(upload_witness5<C>(ctx, dst, src, n2));
+            const F4* const src[5] = {cs.a_L.data() + n1, cs.a_R.data() + n1, cs.a_O.data() + n1, expanded ? nullptr : s_L.data() + n1, expanded ? nullptr : s_R.data() + n1};
+            BPCHK(upload_witness5<C>(ctx, dst, src, n2, expanded ? 3 : 5));
+            if (expanded) BPCHK(blind_expand_launch<C>(ctx, kappa2, 0, n2, dst[3], dst[4]));
+            kappa2 = S::zero();
         }
         tm.upload += now_s() - t0;
         t0 = now_s();
@@ -776,6 +847,7 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     }
     for (auto& s : s_L) s = S::zero();
     for (auto& s : s_R) s = S::zero();
+    pre.kappa1 = S::zero();
     tm.total = now_s() - t_begin + (pre_in && pre_in->rng ? pre.t_rng : 0.0);
     if (ctx->profiling) collect_timers(ctx);
     if (trace) {

@@ -10,12 +10,13 @@
 // is done), the AUX buffer holds what is public (constraint indices, coefficient and power tables, the descriptors themselves).
 #pragma once
 #include "small_batch.cuh"
+#include "blind.cuh"
 
 namespace arkbp {
 
 // One proof's public operands: word offsets into the aux buffer, its sizes, and where its witness lies in the pinned staging.
 struct PfDesc {
-    unsigned long long in_off;   // words: [a_L | a_R | a_O | s_L | s_R], n scalars each (ark words)
+    unsigned long long in_off;   // words: [a_L | a_R | a_O | s_L | s_R], n scalars each (ark words; without the last two for k_pf_import's nvec = 3)
     u32 moff, ment, mc, coefs;   // merged CSC (k_r1cs_flatten) and the coefficient table (resident words)
     u32 ztab, Z, ypow;           // z^(2^j) (32), the split power table (256 + nzhi), y^(2^k) | y^-(2^k) (64): resident words
     u32 n, n1, nzhi, pad;
@@ -35,13 +36,14 @@ struct PfGeom {
 
 // a_L, a_R, a_O, s_L, s_R of every proof: ark words in pinned staging -> resident form in the proof's slices.  grid (ceil(5 max n / 256), B).
 // descs == nullptr: every proof has `cnt_all` scalars per vector, packed proof after proof (a group's phase 1).
+// nvec = 3: the staging holds a_L, a_R, a_O only and k_blind_expand_multi writes s_L, s_R (BP_BLINDING_EXPANDED); grid ceil(nvec max n / 256).
 template <class F> __global__ void __launch_bounds__(256)
-k_pf_import(const u32* __restrict__ in, const PfDesc* __restrict__ descs, u32 cnt_all, PfGeom geo) {
+k_pf_import(const u32* __restrict__ in, const PfDesc* __restrict__ descs, u32 cnt_all, u32 nvec, PfGeom geo) {
     u32 cnt = cnt_all;
-    size_t src = (size_t)blockIdx.y * 5u * cnt_all * 8u;
+    size_t src = (size_t)blockIdx.y * nvec * cnt_all * 8u;
     if (descs) { cnt = descs[blockIdx.y].n; src = (size_t)descs[blockIdx.y].in_off; }
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 5u * cnt) return;
+    if (t >= nvec * cnt) return;
     const u32 v = t / cnt, i = t - v * cnt;
     const u32 off = v == 0 ? geo.aL : v == 1 ? geo.aR : v == 2 ? geo.aO : v == 3 ? geo.sL : geo.sR;
     u32* out = (u32*)(geo.arena + (size_t)blockIdx.y * geo.per_proof + off) + (size_t)i * 8;

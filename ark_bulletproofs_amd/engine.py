@@ -532,6 +532,16 @@ class Statement:
         """host-only head of prove(): the TranscriptRng chain (needs no GPU)"""
         check(lib().bp_stmt_precompute(self.h), "bp_stmt_precompute")
 
+    def set_blinding(self, mode):
+        """BLINDING_TRANSCRIPT / BLINDING_EXPANDED for this statement's prove() (bp_prover_set_blinding through bp_stmt_as_prover)"""
+        check(lib().bp_prover_set_blinding(C.c_void_p(lib().bp_stmt_as_prover(self.h)), int(mode)), "bp_prover_set_blinding")
+
+    @property
+    def blinding(self):
+        m = C.c_int(-1)
+        check(lib().bp_prover_blinding(C.c_void_p(lib().bp_stmt_as_prover(self.h)), C.byref(m)), "bp_prover_blinding")
+        return m.value
+
     def prove(self, eng):
         buf = C.create_string_buffer(1 << 16)
         plen = C.c_size_t(len(buf))
@@ -780,6 +790,21 @@ class ProverCS(_ConstraintSystem):
         check(lib().bp_prover_commit(self.h, engine.ctx if engine is not None else None, ptr(v), ptr(b), C.c_size_t(len(v)), ptr(V), ptr(vars_)), "bp_prover_commit")
         return V, _vars_out(vars_)
 
+    def set_blinding(self, mode):
+        """how prove() obtains s_L, s_R: BLINDING_TRANSCRIPT (the reference's draws, the default) or BLINDING_EXPANDED (one drawn key
+        per phase, expanded on the GPU; include/arkbp.h).  Refused once the head of prove() has run."""
+        check(lib().bp_prover_set_blinding(self.h, int(mode)), "bp_prover_set_blinding")
+
+    @property
+    def blinding(self):
+        m = C.c_int(-1)
+        check(lib().bp_prover_blinding(self.h, C.byref(m)), "bp_prover_blinding")
+        return m.value
+
+    def precompute(self, rng_bytes=None):
+        """the host-only head of prove() (bp_prover_precompute)"""
+        check(lib().bp_prover_precompute(self.h, bytes(rng_bytes) if rng_bytes is not None else None), "bp_prover_precompute")
+
     def prove(self, engine, rng_bytes):
         """Prover::prove(prng, &bp_gens): rng_bytes = the 32 bytes the external prng yields; returns R1CSProof::to_bytes()"""
         buf = C.create_string_buffer(1 << 16)
@@ -923,6 +948,38 @@ def _debug_inner_product(self, a, b):
 
 
 Engine.debug_exp_iter = _debug_exp_iter
+
+
+# ---- blinding vectors from a key (include/arkbp.h BP_BLINDING_*) ------------------------------------------------------------
+BLINDING_TRANSCRIPT = 0
+BLINDING_EXPANDED = 1
+
+
+def host_blind_expand(curve, kappa, j0, count):
+    """(s_L, s_R), each (count, 4) ark words: the expansion of kappa (4 ark words) at the phase-local indices j0 .. j0 + count - 1, on the host"""
+    sL, sR = np.zeros((count, 4), dtype=np.uint64), np.zeros((count, 4), dtype=np.uint64)
+    k = np.ascontiguousarray(kappa, dtype=np.uint64).reshape(4)
+    check(lib().bp_host_blind_expand(curve, ptr(k), C.c_uint64(j0), C.c_size_t(count), ptr(sL), ptr(sR)), "bp_host_blind_expand")
+    return sL, sR
+
+
+def _debug_blind_expand(self, kappa, j0, count):
+    """the same through the production kernel (test hook)"""
+    sL, sR = np.zeros((count, 4), dtype=np.uint64), np.zeros((count, 4), dtype=np.uint64)
+    k = np.ascontiguousarray(kappa, dtype=np.uint64).reshape(4)
+    check(lib().bp_debug_blind_expand(self.ctx, ptr(k), C.c_uint64(j0), C.c_size_t(count), ptr(sL), ptr(sR)), "bp_debug_blind_expand")
+    return sL, sR
+
+
+def _blinding_stats(self):
+    """(scalars the expansion kernels wrote, their launches) since the engine was created"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    check(lib().bp_ctx_blinding_stats(self.ctx, C.byref(a), C.byref(b)), "bp_ctx_blinding_stats")
+    return a.value, b.value
+
+
+Engine.debug_blind_expand = _debug_blind_expand
+Engine.blinding_stats = _blinding_stats
 Engine.debug_inner_product = _debug_inner_product
 
 

@@ -547,6 +547,36 @@ int bp_prover_set_rng(bp_cs* prover, const uint8_t rng_bytes[32]);
 int bp_prover_precompute(bp_cs* prover, const uint8_t rng_bytes_or_null[32]);
 int bp_prover_precompute_batch(bp_cs** provers, size_t count);
 int bp_prover_prove(bp_ctx* ctx, bp_cs* prover, const uint8_t rng_bytes_or_null[32], uint8_t* proof_out, size_t* proof_len, double* timing);
+/* How prove() obtains the blinding vectors s_L, s_R (prover.rs:510-513, 599-602), per prover handle.
+ *   BP_BLINDING_TRANSCRIPT (the default): one `Fr::rand` per entry from the TranscriptRng, as the reference: the proof is the bytes the
+ *     reference prover emits for the same external rng bytes.
+ *   BP_BLINDING_EXPANDED: every draw from the TranscriptRng happens in the reference's order EXCEPT the 2c draws of a phase's s_L then
+ *     s_R (c > 0 multipliers; phase 1: c = n1, first index 0; phase 2: c = n2, first index n1), which are replaced by ONE draw
+ *     kappa = Fr::rand(rng); a phase with c = 0 draws no key.  With key = the 32 canonical little-endian bytes of kappa and the
+ *     phase-local index j < c: s_L[first + j] = W(key, 2j), s_R[first + j] = W(key, 2j + 1), where W(key, t) is the ChaCha20 block of
+ *     `key` at 64-bit block counter t, stream 0 (rand_chacha 0.3's layout), its 64 bytes read as one little-endian 512-bit integer and
+ *     reduced mod r (no rejection; zero stays zero).  The vectors are computed on the GPU where they are used: the host chain of 8
+ *     Keccak-f per multiplier and two of the five witness uploads of a phase disappear.  Such a proof is an ordinary R1CSProof that
+ *     `Verifier::verify` accepts; it is NOT the bytes the reference prover emits (i_blinding1, o_blinding1, s_blinding1 are the same
+ *     draws, so A_I1 and A_O1 — the first 66 bytes — are equal for equal rng bytes and S1 differs).  The bytes are the same on every
+ *     proving route (bp_prover_prove on either path, after bp_prover_precompute[_batch], on a sharded ctx, bp_stmt_prove,
+ *     bp_prover_prove_batch with or without front groups; a batch may hold provers of both modes).
+ * bp_prover_set_blinding: BP_E_ARG for a null or verifier handle, an unknown mode, or once the head of prove() has run on the handle
+ * (bp_prover_precompute*, a consumed prover).  A bp_stmt takes it through bp_stmt_as_prover.  bp_prover_blinding reads the mode back.
+ * bp_host_blind_expand (host only): s_L / s_R (count x 4 ark words each) of the phase-local indices j0 .. j0 + count - 1 under kappa
+ * (ark words of a reduced scalar; j0 + count <= 2^31) — the twin the device kernel is tested against.
+ * bp_debug_blind_expand (test hook): the same values through the production kernel, exported back to ark words (count <= 2^24).
+ * bp_ctx_blinding_stats: scalars the expansion kernels wrote / their launches, since ctx creation.  A single proof of n multipliers
+ * adds 2n and one launch per non-empty phase; a front group of bp_prover_prove_batch makes ONE launch per stage for all its members,
+ * and expands a member's phase-1 vectors once for that phase's commitments and again with the whole witness (as it stages them twice
+ * in the default mode). */
+#define BP_BLINDING_TRANSCRIPT 0
+#define BP_BLINDING_EXPANDED 1
+int bp_prover_set_blinding(bp_cs* prover, int mode);
+int bp_prover_blinding(bp_cs* prover, int* mode_out);
+int bp_host_blind_expand(int curve, const uint64_t kappa[4], uint64_t j0, size_t count, uint64_t* sL, uint64_t* sR);
+int bp_debug_blind_expand(bp_ctx* ctx, const uint64_t kappa[4], uint64_t j0, size_t count, uint64_t* sL, uint64_t* sR);
+int bp_ctx_blinding_stats(bp_ctx* ctx, uint64_t* expanded_scalars, uint64_t* launches);
 /* Batch proving: `count` statements in one call, equivalent to bp_prover_prove(ctx, provers[k], rng_k, ..) for k = 0 .. count-1 in
  * order — the same proof bytes, the same transcript states afterwards, the same status per instance.
  *   rng_bytes: count x 32 bytes, or NULL when every prover has its rng already (bp_prover_set_rng / bp_prover_precompute).
