@@ -364,6 +364,23 @@ struct bp_ctx {
     size_t h_T_cap = 0;
 };
 
+// The ctx's host pool: created by the first data-parallel loop over more than one index (`n`), the calling thread counts as one
+static void host_pool_ensure(bp_ctx* ctx, size_t n) {
+    if (ctx && n > 1 && !ctx->pool) ctx->pool.reset(new host::HostPool(std::max(1u, ctx->tune_host_threads ? (unsigned)ctx->tune_host_threads : host::host_pool_threads()) - 1));
+}
+// fn(lo), .., fn(hi - 1): on the pool when the ctx has one, inline otherwise (no ctx, no pool yet, a single index)
+static void pool_range(bp_ctx* ctx, size_t lo, size_t hi, const std::function<void(size_t)>& fn) {
+    if (hi <= lo) return;
+    if (!ctx || !ctx->pool || hi - lo == 1) { for (size_t k = lo; k < hi; k++) fn(k); return; }
+    ctx->pool->run(lo, hi, fn);
+}
+// off[k] = lens[0] + .. + lens[k - 1] for k <= count
+static std::vector<size_t> prefix_offsets(const size_t* lens, size_t count) {
+    std::vector<size_t> off(count + 1, 0);
+    for (size_t k = 0; k < count; k++) off[k + 1] = off[k] + lens[k];
+    return off;
+}
+
 static int get_event(bp_ctx* c, hipEvent_t* e) {
     if (!c->event_pool.empty()) { *e = c->event_pool.back(); c->event_pool.pop_back(); return BP_OK; }
     HIPCHK(hipEventCreate(e));
@@ -2765,22 +2782,19 @@ template <class C> static int cs_precompute_batch(bp_cs** hs, size_t count) {
 // appends on the pool) or never: k_vfe_points decodes them for a batch the device front end takes (VfyDevBatch::commit_wire).
 template <class C> static int verifier_commit(bp_cs* h, const uint64_t* V_xy, size_t count, bp_var* vars);
 static bool strobe_eq(const host::Strobe& a, const host::Strobe& b) { return !memcmp(a.st.b, b.st.b, 200) && a.pos == b.pos && a.pos_begin == b.pos_begin && a.cur == b.cur; }
-static void wire_pool_range(bp_ctx* ctx, size_t n, const std::function<void(size_t)>& fn) {
-    if (ctx && n > 1 && !ctx->pool) ctx->pool.reset(new host::HostPool(std::max(1u, ctx->tune_host_threads ? (unsigned)ctx->tune_host_threads : host::host_pool_threads()) - 1));
-    if (!ctx || !ctx->pool || n <= 1) { for (size_t i = 0; i < n; i++) fn(i); return; }
-    ctx->pool->run(0, n, fn);
-}
 // n encodings -> affine ark words; a rejected one gives zero words and ok = 0 (ark-serialize's rules, host_math.hpp deser_compressed).
 // With a device: framing on the pool, the roots in ONE k_points_decompress launch.  Without (null or host-only ctx): host roots.
 template <class C> static int wire_decode(bp_ctx* ctx, const uint8_t* c33, size_t n, A4* out, uint8_t* ok) {
     typedef host::Fld<typename C::Fq> Fq;
     if (!n) return BP_OK;
     if (!ctx || ctx->host_only) {
-        wire_pool_range(ctx, n, [&](size_t i) { A4 p; const bool good = host::Grp<C>::deser_compressed(p, c33 + 33 * i); out[i] = good ? p : A4{}; ok[i] = good ? 1 : 0; });
+        host_pool_ensure(ctx, n);
+        pool_range(ctx, 0, n, [&](size_t i) { A4 p; const bool good = host::Grp<C>::deser_compressed(p, c33 + 33 * i); out[i] = good ? p : A4{}; ok[i] = good ? 1 : 0; });
         return BP_OK;
     }
     std::vector<F4> xs(n); std::vector<u32> fl(n);
-    wire_pool_range(ctx, (n + 255) / 256, [&](size_t c) {
+    host_pool_ensure(ctx, (n + 255) / 256);
+    pool_range(ctx, 0, (n + 255) / 256, [&](size_t c) {
         for (size_t i = c * 256, hi = std::min(n, i + 256); i < hi; i++) {
             const uint8_t* d = c33 + 33 * i;
             fl[i] = d[32];
@@ -2806,19 +2820,62 @@ static int wire_check_states(const char* who, size_t count, bp_cs* const* vs) {
     }
     return BP_OK;
 }
+// what every entry point over an array of verifier handles asks of it (`who` opens the message): each handle live, a verifier and
+// on the ctx's curve; none given twice (two pool threads on one recorder would race, and verify(self) takes one instance): any count
+static int verifiers_check(const char* who, const bp_ctx* c, size_t count, bp_cs* const* verifiers) {
+    for (size_t k = 0; k < count; k++) {
+        const bp_cs* h = verifiers[k];
+        if (!h || h->consumed || h->proving || h->curve != c->curve) { g_err = std::string(who) + ": every instance needs a live verifier of the ctx's curve"; return BP_E_ARG; }
+    }
+    if (count > 1) {
+        std::vector<const bp_cs*> sorted(verifiers, verifiers + count);
+        std::sort(sorted.begin(), sorted.end(), std::less<const bp_cs*>());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { g_err = std::string(who) + ": a verifier is consumed by ONE instance"; return BP_E_ARG; }
+    }
+    return BP_OK;
+}
+// bp_r1cs_batch_verify_locate only: a like-instance holds every commitment the shared constraints name (else verify_prepare refuses it mid-pass)
+template <class C> static int verifiers_cover_constraints(const char* who, size_t count, bp_cs* const* verifiers) {
+    const host::FrozenRecording* seen = nullptr;
+    size_t need = 0;
+    for (size_t k = 0; k < count; k++) {
+        const host::ConstraintSystem<C>* cs = verifiers[k]->cs<C>();
+        const host::FrozenRecording* b = cs->base.get();
+        if (!b) continue;
+        if (b != seen) { seen = b; need = 0; for (const auto& vt : b->vterms) need = std::max(need, (size_t)vt.j + 1); }
+        if (cs->V.size() + verifiers[k]->wire_count() < need) { g_err = std::string(who) + ": the constraints refer to more commitments than a verifier holds (bp_verifier_commit)"; return BP_E_ARG; }
+    }
+    return BP_OK;
+}
+// verify(self) over an array of handles: consumed on entry, `running` (the randomized-phase callbacks may record) until the call leaves, however it leaves
+struct VerifyingScope {
+    bp_cs* const* vs;
+    size_t count;
+    VerifyingScope(bp_cs* const* vs_, size_t count_) : vs(vs_), count(count_) { for (size_t k = 0; k < count; k++) { vs[k]->consumed = true; vs[k]->running = true; } }
+    ~VerifyingScope() { for (size_t k = 0; k < count; k++) vs[k]->running = false; }
+    VerifyingScope(const VerifyingScope&) = delete;
+};
+// instances 0 .. n of a call over recorded handles: the array itself (idx null) or the members idx names (the passes of
+// bp_r1cs_batch_verify_locate).  Two pointers: closures hold it by value.
+struct CsView {
+    bp_cs* const* vs;
+    const uint32_t* idx;
+    bp_cs* operator()(size_t j) const { return vs[idx ? idx[j] : j]; }
+};
 // the pending commitments of instances at(0 .. count): decoded together, then Verifier::commit per instance on the pool.  st[k] =
 // BP_E_FORMAT for an instance with a rejected encoding: it keeps its pending bytes, handle and transcript untouched.
-template <class C> static int wire_materialize(bp_ctx* ctx, size_t count, const std::function<bp_cs*(size_t)>& at, int* st) {
+template <class C> static int wire_materialize(bp_ctx* ctx, size_t count, CsView at, int* st) {
     std::vector<size_t> off(count + 1, 0);
     for (size_t k = 0; k < count; k++) { st[k] = BP_OK; off[k + 1] = off[k] + at(k)->wire_count(); }
     const size_t tot = off[count];
     if (!tot) return BP_OK;
     std::vector<uint8_t> all(tot * 33), ok(tot);
     std::vector<A4> pts(tot);
-    wire_pool_range(ctx, count, [&](size_t k) { const bp_cs* h = at(k); if (!h->wire.empty()) memcpy(all.data() + off[k] * 33, h->wire.data(), h->wire.size()); });
+    host_pool_ensure(ctx, count);
+    pool_range(ctx, 0, count, [&](size_t k) { const bp_cs* h = at(k); if (!h->wire.empty()) memcpy(all.data() + off[k] * 33, h->wire.data(), h->wire.size()); });
     BPCHK(wire_decode<C>(ctx, all.data(), tot, pts.data(), ok.data()));
     if (ctx) (ctx->host_only ? ctx->cw_host : ctx->cw_prologue_gpu) += tot;
-    wire_pool_range(ctx, count, [&](size_t k) {
+    pool_range(ctx, 0, count, [&](size_t k) {
         bp_cs* h = at(k);
         const size_t mk = off[k + 1] - off[k];
         if (!mk) return;
@@ -2829,7 +2886,7 @@ template <class C> static int wire_materialize(bp_ctx* ctx, size_t count, const 
     return BP_OK;
 }
 // the device front end's view of a batch of like-instances: all commitments pending (same count), or none
-template <class C> static bool wire_dev_form(size_t n, const std::function<bp_cs*(size_t)>& at, bool& wire, size_t& m) {
+template <class C> static bool wire_dev_form(size_t n, CsView at, bool& wire, size_t& m) {
     bp_cs* h0 = at(0);
     wire =!h0->wire.empty();
     m = wire ? h0->wire_count() : h0->cs<C>()->V.size();
@@ -2850,8 +2907,7 @@ template <class C> static int points_compress_t(const uint64_t* xy, size_t n, ui
 }
 template <class C>
 static int verifier_commit_wire_batch(bp_ctx* c, size_t count, bp_cs* const* vs, const size_t* m_each, const uint8_t* c33, int defer, bp_var* vars_out, int* status) {
-    std::vector<size_t> off(count + 1, 0);
-    for (size_t k = 0; k < count; k++) off[k + 1] = off[k] + m_each[k];
+    const std::vector<size_t> off = prefix_offsets(m_each, count);
     for (size_t k = 0; k < count; k++) {   // the variables are known before anything is decoded: Committed(i) in commit order
         if (status) status[k] = BP_OK;
         const size_t first = vs[k]->cs<C>()->V.size() + vs[k]->wire_count();
@@ -2873,7 +2929,8 @@ static int verifier_commit_wire_batch(bp_ctx* c, size_t count, bp_cs* const* vs,
     BPCHK(wire_decode<C>(c, c33, tot, pts.data(), ok.data()));
     (c->host_only ? c->cw_host : c->cw_prologue_gpu) += tot;
     std::vector<int> st(count, BP_OK);
-    wire_pool_range(c, count, [&](size_t k) {
+    host_pool_ensure(c, count);
+    pool_range(c, 0, count, [&](size_t k) {
         for (size_t j = off[k]; j < off[k + 1]; j++) if (!ok[j]) { st[k] = BP_E_FORMAT; return; }
         if (m_each[k]) st[k] = verifier_commit<C>(vs[k], (const uint64_t*)(pts.data() + off[k]), m_each[k], nullptr);
     });
@@ -2883,45 +2940,53 @@ static int verifier_commit_wire_batch(bp_ctx* c, size_t count, bp_cs* const* vs,
     return first;
 }
 
-// batch_verify over recorded verifier handles (each consumed, like `verify(self)`)
-template <class C>
-static int cs_batch_verify(bp_ctx* c, size_t count, bp_cs* const* vs, const uint8_t* proofs, const size_t* proof_lens, const uint64_t* alphas, double* timing,
-                           uint64_t* point_out) {
-    typedef host::Fld<typename C::Fr> S;
-    std::vector<size_t> poff(count + 1, 0);
-    for (size_t k = 0; k < count; k++) poff[k + 1] = poff[k] + proof_lens[k];
-    std::vector<F4> al(count);
-    for (size_t k = 0; k < count; k++) { if (alphas) memcpy(al[k].v, alphas + 4 * k, 32); else al[k] = S::one(); }
-    VfyProvider<C> prov;
-    prov.m_of = [&](size_t k) { return vs[k]->cs<C>()->V.size(); };
-    prov.get = [&](size_t k, VfyInstance<C>& out) -> int { out.cs = vs[k]->cs<C>(); return BP_OK; };
+// The provider (r1cs_host.inc VfyProvider) over instances at(0 .. n) of recorded verifier handles, for every entry point that takes
+// such handles.  The closures hold the view by value: they outlive the scope a subset was formed in (bp_r1cs_batch_verify_locate).
+template <class C> static void cs_provider(bp_ctx* c, size_t n, CsView at, VfyProvider<C>& prov) {
+    typedef host::ConstraintSystem<C> CS;
+    prov.m_of = [at](size_t k) { return at(k)->cs<C>()->V.size(); };
+    prov.get = [at](size_t k, VfyInstance<C>& out) -> int { out.cs = at(k)->cs<C>(); return BP_OK; };
     // like-instances of one recording (bp_verifier_new_like): the device front end continues their transcripts from where
     // Verifier::commit left them.  Randomized constraints (BP_TUNE_VFY_DEVICE = 2): every instance's callbacks run on its own handle
     // (a C callback records through the handle it receives), with the challenges its transcript produced on the device
     const bool two_ok = c->tune_vfy_device >= 2;
-    prov.dev_batch = [&](VfyDevBatch<C>& db) -> bool {
-        const host::ConstraintSystem<C>* c0 = vs[0]->cs<C>();
+    prov.dev_batch = [at, n, two_ok](VfyDevBatch<C>& db) -> bool {
+        const CS* c0 = at(0)->cs<C>();
         if (!c0->base || !c0->tr || (!c0->deferred.empty() && !two_ok)) return false;
-        for (size_t k = 0; k < count; k++) {
-            const host::ConstraintSystem<C>* ck = vs[k]->cs<C>();
+        for (size_t k = 0; k < n; k++) {
+            const CS* ck = at(k)->cs<C>();
             if (ck->base != c0->base || ck->cs_off.size() != 1 || ck->deferred.size() != c0->deferred.size() || ck->phase2 || ck->num_vars != c0->num_vars || ck->V.size() != c0->V.size() ||
                 !ck->tr)
                 return false;
         }
         bool wire; size_t m;
-        if (!wire_dev_form<C>(count, [&](size_t k) { return vs[k]; }, wire, m)) return false;
+        if (!wire_dev_form<C>(n, at, wire, m)) return false;
         db.src = c0; db.m = m; db.absorb_commitments = wire; db.shared_state = false;
-        db.state_of = [&](size_t k) { return (const host::Strobe*)&vs[k]->cs<C>()->tr->s; };   // (pending commitments: the pre-commit state, checked on entry)
-        if (wire) db.commit_wire = [&](size_t k) { return (const uint8_t*)vs[k]->wire.data(); };
-        else db.commit_xy = [&](size_t k) { return (const uint64_t*)vs[k]->cs<C>()->V.data(); };
-        if (!c0->deferred.empty()) db.cs_of = [&](size_t k) { return vs[k]->cs<C>(); };
+        db.state_of = [at](size_t k) { return (const host::Strobe*)&at(k)->cs<C>()->tr->s; };   // (pending commitments: the pre-commit state, checked on entry)
+        if (wire) db.commit_wire = [at](size_t k) { return (const uint8_t*)at(k)->wire.data(); };   // (the bytes stay pending: a later pass reuses them)
+        else db.commit_xy = [at](size_t k) { return (const uint64_t*)at(k)->cs<C>()->V.data(); };
+        if (!c0->deferred.empty()) db.cs_of = [at](size_t k) { return at(k)->cs<C>(); };
         return true;
     };
-    prov.prologue = [&](int* st) -> int { return wire_materialize<C>(c, count, [&](size_t k) { return vs[k]; }, st); };
-    for (size_t k = 0; k < count; k++) { vs[k]->consumed = true; vs[k]->running = true; }
-    const int rc = batch_verify_core<C>(c, count, prov, proofs, poff.data(), al.data(), timing, point_out);
-    for (size_t k = 0; k < count; k++) vs[k]->running = false;
-    return rc;
+    prov.prologue = [c, n, at](int* st) -> int { return wire_materialize<C>(c, n, at, st); };
+}
+// the weights of a call over recorded handles: the caller's words, or 1 for Verifier::verify's single instance
+template <class C> static std::vector<F4> cs_weights(const uint64_t* alphas, size_t count) {
+    std::vector<F4> al(count);
+    for (size_t k = 0; k < count; k++) { if (alphas) memcpy(al[k].v, alphas + 4 * k, 32); else al[k] = host::Fld<typename C::Fr>::one(); }
+    return al;
+}
+
+// batch_verify over recorded verifier handles (each consumed, like `verify(self)`)
+template <class C>
+static int cs_batch_verify(bp_ctx* c, size_t count, bp_cs* const* vs, const uint8_t* proofs, const size_t* proof_lens, const uint64_t* alphas, double* timing,
+                           uint64_t* point_out) {
+    const std::vector<size_t> poff = prefix_offsets(proof_lens, count);
+    const std::vector<F4> al = cs_weights<C>(alphas, count);
+    VfyProvider<C> prov;
+    cs_provider<C>(c, count, CsView{vs, nullptr}, prov);
+    VerifyingScope scope(vs, count);
+    return batch_verify_core<C>(c, count, prov, proofs, poff.data(), al.data(), timing, point_out);
 }
 
 // ---- debug hooks for the reference-held constants (src/util.rs:147-166, src/inner_product_proof.rs:556-562) ----
@@ -3259,7 +3324,7 @@ static int locate_core(bp_ctx* ctx, size_t count, const LocateSubFn<C>& sub, con
         if (!out.before.empty()) { out.kind = LocateOutcome::FAILED_BEFORE; return BP_OK; }
         if (rc == BP_OK) { out.kind = LocateOutcome::PASSED; return BP_OK; }
         if (rc == BP_E_VERIFICATION) { out.kind = LocateOutcome::FAILED_CHECK; return BP_OK; }
-        return rc;   // (a HIP error, a structure digest collision: the call cannot go on)
+        return rc;   // (a HIP error, two structures under one digest: the call cannot go on)
     };
     // a failing range of at most BP_TUNE_VERIFY_LOCATE_LEAF members: the machinery of bp_verifier_verify_batch, a verdict for each
     const LocatePlanner::ExactFn exact = [&](size_t lo, size_t n, int* st) -> int {
@@ -3289,12 +3354,9 @@ static int locate_core(bp_ctx* ctx, size_t count, const LocateSubFn<C>& sub, con
 template <class C>
 static int cs_batch_verify_locate(bp_ctx* c, size_t count, bp_cs* const* vs, const uint8_t* proofs, const size_t* proof_lens, const uint64_t* alphas, int* status,
                                   double* timing) {
-    typedef host::Fld<typename C::Fr> S;
     typedef host::ConstraintSystem<C> CS;
-    std::vector<size_t> poff(count + 1, 0);
-    for (size_t k = 0; k < count; k++) poff[k + 1] = poff[k] + proof_lens[k];
-    std::vector<F4> al(count);
-    for (size_t k = 0; k < count; k++) { if (alphas) memcpy(al[k].v, alphas + 4 * k, 32); else al[k] = S::one(); }
+    const std::vector<size_t> poff = prefix_offsets(proof_lens, count);
+    const std::vector<F4> al = cs_weights<C>(alphas, count);
     // entry states: the transcript (the host replay advances it) and what the randomized phase changes in the recorder
     const double t_snap = now_s();
     std::vector<host::Strobe> tr0(count);
@@ -3304,42 +3366,20 @@ static int cs_batch_verify_locate(bp_ctx* c, size_t count, bp_cs* const* vs, con
     const std::function<void(const uint32_t*, size_t)> restore = [&](const uint32_t* idx, size_t n) {
         for (size_t j = 0; j < n; j++) { CS* ck = vs[idx[j]]->cs<C>(); if (ck->tr) ck->tr->s = tr0[idx[j]]; ck->restore(cs0[idx[j]]); }
     };
-    const bool two_ok = c->tune_vfy_device >= 2;
     const LocateSubFn<C> sub = [&](const uint32_t* idx, size_t n, VfyProvider<C>& prov) {
-        prov.m_of = [vs, idx](size_t j) { return vs[idx[j]]->cs<C>()->V.size(); };
-        prov.get = [vs, idx](size_t j, VfyInstance<C>& out) -> int { out.cs = vs[idx[j]]->cs<C>(); return BP_OK; };
-        // like-instances of one recording: as in cs_batch_verify, over the subset
-        prov.dev_batch = [vs, idx, n, two_ok](VfyDevBatch<C>& db) -> bool {
-            const CS* c0 = vs[idx[0]]->cs<C>();
-            if (!c0->base || !c0->tr || (!c0->deferred.empty() && !two_ok)) return false;
-            for (size_t j = 0; j < n; j++) {
-                const CS* ck = vs[idx[j]]->cs<C>();
-                if (ck->base != c0->base || ck->cs_off.size() != 1 || ck->deferred.size() != c0->deferred.size() || ck->phase2 || ck->num_vars != c0->num_vars || ck->V.size() != c0->V.size() ||
-                    !ck->tr)
-                    return false;
-            }
-            bool wire; size_t m;
-            if (!wire_dev_form<C>(n, [vs, idx](size_t j) { return vs[idx[j]]; }, wire, m)) return false;
-            db.src = c0; db.m = m; db.absorb_commitments = wire; db.shared_state = false;
-            db.state_of = [vs, idx](size_t j) { return (const host::Strobe*)&vs[idx[j]]->cs<C>()->tr->s; };
-            if (wire) db.commit_wire = [vs, idx](size_t j) { return (const uint8_t*)vs[idx[j]]->wire.data(); };   // (the bytes stay pending: every pass reuses them)
-            else db.commit_xy = [vs, idx](size_t j) { return (const uint64_t*)vs[idx[j]]->cs<C>()->V.data(); };
-            if (!c0->deferred.empty()) db.cs_of = [vs, idx](size_t j) { return vs[idx[j]]->cs<C>(); };
-            return true;
-        };
+        const CsView at{vs, idx};
+        cs_provider<C>(c, n, at, prov);
         // a pass the device front end declines commits the members' pending commitments: from then on THAT is their entry state
-        prov.prologue = [c, vs, idx, n, &tr0](int* st) -> int {
+        prov.prologue = [materialize = prov.prologue, at, n, &tr0](int* st) -> int {
             std::vector<char> had(n);
-            for (size_t j = 0; j < n; j++) had[j] = !vs[idx[j]]->wire.empty();
-            BPCHK(wire_materialize<C>(c, n, [vs, idx](size_t j) { return vs[idx[j]]; }, st));
-            for (size_t j = 0; j < n; j++) if (had[j] && !st[j]) tr0[idx[j]] = vs[idx[j]]->tr->s;
+            for (size_t j = 0; j < n; j++) had[j] = !at(j)->wire.empty();
+            BPCHK(materialize(st));
+            for (size_t j = 0; j < n; j++) if (had[j] && !st[j]) tr0[at.idx[j]] = at(j)->tr->s;
             return BP_OK;
         };
     };
-    for (size_t k = 0; k < count; k++) { vs[k]->consumed = true; vs[k]->running = true; }
-    const int rc = locate_core<C>(c, count, sub, restore, proofs, poff.data(), al.data(), status, timing, snap_s);
-    for (size_t k = 0; k < count; k++) vs[k]->running = false;
-    return rc;
+    VerifyingScope scope(vs, count);
+    return locate_core<C>(c, count, sub, restore, proofs, poff.data(), al.data(), status, timing, snap_s);
 }
 // scenario statements: batch_verify_scenarios' sources, recorders and weights; a subset's provider goes through the index map
 template <class C>
@@ -3349,18 +3389,8 @@ static int scenarios_batch_verify_locate(bp_ctx* c, size_t count, const int* sce
     const VfyCoreFn<C> core = [&](const VfyProvider<C>& full, const size_t* poff, const F4* alphas) -> int {
         for (size_t k = 0; k < count; k++) if (alphas[k].is_zero()) { g_err = "batch_verify_locate: a weight is zero"; return BP_E_ARG; }
         const LocateSubFn<C> sub = [&](const uint32_t* idx, size_t n, VfyProvider<C>& prov) {
-            if (n == count) { prov = full; return; }   // (the lockstep heads need consecutive instances: the whole batch only)
-            prov.m_of = [&full, idx](size_t j) { return full.m_of(idx[j]); };
-            prov.get = [&full, idx](size_t j, VfyInstance<C>& out) -> int { return full.get(idx[j], out); };
-            if (full.dev_batch) prov.dev_batch = [&full, idx](VfyDevBatch<C>& db) -> bool {
-                VfyDevBatch<C> all;
-                if (!full.dev_batch(all)) return false;   // one statement shape for the whole batch, so for every subset of it
-                db = all;
-                db.state_of = [s = all.state_of, idx](size_t j) { return s(idx[j]); };
-                db.commit_xy = [x = all.commit_xy, idx](size_t j) { return x(idx[j]); };
-                if (all.cs_of) db.cs_of = [f = all.cs_of, idx](size_t j) { return f(idx[j]); };
-                return true;
-            };
+            if (n == count) prov = full;   // (the lockstep heads need consecutive instances: the whole batch only)
+            else provider_subset<C>(full, idx, prov);
         };
         const std::function<void(const uint32_t*, size_t)> restore = [](const uint32_t*, size_t) {};
         return locate_core<C>(c, count, sub, restore, proofs, poff, alphas, status, timing, 0.0);
@@ -3377,25 +3407,8 @@ int bp_r1cs_batch_verify_locate(bp_ctx* c, size_t count, bp_cs* const* verifiers
     if (alphas) for (size_t k = 0; k < count; k++) {   // (zero is zero in Montgomery form too)
         if (!(alphas[4 * k] | alphas[4 * k + 1] | alphas[4 * k + 2] | alphas[4 * k + 3])) { g_err = "batch_verify_locate: a zero weight hides its instance from every sum"; return BP_E_ARG; }
     }
-    for (size_t k = 0; k < count; k++) {
-        if (!verifiers[k] || verifiers[k]->consumed || verifiers[k]->proving || verifiers[k]->curve != c->curve) { g_err = "batch_verify_locate: every instance needs a live verifier of the ctx's curve"; return BP_E_ARG; }
-    }
-    if (count > 1) {
-        std::vector<const bp_cs*> sorted(verifiers, verifiers + count);
-        std::sort(sorted.begin(), sorted.end(), std::less<const bp_cs*>());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { g_err = "batch_verify_locate: a verifier is consumed by ONE instance"; return BP_E_ARG; }
-    }
-    {   // a like-instance must hold every commitment the shared constraints name (verify_prepare would refuse it mid-pass)
-        const host::FrozenRecording* seen = nullptr;
-        size_t need = 0;
-        for (size_t k = 0; k < count; k++) {
-            const host::FrozenRecording* b = c->curve == 0 ? verifiers[k]->cs0->base.get() : verifiers[k]->cs1->base.get();
-            if (!b) continue;
-            if (b != seen) { seen = b; need = 0; for (const auto& vt : b->vterms) need = std::max(need, (size_t)vt.j + 1); }
-            const size_t have = (c->curve == 0 ? verifiers[k]->cs0->V.size() : verifiers[k]->cs1->V.size()) + verifiers[k]->wire_count();
-            if (have < need) { g_err = "batch_verify_locate: the constraints refer to more commitments than a verifier holds (bp_verifier_commit)"; return BP_E_ARG; }
-        }
-    }
+    BPCHK(verifiers_check("batch_verify_locate", c, count, verifiers));
+    BPCHK(CS_DISPATCH(c, verifiers_cover_constraints<Secq>("batch_verify_locate", count, verifiers), verifiers_cover_constraints<Zorro>("batch_verify_locate", count, verifiers)));
     if (!c->gens_cap) { g_err = "batch_verify_locate: generators not installed"; return BP_E_GENS_LENGTH; }
     if (c->host_only) { g_err = "batch_verify_locate: a host-only ctx has no device to verify on"; return BP_E_NO_DEVICE; }
     BPCHK(wire_check_states("batch_verify_locate", count, verifiers));
@@ -4223,7 +4236,7 @@ int bp_verifier_materialize(bp_ctx* c, bp_cs* h) {
     BPCHK(wire_check_states("bp_verifier_materialize", 1, &h));
     if (c && !c->host_only) HIPCHK(hipSetDevice(c->device));
     int st = BP_OK;
-    const std::function<bp_cs*(size_t)> at = [h](size_t) { return h; };
+    const CsView at{&h, nullptr};
     BPCHK(CS_DISPATCH(h, wire_materialize<Secq>(c, 1, at, &st), wire_materialize<Zorro>(c, 1, at, &st)));
     if (st == BP_E_FORMAT) g_err = "bp_verifier_materialize: a commitment's encoding was rejected";
     return st;
@@ -4355,14 +4368,7 @@ int bp_r1cs_batch_verify(bp_ctx* c, size_t count, bp_cs* const* verifiers, const
     // The reference weights every instance with a fresh random scalar (verifier.rs:649): with equal weights the errors of two
     // invalid proofs can cancel in the single mega-check.  Only Verifier::verify (one instance) may leave the weight at 1.
     if (count > 1 && !alphas) { g_err = "batch_verify: per-instance weights (alphas) are required for more than one instance"; return BP_E_ARG; }
-    for (size_t k = 0; k < count; k++) {
-        if (!verifiers[k] || verifiers[k]->consumed || verifiers[k]->proving || verifiers[k]->curve != c->curve) { g_err = "batch_verify: every instance needs a live verifier of the ctx's curve"; return BP_E_ARG; }
-    }
-    if (count > 1) {   // a verifier is consumed by ONE instance (two pool threads on one recorder would race): any count
-        std::vector<const bp_cs*> sorted(verifiers, verifiers + count);
-        std::sort(sorted.begin(), sorted.end(), std::less<const bp_cs*>());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { g_err = "batch_verify: a verifier is consumed by ONE instance"; return BP_E_ARG; }
-    }
+    BPCHK(verifiers_check("batch_verify", c, count, verifiers));
     BPCHK(wire_check_states("batch_verify", count, verifiers));
     g_dry = c->host_only;
     HIPCHK(hipSetDevice(c->device));

@@ -100,7 +100,7 @@ template <class S> static void pb_inv_many(const F4* in, size_t count, F4* out) 
 }
 
 static void pb_pool_ensure(bp_ctx* ctx, size_t B) {
-    if (!ctx->pool && B > 1) ctx->pool.reset(new host::HostPool(std::max(1u, ctx->tune_host_threads ? (unsigned)ctx->tune_host_threads : host::host_pool_threads()) - 1));
+    host_pool_ensure(ctx, B);
 }
 static void pb_on_pool(bp_ctx* ctx, size_t count, const std::function<void(size_t)>& fn) {
     if (!ctx->pool || count <= 1) { for (size_t c = 0; c < count; c++) fn(c); return; }

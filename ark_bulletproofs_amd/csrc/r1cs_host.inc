@@ -1083,6 +1083,40 @@ template <class C> static int build_template(bp_ctx* ctx, const host::Constraint
     return BP_OK;
 }
 
+// ---- the ctx's template cache (bp_ctx::templates: structure digest -> VTemplate<C>) ------------------------------------------------
+// circuit templates kept per ctx.  A soft bound: a caller that finds the cache full trims it to what it is about to use (vfy_templates_trim)
+static constexpr size_t VFY_TEMPLATE_CACHE = 64;
+static std::string vfy_template_key(const host::Digest& dg) { return std::string((const char*)&dg, sizeof dg); }
+// The eviction: every entry whose key is not in `used` leaves.  Launches enqueued earlier may still read an evicted template's device
+// arrays, hence the wait; a front-end class names its template by digest and a rebuilt one may hold other constants, so they go too.
+static int vfy_templates_trim(bp_ctx* ctx, const std::set<std::string>& used) {
+    HIPCHK(ctx_stream_wait(ctx));
+    for (auto it = ctx->templates.begin(); it != ctx->templates.end();) { if (used.count(it->first)) ++it; else it = ctx->templates.erase(it); }
+    ctx->vfe_classes.clear();
+    return BP_OK;
+}
+// The template of structure `dg`: cached, or built from `rec` (upload + sync, once per gadget; null: the caller's recording is gone).
+// A template found under the digest must match the caller's (n, n1, q, ncoef).  `keep` shares ownership past an eviction.
+template <class C>
+static int vfy_template_get(bp_ctx* ctx, const host::Digest& dg, const host::ConstraintSystem<C>* rec, size_t n, size_t n1, size_t q, size_t ncoef, const char* who,
+                            std::shared_ptr<void>& keep, const VTemplate<C>*& tmpl) {
+    const std::string key = vfy_template_key(dg);
+    auto it = ctx->templates.find(key);
+    if (it == ctx->templates.end()) {
+        if (!rec) { g_err = std::string(who) + ": recording released before its template was built"; return BP_E_ARG; }
+        VTemplate<C>* t = new VTemplate<C>();
+        std::shared_ptr<void> holder(t, [](void* p) { delete (VTemplate<C>*)p; });
+        BPCHK(build_template<C>(ctx, *rec, *t));
+        it = ctx->templates.emplace(key, holder).first;
+    }
+    keep = it->second;
+    tmpl = (const VTemplate<C>*)keep.get();
+    if (tmpl->n != n || tmpl->n1 != n1 || tmpl->q != q || tmpl->ncoef != ncoef) { g_err = std::string(who) + ": structure digest collision"; return BP_E_ARG; }
+    return BP_OK;
+}
+// an instance ships a coefficient table of its own when its values are not the ones the template's creator had
+template <class C> static bool vfy_own_table(const VTemplate<C>& t, const VerifyPrep<C>& vp) { return t.ncoef && memcmp(t.coefs_host.data(), vp.coef_ptr, t.ncoef * 32) != 0; }
+
 // Everything of verification_scalars (verifier.rs:394-541) that is not of length N.  cs: the recorded verifier (phase 1 done, its
 // transcript positioned after the recording); the randomized phase runs in here (:441), so cs is consumed like `verify(self)`.
 // The Fiat-Shamir side of the replay behind a small interface: LiveTr drives the instance's own merlin transcript; PrecompTr hands out
@@ -1449,6 +1483,22 @@ template <class C> struct VfyProvider {
     // instance, BP_E_FORMAT for an instance with a rejected encoding (it received none); the return value is an error of the call.
     std::function<int(int*)> prologue;
 };
+// The provider whose instance j is instance idx[j] of `full`, which must outlive it (as must idx).  Without head8 — the lockstep heads
+// need consecutive instances — and without the prologue: the pending commitments are the whole call's business.
+template <class C> static void provider_subset(const VfyProvider<C>& full, const uint32_t* idx, VfyProvider<C>& prov) {
+    prov.m_of = [&full, idx](size_t j) { return full.m_of(idx[j]); };
+    prov.get = [&full, idx](size_t j, VfyInstance<C>& out) -> int { return full.get(idx[j], out); };
+    if (full.dev_batch) prov.dev_batch = [&full, idx](VfyDevBatch<C>& db) -> bool {
+        VfyDevBatch<C> all;
+        if (!full.dev_batch(all)) return false;   // like-instances of one recording as a whole, so every subset of them is
+        db = all;
+        db.state_of = [s = all.state_of, idx](size_t j) { return s(idx[j]); };
+        if (all.commit_xy) db.commit_xy = [x = all.commit_xy, idx](size_t j) { return x(idx[j]); };
+        if (all.commit_wire) db.commit_wire = [w = all.commit_wire, idx](size_t j) { return w(idx[j]); };
+        if (all.cs_of) db.cs_of = [f = all.cs_of, idx](size_t j) { return f(idx[j]); };
+        return true;
+    };
+}
 
 // ---- batch_verify with the per-proof front end on the GPU -------------------------------------------------------------------
 // For a batch of like-instances of one single-phase statement the host does NOT replay transcripts: it stages the proofs' bytes,
@@ -1460,7 +1510,6 @@ template <class C> struct VfyProvider {
 // flagged anything the reference rejects (malformed bytes, an identity point under validate_and_append_point, ...): the caller then
 // runs the host replay, which reports the reference's error in instance order.
 static constexpr size_t VFY_BLOCK = 512;           // proofs per k_vfy_tables / k_vfy_batch launch
-static constexpr size_t VFY_TEMPLATE_CACHE = 64;   // circuit templates kept per ctx (soft bound, see the eviction in batch_verify_core)
 template <class C> struct VfeClassDev {
     std::weak_ptr<const host::FrozenRecording> base;
     const host::FrozenRecording* base_ptr = nullptr;
@@ -1527,11 +1576,6 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     if (!db.shared_state) for (size_t i = 1; i < count; i++) { const host::Strobe* si = db.state_of(i); if (!si || si->pos != s0->pos || si->pos_begin != s0->pos_begin) return BP_OK; }
     const double t_entry = now_s();
     hipStream_t st = ctx->stream;
-    auto parallel_range = [&](size_t lo, size_t hi, const std::function<void(size_t)>& fn) {
-        if (hi <= lo) return;
-        if (!ctx->pool || hi - lo == 1) { for (size_t i = lo; i < hi; i++) fn(i); return; }
-        ctx->pool->run(lo, hi, fn);
-    };
     const F4 one = S::one(), mone = S::neg(S::one());
     // the circuit template (constraint matrices on the GPU, keyed by structure) and this class's device-side constants
     CS like;
@@ -1544,19 +1588,10 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     std::shared_ptr<void> tkeep;
     auto template_for = [&](const CS& rec, const host::CanonState& cst) -> int {   // look up / build (upload + sync) the template of `rec`
         dg = cst.digest(rec.n1, n, rec.num_constraints());
-        const std::string tkey((const char*)&dg, sizeof dg);
-        auto tit = ctx->templates.find(tkey);
-        if (tit == ctx->templates.end()) {
-            if (ctx->templates.size() >= VFY_TEMPLATE_CACHE) { HIPCHK(ctx_stream_wait(ctx)); ctx->templates.clear(); ctx->vfe_classes.clear(); }
-            VTemplate<C>* t = new VTemplate<C>();
-            std::shared_ptr<void> holder(t, [](void* q) { delete (VTemplate<C>*)q; });
-            BPCHK(build_template<C>(ctx, rec, *t));
-            tit = ctx->templates.emplace(tkey, holder).first;
-        }
-        tkeep = tit->second;
-        const VTemplate<C>& T = *(const VTemplate<C>*)tkeep.get();
-        if (T.n != n || T.n1 != rec.n1 || T.q != rec.num_constraints() || T.ncoef != cst.coefs.size()) { g_err = "batch_verify: structure digest collision"; return BP_E_ARG; }
-        return BP_OK;
+        // a miss with a full cache: the one template this batch needs is the one that is missing, so everything leaves
+        if (ctx->templates.size() >= VFY_TEMPLATE_CACHE && !ctx->templates.count(vfy_template_key(dg))) BPCHK(vfy_templates_trim(ctx, {}));
+        const VTemplate<C>* T;
+        return vfy_template_get<C>(ctx, dg, &rec, n, rec.n1, rec.num_constraints(), cst.coefs.size(), "batch_verify", tkeep, T);
     };
     if (!two) {
         like.n1 = like.num_vars;   // single phase: every multiplier is a phase-1 multiplier (run_randomized with nothing deferred)
@@ -1726,7 +1761,7 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     uint8_t* h_small = hs + ctx->h_vfe_cap - 4096;      // results: [deltas (<= 96 slots) | sums 2 | status]
     {
         const size_t chunk = 64;
-        parallel_range(0, (count + chunk - 1) / chunk, [&](size_t c) {
+        pool_range(ctx, 0, (count + chunk - 1) / chunk, [&](size_t c) {
             const size_t lo = c * chunk, hi = std::min(count, lo + chunk);
             memcpy(hs + lo * plen, proofs + poff[lo], (hi - lo) * plen);
             for (size_t i = lo; i < hi; i++) {
@@ -1807,7 +1842,7 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
         for (size_t blk = 0; blk < nblocks; blk++) {
             const size_t lo = blk * VFY_BLOCK, nb = std::min(count, lo + VFY_BLOCK) - lo;
             std::atomic<bool> bad{false};
-            parallel_range(lo, lo + nb, [&](size_t i) {
+            pool_range(ctx, lo, lo + nb, [&](size_t i) {
                 if (bad.load(std::memory_order_relaxed)) return;
                 std::unique_ptr<CS> tmp;
                 CS* ci;
@@ -1921,12 +1956,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
     static const bool vtrace = getenv("ARKBP_VFY_TRACE") != nullptr;
     double t_last = t_entry;
     auto mark = [&](const char* what) { if (vtrace) { double t = now_s(); fprintf(stderr, "[vfy] %-28s %8.3f ms\n", what, (t - t_last) * 1e3); t_last = t; } };
-    if (!ctx->pool && count > 1) ctx->pool.reset(new host::HostPool(std::max(1u, ctx->tune_host_threads ? (unsigned)ctx->tune_host_threads : host::host_pool_threads()) - 1));   // + the calling thread
-    auto parallel_range = [&](size_t lo, size_t hi, const std::function<void(size_t)>& fn) {
-        if (hi <= lo) return;
-        if (!ctx->pool || hi - lo == 1) { for (size_t k = lo; k < hi; k++) fn(k); return; }
-        ctx->pool->run(lo, hi, fn);
-    };
+    host_pool_ensure(ctx, count);
     // same-shaped single-phase batches: codec, transcript replay and challenge arithmetic on the GPU (batch_verify_device).  It
     // declines (handled = false) whenever anything is unusual — then the replay below reports what the reference would.
     if (prov.dev_batch) {
@@ -1951,7 +1981,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
     // decode: framing + x coordinates on the host, the square roots of all compressed points on the GPU
     std::vector<int> rcs(count, BP_OK);
     std::vector<host::LazyProof> lps(count);
-    parallel_range(0, count, [&](size_t k) { rcs[k] = host::proof_parse_lazy<C>(lps[k], proofs + poff[k], poff[k + 1] - poff[k]); });
+    pool_range(ctx, 0, count, [&](size_t k) { rcs[k] = host::proof_parse_lazy<C>(lps[k], proofs + poff[k], poff[k + 1] - poff[k]); });
     for (size_t k = 0; k < count; k++) if (rcs[k]) {
         if (!inst_status) return rcs[k];
         lps[k].xs.clear(); lps[k].flags.clear(); lps[k].k = (size_t)-1;   // no points of its own; it dooms the batch below
@@ -1981,14 +2011,14 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
     u32* d_pts = d_x + xtot * 8;
     u32* d_f = d_pts + xtot * 16;
     u32* d_ok = d_f + xtot;
-    parallel_range(0, count, [&](size_t k) { std::copy(lps[k].xs.begin(), lps[k].xs.end(), all_x + xoff[k]); std::copy(lps[k].flags.begin(), lps[k].flags.end(), all_f + xoff[k]); });
+    pool_range(ctx, 0, count, [&](size_t k) { std::copy(lps[k].xs.begin(), lps[k].xs.end(), all_x + xoff[k]); std::copy(lps[k].flags.begin(), lps[k].flags.end(), all_f + xoff[k]); });
     mark("parse + gather x");
     size_t decoded_upto = 0;   // instances [0, decoded_upto) have their decode enqueued on the aux stream
     auto issue_decode = [&](size_t k_hi, int ev) -> int {   // enqueue the decode of instances [decoded_upto, k_hi)
         const size_t x0 = xoff[decoded_upto], x1 = xoff[k_hi];
         if (x1 > x0 && ctx->host_only) {
             // dry run without a device: the square roots on the host pool (what k_points_decompress computes)
-            parallel_range(x0, x1, [&](size_t j) {
+            pool_range(ctx, x0, x1, [&](size_t j) {
                 A4 pt{}; bool good = true;
                 const u32 fl = all_f[j];
                 if (!(fl & 0x40)) good = host::Grp<C>::from_x(pt, all_x[j], (fl & 0x80) != 0);
@@ -2046,7 +2076,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
         HIPCHK(hipStreamSynchronize(ctx->aux_stream));
         std::vector<int> erc(count, BP_OK);
         std::vector<const char*> emsg(count, nullptr);
-        parallel_range(from, count, [&](size_t k) {
+        pool_range(ctx, from, count, [&](size_t k) {
             if (rcs[k]) { erc[k] = rcs[k]; return; }
             for (size_t j = xoff[k]; j < xoff[k + 1]; j++) if (!all_ok[j]) { erc[k] = BP_E_FORMAT; return; }
             Replayed r;
@@ -2062,7 +2092,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
     if (doomed) {
         std::vector<int> erc(count, BP_OK);
         std::vector<const char*> emsg(count, nullptr);
-        parallel_range(0, count, [&](size_t k) { Replayed r; erc[k] = replay(k, r); emsg[k] = r.vp.err; });
+        pool_range(ctx, 0, count, [&](size_t k) { Replayed r; erc[k] = replay(k, r); emsg[k] = r.vp.err; });
         for (size_t k = 0; k < count; k++) if (erc[k]) { if (emsg[k]) g_err = emsg[k]; return erc[k]; }
         return BP_E_VERIFICATION;   // (not reached: a doomed instance fails its own replay)
     }
@@ -2143,7 +2173,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
             r.pf = host::ProofData();
         };
         // groups of eight: their transcripts take the commitments in lockstep where the provider can do that (AVX-512 Keccak x8)
-        parallel_range(0, (nb + 7) / 8, [&](size_t g) {
+        pool_range(ctx, 0, (nb + 7) / 8, [&](size_t g) {
             const size_t p0 = g * 8, cnt = std::min<size_t>(8, nb - p0);
             if (prov.head8) {
                 std::unique_ptr<host::Transcript> heads[8];
@@ -2202,10 +2232,8 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
         // and only takes entries no instance of this block resolves to (the bound is soft: a block of > 64 new shapes grows it).
         if (ctx->templates.size() >= VFY_TEMPLATE_CACHE) {
             std::set<std::string> used;
-            for (size_t p = 0; p < nb; p++) used.insert(std::string((const char*)&rep[p].vp.digest, sizeof rep[p].vp.digest));
-            HIPCHK(ctx_stream_wait(ctx));   // earlier blocks' launches may still read the evicted templates' device arrays
-            for (auto it = ctx->templates.begin(); it != ctx->templates.end();) { if (used.count(it->first)) ++it; else it = ctx->templates.erase(it); }
-            ctx->vfe_classes.clear();   // (a class names its template by digest: a rebuilt one may hold other constants)
+            for (size_t p = 0; p < nb; p++) used.insert(vfy_template_key(rep[p].vp.digest));
+            BPCHK(vfy_templates_trim(ctx, used));
         }
         for (size_t p = 0; p < nb; p++) {
             const VerifyPrep<C>& vp = rep[p].vp;
@@ -2214,22 +2242,10 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
                 continue;
             }
             if (p > 0) uniform = false;
-            const std::string key((const char*)&vp.digest, sizeof vp.digest);
-            auto it = ctx->templates.find(key);
-            if (it == ctx->templates.end()) {
-                // (a miss means the template was not cached during the replay either — entries only leave the cache above, and never one
-                // this block uses — so the worker kept this instance's recording)
-                if (!rep[p].inst.cs) { g_err = "batch_verify: recording released before its template was built"; return BP_E_ARG; }
-                VTemplate<C>* t = new VTemplate<C>();
-                std::shared_ptr<void> holder(t, [](void* q) { delete (VTemplate<C>*)q; });
-                BPCHK(build_template<C>(ctx, *rep[p].inst.cs, *t));
-                it = ctx->templates.emplace(key, holder).first;
-            }
-            keep[p] = it->second;
-            const VTemplate<C>* t = (const VTemplate<C>*)it->second.get();
-            if (t->n != vp.n || t->n1 != vp.n1 || t->q != vp.nq || t->ncoef != vp.ncoef) { g_err = "batch_verify: structure digest collision"; return BP_E_ARG; }
-            tm[p] = t;
-            own_tab[p] = t->ncoef && memcmp(t->coefs_host.data(), vp.coef_ptr, t->ncoef * 32) != 0;
+            // (a miss means the template was not cached during the replay either — entries only leave the cache above, and never one
+            // this block uses — so the worker kept this instance's recording: inst.cs is null only for a template that is found)
+            BPCHK(vfy_template_get<C>(ctx, vp.digest, rep[p].inst.cs, vp.n, vp.n1, vp.nq, vp.ncoef, "batch_verify", keep[p], tm[p]));
+            own_tab[p] = vfy_own_table<C>(*tm[p], vp);
         }
         mark("  block: templates");
         // groups: same template, same kind of coefficient table; instance order inside a group
@@ -2279,7 +2295,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
         {   // recordings that were kept for a template build: rare, but then there may be hundreds (a new gadget's first block)
             size_t kept = 0;
             for (size_t p = 0; p < nb; p++) kept += rep[p].inst.owned_cs ? 1 : 0;
-            if (kept > 8) parallel_range(0, nb, [&](size_t p) { rep[p].inst.owned_cs.reset(); rep[p].inst.owned_tr.reset(); });
+            if (kept > 8) pool_range(ctx, 0, nb, [&](size_t p) { rep[p].inst.owned_cs.reset(); rep[p].inst.owned_tr.reset(); });
         }
         mark("  block: release");
     }
@@ -2407,8 +2423,7 @@ static int batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenario
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
     if (point_out) memset(point_out, 0, 64);
-    std::vector<size_t> poff(count + 1, 0), coff(count + 1, 0), uoff(count + 1, 0);
-    for (size_t k = 0; k < count; k++) { poff[k + 1] = poff[k] + proof_lens[k]; coff[k + 1] = coff[k] + ms[k]; uoff[k + 1] = uoff[k] + npubs[k]; }
+    const std::vector<size_t> poff = prefix_offsets(proof_lens, count), coff = prefix_offsets(ms, count), uoff = prefix_offsets(npubs, count);
     auto make_io = [&](size_t k, host::StatementIO& io) {
         io.commitments.resize(ms[k]); io.publics.resize(npubs[k]);
         if (ms[k]) memcpy(io.commitments.data(), commit_xy + 8 * coff[k], ms[k] * 64);
@@ -2419,7 +2434,7 @@ static int batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenario
     // 64-bit hash of (scenario, params, publics) computed on the pool; equal hashes are confirmed byte for byte.
     std::vector<std::shared_ptr<ScenarioSource<C>>> src(count);
     {
-        if (!ctx->pool && count > 1) ctx->pool.reset(new host::HostPool(std::max(1u, ctx->tune_host_threads ? (unsigned)ctx->tune_host_threads : host::host_pool_threads()) - 1));
+        host_pool_ensure(ctx, count);
         std::vector<u64> hk(count);
         auto hash_one = [&](size_t k) {
             u64 h = 0xcbf29ce484222325ULL ^ (u64)(u32)scenarios[k] ^ ((u64)npubs[k] << 40);

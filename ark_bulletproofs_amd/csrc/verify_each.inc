@@ -183,19 +183,14 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
     auto mark = [&](const char* what) { if (vtrace) { double t = now_s(); fprintf(stderr, "[vfy-each] %-28s %8.3f ms\n", what, (t - t_last) * 1e3); t_last = t; } };
     if (points) memset(points, 0, count * 64);
     std::vector<int> stv(count, BP_OK);
-    if (!ctx->pool && count > 1) ctx->pool.reset(new host::HostPool(std::max(1u, ctx->tune_host_threads ? (unsigned)ctx->tune_host_threads : host::host_pool_threads()) - 1));
-    auto parallel_range = [&](size_t lo, size_t hi, const std::function<void(size_t)>& fn) {
-        if (hi <= lo) return;
-        if (!ctx->pool || hi - lo == 1) { for (size_t k = lo; k < hi; k++) fn(k); return; }
-        ctx->pool->run(lo, hi, fn);
-    };
+    host_pool_ensure(ctx, count);
     // 0. pending wire commitments: decoded and committed first; an instance with a rejected encoding is left out with BP_E_FORMAT
     std::vector<int> pst(count, BP_OK);
     if (prov.prologue) BPCHK(prov.prologue(pst.data()));
     // 1. framing; the proof's claim decides the route
     std::vector<host::LazyProof> lps(count);
     std::vector<int> prc(count, BP_OK);
-    parallel_range(0, count, [&](size_t k) { prc[k] = host::proof_parse_lazy<C>(lps[k], proofs + poff[k], poff[k + 1] - poff[k]); });
+    pool_range(ctx, 0, count, [&](size_t k) { prc[k] = host::proof_parse_lazy<C>(lps[k], proofs + poff[k], poff[k + 1] - poff[k]); });
     const size_t reach_max = ctx->shard_world <= 1 && ctx->tune_direct_max >= 2 ? std::min(ctx->gens_cap, ctx->tune_direct_max) : 0;
     auto claim = [&](size_t k) -> size_t {   // the padded size the proof claims, 0 when it cannot take the grouped path
         const size_t kk = lps[k].k;
@@ -224,13 +219,13 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
     std::vector<F4> all_x(xoff[ng]);
     std::vector<u32> all_f(xoff[ng]), all_ok;
     std::vector<A4> all_pts;
-    parallel_range(0, ng, [&](size_t j) { const host::LazyProof& lp = lps[gl[j]]; std::copy(lp.xs.begin(), lp.xs.end(), all_x.begin() + xoff[j]); std::copy(lp.flags.begin(), lp.flags.end(), all_f.begin() + xoff[j]); });
+    pool_range(ctx, 0, ng, [&](size_t j) { const host::LazyProof& lp = lps[gl[j]]; std::copy(lp.xs.begin(), lp.xs.end(), all_x.begin() + xoff[j]); std::copy(lp.flags.begin(), lp.flags.end(), all_f.begin() + xoff[j]); });
     BPCHK(decompress_points<C>(ctx, all_x.data(), all_f.data(), xoff[ng], all_pts, all_ok));
     const double t_dec = now_s();
     mark("gpu decompress");
     // 3. replay on the pool: every instance keeps its own status
     std::vector<VeRep<C>> rep(ng);
-    parallel_range(0, ng, [&](size_t j) {
+    pool_range(ctx, 0, ng, [&](size_t j) {
         VeRep<C>& r = rep[j];
         r.k = gl[j]; r.kk = lps[r.k].k;
         for (size_t x = xoff[j]; x < xoff[j + 1]; x++) if (!all_ok[x]) { r.rc = BP_E_FORMAT; return; }   // x not on the curve: FormatError
@@ -252,26 +247,13 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
     // 4. templates: by structure digest; a miss records the matrices from this instance (upload + sync, once per gadget)
     if (!live.empty() && ctx->templates.size() >= VFY_TEMPLATE_CACHE) {   // bounded cache: only entries no instance of this call resolves to leave it
         std::set<std::string> used;
-        for (auto* r : live) used.insert(std::string((const char*)&r->vp.digest, sizeof r->vp.digest));
-        HIPCHK(ctx_stream_wait(ctx));
-        for (auto it = ctx->templates.begin(); it != ctx->templates.end();) { if (used.count(it->first)) ++it; else it = ctx->templates.erase(it); }
-        ctx->vfe_classes.clear();
+        for (auto* r : live) used.insert(vfy_template_key(r->vp.digest));
+        BPCHK(vfy_templates_trim(ctx, used));
     }
     for (auto* r : live) {
         const VerifyPrep<C>& vp = r->vp;
-        const std::string key((const char*)&vp.digest, sizeof vp.digest);
-        auto it = ctx->templates.find(key);
-        if (it == ctx->templates.end()) {
-            VTemplate<C>* t = new VTemplate<C>();
-            std::shared_ptr<void> holder(t, [](void* q) { delete (VTemplate<C>*)q; });
-            BPCHK(build_template<C>(ctx, *r->inst.cs, *t));
-            it = ctx->templates.emplace(key, holder).first;
-        }
-        r->keep = it->second;
-        const VTemplate<C>* t = (const VTemplate<C>*)it->second.get();
-        if (t->n != vp.n || t->n1 != vp.n1 || t->q != vp.nq || t->ncoef != vp.ncoef) { g_err = "verify_batch: structure digest collision"; return BP_E_ARG; }
-        r->tm = t;
-        r->own_tab = t->ncoef && memcmp(t->coefs_host.data(), vp.coef_ptr, t->ncoef * 32) != 0;
+        BPCHK(vfy_template_get<C>(ctx, vp.digest, r->inst.cs, vp.n, vp.n1, vp.nq, vp.ncoef, "verify_batch", r->keep, r->tm));
+        r->own_tab = vfy_own_table<C>(*r->tm, vp);
     }
     {   // one kind of coefficient table per template: when any instance carries values of its own (public constants, the challenges of
         // randomized constraints), every instance of the template ships its table — the template's creator among them — so that the
@@ -318,9 +300,10 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
     // 6. everything else: the single-instance route, in instance order
     const double t_single = now_s();
     for (size_t k : sl) {
+        const uint32_t self = (uint32_t)k;
         VfyProvider<C> one;
-        one.m_of = [&, k](size_t) { return prov.m_of(k); };
-        one.get = [&, k](size_t, VfyInstance<C>& out) -> int { return prov.get(k, out); };
+        provider_subset<C>(prov, &self, one);
+        one.dev_batch = nullptr;   // (one instance: the host replay)
         const F4 alpha = S::one();
         const size_t po[2] = {0, poff[k + 1] - poff[k]};
         stv[k] = batch_verify_core<C>(ctx, 1, one, proofs + poff[k], po, &alpha, nullptr, points ? points + 8 * k : nullptr);
@@ -335,16 +318,22 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
 
 template <class C>
 static int cs_verify_each(bp_ctx* c, size_t count, bp_cs* const* vs, const uint8_t* proofs, const size_t* proof_lens, int* status, uint64_t* points, double* timing) {
-    std::vector<size_t> poff(count + 1, 0);
-    for (size_t k = 0; k < count; k++) poff[k + 1] = poff[k] + proof_lens[k];
+    const std::vector<size_t> poff = prefix_offsets(proof_lens, count);
     VfyProvider<C> prov;
-    prov.m_of = [&](size_t k) { return vs[k]->cs<C>()->V.size(); };
-    prov.get = [&](size_t k, VfyInstance<C>& out) -> int { out.cs = vs[k]->cs<C>(); return BP_OK; };
-    prov.prologue = [&](int* st) -> int { return wire_materialize<C>(c, count, [&](size_t k) { return vs[k]; }, st); };
-    for (size_t k = 0; k < count; k++) { vs[k]->consumed = true; vs[k]->running = true; }
-    const int rc = verify_each_core<C>(c, count, prov, proofs, poff.data(), status, points, timing);
-    for (size_t k = 0; k < count; k++) vs[k]->running = false;
-    return rc;
+    cs_provider<C>(c, count, CsView{vs, nullptr}, prov);
+    prov.dev_batch = nullptr;   // (the device front end gives one verdict for a batch, not one per instance)
+    VerifyingScope scope(vs, count);
+    return verify_each_core<C>(c, count, prov, proofs, poff.data(), status, points, timing);
+}
+// scenario statements: the statement sources, the per-instance recorders and the lockstep transcript heads are batch_verify_scenarios'
+// own; only the core differs
+template <class C>
+static int scenarios_verify_each(bp_ctx* c, size_t count, const int* scenarios, const uint64_t* params, const uint8_t* proofs, const size_t* proof_lens,
+                                 const uint64_t* commit_xy, const size_t* ms, const uint64_t* publics, const size_t* npubs, int* status, uint64_t* points, double* timing) {
+    const VfyCoreFn<C> core = [&](const VfyProvider<C>& prov, const size_t* poff, const F4*) {
+        return verify_each_core<C>(c, count, prov, proofs, poff, status, points, timing);
+    };
+    return batch_verify_scenarios<C>(c, count, scenarios, params, proofs, proof_lens, commit_xy, ms, publics, npubs, nullptr, nullptr, 0, nullptr, &core);
 }
 
 int bp_verifier_verify_batch(bp_ctx* c, size_t count, bp_cs* const* verifiers, const uint8_t* proofs, const size_t* proof_lens, int* status, uint64_t* check_points_xy,
@@ -352,14 +341,7 @@ int bp_verifier_verify_batch(bp_ctx* c, size_t count, bp_cs* const* verifiers, c
     if (!c) return BP_E_ARG;
     if (count == 0) return BP_OK;
     if (!verifiers || !proofs || !proof_lens || !status) return BP_E_ARG;
-    for (size_t k = 0; k < count; k++) {
-        if (!verifiers[k] || verifiers[k]->consumed || verifiers[k]->proving || verifiers[k]->curve != c->curve) { g_err = "verify_batch: every instance needs a live verifier of the ctx's curve"; return BP_E_ARG; }
-    }
-    if (count > 1) {
-        std::vector<const bp_cs*> sorted(verifiers, verifiers + count);
-        std::sort(sorted.begin(), sorted.end(), std::less<const bp_cs*>());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { g_err = "verify_batch: a verifier is consumed by ONE instance"; return BP_E_ARG; }
-    }
+    BPCHK(verifiers_check("verify_batch", c, count, verifiers));
     if (!c->gens_cap) { g_err = "verify_batch: generators not installed"; return BP_E_GENS_LENGTH; }
     if (c->host_only) { g_err = "verify_batch: a host-only ctx has no device to verify on"; return BP_E_NO_DEVICE; }
     BPCHK(wire_check_states("verify_batch", count, verifiers));
@@ -380,17 +362,8 @@ int bp_r1cs_verify_each_scenarios(bp_ctx* c, size_t count, const int* scenarios,
     if (!c->gens_cap) { g_err = "verify_each: generators not installed"; return BP_E_GENS_LENGTH; }
     if (c->host_only) { g_err = "verify_each: a host-only ctx has no device to verify on"; return BP_E_NO_DEVICE; }
     HIPCHK(hipSetDevice(c->device));
-    // the statement sources, the per-instance recorders and the lockstep transcript heads are batch_verify_scenarios' own; only the core differs
-    if (c->curve == 0) {
-        const VfyCoreFn<Secq> core = [&](const VfyProvider<Secq>& prov, const size_t* poff, const F4*) {
-            return verify_each_core<Secq>(c, count, prov, proofs, poff, status, check_points_xy, timing);
-        };
-        return batch_verify_scenarios<Secq>(c, count, scenarios, params, proofs, proof_lens, commit_xy, ms, publics, npubs, nullptr, nullptr, 0, nullptr, &core);
-    }
-    const VfyCoreFn<Zorro> core = [&](const VfyProvider<Zorro>& prov, const size_t* poff, const F4*) {
-        return verify_each_core<Zorro>(c, count, prov, proofs, poff, status, check_points_xy, timing);
-    };
-    return batch_verify_scenarios<Zorro>(c, count, scenarios, params, proofs, proof_lens, commit_xy, ms, publics, npubs, nullptr, nullptr, 0, nullptr, &core);
+    return c->curve == 0 ? scenarios_verify_each<Secq>(c, count, scenarios, params, proofs, proof_lens, commit_xy, ms, publics, npubs, status, check_points_xy, timing)
+                         : scenarios_verify_each<Zorro>(c, count, scenarios, params, proofs, proof_lens, commit_xy, ms, publics, npubs, status, check_points_xy, timing);
 }
 
 int bp_ctx_verify_each_stats(bp_ctx* c, uint64_t* grouped_instances, uint64_t* single_instances, uint64_t* groups, uint64_t* host_waits) {

@@ -424,3 +424,35 @@ def test_three_ctxs_share_one_table_set_from_three_threads(env):
     finally:
         for o in others:
             o.close()
+
+
+def test_template_cache_eviction_under_verify_each(oracle):
+    """the verify_each counterpart of test_gpu_verify.py::test_template_cache_eviction_keeps_what_the_block_uses: a ctx whose template
+    cache is past its bound, then ONE call that mixes new shapes (first) with shapes cached before.  The eviction of that call must
+    keep every template an instance of the call resolves to, and every instance still gets the oracle's verdict."""
+    import ark_bulletproofs_amd as A
+
+    O, cv, gens = oracle, 0, 128
+    e = A.Engine(curve=cv)
+    e.gens_derive(gens)
+    try:
+        def stmt(n):
+            pr = e.prove_scenario(3, [n, 0], bytes([n & 255]) * 32, m_cap=8)   # square chain with n multipliers: one shape per n
+            return (3, [n, 0], pr.proof, pr.commitments, pr.publics)
+
+        shapes = {n: stmt(n) for n in range(2, 76)}
+        # 70 shapes, each twice (a shape used once is recorded inside its own replay): more than the cache holds
+        rc, _, pt = e.batch_verify([shapes[n] for n in range(2, 72)] * 2, bytes([11]) * 32, want_point=True)
+        assert rc == OK and not pt.any()
+        mixed = [shapes[n] for n in (72, 73, 74, 75)] + [shapes[n] for n in range(40, 72)]
+        sc, prm, proof, cm, pb = mixed[20]
+        bad = bytearray(proof)
+        bad[11 * 33 + 40] ^= 2                                                  # a low byte of t_x_blinding: still a canonical scalar
+        mixed[20] = (sc, prm, bytes(bad), cm, pb)
+        want = [FROM_ORACLE[O.r1cs_verify(cv, i[0], i[1], gens, i[2], i[3], i[4])] for i in mixed]
+        assert want[20] == E_VERIFICATION and want.count(OK) == len(mixed) - 1
+        rc, st, _, d = each(e, mixed)
+        assert st == want
+        assert d[0] == len(mixed) and d[1] == 0 and d[2] >= 1, d               # every instance took the grouped path
+    finally:
+        e.close()
