@@ -28,7 +28,7 @@ EXPORTS = [
     "bp_msm_batch", "bp_msm_batch_dev", "bp_ctx_msm_batch_stats", "bp_debug_msm_batch_plan",
     "bp_ctx_set_shard_allgather", "bp_gens_fold_tables", "bp_gens_msm_tables", "bp_debug_exp_iter", "bp_debug_inner_product", "bp_verifier_verify", "bp_r1cs_batch_verify", "bp_stmt_as_prover", "bp_transcript_export_state", "bp_transcript_import_state", "bp_transcript_clone",
     "bp_gens_tables_check", "bp_debug_tables_ptr", "bp_debug_msm_direct", "bp_rccl_unique_id", "bp_ctx_rccl_init", "bp_ctx_rccl_shutdown", "bp_ctx_collective_stats", "bp_debug_rccl_allgather",
-    "bp_debug_vfe_schedule_replay", "bp_debug_vfe_schedule_replay_2phase", "bp_debug_vfe_challenges", "bp_ctx_vfe_stats", "bp_debug_verify_challenges", "bp_debug_ctx_create_hostonly", "bp_ctx_msm_stats", "bp_ctx_direct_stats", "bp_gens_direct_tables", "bp_ctx_fold_stats", "bp_gens_fold_tables_slice",
+    "bp_debug_vfe_schedule_replay", "bp_debug_vfe_schedule_replay_2phase", "bp_debug_vfe_challenges", "bp_ctx_vfe_stats", "bp_ctx_vfe_class_stats", "bp_debug_vfy_class_plan", "bp_debug_verify_challenges", "bp_debug_ctx_create_hostonly", "bp_ctx_msm_stats", "bp_ctx_direct_stats", "bp_gens_direct_tables", "bp_ctx_fold_stats", "bp_gens_fold_tables_slice",
     "bp_ctx_msm_pair_stats", "bp_debug_msm_pair", "bp_debug_fold", "bp_gens_direct_tables_check",
     # verifier commitments from the wire
     "bp_points_decompress", "bp_points_compress", "bp_verifier_commit_compressed_batch", "bp_verifier_materialize", "bp_ctx_commit_wire_stats",

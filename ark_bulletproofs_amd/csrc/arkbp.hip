@@ -10,12 +10,14 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <deque>
 #include <array>
 #include <functional>
 #include <map>
 #include <memory>
 #include <set>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 #include "../../include/arkbp.h"
@@ -259,7 +261,7 @@ struct bp_ctx {
     DevBuf v_params, v_gpart, v_hpart, v_alpha, v_tables, v_dec;
     DevBuf p_moff, p_ment, p_mc, p_coefs, p_ztab;   // prover-side constraint index of the statement being proved (k_r1cs_flatten)
     // verifier front end on the device (vfe.hip; r1cs_host.inc batch_verify_device): raw inputs, serialized items, challenges, scratch
-    DevBuf vfe_in, vfe_msg, vfe_chal, vfe_ws, vfe_small;
+    DevBuf vfe_in, vfe_msg, vfe_chal, vfe_ws, vfe_small, vfe_flags;   // (vfe_flags: the kernels' reject bits per proof, beside the batch-wide word in vfe_small)
     void* h_vfe = nullptr;                    // pinned staging: [proof bytes | commitments | transcript states | small results]
     size_t h_vfe_cap = 0;
     DevBuf vfe2_sched, vfe2_voff, vfe2_vq, vfe2_vcid, vfe2_gch, vfe2_coef;   // two-phase batches: per-batch schedule, terms on commitments, gadget challenges, coefficient tables
@@ -269,6 +271,8 @@ struct bp_ctx {
     int tune_vfy_device = 1;                  // BP_TUNE_VFY_DEVICE: 0 host replay, 1 single-phase like-instances on the device, 2 two-phase ones too
     uint64_t fb_runs = 0, fb_runs_sharded = 0; // fixed-base MSMs completed on this ctx / of those, on a rank's share of the terms of a sharded proof
     uint64_t vfe_batches = 0, vfe_fallbacks = 0;                 // batches the device front end completed / handed to the host replay
+    uint64_t tune_vfy_class_min = 0;          // BP_TUNE_VFY_CLASS_MIN (0 = default: VFY_CLASS_MIN_DEFAULT)
+    uint64_t vcl_calls = 0, vcl_classes = 0, vcl_instances = 0, vcl_remainder = 0, vcl_flagged = 0;   // bp_ctx_vfe_class_stats
     uint64_t cw_front_end = 0, cw_prologue_gpu = 0, cw_host = 0;  // wire commitments decoded by k_vfe_points / by k_points_decompress / by host roots
     void* h_vstage[2] = {nullptr, nullptr};   // pinned staging halves of the batch-verify pipeline
     size_t h_vstage_cap[2] = {0, 0};
@@ -2968,7 +2972,33 @@ template <class C> static void cs_provider(bp_ctx* c, size_t n, CsView at, VfyPr
         if (!c0->deferred.empty()) db.cs_of = [at](size_t k) { return at(k)->cs<C>(); };
         return true;
     };
-    prov.prologue = [c, n, at](int* st) -> int { return wire_materialize<C>(c, n, at, st); };
+    // batches of several gadgets: what makes a handle a like-instance of others, and a class of them as the front end sees it
+    prov.class_id = [at](size_t k, VfyClassId& id) -> bool {
+        bp_cs* h = at(k);
+        const CS* ck = h->cs<C>();
+        if (!ck->base || !ck->tr || ck->cs_off.size() != 1 || ck->phase2 || ck->num_vars != ck->base->num_vars) return false;
+        id.wire = !h->wire.empty();
+        if (id.wire && !ck->V.empty()) return false;   // (some commitments committed, some pending: the host replay's)
+        id.rec = ck->base.get(); id.m = id.wire ? h->wire_count() : ck->V.size(); id.two = !ck->deferred.empty();
+        id.pos = ck->tr->s.pos; id.pos_begin = ck->tr->s.pos_begin;
+        return true;
+    };
+    prov.dev_class = [at](const uint32_t* idx, size_t cnt, VfyDevBatch<C>& db) -> bool {
+        bp_cs* h0 = at(idx[0]);
+        const bool wire = !h0->wire.empty();
+        db.src = h0->cs<C>(); db.m = wire ? h0->wire_count() : h0->cs<C>()->V.size(); db.absorb_commitments = wire; db.shared_state = false;
+        db.state_of = [at, idx](size_t j) { return (const host::Strobe*)&at(idx[j])->cs<C>()->tr->s; };
+        if (wire) db.commit_wire = [at, idx](size_t j) { return (const uint8_t*)at(idx[j])->wire.data(); };
+        else db.commit_xy = [at, idx](size_t j) { return (const uint64_t*)at(idx[j])->cs<C>()->V.data(); };
+        (void)cnt;
+        return true;
+    };
+    prov.prologue = [c, n, at](const uint32_t* idx, size_t cnt, int* st) -> int {
+        if (!idx) return wire_materialize<C>(c, n, at, st);
+        std::vector<uint32_t> map(cnt);   // (a view holds one index map: the two composed)
+        for (size_t j = 0; j < cnt; j++) map[j] = at.idx ? at.idx[idx[j]] : idx[j];
+        return wire_materialize<C>(c, cnt, CsView{at.vs, map.data()}, st);
+    };
 }
 // the weights of a call over recorded handles: the caller's words, or 1 for Verifier::verify's single instance
 template <class C> static std::vector<F4> cs_weights(const uint64_t* alphas, size_t count) {
@@ -3370,11 +3400,12 @@ static int cs_batch_verify_locate(bp_ctx* c, size_t count, bp_cs* const* vs, con
         const CsView at{vs, idx};
         cs_provider<C>(c, n, at, prov);
         // a pass the device front end declines commits the members' pending commitments: from then on THAT is their entry state
-        prov.prologue = [materialize = prov.prologue, at, n, &tr0](int* st) -> int {
-            std::vector<char> had(n);
-            for (size_t j = 0; j < n; j++) had[j] = !at(j)->wire.empty();
-            BPCHK(materialize(st));
-            for (size_t j = 0; j < n; j++) if (had[j] && !st[j]) tr0[at.idx[j]] = at(j)->tr->s;
+        prov.prologue = [materialize = prov.prologue, at, &tr0](const uint32_t* idx, size_t cnt, int* st) -> int {
+            auto member = [idx](size_t j) { return idx ? (size_t)idx[j] : j; };
+            std::vector<char> had(cnt);
+            for (size_t j = 0; j < cnt; j++) had[j] = !at(member(j))->wire.empty();
+            BPCHK(materialize(idx, cnt, st));
+            for (size_t j = 0; j < cnt; j++) if (had[j] && !st[j]) tr0[at.idx[member(j)]] = at(member(j))->tr->s;
             return BP_OK;
         };
     };
@@ -3566,7 +3597,7 @@ void bp_ctx_destroy(bp_ctx* c) {
     c->templates.clear();
     c->vfe_classes.clear();
     for (auto b : bufs) b->release();
-    DevBuf* vbufs[] = {&c->vfe_in, &c->vfe_msg, &c->vfe_chal, &c->vfe_ws, &c->vfe_small, &c->vfe2_sched, &c->vfe2_voff, &c->vfe2_vq, &c->vfe2_vcid, &c->vfe2_gch, &c->vfe2_coef};
+    DevBuf* vbufs[] = {&c->vfe_in, &c->vfe_msg, &c->vfe_chal, &c->vfe_ws, &c->vfe_small, &c->vfe_flags, &c->vfe2_sched, &c->vfe2_voff, &c->vfe2_vq, &c->vfe2_vcid, &c->vfe2_gch, &c->vfe2_coef};
     for (auto b : vbufs) b->release();
     if (c->h_vfe) (void)hipHostFree(c->h_vfe);
     if (c->h_vfe2) (void)hipHostFree(c->h_vfe2);
@@ -3679,6 +3710,7 @@ int bp_ctx_set_tuning(bp_ctx* c, int knob, uint64_t value) {
         case BP_TUNE_MSM_BATCH_MAX: c->tune_msb_max = value; return BP_OK;
         case BP_TUNE_MSM_PAIR: if (value > 1) return BP_E_ARG; c->tune_msm_pair = (int)value; return BP_OK;
         case BP_TUNE_VERIFY_LOCATE_LEAF: if (value > 4096) return BP_E_ARG; c->tune_verify_locate_leaf = (size_t)value; return BP_OK;
+        case BP_TUNE_VFY_CLASS_MIN: c->tune_vfy_class_min = std::min<uint64_t>(value, 65535); return BP_OK;
     }
     return BP_E_ARG;
 }
@@ -4512,7 +4544,7 @@ int bp_debug_vfe_challenges(bp_ctx* c, size_t count, const uint8_t* proofs, size
     HIPCHK(hipMemcpyAsync(d_in + b_proofs + b_V, states.data(), nst * 200, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_in + b_proofs + b_V + b_st, enc.data(), enc.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(c->vfe_small.p, 0, 256, st));
-    if (vfe::launch_points(c->curve, st, sh, d_in, (const u32*)(d_in + b_proofs), (uint64_t*)c->vfe_msg.p, c->r_tail.as<u32>(), c->vfe_small.as<u32>())) return BP_E_HIP;
+    if (vfe::launch_points(c->curve, st, sh, d_in, (const u32*)(d_in + b_proofs), (uint64_t*)c->vfe_msg.p, c->r_tail.as<u32>(), c->vfe_small.as<u32>(), nullptr)) return BP_E_HIP;
     uint8_t* d_seeds = (uint8_t*)c->vfe_ws.p;
     u32* d_ark = c->vfe_ws.as<u32>() + count * nch * 8;
     if (vfe::launch_sponge(c->curve, st, sh, (const u32*)(d_in + b_proofs + b_V + b_st), (const uint64_t*)(d_in + b_proofs + b_V), shared_state ? 0u : 25u, (const uint64_t*)c->vfe_msg.p,
@@ -4560,6 +4592,20 @@ int bp_ctx_vfe_stats(bp_ctx* c, uint64_t* device_batches, uint64_t* host_fallbac
     if (!c) return BP_E_ARG;
     if (device_batches) *device_batches = c->vfe_batches;
     if (host_fallbacks) *host_fallbacks = c->vfe_fallbacks;
+    return BP_OK;
+}
+int bp_ctx_vfe_class_stats(bp_ctx* c, uint64_t* class_calls, uint64_t* device_classes, uint64_t* device_instances, uint64_t* remainder_instances, uint64_t* flagged_replayed) {
+    if (!c) return BP_E_ARG;
+    if (class_calls) *class_calls = c->vcl_calls;
+    if (device_classes) *device_classes = c->vcl_classes;
+    if (device_instances) *device_instances = c->vcl_instances;
+    if (remainder_instances) *remainder_instances = c->vcl_remainder;
+    if (flagged_replayed) *flagged_replayed = c->vcl_flagged;
+    return BP_OK;
+}
+int bp_debug_vfy_class_plan(size_t count, const uint64_t* keys, const uint8_t* eligible, uint64_t class_min, uint32_t max_classes, int32_t* class_of, uint32_t* nclasses) {
+    if (!nclasses || (count && (!keys || !class_of))) return BP_E_ARG;
+    vfy_class_plan(count, keys, eligible, class_min, max_classes, class_of, nclasses);
     return BP_OK;
 }
 

@@ -1469,7 +1469,11 @@ template <class C> struct VfyDevBatch {
     // record through a handle (bp_cs); absent: a like-instance of src made for the purpose (the closures record into the recorder
     // they receive)
     std::function<host::ConstraintSystem<C>*(size_t)> cs_of;
+    std::shared_ptr<void> keep;                              // whatever the accessors refer to that has no other owner (an index map)
 };
+// What makes instance k a like-instance of others, as far as its provider knows: the shared recording (cs->base for handles, the
+// scenario source), the commitment count and form, the transcript position.  The core adds the proof length (vfy_class_plan's keys).
+struct VfyClassId { const void* rec = nullptr; size_t m = 0; bool wire = false, two = false; unsigned pos = 0, pos_begin = 0; };
 template <class C> struct VfyProvider {
     std::function<size_t(size_t)> m_of;                          // number of commitments of instance k (cheap; sizes the tails)
     std::function<int(size_t, VfyInstance<C>&)> get;            // the recorded verifier of instance k; called from pool threads
@@ -1478,10 +1482,17 @@ template <class C> struct VfyProvider {
     std::function<void(size_t, size_t, std::unique_ptr<host::Transcript>*)> head8;
     // optional: the whole batch as like-instances of ONE single-phase recording (the device front end, batch_verify_device)
     std::function<bool(VfyDevBatch<C>&)> dev_batch;
+    // optional, both or neither: batches of several gadgets (batch_verify_classes).  class_id(k, id): false for an instance without a
+    // shared recording.  dev_class(idx, n, db): instances idx[0 .. n), which have equal ids, as a VfyDevBatch whose accessors take
+    // j < n; idx outlives db.
+    std::function<bool(size_t, VfyClassId&)> class_id;
+    std::function<bool(const uint32_t*, size_t, VfyDevBatch<C>&)> dev_class;
     // optional: instances may still hold their commitments as wire bytes.  Called once, when the device front end did not take the
     // batch and before anything else looks at the instances: decodes and commits them (Verifier::commit).  st: one status per
     // instance, BP_E_FORMAT for an instance with a rejected encoding (it received none); the return value is an error of the call.
-    std::function<int(int*)> prologue;
+    // idx / n: for instances idx[0 .. n) only (the remainder of a call whose device classes keep their bytes pending), st[j] for
+    // idx[j]; idx null: every instance.
+    std::function<int(const uint32_t*, size_t, int*)> prologue;
 };
 // The provider whose instance j is instance idx[j] of `full`, which must outlive it (as must idx).  Without head8 — the lockstep heads
 // need consecutive instances — and without the prologue: the pending commitments are the whole call's business.
@@ -1498,6 +1509,26 @@ template <class C> static void provider_subset(const VfyProvider<C>& full, const
         if (all.cs_of) db.cs_of = [f = all.cs_of, idx](size_t j) { return f(idx[j]); };
         return true;
     };
+    if (full.class_id && full.dev_class) {
+        prov.class_id = [&full, idx](size_t j, VfyClassId& id) { return full.class_id(idx[j], id); };
+        prov.dev_class = [&full, idx](const uint32_t* sub, size_t n, VfyDevBatch<C>& db) -> bool {
+            auto map = std::make_shared<std::vector<uint32_t>>(n);
+            for (size_t j = 0; j < n; j++) (*map)[j] = idx[sub[j]];
+            if (!full.dev_class(map->data(), n, db)) return false;
+            db.keep = map;
+            return true;
+        };
+    }
+}
+// ... and with the prologue, for the members of a call that the host replays while the others stay on the device
+template <class C> static void provider_subset_with_prologue(const VfyProvider<C>& full, const uint32_t* idx, size_t n, VfyProvider<C>& prov) {
+    provider_subset<C>(full, idx, prov);
+    if (full.prologue) prov.prologue = [&full, idx, n](const uint32_t* sub, size_t cnt, int* st) -> int {
+        if (!sub) return full.prologue(idx, n, st);
+        std::vector<uint32_t> map(cnt);
+        for (size_t j = 0; j < cnt; j++) map[j] = idx[sub[j]];
+        return full.prologue(map.data(), cnt, st);
+    };
 }
 
 // ---- batch_verify with the per-proof front end on the GPU -------------------------------------------------------------------
@@ -1508,7 +1539,8 @@ template <class C> static void provider_subset(const VfyProvider<C>& full, const
 // on the ctx's stream; one wait at the end.  The challenges are derived on the device (Keccak-f / STROBE schedule / ChaCha20 /
 // Fr::rand), the decompressed points never leave it.  `handled` stays false when the batch does not qualify or when the kernels
 // flagged anything the reference rejects (malformed bytes, an identity point under validate_and_append_point, ...): the caller then
-// runs the host replay, which reports the reference's error in instance order.
+// runs the host replay — of the flagged instances alone where the kernels named them (vfy_replay_flagged) —, which reports the
+// reference's error in instance order.
 static constexpr size_t VFY_BLOCK = 512;           // proofs per k_vfy_tables / k_vfy_batch launch
 template <class C> struct VfeClassDev {
     std::weak_ptr<const host::FrozenRecording> base;
@@ -1544,48 +1576,89 @@ static hipError_t vfe_poll(bp_ctx* ctx, hipEvent_t ev) {
         nanosleep(&ts, nullptr);
     }
 }
-template <class C>
-static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& db, const uint8_t* proofs, const size_t* poff, const F4* alphas, double* timing,
-                               uint64_t* point_out, bool& handled) {
-    typedef typename C::Fr FrP;
-    typedef host::Fld<FrP> S;
+// One class of like-instances on its way through the device front end: batch_verify_device runs ONE job that is the whole batch,
+// batch_verify_classes several, which share the g / h accumulators, the tail array, the wait and the mega-check MSM.  The steps:
+// vfy_dev_admit (entry conditions, template, class constants; may decline, may wait for a cold upload) -> vfy_dev_place (where
+// each job lives in the ctx's buffers) -> vfy_dev_reserve (every allocation of the call, the zeroing) -> vfy_dev_launch per job
+// (staging, the launch chain) -> vfy_dev_finish (ONE wait, the head scalars, ONE MSM).
+static constexpr size_t VFY_SLOTS = 96;                              // block result slots (r_small / h_small) of one call, all jobs together
+static constexpr size_t VFY_HS_SUMS = VFY_SLOTS * 32;                // h_small: [deltas (VFY_SLOTS) | B / B_blinding sums (2 per job) | status]
+static constexpr size_t VFY_HS_STATUS = VFY_HS_SUMS + BP_VFY_MAX_CLASSES * 64;
+static_assert(VFY_HS_STATUS + 4 <= 4096 && 64 * 4 + BP_VFY_MAX_CLASSES * 64 <= 4096, "the small result areas are 4096 bytes");
+struct VfyDevPlace { size_t in = 0, msg = 0, chal = 0, ws = 0, inst = 0, tail = 0, blk = 0, cls = 0; };   // a job's offsets: bytes (in), 64-bit words (msg), scalars, instances, tail terms, slots
+struct VfyDevTotals { size_t b_in = 0, msg = 0, chal = 0, ws = 0, inst = 0, tail = 0, blocks = 0, classes = 0, Nmax = 0; };
+struct VfyDrain { bp_ctx* c; bool armed; ~VfyDrain() { if (armed) (void)hipStreamSynchronize(c->stream); } };   // the stream reads pinned memory of this call: a decline waits for it first
+template <class C> struct VfyDevJob {
     typedef host::ConstraintSystem<C> CS;
-    handled = false;
-    static const bool off = getenv("ARKBP_VFY_HOST") != nullptr;   // A/B switch: the host replay for every batch
-    if (off || ctx->host_only || !ctx->tune_vfy_device || !db.src || !count || ctx->shard_world > 1) return BP_OK;
-    const CS& src = *db.src;
-    const bool two = !src.deferred.empty();   // randomized constraints: the device derives every challenge, the host runs the callbacks
-    if (two && ctx->tune_vfy_device < 2) return BP_OK;
-    if (!src.base || src.cs_off.size() != 1 || src.phase2 || src.num_vars != src.base->num_vars) return BP_OK;
-    const size_t plen = poff[1] - poff[0];
-    if (plen < 539 || (plen - 539) % 66) return BP_OK;
-    const size_t k = (plen - 539) / 66, m = db.m;
-    if (k >= 32) return BP_OK;
-    for (size_t i = 0; i < count; i++) if (poff[i + 1] - poff[i] != plen) return BP_OK;
-    for (const auto& vt : src.base->vterms) if (vt.j >= m) return BP_OK;                // (a weaker statement than the recorded one: BP_E_ARG there)
-    const size_t tail = 6 + m + 5 + 2 * k, nV = db.absorb_commitments ? m : 0;
-    const bool wire = (bool)db.commit_wire;
-    if (wire && (!db.absorb_commitments || db.commit_xy)) return BP_OK;
-    const size_t vbytes = wire ? 33 : 64;   // per commitment in the staging area
-    const size_t nitems = nV + 11 + 2 * k + 3;
-    if (count > 65535 || m > 65535 || count * tail >= ((size_t)1 << 31) || nitems * vfe::ITEM_WORDS * count >= ((size_t)1 << 32)) return BP_OK;
-    const size_t nblocks = (count + VFY_BLOCK - 1) / VFY_BLOCK;
-    if (nblocks > 96) return BP_OK;                                                      // (one result slot per block)
-    const host::Strobe* s0 = db.state_of(0);
-    if (!s0) return BP_OK;
-    if (!db.shared_state) for (size_t i = 1; i < count; i++) { const host::Strobe* si = db.state_of(i); if (!si || si->pos != s0->pos || si->pos_begin != s0->pos_begin) return BP_OK; }
-    const double t_entry = now_s();
-    hipStream_t st = ctx->stream;
-    const F4 one = S::one(), mone = S::neg(S::one());
-    // the circuit template (constraint matrices on the GPU, keyed by structure) and this class's device-side constants
+    // the class: member j is instance idx[j] of the call's proofs / poff / alphas (idx null: j itself); db's accessors take j
+    size_t count = 0;
+    VfyDevBatch<C> db;
+    const uint32_t* idx = nullptr;
+    size_t at(size_t j) const { return idx ? idx[j] : j; }
+    // shape and constants (vfy_dev_admit)
+    bool two = false, wire = false, own_coefs = false;
+    size_t plen = 0, k = 0, m = 0, tail = 0, nV = 0, vbytes = 0, nitems = 0, nblocks = 0, n = 0, N = 0, G = 0, ncoef = 0;
+    const host::Strobe* s0 = nullptr;
+    double t_entry = 0;
     CS like;
-    like.init_like(src);
     host::CanonState scratch;
-    size_t n = src.num_vars, N = host::next_pow2(n);
     host::Digest dg;
     Vfe2Ref<C> ref;
     std::vector<u32> v2off, v2q, v2cid;   // two-phase: the terms on commitments by commitment (CSR), coefficient ids
-    std::shared_ptr<void> tkeep;
+    std::vector<uint32_t> enc2;
+    std::shared_ptr<void> tkeep, ckeep;   // the template and the class constants stay alive until the call's wait
+    const u32 *d_sched = nullptr, *d_voff = nullptr, *d_vq = nullptr, *d_vc = nullptr, *d_iota = nullptr;
+    // placement (vfy_dev_place)
+    size_t b_proofs = 0, b_V = 0, b_st = 0, b_in = 0;
+    VfyDevPlace pl;
+};
+static bool vfy_device_on(const bp_ctx* ctx) {
+    static const bool off = getenv("ARKBP_VFY_HOST") != nullptr;   // A/B switch: the host replay for every batch
+    return !off && !ctx->host_only && ctx->tune_vfy_device && ctx->shard_world <= 1;
+}
+template <class C>
+static int vfy_dev_admit(bp_ctx* ctx, VfyDevJob<C>& J, const uint8_t* proofs, const size_t* poff, bool& ok) {
+    typedef typename C::Fr FrP;
+    typedef host::Fld<FrP> S;
+    typedef host::ConstraintSystem<C> CS;
+    ok = false;
+    const VfyDevBatch<C>& db = J.db;
+    const size_t count = J.count;
+    if (!vfy_device_on(ctx) || !db.src || !count) return BP_OK;
+    const CS& src = *db.src;
+    const bool two = J.two = !src.deferred.empty();   // randomized constraints: the device derives every challenge, the host runs the callbacks
+    if (two && ctx->tune_vfy_device < 2) return BP_OK;
+    if (!src.base || src.cs_off.size() != 1 || src.phase2 || src.num_vars != src.base->num_vars) return BP_OK;
+    const size_t plen = J.plen = poff[J.at(0) + 1] - poff[J.at(0)];
+    if (plen < 539 || (plen - 539) % 66) return BP_OK;
+    const size_t k = J.k = (plen - 539) / 66, m = J.m = db.m;
+    if (k >= 32) return BP_OK;
+    for (size_t i = 0; i < count; i++) if (poff[J.at(i) + 1] - poff[J.at(i)] != plen) return BP_OK;
+    for (const auto& vt : src.base->vterms) if (vt.j >= m) return BP_OK;                // (a weaker statement than the recorded one: BP_E_ARG there)
+    const size_t tail = J.tail = 6 + m + 5 + 2 * k;
+    J.nV = db.absorb_commitments ? m : 0;
+    const bool wire = J.wire = (bool)db.commit_wire;
+    if (wire && (!db.absorb_commitments || db.commit_xy)) return BP_OK;
+    J.vbytes = wire ? 33 : 64;   // per commitment in the staging area
+    const size_t nitems = J.nitems = J.nV + 11 + 2 * k + 3;
+    if (count > 65535 || m > 65535 || count * tail >= ((size_t)1 << 31) || nitems * vfe::ITEM_WORDS * count >= ((size_t)1 << 32)) return BP_OK;
+    const size_t nblocks = J.nblocks = (count + VFY_BLOCK - 1) / VFY_BLOCK;
+    if (nblocks > VFY_SLOTS) return BP_OK;                                                      // (one result slot per block)
+    const host::Strobe* s0 = J.s0 = db.state_of(0);
+    if (!s0) return BP_OK;
+    if (!db.shared_state) for (size_t i = 1; i < count; i++) { const host::Strobe* si = db.state_of(i); if (!si || si->pos != s0->pos || si->pos_begin != s0->pos_begin) return BP_OK; }
+    J.t_entry = now_s();
+    hipStream_t st = ctx->stream;
+    const F4 one = S::one(), mone = S::neg(S::one());
+    // the circuit template (constraint matrices on the GPU, keyed by structure) and this class's device-side constants
+    CS& like = J.like;
+    like.init_like(src);
+    host::CanonState& scratch = J.scratch;
+    size_t n = src.num_vars, N = host::next_pow2(n);
+    host::Digest& dg = J.dg;
+    Vfe2Ref<C>& ref = J.ref;
+    std::vector<u32>&v2off = J.v2off, &v2q = J.v2q, &v2cid = J.v2cid;
+    std::shared_ptr<void>& tkeep = J.tkeep;
     auto template_for = [&](const CS& rec, const host::CanonState& cst) -> int {   // look up / build (upload + sync) the template of `rec`
         dg = cst.digest(rec.n1, n, rec.num_constraints());
         // a miss with a full cache: the one template this batch needs is the one that is missing, so everything leaves
@@ -1614,7 +1687,7 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
         A4 p3[3];
         static const char* const lab3[3] = {"A_I1", "A_O1", "S1"};
         for (int j = 0; j < 3; j++) {
-            if (!host::Grp<C>::deser_compressed(p3[j], proofs + poff[0] + 33 * j) || !host::TP<C>::validate_and_append_point(t0, lab3[j], p3[j])) {
+            if (!host::Grp<C>::deser_compressed(p3[j], proofs + poff[J.at(0)] + 33 * j) || !host::TP<C>::validate_and_append_point(t0, lab3[j], p3[j])) {
                 ctx->vfe_fallbacks++;   // something the reference rejects: the host replay reports it
                 return BP_OK;
             }
@@ -1665,11 +1738,11 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     }
     const VTemplate<C>& T = *(const VTemplate<C>*)tkeep.get();
     const std::string tkey((const char*)&dg, sizeof dg);
-    const size_t G = ref.labels.size(), ncoef = two ? ref.ncoef : 0;
-    std::shared_ptr<void> ckeep;
-    bool own_coefs = false;
-    const u32 *d_sched = nullptr, *d_voff = nullptr, *d_vq = nullptr, *d_vc = nullptr, *d_iota = nullptr;
-    std::vector<uint32_t> enc2;
+    J.n = n; J.N = N; J.G = ref.labels.size(); J.ncoef = two ? ref.ncoef : 0;
+    std::shared_ptr<void>& ckeep = J.ckeep;
+    bool& own_coefs = J.own_coefs;
+    const u32 *&d_sched = J.d_sched, *&d_voff = J.d_voff, *&d_vq = J.d_vq, *&d_vc = J.d_vc, *&d_iota = J.d_iota;
+    std::vector<uint32_t>& enc2 = J.enc2;
     if (!two) {
         char ckeyb[96];
         snprintf(ckeyb, sizeof ckeyb, "%p/%zu/%zu/%u/%u/%d", (const void*)src.base.get(), m, k, (unsigned)s0->pos, (unsigned)s0->pos_begin, (int)db.absorb_commitments);
@@ -1737,16 +1810,75 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
         HIPCHK(ctx_stream_wait(ctx));   // (the host arrays above are locals)
         d_sched = ctx->vfe2_sched.as<u32>(); d_iota = d_sched + enc2.size(); d_voff = ctx->vfe2_voff.as<u32>(); d_vq = ctx->vfe2_vq.as<u32>(); d_vc = ctx->vfe2_vcid.as<u32>();
     }
-    // staging: [proof bytes | commitments | transcript states], 256-byte aligned parts
+    ok = true;
+    return BP_OK;
+}
+// where the jobs of one call live in the ctx's buffers: one after the other, job order = launch order
+template <class C> static void vfy_dev_place(VfyDevJob<C>* const* jobs, size_t nj, VfyDevTotals& tot) {
     auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_proofs = up256(count * plen), b_V = up256(count * m * vbytes), b_st = up256((db.shared_state ? 1 : count) * 200), b_al = up256(count * 32);
-    const size_t b_in = b_proofs + b_V + b_st + b_al;
-    if (ctx->h_vfe_cap < b_in + 4096) {
+    tot = VfyDevTotals();
+    for (size_t c = 0; c < nj; c++) {
+        VfyDevJob<C>& J = *jobs[c];
+        // staging: [proof bytes | commitments | transcript states | weights], 256-byte aligned parts
+        J.b_proofs = up256(J.count * J.plen); J.b_V = up256(J.count * J.m * J.vbytes); J.b_st = up256((J.db.shared_state ? 1 : J.count) * 200);
+        J.b_in = J.b_proofs + J.b_V + J.b_st + up256(J.count * 32);
+        J.pl.in = tot.b_in; J.pl.msg = tot.msg; J.pl.chal = tot.chal; J.pl.ws = tot.ws; J.pl.inst = tot.inst; J.pl.tail = tot.tail; J.pl.blk = tot.blocks; J.pl.cls = tot.classes;
+        tot.b_in += J.b_in; tot.msg += J.nitems * vfe::ITEM_WORDS * J.count; tot.chal += J.count * (6 + J.k + J.G); tot.ws += J.count * 34; tot.inst += J.count;
+        tot.tail += J.count * J.tail; tot.blocks += J.nblocks; tot.classes++;
+        tot.Nmax = std::max(tot.Nmax, J.N);
+    }
+}
+// every buffer of the call at its final size BEFORE the first launch (a later ensure() could move one under a running kernel), the
+// accumulators, the status word and the per-proof flags zeroed.  Pinned staging: [the jobs' inputs | flags, one word per instance |
+// .. | small results (the last 4096 bytes)].
+static size_t vfy_dev_flags_at(const VfyDevTotals& tot) { return tot.b_in; }
+template <class C> static int vfy_dev_reserve(bp_ctx* ctx, const VfyDevTotals& tot) {
+    hipStream_t st = ctx->stream;
+    const size_t need = tot.b_in + ((tot.inst * 4 + 255) & ~(size_t)255);
+    if (ctx->h_vfe_cap < need + 4096) {
         if (ctx->h_vfe) { HIPCHK(ctx_stream_wait(ctx)); HIPCHK(hipHostFree(ctx->h_vfe)); }
         ctx->h_vfe = nullptr; ctx->h_vfe_cap = 0;
-        HIPCHK(hipHostMalloc(&ctx->h_vfe, b_in + b_in / 8 + 4096));
-        ctx->h_vfe_cap = b_in + b_in / 8 + 4096;
+        HIPCHK(hipHostMalloc(&ctx->h_vfe, need + need / 8 + 4096));
+        ctx->h_vfe_cap = need + need / 8 + 4096;
     }
+    BPCHK(ctx->vfe_in.ensure(tot.b_in));
+    BPCHK(ctx->vfe_msg.ensure(tot.msg * 8));
+    BPCHK(ctx->vfe_chal.ensure(tot.chal * 32));
+    BPCHK(ctx->vfe_ws.ensure(tot.ws * 32));
+    BPCHK(ctx->vfe_small.ensure(4096));
+    BPCHK(ctx->vfe_flags.ensure(std::max<size_t>(tot.inst, 1) * 4));
+    BPCHK(ctx->r_g.ensure((2 + 2 * tot.Nmax + tot.tail) * 32));
+    BPCHK(ctx->r_tail.ensure(std::max<size_t>(tot.tail, 1) * 64));
+    BPCHK(ctx->r_small.ensure((tot.blocks + 8) * 32));
+    BPCHK(ctx->v_alpha.ensure(tot.inst * 32));
+    BPCHK(ctx->v_params.ensure(tot.inst * VFY_PB_WORDS * 4));
+    if (!ctx->sync_ev) HIPCHK(hipEventCreateWithFlags(&ctx->sync_ev, hipEventDisableTiming));
+    HIPCHK(hipMemsetAsync(ctx->r_g.p, 0, (2 + 2 * tot.Nmax) * 32, st));
+    HIPCHK(hipMemsetAsync(ctx->vfe_small.p, 0, 256, st));                  // [status | pad .. | sums at word 64, 16 words per job]
+    HIPCHK(hipMemsetAsync(ctx->vfe_flags.p, 0, std::max<size_t>(tot.inst, 1) * 4, st));
+    return BP_OK;
+}
+// staging and the launch chain of one job: k_vfe_points -> k_vfe_sponge -> prepare -> k_vfy_tables / k_vfy_batch per block.  ok stays
+// false when a two-phase batch declines on the way (its kernels flagged something, a callback recorded another structure).
+template <class C>
+static int vfy_dev_launch(bp_ctx* ctx, VfyDevJob<C>& J, const VfyDevTotals& tot, const uint8_t* proofs, const size_t* poff, const F4* alphas, double* timing, bool& ok) {
+    typedef typename C::Fr FrP;
+    typedef host::Fld<FrP> S;
+    typedef host::ConstraintSystem<C> CS;
+    ok = false;
+    const VfyDevBatch<C>& db = J.db;
+    const CS& src = *db.src;
+    const size_t count = J.count, plen = J.plen, k = J.k, m = J.m, tail = J.tail, nV = J.nV, vbytes = J.vbytes, nitems = J.nitems, nblocks = J.nblocks, N = J.N, G = J.G, ncoef = J.ncoef;
+    const bool two = J.two, wire = J.wire, own_coefs = J.own_coefs;
+    const size_t b_proofs = J.b_proofs, b_V = J.b_V, b_st = J.b_st, b_in = J.b_in;
+    const VfyDevPlace& pl = J.pl;
+    const Vfe2Ref<C>& ref = J.ref;
+    const host::Strobe* s0 = J.s0;
+    const VTemplate<C>& T = *(const VTemplate<C>*)J.tkeep.get();
+    const std::shared_ptr<void>& ckeep = J.ckeep;
+    const u32 *d_voff = J.d_voff, *d_vq = J.d_vq, *d_vc = J.d_vc, *d_iota = J.d_iota, *d_sched = J.d_sched;
+    hipStream_t st = ctx->stream;
+    const F4 one = S::one(), mone = S::neg(S::one());
     // two-phase: [gadget challenges count x G | coefficient tables count x ncoef] (ark words, host form)
     const size_t b_gch = count * G * 32, b_tab = count * ncoef * 32;
     if (two && ctx->h_vfe2_cap < b_gch + b_tab + 64) {
@@ -1757,85 +1889,77 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     }
     F4* h_gch = two ? (F4*)ctx->h_vfe2 : nullptr;
     F4* h_tab = two ? (F4*)((char*)ctx->h_vfe2 + b_gch) : nullptr;
-    uint8_t* hs = (uint8_t*)ctx->h_vfe;
-    uint8_t* h_small = hs + ctx->h_vfe_cap - 4096;      // results: [deltas (<= 96 slots) | sums 2 | status]
+    uint8_t* hs = (uint8_t*)ctx->h_vfe + pl.in;
+    uint8_t* h_small = (uint8_t*)ctx->h_vfe + ctx->h_vfe_cap - 4096;
     {
         const size_t chunk = 64;
         pool_range(ctx, 0, (count + chunk - 1) / chunk, [&](size_t c) {
             const size_t lo = c * chunk, hi = std::min(count, lo + chunk);
-            memcpy(hs + lo * plen, proofs + poff[lo], (hi - lo) * plen);
+            if (!J.idx) memcpy(hs + lo * plen, proofs + poff[lo], (hi - lo) * plen);
             for (size_t i = lo; i < hi; i++) {
+                if (J.idx) { memcpy(hs + i * plen, proofs + poff[J.idx[i]], plen); memcpy(hs + b_proofs + b_V + b_st + i * 32, alphas + J.idx[i], 32); }
                 if (m) memcpy(hs + b_proofs + i * m * vbytes, wire ? (const void*)db.commit_wire(i) : (const void*)db.commit_xy(i), m * vbytes);
                 if (!db.shared_state) memcpy(hs + b_proofs + b_V + i * 200, db.state_of(i)->st.b, 200);
             }
         });
         if (db.shared_state) memcpy(hs + b_proofs + b_V, s0->st.b, 200);
-        memcpy(hs + b_proofs + b_V + b_st, alphas, count * 32);
+        if (!J.idx) memcpy(hs + b_proofs + b_V + b_st, alphas, count * 32);
     }
-    if (timing) timing[4] = now_s() - t_entry;
-    BPCHK(ctx->vfe_in.ensure(b_in));
-    BPCHK(ctx->vfe_msg.ensure(nitems * vfe::ITEM_WORDS * count * 8));
-    BPCHK(ctx->vfe_chal.ensure(count * (6 + k + G) * 32));
-    BPCHK(ctx->vfe_ws.ensure(count * 34 * 32));
-    BPCHK(ctx->vfe_small.ensure(4096));
+    if (timing) timing[4] = now_s() - J.t_entry;
     if (two) { BPCHK(ctx->vfe2_gch.ensure(std::max<size_t>(b_gch, 32))); BPCHK(ctx->vfe2_coef.ensure(std::max<size_t>(b_tab, 32))); }
-    const size_t Ttot = count * tail;
-    BPCHK(ctx->r_g.ensure((2 + 2 * N + Ttot) * 32));
-    BPCHK(ctx->r_tail.ensure(std::max<size_t>(Ttot, 1) * 64));
-    BPCHK(ctx->r_small.ensure((nblocks + 8) * 32));
-    BPCHK(ctx->v_alpha.ensure(count * 32));
-    BPCHK(ctx->v_params.ensure(count * VFY_PB_WORDS * 4));
     u32* sc = ctx->r_g.as<u32>();
-    u32* acc_g = sc + 2 * 8;
-    u32* acc_h = sc + (2 + N) * 8;
-    u32* d_tail_sc = sc + (2 + 2 * N) * 8;
-    u32* d_alpha = ctx->v_alpha.as<u32>();
-    u32* d_status = ctx->vfe_small.as<u32>();            // [status | pad .. | sums at word 64]
-    u32* d_sums = d_status + 64;
-    const uint8_t* d_in = (const uint8_t*)ctx->vfe_in.p;
-    // from here on the stream reads pinned memory of this call: a decline waits for it first (the host replay reuses the buffers)
-    struct Drain { bp_ctx* c; bool armed; ~Drain() { if (armed) (void)hipStreamSynchronize(c->stream); } } drain{ctx, true};
-    HIPCHK(hipMemsetAsync(sc, 0, (2 + 2 * N) * 32, st));
-    HIPCHK(hipMemsetAsync(d_status, 0, 256, st));
-    HIPCHK(hipMemcpyAsync(ctx->vfe_in.p, hs, b_in, hipMemcpyHostToDevice, st));
+    u32* acc_g = sc + 2 * 8;                                   // every job accumulates into the front of the call's g / h accumulators
+    u32* acc_h = sc + (2 + tot.Nmax) * 8;
+    u32* d_tail_sc = sc + (2 + 2 * tot.Nmax + pl.tail) * 8;    // its tails: scalars behind the accumulators, points in r_tail
+    u32* d_tail_pts = ctx->r_tail.as<u32>() + pl.tail * 16;
+    u32* d_alpha = ctx->v_alpha.as<u32>() + pl.inst * 8;
+    u32* d_pb = ctx->v_params.as<u32>() + pl.inst * VFY_PB_WORDS;
+    u32* d_status = ctx->vfe_small.as<u32>();
+    u32* d_sums = d_status + 64 + 16 * pl.cls;
+    u32* d_flags = ctx->vfe_flags.as<u32>() + pl.inst;
+    u32* d_slots = ctx->r_small.as<u32>() + pl.blk * 8;
+    uint64_t* d_msg = (uint64_t*)ctx->vfe_msg.p + pl.msg;
+    u32* d_chal = ctx->vfe_chal.as<u32>() + pl.chal * 8;
+    u32* d_ws = ctx->vfe_ws.as<u32>() + pl.ws * 8;
+    uint8_t* d_in = (uint8_t*)ctx->vfe_in.p + pl.in;
+    HIPCHK(hipMemcpyAsync(d_in, hs, b_in, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((count + 255) / 256)), dim3(256), 0, st, (const u32*)(d_in + b_proofs + b_V + b_st), d_alpha, (u32)count);
     vfe::Shape sh;
     sh.P = (uint32_t)count; sh.m = (uint32_t)m; sh.nV = (uint32_t)nV; sh.k = (uint32_t)k; sh.plen = (uint32_t)plen; sh.tail = (uint32_t)tail; sh.nitems = (uint32_t)nitems;
     sh.G = (uint32_t)G; sh.vwire = wire ? 1u : 0u;
     {
         ScopedK tk(ctx, BP_K_VFE_POINTS);
-        if (vfe::launch_points(C::ID, st, sh, d_in, (const u32*)(d_in + b_proofs), (uint64_t*)ctx->vfe_msg.p, ctx->r_tail.as<u32>(), d_status)) { g_err = "k_vfe_points: launch failed"; return BP_E_HIP; }
+        if (vfe::launch_points(C::ID, st, sh, d_in, (const u32*)(d_in + b_proofs), d_msg, d_tail_pts, d_status, d_flags)) { g_err = "k_vfe_points: launch failed"; return BP_E_HIP; }
     }
     {
         ScopedK tk(ctx, BP_K_VFE_SPONGE);
-        if (vfe::launch_sponge(C::ID, st, sh, d_sched, (const uint64_t*)(d_in + b_proofs + b_V), db.shared_state ? 0u : 25u, (const uint64_t*)ctx->vfe_msg.p,
-                               ctx->vfe_chal.as<u32>(), nullptr, two ? ctx->vfe2_gch.as<u32>() : nullptr)) { g_err = "k_vfe_sponge: launch failed"; return BP_E_HIP; }
+        if (vfe::launch_sponge(C::ID, st, sh, d_sched, (const uint64_t*)(d_in + b_proofs + b_V), db.shared_state ? 0u : 25u, d_msg, d_chal, nullptr,
+                               two ? ctx->vfe2_gch.as<u32>() : nullptr)) { g_err = "k_vfe_sponge: launch failed"; return BP_E_HIP; }
     }
-    if (!ctx->sync_ev) HIPCHK(hipEventCreateWithFlags(&ctx->sync_ev, hipEventDisableTiming));
     if (!two) {
         ScopedK tk(ctx, BP_K_VFE_PREPARE);
-        if (vfe::launch_prepare(C::ID, st, sh, d_in, ctx->vfe_chal.as<u32>(), d_alpha, d_voff, d_vq, d_vc, ctx->v_params.as<u32>(), d_tail_sc,
-                                ctx->vfe_ws.as<u32>(), d_sums)) { g_err = "k_vfe_consts: launch failed"; return BP_E_HIP; }
+        if (vfe::launch_prepare(C::ID, st, sh, d_in, d_chal, d_alpha, d_voff, d_vq, d_vc, d_pb, d_tail_sc,
+                                d_ws, d_sums)) { g_err = "k_vfe_consts: launch failed"; return BP_E_HIP; }
         for (size_t blk = 0; blk < nblocks; blk++) {
             const size_t lo = blk * VFY_BLOCK, nb = std::min(count, lo + VFY_BLOCK) - lo;
             VfeClassDev<C>& cls = *(VfeClassDev<C>*)ckeep.get();
-            BPCHK(verify_launch_template_group<C>(ctx, T, ctx->v_params.as<u32>() + lo * VFY_PB_WORDS, d_iota, own_coefs ? (u32*)cls.coefs.p : nullptr, nb, N, k,
-                                                  acc_g, acc_h, ctx->r_small.as<u32>() + blk * 8, true));
+            BPCHK(verify_launch_template_group<C>(ctx, T, d_pb + lo * VFY_PB_WORDS, d_iota, own_coefs ? (u32*)cls.coefs.p : nullptr, nb, N, k,
+                                                  acc_g, acc_h, d_slots + blk * 8, true));
         }
     } else {
         // the gadget challenges (and the kernels' reject bits) come back while k_vfe_consts runs; the host then runs every instance's
         // callbacks with its challenges, block by block, each block's launches behind its tables
         if (b_gch) HIPCHK(hipMemcpyAsync(h_gch, ctx->vfe2_gch.p, b_gch, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(h_small + 98 * 32, d_status, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_small + VFY_HS_STATUS, d_status, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipEventRecord(ctx->sync_ev, st));
         {
             ScopedK tk(ctx, BP_K_VFE_PREPARE);
-            if (vfe::launch_consts(C::ID, st, sh, d_in, ctx->vfe_chal.as<u32>(), d_alpha, ctx->v_params.as<u32>(), d_tail_sc, ctx->vfe_ws.as<u32>(), d_sums)) {
+            if (vfe::launch_consts(C::ID, st, sh, d_in, d_chal, d_alpha, d_pb, d_tail_sc, d_ws, d_sums)) {
                 g_err = "k_vfe_consts: launch failed"; return BP_E_HIP;
             }
         }
         HIPCHK(vfe_poll(ctx, ctx->sync_ev));
-        u32 status0; memcpy(&status0, h_small + 98 * 32, 4);
+        u32 status0; memcpy(&status0, h_small + VFY_HS_STATUS, 4);
         if (status0) { ctx->vfe_fallbacks++; return BP_OK; }
         for (size_t g = 0; g < G; g++) if (h_gch[g] != ref.chal0[g]) return BP_OK;   // (the device's transcript is not instance 0's: never expected)
         u32* d_coef = ctx->vfe2_coef.as<u32>();
@@ -1885,30 +2009,47 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
             }
             {
                 ScopedK tk(ctx, BP_K_VFE_PREPARE);
-                if (vfe::launch_wv_tab(C::ID, st, sh, (uint32_t)lo, (uint32_t)nb, ctx->v_params.as<u32>(), d_voff, d_vq, d_vc, d_tab, (uint32_t)(ncoef * 8), d_tail_sc)) {
+                if (vfe::launch_wv_tab(C::ID, st, sh, (uint32_t)lo, (uint32_t)nb, d_pb, d_voff, d_vq, d_vc, d_tab, (uint32_t)(ncoef * 8), d_tail_sc)) {
                     g_err = "k_vfe_wv_tab: launch failed"; return BP_E_HIP;
                 }
             }
-            BPCHK(verify_launch_template_group<C>(ctx, T, ctx->v_params.as<u32>() + lo * VFY_PB_WORDS, d_iota, ncoef ? d_tab : nullptr, nb, N, k,
-                                                  acc_g, acc_h, ctx->r_small.as<u32>() + blk * 8, false));
+            BPCHK(verify_launch_template_group<C>(ctx, T, d_pb + lo * VFY_PB_WORDS, d_iota, ncoef ? d_tab : nullptr, nb, N, k,
+                                                  acc_g, acc_h, d_slots + blk * 8, false));
         }
     }
-    hipLaunchKernelGGL(k_scalars_to_canon<FrP>, dim3((u32)((2 * N + 255) / 256)), dim3(256), 0, st, sc + 2 * 8, (u32)(2 * N));
-    HIPCHK(hipMemcpyAsync(h_small, ctx->r_small.p, nblocks * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h_small + 96 * 32, d_sums, 64, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h_small + 98 * 32, d_status, 4, hipMemcpyDeviceToHost, st));
+    ok = true;
+    return BP_OK;
+}
+// After the last job: the accumulators to canonical integers, ONE copy back, ONE polled wait, the head scalars summed on the host,
+// ONE MSM over [pc | G[0..Nmax) | H[0..Nmax) | every job's tails].  flagged: a kernel raised a reject bit (no MSM then; the
+// per-instance flag words are in pinned memory, vfy_dev_flagged reads them).
+template <class C>
+static int vfy_dev_finish(bp_ctx* ctx, VfyDevJob<C>* const* jobs, size_t nj, const VfyDevTotals& tot, VfyDrain& drain, double* timing, J4& r, bool& flagged) {
+    typedef typename C::Fr FrP;
+    typedef host::Fld<FrP> S;
+    hipStream_t st = ctx->stream;
+    flagged = false;
+    u32* sc = ctx->r_g.as<u32>();
+    const u32* d_status = ctx->vfe_small.as<u32>();
+    uint8_t* h_small = (uint8_t*)ctx->h_vfe + ctx->h_vfe_cap - 4096;
+    const size_t Nmax = tot.Nmax, Ttot = tot.tail;
+    hipLaunchKernelGGL(k_scalars_to_canon<FrP>, dim3((u32)((2 * Nmax + 255) / 256)), dim3(256), 0, st, sc + 2 * 8, (u32)(2 * Nmax));
+    HIPCHK(hipMemcpyAsync(h_small, ctx->r_small.p, tot.blocks * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_small + VFY_HS_SUMS, d_status + 64, nj * 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_small + VFY_HS_STATUS, d_status, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync((uint8_t*)ctx->h_vfe + vfy_dev_flags_at(tot), ctx->vfe_flags.p, tot.inst * 4, hipMemcpyDeviceToHost, st));
     const double t_drain = now_s();
-    // ONE wait per batch, ~10 ms long: poll and sleep (HIP's own synchronisation calls busy-wait on this stack: a core per batch in
+    // ONE wait per call, ~10 ms long: poll and sleep (HIP's own synchronisation calls busy-wait on this stack: a core per batch in
     // flight for nothing; see event_wait)
     HIPCHK(hipEventRecord(ctx->sync_ev, st));
     HIPCHK(vfe_poll(ctx, ctx->sync_ev));
     drain.armed = false;
     HIPCHK(hipGetLastError());
-    u32 status; memcpy(&status, h_small + 98 * 32, 4);
-    if (status) { ctx->vfe_fallbacks++; return BP_OK; }   // something the reference rejects: the host replay decides which error, in instance order
-    F4 sB, sBb;
-    memcpy(sB.v, h_small + 96 * 32, 32); memcpy(sBb.v, h_small + 97 * 32, 32);
-    for (size_t j = 0; j < nblocks; j++) { F4 d; memcpy(d.v, h_small + j * 32, 32); sB = S::add(sB, d); }
+    u32 status; memcpy(&status, h_small + VFY_HS_STATUS, 4);
+    if (status) { flagged = true; return BP_OK; }   // something the reference rejects: the host replay decides which error, in instance order
+    F4 sB = S::zero(), sBb = S::zero();
+    for (size_t c = 0; c < nj; c++) { F4 a, b; memcpy(a.v, h_small + VFY_HS_SUMS + c * 64, 32); memcpy(b.v, h_small + VFY_HS_SUMS + c * 64 + 32, 32); sB = S::add(sB, a); sBb = S::add(sBb, b); }
+    for (size_t j = 0; j < tot.blocks; j++) { F4 d; memcpy(d.v, h_small + j * 32, 32); sB = S::add(sB, d); }
     uint64_t head[8];
     canon_words<FrP>(head, sB); canon_words<FrP>(head + 4, sBb);
     HIPCHK(hipMemcpyAsync(sc, head, 64, hipMemcpyHostToDevice, st));
@@ -1916,18 +2057,45 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     BaseSegs sg; memset(&sg, 0, sizeof sg);
     sg.nseg = 4;
     sg.ptr[0] = ctx->d_pc.as<u32>(); sg.ptr[1] = ctx->d_G.as<u32>(); sg.ptr[2] = ctx->d_H.as<u32>(); sg.ptr[3] = ctx->r_tail.as<u32>();
-    sg.start[0] = 0; sg.start[1] = 2; sg.start[2] = (u32)(2 + N); sg.start[3] = (u32)(2 + 2 * N); sg.start[4] = (u32)(2 + 2 * N + Ttot);
-    J4 r;
-    BPCHK(msm_run<C>(ctx, sg, sc, 2 + 2 * N + Ttot, 0, r));
-    const bool ok = host::Grp<C>::is_inf(r);
-    if (point_out) { A4 pt = host::Grp<C>::to_aff(r); memcpy(point_out, pt.x.v, 32); memcpy(point_out + 4, pt.y.v, 32); }
-    const double t_end = now_s();
+    sg.start[0] = 0; sg.start[1] = 2; sg.start[2] = (u32)(2 + Nmax); sg.start[3] = (u32)(2 + 2 * Nmax); sg.start[4] = (u32)(2 + 2 * Nmax + Ttot);
+    BPCHK(msm_run<C>(ctx, sg, sc, 2 + 2 * Nmax + Ttot, 0, r));
+    const double t_end = now_s(), t_entry = jobs[0]->t_entry;
     if (timing) { timing[0] = t_end - t_entry; timing[1] = 0; timing[2] = t_msm - t_drain; timing[3] = t_end - t_msm; }
     if (ctx->profiling) collect_timers(ctx);
+    return BP_OK;
+}
+// the instances the kernels flagged (after a flagged vfy_dev_finish), as instance numbers of the call, ascending
+template <class C> static void vfy_dev_flagged(bp_ctx* ctx, VfyDevJob<C>* const* jobs, size_t nj, const VfyDevTotals& tot, std::vector<uint32_t>& out) {
+    const u32* fl = (const u32*)((const uint8_t*)ctx->h_vfe + vfy_dev_flags_at(tot));
+    for (size_t c = 0; c < nj; c++) for (size_t j = 0; j < jobs[c]->count; j++) if (fl[jobs[c]->pl.inst + j]) out.push_back((uint32_t)jobs[c]->at(j));
+    std::sort(out.begin(), out.end());
+}
+// The whole batch as one job.  flagged (optional): the instances the kernels flagged when the batch is declined for that reason.
+template <class C>
+static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& db, const uint8_t* proofs, const size_t* poff, const F4* alphas, double* timing,
+                               uint64_t* point_out, bool& handled, std::vector<uint32_t>* flagged = nullptr) {
+    handled = false;
+    VfyDevJob<C> J;
+    J.count = count; J.db = db;
+    bool ok = false;
+    BPCHK(vfy_dev_admit<C>(ctx, J, proofs, poff, ok));
+    if (!ok) return BP_OK;
+    VfyDevJob<C>* jobs[1] = {&J};
+    VfyDevTotals tot;
+    vfy_dev_place<C>(jobs, 1, tot);
+    VfyDrain drain{ctx, true};
+    BPCHK(vfy_dev_reserve<C>(ctx, tot));
+    BPCHK(vfy_dev_launch<C>(ctx, J, tot, proofs, poff, alphas, timing, ok));
+    if (!ok) return BP_OK;
+    J4 r;
+    bool bad = false;
+    BPCHK(vfy_dev_finish<C>(ctx, jobs, 1, tot, drain, timing, r, bad));
+    if (bad) { ctx->vfe_fallbacks++; if (flagged) vfy_dev_flagged<C>(ctx, jobs, 1, tot, *flagged); return BP_OK; }
+    if (point_out) { A4 pt = host::Grp<C>::to_aff(r); memcpy(point_out, pt.x.v, 32); memcpy(point_out + 4, pt.y.v, 32); }
     ctx->vfe_batches++;
-    if (wire) ctx->cw_front_end += count * m;
+    if (J.wire) ctx->cw_front_end += count * J.m;
     handled = true;
-    return ok ? BP_OK : BP_E_VERIFICATION;
+    return host::Grp<C>::is_inf(r) ? BP_OK : BP_E_VERIFICATION;
 }
 
 // batch_verify (src/r1cs/verifier.rs:604-691); Verifier::verify (:559-600) is a batch of one with alpha = 1.
@@ -1944,32 +2112,25 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
 // before the mega-check (framing, decompression, verify_prepare).  EVERY such instance of the batch gets its own status — what a
 // batch of that instance alone returns — the others stay BP_OK, and the call returns the first of them in instance order without
 // a mega-check verdict.  When no instance fails that way the statuses are all BP_OK and the return value is the mega-check's.
+//
+// checked (optional): set when the call reached its mega-check, i.e. no instance failed before it.
 template <class C>
-static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& prov, const uint8_t* proofs, const size_t* poff /* count + 1 */, const F4* alphas,
-                             double* timing, uint64_t* point_out, int* inst_status = nullptr) {
+static int batch_verify_host(bp_ctx* ctx, size_t count, const VfyProvider<C>& prov, const uint8_t* proofs, const size_t* poff /* count + 1 */, const F4* alphas,
+                             double* timing, uint64_t* point_out, int* inst_status, bool* checked) {
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
     hipStream_t st = ctx->stream;
     const double t_entry = now_s();
+    if (checked) *checked = false;
     if (point_out) memset(point_out, 0, 64);   // every early exit leaves a defined (identity) check point
     if (inst_status) std::fill(inst_status, inst_status + count, BP_OK);
     static const bool vtrace = getenv("ARKBP_VFY_TRACE") != nullptr;
     double t_last = t_entry;
     auto mark = [&](const char* what) { if (vtrace) { double t = now_s(); fprintf(stderr, "[vfy] %-28s %8.3f ms\n", what, (t - t_last) * 1e3); t_last = t; } };
     host_pool_ensure(ctx, count);
-    // same-shaped single-phase batches: codec, transcript replay and challenge arithmetic on the GPU (batch_verify_device).  It
-    // declines (handled = false) whenever anything is unusual — then the replay below reports what the reference would.
-    if (prov.dev_batch) {
-        VfyDevBatch<C> db;
-        if (prov.dev_batch(db)) {
-            bool handled = false;
-            const int rc = batch_verify_device<C>(ctx, count, db, proofs, poff, alphas, timing, point_out, handled);
-            if (handled || rc) return rc;
-        }
-    }
     if (prov.prologue) {   // pending wire commitments: a rejected encoding is reported before anything the proof bytes would give
         std::vector<int> pst(count, BP_OK);
-        BPCHK(prov.prologue(pst.data()));
+        BPCHK(prov.prologue(nullptr, count, pst.data()));
         int first = BP_OK;
         for (size_t k = 0; k < count && !first; k++) first = pst[k];
         if (first) {
@@ -2309,6 +2470,7 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
         } else (void)hipStreamSynchronize(ctx->aux_stream);
         return first_err;
     }
+    if (checked) *checked = true;
     if (ctx->host_only) {   // dry run: no mega-check; the checksum of everything the host staged comes back in the check point's words
         if (point_out) { memset(point_out, 0, 64); point_out[0] = dry_sum; point_out[1] = count; point_out[2] = nslots; }
         if (timing) { timing[0] = now_s() - t_entry; timing[1] = host_busy; }
@@ -2346,6 +2508,215 @@ static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pr
     if (timing) { timing[0] = t_end - t_entry; timing[1] = host_busy; timing[2] = t_msm - t_drain; timing[3] = t_end - t_msm; }
     if (ctx->profiling) collect_timers(ctx);
     return ok ? BP_OK : BP_E_VERIFICATION;
+}
+
+// ---- batches of several gadgets --------------------------------------------------------------------------------------------------
+// The partition of a batch into device classes: the one place the rule lives (bp_debug_vfy_class_plan is this function).  keys[k]
+// names the class of instance k — equal keys: like-instances of one recording with the same commitment count and form, proof length
+// and transcript position —, eligible[k] = 0 (eligible may be null: all) an instance that stays on the host whatever its class
+// (no shared recording, a two-phase statement).  Classes are ordered by size, largest first, ties by their first member; the first
+// max_classes of them with at least class_min eligible members become device classes 0, 1, .. in that (launch) order.  class_of[k]:
+// the device class of instance k, or -1 for the remainder.
+static constexpr uint64_t VFY_CLASS_MIN_DEFAULT = 65535;   // BP_TUNE_VFY_CLASS_MIN = 0: no class size measured so far beats the host replay of
+                                                           // the same members in the latency of one call (profiles/r15_vfy_mixed.txt; include/arkbp.h)
+static void vfy_class_plan(size_t count, const uint64_t* keys, const uint8_t* eligible, uint64_t class_min, uint32_t max_classes, int32_t* class_of, uint32_t* nclasses) {
+    if (!class_min) class_min = VFY_CLASS_MIN_DEFAULT;
+    class_min = std::min<uint64_t>(class_min, 65535);
+    if (!max_classes) max_classes = BP_VFY_MAX_CLASSES;
+    struct Cls { uint64_t key; size_t first, size; };
+    std::vector<Cls> cls;
+    std::unordered_map<uint64_t, size_t> at;
+    std::vector<size_t> of(count, (size_t)-1);
+    for (size_t k = 0; k < count; k++) {
+        class_of[k] = -1;
+        if (eligible && !eligible[k]) continue;
+        auto it = at.find(keys[k]);
+        if (it == at.end()) { it = at.emplace(keys[k], cls.size()).first; cls.push_back(Cls{keys[k], k, 0}); }
+        cls[it->second].size++;
+        of[k] = it->second;
+    }
+    std::vector<size_t> order(cls.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return cls[a].size != cls[b].size ? cls[a].size > cls[b].size : cls[a].first < cls[b].first; });
+    std::vector<int32_t> num(cls.size(), -1);
+    uint32_t n = 0;
+    for (size_t i = 0; i < order.size() && n < max_classes; i++) if (cls[order[i]].size >= class_min) num[order[i]] = (int32_t)n++;
+    for (size_t k = 0; k < count; k++) if (of[k] != (size_t)-1) class_of[k] = num[of[k]];
+    if (nclasses) *nclasses = n;
+}
+// The host replay of instances idx[0 .. n) of a call (ascending), as a call of its own: their provider with the prologue, their
+// proofs and weights gathered.  st / checked / point as batch_verify_host takes them.
+template <class C>
+static int vfy_host_subset(bp_ctx* ctx, const VfyProvider<C>& prov, const uint32_t* idx, size_t n, const uint8_t* proofs, const size_t* poff, const F4* alphas,
+                           uint64_t* point_out, int* st, bool* checked) {
+    VfyProvider<C> sub;
+    provider_subset_with_prologue<C>(prov, idx, n, sub);
+    sub.dev_batch = nullptr; sub.class_id = nullptr; sub.dev_class = nullptr;
+    std::vector<size_t> spoff(n + 1, 0);
+    for (size_t j = 0; j < n; j++) spoff[j + 1] = spoff[j] + (poff[idx[j] + 1] - poff[idx[j]]);
+    std::vector<uint8_t> buf(spoff[n] ? spoff[n] : 1);
+    std::vector<F4> sal(n);
+    for (size_t j = 0; j < n; j++) { memcpy(buf.data() + spoff[j], proofs + poff[idx[j]], spoff[j + 1] - spoff[j]); sal[j] = alphas[idx[j]]; }
+    return batch_verify_host<C>(ctx, n, sub, buf.data(), spoff.data(), sal.data(), nullptr, point_out, st, checked);
+}
+// A call the device cannot accept because its kernels flagged instances: the host replay of THOSE instances (and whatever else the
+// caller puts into idx: the remainder of a class call), in instance order, gives the whole call's answer — every instance that fails
+// before its check is among them.  done stays false when that replay finds no failing instance (never expected: the device flagged
+// what the host accepts); the caller then replays the whole batch.
+template <class C>
+static int vfy_replay_flagged(bp_ctx* ctx, size_t count, const VfyProvider<C>& prov, const std::vector<uint32_t>& idx, const uint8_t* proofs, const size_t* poff,
+                              const F4* alphas, int* inst_status, bool& done) {
+    done = false;
+    const size_t n = idx.size();
+    bool checked = false;
+    if (!inst_status) {   // the first error as the reference orders them (every FormatError before any VerificationError)
+        const int rc = vfy_host_subset<C>(ctx, prov, idx.data(), n, proofs, poff, alphas, nullptr, nullptr, &checked);
+        if (checked || !rc) return BP_OK;
+        done = true;
+        return rc;
+    }
+    std::vector<int> st(n, BP_OK);
+    const int rc = vfy_host_subset<C>(ctx, prov, idx.data(), n, proofs, poff, alphas, nullptr, st.data(), &checked);
+    bool any = false;
+    for (size_t j = 0; j < n; j++) any = any || st[j] != BP_OK;
+    if (!any) return rc == BP_E_VERIFICATION ? BP_OK : rc;   // (its mega-check says nothing about the call's)
+    std::fill(inst_status, inst_status + count, BP_OK);
+    for (size_t j = 0; j < n; j++) inst_status[idx[j]] = st[j];
+    done = true;
+    return rc;
+}
+// A batch that is not one class of like-instances: the classes vfy_class_plan names run on the device as ONE launch chain with one
+// pair of accumulators, one tail array, one wait and one MSM; everything else (the remainder) is one host replay with its own check
+// point.  The call's check point is the group sum of the two — by linearity the reference's single MSM (verifier.rs:685).  done
+// stays false when no class runs on the device (the caller replays the whole batch, and nothing is counted).
+template <class C>
+static int batch_verify_classes(bp_ctx* ctx, size_t count, const VfyProvider<C>& prov, const uint8_t* proofs, const size_t* poff, const F4* alphas, double* timing,
+                                uint64_t* point_out, int* inst_status, bool& done) {
+    done = false;
+    if (!vfy_device_on(ctx) || count < 2 || count >= ((size_t)1 << 31)) return BP_OK;
+    // keys: the providers' ids and the proof lengths, numbered in order of appearance
+    std::vector<uint64_t> keys(count, 0);
+    std::vector<uint8_t> elig(count, 0);
+    {
+        typedef std::tuple<const void*, size_t, size_t, unsigned, unsigned, unsigned> Id;
+        std::map<Id, uint64_t> ids;
+        Id last{};
+        uint64_t last_key = 0;
+        for (size_t k = 0; k < count; k++) {
+            VfyClassId id;
+            if (!prov.class_id(k, id) || !id.rec) continue;
+            const Id t{id.rec, id.m, poff[k + 1] - poff[k], (id.wire ? 1u : 0u) | (id.two ? 2u : 0u), id.pos, id.pos_begin};
+            if (!last_key || t != last) { last = t; last_key = ids.emplace(t, ids.size() + 1).first->second; }
+            keys[k] = last_key;
+            elig[k] = id.two ? 0 : 1;   // (two-phase classes stay on the host replay)
+        }
+    }
+    std::vector<int32_t> class_of(count);
+    uint32_t ncls = 0;
+    vfy_class_plan(count, keys.data(), elig.data(), ctx->tune_vfy_class_min, BP_VFY_MAX_CLASSES, class_of.data(), &ncls);
+    if (!ncls) return BP_OK;
+    std::vector<std::vector<uint32_t>> members(ncls);
+    for (size_t k = 0; k < count; k++) if (class_of[k] >= 0) members[class_of[k]].push_back((uint32_t)k);
+    // the classes the device front end admits, in launch order, while their blocks and tails fit the call's one set of buffers
+    std::vector<std::unique_ptr<VfyDevJob<C>>> owned;
+    std::vector<VfyDevJob<C>*> jobs;
+    std::vector<char> on_device(count, 0);
+    {
+        size_t blocks = 0, tails = 0;
+        for (uint32_t c = 0; c < ncls; c++) {
+            std::unique_ptr<VfyDevJob<C>> J(new VfyDevJob<C>());
+            J->count = members[c].size(); J->idx = members[c].data();
+            if (!prov.dev_class(J->idx, J->count, J->db)) continue;
+            bool ok = false;
+            BPCHK(vfy_dev_admit<C>(ctx, *J, proofs, poff, ok));
+            if (!ok || J->two) continue;
+            if (blocks + J->nblocks > VFY_SLOTS || tails + J->count * J->tail + 2 + 2 * std::max<size_t>(J->N, 1) >= ((size_t)1 << 30)) continue;
+            blocks += J->nblocks; tails += J->count * J->tail;
+            for (uint32_t k : members[c]) on_device[k] = 1;
+            jobs.push_back(J.get());
+            owned.push_back(std::move(J));
+        }
+    }
+    if (jobs.empty()) return BP_OK;
+    std::vector<uint32_t> rest;
+    for (size_t k = 0; k < count; k++) if (!on_device[k]) rest.push_back((uint32_t)k);
+    VfyDevTotals tot;
+    vfy_dev_place<C>(jobs.data(), jobs.size(), tot);
+    J4 r;
+    bool bad = false;
+    {
+        VfyDrain drain{ctx, true};
+        BPCHK(vfy_dev_reserve<C>(ctx, tot));
+        for (VfyDevJob<C>* J : jobs) {
+            bool ok = false;
+            BPCHK(vfy_dev_launch<C>(ctx, *J, tot, proofs, poff, alphas, jobs.size() == 1 ? timing : nullptr, ok));
+            if (!ok) return BP_OK;   // (single-phase jobs do not decline on the way)
+        }
+        BPCHK(vfy_dev_finish<C>(ctx, jobs.data(), jobs.size(), tot, drain, timing, r, bad));
+    }
+    ctx->vcl_calls++;
+    ctx->vcl_remainder += rest.size();
+    if (bad) {
+        std::vector<uint32_t> sub;
+        vfy_dev_flagged<C>(ctx, jobs.data(), jobs.size(), tot, sub);
+        ctx->vfe_fallbacks++;
+        sub.insert(sub.end(), rest.begin(), rest.end());
+        std::sort(sub.begin(), sub.end());
+        ctx->vcl_flagged += sub.size();   // (the flagged instances and the remainder are replayed as one subset)
+        return vfy_replay_flagged<C>(ctx, count, prov, sub, proofs, poff, alphas, inst_status, done);
+    }
+    ctx->vcl_classes += jobs.size();
+    for (VfyDevJob<C>* J : jobs) { ctx->vcl_instances += J->count; if (J->wire) ctx->cw_front_end += J->count * J->m; }
+    done = true;
+    if (!rest.empty()) {
+        uint64_t pt[8];
+        std::vector<int> st(inst_status ? rest.size() : 0);
+        bool checked = false;
+        const int rc = vfy_host_subset<C>(ctx, prov, rest.data(), rest.size(), proofs, poff, alphas, pt, inst_status ? st.data() : nullptr, &checked);
+        if (inst_status) for (size_t j = 0; j < rest.size(); j++) inst_status[rest[j]] = st[j];
+        if (!checked || (rc && rc != BP_E_VERIFICATION)) return rc;   // an instance failed before its check (or the call itself did): no verdict of the sum
+        A4 p;
+        memcpy(p.x.v, pt, 32); memcpy(p.y.v, pt + 4, 32);
+        r = host::Grp<C>::madd(r, p);
+    }
+    if (point_out) { A4 pt = host::Grp<C>::to_aff(r); memcpy(point_out, pt.x.v, 32); memcpy(point_out + 4, pt.y.v, 32); }
+    return host::Grp<C>::is_inf(r) ? BP_OK : BP_E_VERIFICATION;
+}
+
+// The entry of every batch verification.  A batch of like-instances of one recording goes to the device front end as a whole
+// (batch_verify_device), a batch of several gadgets class by class (batch_verify_classes); whatever neither takes, and whatever they
+// decline, is the host replay's (batch_verify_host).  A call whose only obstacle is a proof the kernels flagged replays just the
+// flagged instances.  The answers are the host replay's in every case.
+template <class C>
+static int batch_verify_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& prov, const uint8_t* proofs, const size_t* poff /* count + 1 */, const F4* alphas,
+                             double* timing, uint64_t* point_out, int* inst_status = nullptr) {
+    if (point_out) memset(point_out, 0, 64);   // every early exit leaves a defined (identity) check point
+    if (inst_status) std::fill(inst_status, inst_status + count, BP_OK);
+    host_pool_ensure(ctx, count);
+    // same-shaped single-phase batches: codec, transcript replay and challenge arithmetic on the GPU (batch_verify_device).  It
+    // declines (handled = false) whenever anything is unusual — then the replay below reports what the reference would.
+    if (prov.dev_batch) {
+        VfyDevBatch<C> db;
+        if (prov.dev_batch(db)) {
+            bool handled = false;
+            std::vector<uint32_t> flagged;
+            const int rc = batch_verify_device<C>(ctx, count, db, proofs, poff, alphas, timing, point_out, handled, &flagged);
+            if (handled || rc) return rc;
+            if (!flagged.empty()) {
+                ctx->vcl_flagged += flagged.size();
+                bool done = false;
+                const int frc = vfy_replay_flagged<C>(ctx, count, prov, flagged, proofs, poff, alphas, inst_status, done);
+                if (done || frc) return frc;
+            }
+        } else if (prov.class_id && prov.dev_class) {
+            bool done = false;
+            const int rc = batch_verify_classes<C>(ctx, count, prov, proofs, poff, alphas, timing, point_out, inst_status, done);
+            if (done || rc) return rc;
+            if (point_out) memset(point_out, 0, 64);
+            if (inst_status) std::fill(inst_status, inst_status + count, BP_OK);
+        }
+    }
+    return batch_verify_host<C>(ctx, count, prov, proofs, poff, alphas, timing, point_out, inst_status, nullptr);
 }
 
 // what batch_verify_scenarios hands its provider to: batch_verify_core, or another core over the same instances (verify_each.inc)
@@ -2449,6 +2820,8 @@ static int batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenario
                    (!npubs[a] || !memcmp(publics + 4 * uoff[a], publics + 4 * uoff[b], npubs[a] * 32));
         };
         struct Cls { size_t rep, uses; std::shared_ptr<ScenarioSource<C>> s; bool resolved; };
+        // (a one-off statement gets a source of its own only where it can be a device class: BP_TUNE_VFY_CLASS_MIN = 1)
+        const size_t src_min = count > 1 && ctx->tune_vfy_class_min == 1 && vfy_device_on(ctx) ? 1 : 2;
         std::unordered_map<u64, std::vector<Cls>> classes;   // (a vector per hash: distinct shapes with equal hashes stay apart)
         std::vector<Cls*> cls_of(count, nullptr);
         classes.reserve(64);
@@ -2467,7 +2840,7 @@ static int batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenario
             const std::string key = scenario_key<C>(scenarios[k], params + 8 * k, publics + 4 * uoff[k], npubs[k]);
             auto it = ctx->scenario_sources.find(key);
             if (it != ctx->scenario_sources.end()) { c.s = std::static_pointer_cast<ScenarioSource<C>>(it->second); src[k] = c.s; continue; }
-            if (c.uses < 2) continue;
+            if (c.uses < src_min) continue;
             auto s = std::make_shared<ScenarioSource<C>>();
             s->tr = host::Transcript(host::scenario_label(scenarios[k]));
             host::StatementIO io; make_io(k, io);
@@ -2530,6 +2903,27 @@ static int batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenario
         db.src = &src[0]->cs; db.m = ms[0]; db.absorb_commitments = true; db.shared_state = true;
         db.state_of = [&](size_t) { return (const host::Strobe*)&proto.s; };
         db.commit_xy = [&](size_t k) { return commit_xy + 8 * coff[k]; };
+        return true;
+    };
+    // several statement shapes: an instance's class is its source recording; a class takes its transcripts from its own prefix state
+    std::deque<host::Transcript> protos;
+    prov.class_id = [&](size_t k, VfyClassId& id) -> bool {
+        if (!src[k] || src[k]->m != ms[k]) return false;
+        id.rec = src[k].get(); id.m = ms[k]; id.two = !src[k]->cs.deferred.empty();
+        return true;
+    };
+    prov.dev_class = [&](const uint32_t* idx, size_t, VfyDevBatch<C>& db) -> bool {
+        const size_t k0 = idx[0];
+        host::Transcript pr(host::scenario_label(scenarios[k0]));
+        host::TP<C>::r1cs_domain_sep(pr);
+        host::StatementIO io0; make_io(k0, io0);
+        size_t expect = 0;
+        if (host::scenario_verifier_prefix<C>(pr, scenarios[k0], params + 8 * k0, io0, &expect) || expect != ms[k0]) return false;
+        protos.push_back(pr);
+        const host::Strobe* state = &protos.back().s;
+        db.src = &src[k0]->cs; db.m = ms[k0]; db.absorb_commitments = true; db.shared_state = true;
+        db.state_of = [state](size_t) { return state; };
+        db.commit_xy = [&, idx](size_t j) { return commit_xy + 8 * coff[idx[j]]; };
         return true;
     };
     if (other_core) return (*other_core)(prov, poff.data(), alphas.data());

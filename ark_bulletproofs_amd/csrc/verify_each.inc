@@ -186,7 +186,7 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
     host_pool_ensure(ctx, count);
     // 0. pending wire commitments: decoded and committed first; an instance with a rejected encoding is left out with BP_E_FORMAT
     std::vector<int> pst(count, BP_OK);
-    if (prov.prologue) BPCHK(prov.prologue(pst.data()));
+    if (prov.prologue) BPCHK(prov.prologue(nullptr, count, pst.data()));
     // 1. framing; the proof's claim decides the route
     std::vector<host::LazyProof> lps(count);
     std::vector<int> prc(count, BP_OK);

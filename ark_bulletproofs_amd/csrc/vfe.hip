@@ -62,13 +62,14 @@ template <class F> __device__ __forceinline__ u32 y_sign_flag(const Fe& y_rform_
 // Thread order: the (11 + 2k) * P proof points first (point-major: consecutive lanes = consecutive proofs, so the waves that take
 // square roots are full and their item stores coalesce), then the m * P commitments, then 5 * P scalars.
 template <class C> __global__ void __launch_bounds__(256)
-k_vfe_points(Shape sh, const u8* __restrict__ proofs, const u32* __restrict__ V, u64* __restrict__ msg, u32* __restrict__ tail_pts, u32* __restrict__ status) {
+k_vfe_points(Shape sh, const u8* __restrict__ proofs, const u32* __restrict__ V, u64* __restrict__ msg, u32* __restrict__ tail_pts, u32* __restrict__ status,
+             u32* __restrict__ flags) {
     typedef typename C::Fq F;
     typedef typename C::Fr S;
     const u32 P = sh.P, k = sh.k, m = sh.m;
     const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u64 n_pp = (u64)(11 + 2 * k) * P, n_v = (u64)m * P, n_s = (u64)5 * P;
-    u32 bad = 0;
+    u32 bad = 0, bad_p = 0;   // reject bits of this thread's element, and the proof it belongs to
     const bool wire_v = sh.vwire && gid >= n_pp && gid < n_pp + n_v;   // a commitment in its 33-byte wire form: decoded as the proof points are
     if (gid < n_pp || wire_v) {
         u32 j, p, slot, item;
@@ -130,6 +131,7 @@ k_vfe_points(Shape sh, const u8* __restrict__ proofs, const u32* __restrict__ V,
                 flag_out = y_sign_flag<F>(a.y);
             }
         }
+        bad_p = p;
         if (!wire_v || sh.nV) store_item(msg, P, item, p, xw, yw, flag_out);
         u32* tp = tail_pts + ((size_t)p * sh.tail + slot) * 16;
         store_words8(tp, o);
@@ -162,10 +164,13 @@ k_vfe_points(Shape sh, const u8* __restrict__ proofs, const u32* __restrict__ V,
         load_le_words8(w, pr + off);
 #pragma unroll
         for (int i = 0; i < 8; i++) z[i] = 0;
-        if (!words_lt_p<S>(w)) bad |= ST_FORMAT;
+        if (!words_lt_p<S>(w)) { bad |= ST_FORMAT; bad_p = p; }
         if (j < 3) store_item(msg, P, sh.nV + 11 + 2 * k + j, p, w, z, 0);   // (only the first 32 bytes of a scalar item are absorbed)
     }
-    if (bad) atomicOr(status, bad);
+    if (bad) {   // (rare: one atomic per rejected element)
+        atomicOr(status, bad);
+        if (flags) atomicOr(flags + bad_p, bad);
+    }
 }
 
 // ---- Keccak-f[1600], one state per lane ---------------------------------------------------------------------------------
@@ -430,9 +435,9 @@ k_vfe_sum2(const u32* __restrict__ in, u32 P, u32* __restrict__ sums) {
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
-template <class C> static int t_points(hipStream_t st, const Shape& sh, const u8* d_proofs, const u32* d_V, u64* d_msg, u32* d_tail_pts, u32* d_status) {
+template <class C> static int t_points(hipStream_t st, const Shape& sh, const u8* d_proofs, const u32* d_V, u64* d_msg, u32* d_tail_pts, u32* d_status, u32* d_flags) {
     const u64 total = (u64)(11 + 2 * sh.k + sh.m + 5) * sh.P;
-    hipLaunchKernelGGL(k_vfe_points<C>, dim3((u32)((total + 255) / 256)), dim3(256), 0, st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status);
+    hipLaunchKernelGGL(k_vfe_points<C>, dim3((u32)((total + 255) / 256)), dim3(256), 0, st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status, d_flags);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 template <class C> static int t_sponge(hipStream_t st, const Shape& sh, const u32* d_sched, const u64* d_state0, u32 stride, const u64* d_msg, u32* d_chal, u8* d_seeds,
@@ -464,8 +469,9 @@ template <class C> static int t_wv_tab(hipStream_t st, const Shape& sh, u32 p0, 
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int launch_points(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_V, uint64_t* d_msg, uint32_t* d_tail_pts, uint32_t* d_status) {
-    return curve == 0 ? t_points<Secq>(st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status) : t_points<Zorro>(st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status);
+int launch_points(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_V, uint64_t* d_msg, uint32_t* d_tail_pts, uint32_t* d_status,
+                  uint32_t* d_flags) {
+    return curve == 0 ? t_points<Secq>(st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status, d_flags) : t_points<Zorro>(st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status, d_flags);
 }
 int launch_sponge(int curve, hipStream_t st, const Shape& sh, const uint32_t* d_sched, const uint64_t* d_state0, uint32_t state_stride, const uint64_t* d_msg, uint32_t* d_chal,
                   uint8_t* d_seeds_or_null, uint32_t* d_gch) {

@@ -34,7 +34,9 @@ static constexpr uint32_t ST_FRAMING = 4;       // L_vec / R_vec length fields d
 //   d_msg      nitems x 9 x P 64-bit words: word w of item `it` of proof p at [(it * 9 + w) * P + p]
 //   d_tail_pts P x tail x 16 words, resident layout, the mega-check's per-proof bases in verification_scalars' order
 //   d_status   one word, OR of ST_*
-int launch_points(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_V, uint64_t* d_msg, uint32_t* d_tail_pts, uint32_t* d_status);
+//   d_flags    P words (may be null): the same bits per proof — word p holds what proof p raised
+int launch_points(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_proofs, const uint32_t* d_V, uint64_t* d_msg, uint32_t* d_tail_pts, uint32_t* d_status,
+                  uint32_t* d_flags);
 
 // k_vfe_sponge: one lane per proof runs the schedule (vfe_sched.hpp) from its transcript state; d_state0: 25 words per proof
 // (state_stride = 25) or one shared state (0).  d_chal: P x (6 + k + G) x 8 words, resident form, order y z u x w u_1..u_k r g_1..g_G.

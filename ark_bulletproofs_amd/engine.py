@@ -1193,6 +1193,35 @@ def _vfe_stats(self):
 Engine.debug_vfe_challenges = _debug_vfe_challenges
 Engine.vfe_stats = _vfe_stats
 
+# batches of several gadgets: classes of like-instances inside one call (include/arkbp.h "Batches of several gadgets")
+TUNE_VFY_CLASS_MIN = 24              # include/arkbp.h BP_TUNE_VFY_CLASS_MIN (Engine.set_tuning; 0 = default, 1 = every class)
+VFY_MAX_CLASSES = 8                  # BP_VFY_MAX_CLASSES
+
+
+def _vfe_class_stats(self):
+    """(calls that took the class path, classes the device finished, their members, instances the host replay took in such calls,
+    instances replayed because the device flagged something) since ctx creation (bp_ctx_vfe_class_stats)"""
+    v = [C.c_uint64(0) for _ in range(5)]
+    check(lib().bp_ctx_vfe_class_stats(self.ctx, *[C.byref(x) for x in v]), "bp_ctx_vfe_class_stats")
+    return tuple(x.value for x in v)
+
+
+def debug_vfy_class_plan(keys, eligible=None, class_min=0, max_classes=0):
+    """host only (bp_debug_vfy_class_plan): the partition of a batch into device classes.  keys: one 64-bit class key per instance;
+    eligible: one truth value per instance (None: all).  class_min / max_classes 0 = the defaults.  Returns (class_of, nclasses):
+    class_of[k] is the device class of instance k in launch order, or -1 for the remainder."""
+    n = len(keys)
+    ks = np.ascontiguousarray(list(keys) + [0], dtype=np.uint64)
+    el = None if eligible is None else np.ascontiguousarray([1 if x else 0 for x in eligible] + [0], dtype=np.uint8)
+    out = np.full(n + 1, -2, dtype=np.int32)
+    nc = C.c_uint32(0)
+    check(lib().bp_debug_vfy_class_plan(C.c_size_t(n), ptr(ks), ptr(el) if el is not None else None, C.c_uint64(class_min), C.c_uint32(max_classes), ptr(out), C.byref(nc)),
+          "bp_debug_vfy_class_plan")
+    return [int(x) for x in out[:n]], nc.value
+
+
+Engine.vfe_class_stats = _vfe_class_stats
+
 
 def debug_verify_challenges(curve, instances, use_x8):
     """host only: the challenge sequences of up to eight scenario verifications (bp_debug_verify_challenges).  Returns a list of

@@ -623,7 +623,11 @@ int bp_verifier_verify(bp_ctx* ctx, bp_cs* verifier, const uint8_t* proof, size_
  * two invalid proofs can cancel in the one mega-check); NULL is accepted for count == 1 only (Verifier::verify, weight 1).  The same
  * handle twice in one batch is BP_E_ARG at any count.  A verifier created by bp_verifier_new_like that holds fewer commitments than
  * the shared constraints name is BP_E_ARG (the reference would index past its V vector).  check_point_xy (may be NULL): the value
- * of the mega-check MSM, all-zero iff it is the identity.  timing (5 doubles, may be NULL) as in bp_r1cs_batch_verify_scenarios. */
+ * of the mega-check MSM, all-zero iff it is the identity.  timing (5 doubles, may be NULL) as in bp_r1cs_batch_verify_scenarios.
+ * A batch of like-instances of one recording (bp_verifier_new_like) runs its per-proof front end on the GPU as a whole; a batch that
+ * mixes several recordings runs every large enough class of like-instances there and the rest on the host, in one call with one
+ * check point ("verifier front end on the device", "Batches of several gadgets" below).  Return value, check point and errors never
+ * depend on which of the paths a call took. */
 int bp_r1cs_batch_verify(bp_ctx* ctx, size_t count, bp_cs* const* verifiers, const uint8_t* proofs, const size_t* proof_lens, const uint64_t* alphas,
                          double* timing, uint64_t* check_point_xy);
 /* The next instance of the SAME gadget without recording it again: a verifier that shares `of`'s phase-1 constraints and its
@@ -836,6 +840,10 @@ int bp_ctx_reset_profiling(bp_ctx* ctx);
                                     * 0: one MSM after the other (A/B, tests).  Results never depend on it */
 #define BP_TUNE_VERIFY_LOCATE_LEAF 22 /* bp_r1cs_batch_verify_locate: a failing subset of at most this many instances is decided by the machinery of
                                       * bp_verifier_verify_batch instead of being split further (0 = default: 1, pure bisection; at most 4096) */
+#define BP_TUNE_VFY_CLASS_MIN 24   /* (23, like 20, stays unassigned: tests/test_verify_locate_cpu.py pins it as refused.)  Batches of several gadgets: the
+                                    * fewest members a class of like-instances needs to run its front end on the device; smaller classes join the host
+                                    * replay of the call's remainder.  0 = default: 65535, i.e. the class path is OPT-IN — measured, see "Batches of
+                                    * several gadgets" below; 1 = every class; values above 65535 act as 65535.  Results never depend on it */
 int bp_ctx_set_tuning(bp_ctx* ctx, int knob, uint64_t value);
 
 /* The O(N) part of `Verifier::verification_scalars` (src/r1cs/verifier.rs:465-514, s from inner_product_proof.rs:279-311) for a
@@ -871,7 +879,8 @@ int bp_debug_glv_decompose(int curve, const uint64_t t[4], uint32_t masks[20], u
  * (src/r1cs/proof.rs:83-91), the merlin transcript replay of verification_scalars (verifier.rs:403-460, 516-519;
  * src/inner_product_proof.rs:266-280; src/transcript.rs:45-102: Keccak-f[1600] / STROBE-128 / ChaCha20 -> Fr::rand) and the
  * O(k + m) challenge arithmetic (:462-541).  Anything unusual (malformed bytes, an identity point that
- * validate_and_append_point rejects, mixed shapes) takes the host replay instead, which reports the reference's error.
+ * validate_and_append_point rejects) takes the host replay instead, which reports the reference's error; see "A reject flag per
+ * proof" and "Batches of several gadgets" below for how much of the batch that is.
  * ARKBP_VFY_HOST=1 in the environment forces the host replay (A/B).
  * Two-phase statements (randomized constraints) take this path with BP_TUNE_VFY_DEVICE = 2 only: the device derives every
  * challenge, the gadget challenges of the callbacks included; the host then runs each instance's callbacks with its own
@@ -896,7 +905,48 @@ int bp_debug_glv_decompose(int curve, const uint64_t t[4], uint32_t masks[20], u
  * labels[0..nlabels) in this order ("r1cs-2phase" separator after S1, the squeezes before A_I2); seeds_out: (6 + k + nlabels) x 32
  * bytes in the order y z u x w u_1..u_k r g_1..g_nlabels.
  * bp_ctx_vfe_stats: batches the device front end completed / batches it handed to the host replay on this ctx (two-phase
- * batches included). */
+ * batches included).
+ *
+ * A reject flag per proof.  Beside the batch-wide status word k_vfe_points keeps one word per proof with the same bits.  A call
+ * whose only obstacle is a flagged proof cannot succeed, so it runs no mega-check: the host replays ONLY the flagged instances (in
+ * instance order, as a batch of their own) and the call returns what that replay returns — the host replay's answer for the whole
+ * batch, because every instance that fails before its check is among them.  Should that replay find nothing wrong (never expected),
+ * the whole batch is replayed as before.  Such a call still counts one host_fallback and no device_batch.  Two-phase batches
+ * (BP_TUNE_VFY_DEVICE = 2) learn of a flag in the middle of their chain and replay the whole batch.
+ *
+ * Batches of several gadgets.  A verifying service sees a few gadget shapes mixed in arrival order.  When the batch as a whole is not
+ * one class of like-instances, the instances are partitioned: like-instances share the recording (cs->base of a handle, the source
+ * of a scenario statement), the commitment count and form (affine, or wire bytes still pending), the proof length, the transcript
+ * position, and being single-phase.  Classes are ordered by size, largest first, ties by their first member; the largest
+ * BP_VFY_MAX_CLASSES classes with at least BP_TUNE_VFY_CLASS_MIN members become DEVICE CLASSES.  They run back to back on the
+ * ctx's stream — k_vfe_points, k_vfe_sponge, the challenge arithmetic, k_vfy_tables / k_vfy_batch per block of 512, each class on
+ * its own slice of one staging area — into ONE pair of g / h accumulators sized for the largest N, ONE tail array, with one result
+ * slot per class and block (96 blocks per call over all classes); then one copy back, ONE wait, ONE mega-check MSM.  Everything
+ * else is the REMAINDER: smaller classes, classes beyond the eighth or beyond the 96 blocks, two-phase classes (they stay on the
+ * host replay, whatever BP_TUNE_VFY_DEVICE says), instances without a shared recording, and every member of a class the front end's
+ * own entry conditions decline (k >= 32, too few generators, N != 2^k, the 2^31 limits).  The remainder is ONE host replay with its
+ * own check point; pending wire commitments are decoded and committed for its members only, a device class keeps its bytes
+ * pending.  The call's check point is the group sum of the two points, which by linearity is the reference's single MSM
+ * (verifier.rs:685); the batch is accepted iff no instance failed before its check and that sum is the identity.  A flagged
+ * proof in a device class is handled as above: the flagged instances and the remainder are replayed as one subset.  The passes of
+ * bp_r1cs_batch_verify_locate take the same path.  A sharded ctx, ARKBP_VFY_HOST and BP_TUNE_VFY_DEVICE = 0 keep the host replay.
+ * The default of BP_TUNE_VFY_CLASS_MIN is 65535: measured against the host replay of the same members (tools/exp_vfy_mixed.py,
+ * profiles/r15_vfy_mixed.txt; one run on one MI355X, 16 host threads, one call at a time), two classes of cfg4's statement with 8 .. 512
+ * members each were SLOWER on the device at every size (7.6 against 1.4 ms at 8, 11.6 against 5.4 ms at 512; 2 x 2048: 21.6 against
+ * 16.0 ms), so no crossover exists in that range and the class path is opt-in.  Each class adds the latency of its own k_vfe_sponge
+ * (about 3 ms, one lane per proof, whatever the class size) to the one stream.  The host threads a call keeps busy were not
+ * measured: a device class costs the host one staging memcpy, the host replay a transcript replay per proof on the ctx's pool.  A
+ * service for which that matters more than one call's latency sets the knob to the smallest class it wants on the device.
+ * bp_ctx_vfe_class_stats, since ctx creation: calls that took the class path / classes the device finished / their members /
+ * instances the host replay took in such calls / instances replayed because the device flagged something, on either path (in a class
+ * call: the flagged ones and the remainder, which are replayed together).  bp_ctx_vfe_stats is not touched by an unflagged class call.
+ * bp_debug_vfy_class_plan (host only): the partition itself.  keys: one 64-bit class key per instance; eligible (may be NULL: all):
+ * 0 keeps an instance in the remainder; class_min / max_classes: 0 = the defaults (the knob's, BP_VFY_MAX_CLASSES).  class_of[k]:
+ * the device class of instance k in launch order, or -1 for the remainder; *nclasses: device classes. */
+#define BP_VFY_MAX_CLASSES 8
+int bp_ctx_vfe_class_stats(bp_ctx* ctx, uint64_t* class_calls, uint64_t* device_classes, uint64_t* device_instances, uint64_t* remainder_instances,
+                           uint64_t* flagged_replayed);
+int bp_debug_vfy_class_plan(size_t count, const uint64_t* keys, const uint8_t* eligible, uint64_t class_min, uint32_t max_classes, int32_t* class_of, uint32_t* nclasses);
 int bp_debug_vfe_schedule_replay(const uint8_t state203[203], int absorb_commitments, uint64_t m, uint32_t k, uint64_t n, const uint8_t* items, uint8_t* seeds_out,
                                  uint32_t* nblocks_out);
 int bp_debug_vfe_schedule_replay_2phase(const uint8_t state203[203], int absorb_commitments, uint64_t m, uint32_t k, uint64_t n, const char* const* labels, size_t nlabels,
