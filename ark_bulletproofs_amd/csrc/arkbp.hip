@@ -24,6 +24,7 @@
 #include <atomic>
 #include <chrono>
 #include "host_proto.hpp"
+#include "prove_steps.hpp"
 #include "r1cs.cuh"
 #include "pedersen.cuh"
 #include "small.cuh"
@@ -39,6 +40,10 @@ using namespace arkbp;
 using arkbp::host::A4;
 using arkbp::host::F4;
 using arkbp::host::J4;
+using arkbp::host::HostCsc;
+using arkbp::host::build_host_csc;
+using arkbp::host::jac_from_words;
+using arkbp::host::to_aff_many;
 
 static thread_local std::string g_err;
 const char* bp_last_error(void) { return g_err.c_str(); }
@@ -180,6 +185,15 @@ struct DevBuf {
     void release() { if (p && owned) (void)hipFree(p); p = nullptr; cap = 0; owned = true; }
     template <class T> T* as() { return (T*)p; }
 };
+// Pinned host staging that only grows: at least `bytes`, allocated with `slack` bytes on top (each site's own rule)
+static int pinned_ensure(void*& p, size_t& cap, size_t bytes, size_t slack) {
+    if (cap >= bytes) return BP_OK;
+    if (p) HIPCHK(hipHostFree(p));
+    p = nullptr; cap = 0;
+    HIPCHK(hipHostMalloc(&p, bytes + slack));
+    cap = bytes + slack;
+    return BP_OK;
+}
 
 struct KTimer {
     double ms = 0;
@@ -1881,7 +1895,7 @@ template <class C> static void msm_direct_collect(bp_ctx* ctx, int nout, J4* res
         J4 acc = G::inf();
         for (u32 j = 0; j < np; j++) {
             const u64* P = T + 12 * ((size_t)o * np + j);
-            J4 pnt; memcpy(pnt.X.v, P, 32); memcpy(pnt.Y.v, P + 4, 32); memcpy(pnt.Z.v, P + 8, 32);
+            const J4 pnt = jac_from_words(P);
             if (pnt.Z.is_zero()) continue;
             acc = np == 1 ? pnt : G::add(acc, pnt);
         }
@@ -1896,22 +1910,6 @@ template <class C> static int msm_direct(bp_ctx* ctx, const DtJobs& jobs, int no
     msm_direct_collect<C>(ctx, nout, results);
     return BP_OK;
 }
-// affine forms of several Jacobian points with ONE field inversion (Montgomery's trick; the identity stays (0, 0))
-template <class C> static void to_aff_batch(const J4* in, int count, A4* out) {
-    typedef host::Grp<C> G;
-    typedef host::Fld<typename C::Fq> F;
-    F4 pref[DT_MAXOUT];
-    F4 run = F::one();
-    for (int i = 0; i < count; i++) { pref[i] = run; if (!G::is_inf(in[i])) run = F::mul(run, in[i].Z); }
-    F4 inv = F::inv(run);
-    for (int i = count - 1; i >= 0; i--) {
-        if (G::is_inf(in[i])) { out[i] = G::aff_inf(); continue; }
-        const F4 zi = F::mul(inv, pref[i]), zi2 = F::sqr(zi);
-        inv = F::mul(inv, in[i].Z);
-        out[i] = A4{F::mul(in[i].X, zi2), F::mul(in[i].Y, F::mul(zi2, zi))};
-    }
-}
-
 // Two MSMs of n terms each that do not depend on each other — L and R of an inner-product round — as two jobs of ONE fixed-shape
 // launch chain (msm_fs_jobs): half the launches and one host wait instead of two, and the two latency-bound trees run side by side.
 // Where the pair does not go through that pipeline alone on this ctx, the two msm_run calls run as they always did, in order: a
@@ -1949,7 +1947,7 @@ template <class C> static int msm_run_pair_aff(bp_ctx* ctx, const BaseSegs segs[
                                                int shard_mode = -1) {
     J4 r[2]; A4 a[2];
     BPCHK(msm_run_pair<C>(ctx, segs, d_scalars, n, scalars_mont, r, shard_mode));
-    to_aff_batch<C>(r, 2, a);
+    to_aff_many<C>(r, 2, a);
     memcpy(out0, a[0].x.v, 32); memcpy(out0 + 4, a[0].y.v, 32);
     memcpy(out1, a[1].x.v, 32); memcpy(out1 + 4, a[1].y.v, 32);
     return BP_OK;
@@ -2039,7 +2037,7 @@ template <class C> static int ipa_round_lr(bp_ctx* ctx, IpaState& s, uint64_t Lw
             J4 LR[2];
             BPCHK(msm_direct<C>(ctx, jobs, 2, LR));
             A4 LRa[2];
-            to_aff_batch<C>(LR, 2, LRa);
+            to_aff_many<C>(LR, 2, LRa);
             const A4 &La = LRa[0], &Ra = LRa[1];
             memcpy(Lw, La.x.v, 32); memcpy(Lw + 4, La.y.v, 32);
             memcpy(Rw, Ra.x.v, 32); memcpy(Rw + 4, Ra.y.v, 32);
@@ -3554,7 +3552,7 @@ static int dbg_msm_direct(bp_ctx* ctx, size_t njobs, const uint32_t* desc, const
     A4 a[DT_MAXOUT];
     BPCHK(msm_direct<C>(ctx, jobs, (int)njobs, r));
     if (workgroups) *workgroups = ctx->dt_last_nblk;
-    to_aff_batch<C>(r, (int)njobs, a);
+    to_aff_many<C>(r, njobs, a);
     for (size_t j = 0; j < njobs; j++) { memcpy(out_xy + 8 * j, a[j].x.v, 32); memcpy(out_xy + 8 * j + 4, a[j].y.v, 32); }
     return BP_OK;
 }

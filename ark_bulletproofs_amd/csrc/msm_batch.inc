@@ -112,7 +112,7 @@ static int msb_group(bp_ctx* ctx, const MsbKnobs& kn, size_t j0, size_t j1, cons
     std::vector<J4> jp(cnt);
     std::vector<A4> ap(cnt);
     pf_points_in(res.data(), cnt, jp.data());
-    pb_to_aff<C>(jp.data(), cnt, ap.data());   // one shared inversion
+    to_aff_many<C>(jp.data(), cnt, ap.data());   // one shared inversion
     for (size_t j = 0; j < cnt; j++) { memcpy(out_xy + 8 * (j0 + j), ap[j].x.v, 32); memcpy(out_xy + 8 * (j0 + j) + 4, ap[j].y.v, 32); }
     return BP_OK;
 }

@@ -76,21 +76,6 @@ template <class C> struct PbGroup {
     bool open = false;
 };
 
-// Montgomery's trick over a chunk: affine forms of `count` Jacobian points with one field inversion (the identity stays (0, 0))
-template <class C> static void pb_to_aff(const J4* in, size_t count, A4* out) {
-    typedef host::Grp<C> G;
-    typedef host::Fld<typename C::Fq> F;
-    std::vector<F4> pref(count);
-    F4 run = F::one();
-    for (size_t i = 0; i < count; i++) { pref[i] = run; if (!G::is_inf(in[i])) run = F::mul(run, in[i].Z); }
-    F4 inv = F::inv(run);
-    for (size_t i = count; i-- > 0;) {
-        if (G::is_inf(in[i])) { out[i] = G::aff_inf(); continue; }
-        const F4 zi = F::mul(inv, pref[i]), zi2 = F::sqr(zi);
-        inv = F::mul(inv, in[i].Z);
-        out[i] = A4{F::mul(in[i].X, zi2), F::mul(in[i].Y, F::mul(zi2, zi))};
-    }
-}
 template <class S> static void pb_inv_many(const F4* in, size_t count, F4* out) {   // (challenges are never zero)
     std::vector<F4> pref(count);
     F4 run = S::one();
@@ -110,7 +95,6 @@ static void pb_on_pool(bp_ctx* ctx, size_t count, const std::function<void(size_
 template <class C> static int pb_run_group(bp_ctx* ctx, PbGroup<C>& g) {
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
-    typedef host::TP<C> TP;
     const PbLayout& L = g.lay;
     const size_t B = g.mem.size(), N = L.N, lg = pb_lg(N);
     hipStream_t st = ctx->stream;
@@ -177,14 +161,12 @@ template <class C> static int pb_run_group(bp_ctx* ctx, PbGroup<C>& g) {
         const u64* res = (const u64*)(hs + L.stage_res);
         on_pool([&](size_t c) {
             const size_t lo = c * chunk, hi = std::min(B, lo + chunk);
-            for (size_t i = 2 * lo; i < 2 * hi; i++) { const u64* P = res + 12 * i; memcpy(pts[i].X.v, P, 32); memcpy(pts[i].Y.v, P + 4, 32); memcpy(pts[i].Z.v, P + 8, 32); }
-            pb_to_aff<C>(pts.data() + 2 * lo, 2 * (hi - lo), aff.data() + 2 * lo);
+            for (size_t i = 2 * lo; i < 2 * hi; i++) pts[i] = jac_from_words(res + 12 * i);
+            to_aff_many<C>(pts.data() + 2 * lo, 2 * (hi - lo), aff.data() + 2 * lo);
             for (size_t j = lo; j < hi; j++) {
                 host::ProofData& pf = *g.mem[j].pf;
                 pf.L_vec[r] = aff[2 * j]; pf.R_vec[r] = aff[2 * j + 1];
-                host::Transcript& tr = *g.mem[j].tr;
-                TP::append_point(tr, "L", aff[2 * j]); TP::append_point(tr, "R", aff[2 * j + 1]);
-                u[j] = TP::challenge_scalar(tr, "u");
+                u[j] = host::prove_round_challenge<C>(*g.mem[j].tr, aff[2 * j], aff[2 * j + 1]);
             }
             pb_inv_many<S>(u.data() + lo, hi - lo, ui.data() + lo);
         });
@@ -222,27 +204,16 @@ template <class C> struct PfMember {
     size_t n1 = 0, n = 0, N = 0;
     A4 c1[3];                           // A_I1, A_O1, S1
     F4 bl2[3], tb[5];                   // i_b2, o_b2, s_b2; the blinding factors of T_1, T_3 .. T_6
-    F4 y, z, ztab[32];
+    F4 y, z;
     F4 kappa2 = F4{{0, 0, 0, 0}};       // BP_BLINDING_EXPANDED: phase 2's key
     std::vector<F4> wV;
     F4 w;
     bool csc_ok = true;
 };
 
-static int pf_stage_ensure(bp_ctx* c, size_t bytes) {
-    if (c->h_pf_cap >= bytes) return BP_OK;
-    if (c->h_pf) HIPCHK(hipHostFree(c->h_pf));
-    c->h_pf = nullptr; c->h_pf_cap = 0;
-    HIPCHK(hipHostMalloc(&c->h_pf, bytes + bytes / 4 + 4096));
-    c->h_pf_cap = bytes + bytes / 4 + 4096;
-    return BP_OK;
-}
+static int pf_stage_ensure(bp_ctx* c, size_t bytes) { return pinned_ensure(c->h_pf, c->h_pf_cap, bytes, bytes / 4 + 4096); }
 static int pb_stage_ensure(bp_ctx* c, size_t bytes) {   // the rounds' staging (pb_run_group)
-    if (c->h_pb_cap >= bytes) return BP_OK;
-    if (c->h_pb) (void)hipHostFree(c->h_pb);
-    c->h_pb = nullptr; c->h_pb_cap = 0;
-    if (hipHostMalloc(&c->h_pb, bytes) != hipSuccess) { c->h_pb = nullptr; g_err = "prove_batch: pinned staging"; return BP_E_HIP; }
-    c->h_pb_cap = bytes;
+    if (pinned_ensure(c->h_pb, c->h_pb_cap, bytes, 0)) { c->h_pb = nullptr; c->h_pb_cap = 0; g_err = "prove_batch: pinned staging"; return BP_E_HIP; }
     return BP_OK;
 }
 // workgroups per table sum, as pb_run_group sizes a round's
@@ -265,16 +236,12 @@ template <class C> static int pf_accum(bp_ctx* ctx, const DtJob* d_jobs, size_t 
     ctx->dt_runs += njobs;
     return BP_OK;
 }
-static void pf_points_in(const void* res, size_t count, J4* out) {
-    const u64* r = (const u64*)res;
-    for (size_t i = 0; i < count; i++) { const u64* P = r + 12 * i; memcpy(out[i].X.v, P, 32); memcpy(out[i].Y.v, P + 4, 32); memcpy(out[i].Z.v, P + 8, 32); }
-}
+static void pf_points_in(const void* res, size_t count, J4* out) { for (size_t i = 0; i < count; i++) out[i] = jac_from_words((const u64*)res + 12 * i); }
 
 // Phase 1 of a front group (equal n1): A_I1, A_O1, S1 of every member into its transcript
 template <class C> static int pf_phase1(bp_ctx* ctx, std::vector<PfMember<C>>& mem, StageTimes& tm) {
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
-    typedef host::TP<C> TP;
     const size_t B = mem.size(), n1 = mem[0].n1;
     const bool expanded = mem[0].pre->mode == BP_BLINDING_EXPANDED;   // (a front group holds members of ONE mode: cs_prove_batch)
     const size_t nv = expanded ? 3 : 5;                              // vectors that come through the staging
@@ -282,7 +249,7 @@ template <class C> static int pf_phase1(bp_ctx* ctx, std::vector<PfMember<C>>& m
     pb_pool_ensure(ctx, B);
     std::vector<J4> pts(3 * B);
     double t0 = now_s();
-    if (n1 == 0) {   // no multipliers in this phase (a k-shuffle's phase 1): single Pedersen terms on the host's tables, as r1cs_prove
+    if (n1 == 0) {   // no multipliers in this phase (a k-shuffle's phase 1): single Pedersen terms on the host's tables
         host::PedersenGens<C> pc; pc.B = ctx->pc_B; pc.B_blinding = ctx->pc_Bb;
         pb_on_pool(ctx, B, [&](size_t j) {
             const ProvePre<C>& pre = *mem[j].pre;
@@ -319,15 +286,7 @@ template <class C> static int pf_phase1(bp_ctx* ctx, std::vector<PfMember<C>>& m
             const u32* blp = (const u32*)(ar + bl_off + j * 96);
             const u32* xs[3] = {base, base + 2 * vb / 4, base + 3 * vb / 4};
             const u32* ys[3] = {base + vb / 4, nullptr, base + 4 * vb / 4};
-            for (int o = 0; o < 3; o++) {
-                DtJob& jb = hj[3 * j + o];
-                memset(&jb, 0, sizeof jb);
-                int ns = 0;
-                jb.seg[ns++] = DtSeg{xs[o], dt_base_G(ctx, 0), (u32)n1, 1, 0, 0};
-                if (ys[o]) jb.seg[ns++] = DtSeg{ys[o], dt_base_H(ctx, 0), (u32)n1, 1, 0, 0};
-                jb.seg[ns++] = DtSeg{blp + 8 * o, dt_base_pc(1), 1, 2, 0, 0};
-                jb.nseg = (u32)ns; jb.terms = (u32)(n1 * (ys[o] ? 2 : 1) + 1);
-            }
+            dt_commit_jobs<C>(ctx, hj + 3 * j, xs, ys, 0, n1, nullptr, blp);
         });
         tm.upload += now_s() - t0; t0 = now_s();
         PfGeom geo; memset(&geo, 0, sizeof geo);
@@ -353,11 +312,10 @@ template <class C> static int pf_phase1(bp_ctx* ctx, std::vector<PfMember<C>>& m
     std::vector<A4> aff(3 * B);
     pb_on_pool(ctx, nchunks, [&](size_t c) {
         const size_t lo = c * chunk, hi = std::min(B, lo + chunk);
-        pb_to_aff<C>(pts.data() + 3 * lo, 3 * (hi - lo), aff.data() + 3 * lo);
+        to_aff_many<C>(pts.data() + 3 * lo, 3 * (hi - lo), aff.data() + 3 * lo);
         for (size_t j = lo; j < hi; j++) {
-            host::Transcript& tr = *mem[j].cs->tr;
             for (int o = 0; o < 3; o++) mem[j].c1[o] = aff[3 * j + o];
-            TP::append_point(tr, "A_I1", aff[3 * j]); TP::append_point(tr, "A_O1", aff[3 * j + 1]); TP::append_point(tr, "S1", aff[3 * j + 2]);
+            host::prove_append_phase<C>(*mem[j].cs->tr, 1, aff[3 * j], aff[3 * j + 1], aff[3 * j + 2]);
         }
     });
     tm.commit_msm += now_s() - t0;
@@ -451,18 +409,8 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     pb_on_pool(ctx, B, [&](size_t j) {
         PfMember<C>& m = *part[j];
         ProvePre<C>& pre = *m.pre;
-        host::TranscriptRng& rng = *pre.rng;
-        const size_t n = m.n, n1 = m.n1;
-        for (auto& b : m.bl2) b = S::zero();
-        const bool has2 = n > n1;
-        if (has2) { m.bl2[0] = host::rand_fe<FrP>(rng); m.bl2[1] = host::rand_fe<FrP>(rng); m.bl2[2] = host::rand_fe<FrP>(rng); }
-        if (expanded) { if (has2) m.kappa2 = host::rand_fe<FrP>(rng); }   // one draw where the 2 (n - n1) would begin
-        else {
-            pre.s_L.resize(n); pre.s_R.resize(n);
-            for (size_t i = n1; i < n; i++) pre.s_L[i] = host::rand_fe<FrP>(rng);
-            for (size_t i = n1; i < n; i++) pre.s_R[i] = host::rand_fe<FrP>(rng);
-        }
-        for (auto& b : m.tb) b = host::rand_fe<FrP>(rng);   // T_1, T_3 .. T_6: the next draws whatever t(x) turns out to be (r1cs_prove)
+        host::prove_draw_phase2<C>(*pre.rng, m.n > m.n1, expanded, m.n1, m.n, m.bl2, m.kappa2, pre.s_L, pre.s_R);
+        host::prove_draw_t<C>(*pre.rng, m.tb);
     });
     tm.rng += now_s() - t0; t0 = now_s();
     // staging of the witness, the descriptors, the jobs of both commitment stages, the constraint index and its coefficients
@@ -487,24 +435,9 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
             const size_t n2 = n - n1;
             const u32* xs[3] = {wit(j, L.o_waL) + n1 * 8, wit(j, L.o_waO) + n1 * 8, wit(j, L.o_wsL) + n1 * 8};
             const u32* ys[3] = {wit(j, L.o_waR) + n1 * 8, nullptr, wit(j, L.o_wsR) + n1 * 8};
-            for (int o = 0; o < 3; o++) {
-                DtJob& jb = hj2[3 * job2_of[j] + o];
-                memset(&jb, 0, sizeof jb);
-                int ns = 0;
-                jb.seg[ns++] = DtSeg{xs[o], dt_base_G(ctx, n1), (u32)n2, 1, 0, 0};
-                if (ys[o]) jb.seg[ns++] = DtSeg{ys[o], dt_base_H(ctx, n1), (u32)n2, 1, 0, 0};
-                jb.seg[ns++] = DtSeg{blp + 8 * o, dt_base_pc(1), 1, 2, 0, 0};
-                jb.nseg = (u32)ns; jb.terms = (u32)(n2 * (ys[o] ? 2 : 1) + 1);
-            }
+            dt_commit_jobs<C>(ctx, hj2 + 3 * job2_of[j], xs, ys, n1, n2, nullptr, blp);
         }
-        const int slot[5] = {0, 2, 3, 4, 5};
-        for (int o = 0; o < 5; o++) {   // T_i = t_i * B + blinding_i * B_blinding, t_i read where the t(x) kernels leave it
-            DtJob& jb = hjT[5 * j + o];
-            memset(&jb, 0, sizeof jb);
-            jb.nseg = 2; jb.terms = 2;
-            jb.seg[0] = DtSeg{geo.tsum + (j * 6 + slot[o]) * 8, dt_base_pc(0), 1, 2, 0, 0};
-            jb.seg[1] = DtSeg{blp + 8 * (3 + o), dt_base_pc(1), 1, 2, 0, 0};
-        }
+        dt_t_jobs<C>(hjT + 5 * j, geo.tsum + j * 6 * 8, nullptr, blp + 8 * 3);
         char* u1 = hs + s_u1;
         memcpy(u1 + j * sizeof(PfDesc), &descs[j], sizeof(PfDesc));
         const HostCsc& cc = *m.csc;
@@ -540,7 +473,7 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     if (B2) pf_points_in(hs + s_res2, 3 * B2, pts2.data());
     {   // (one inversion per chunk of the phase-2 members)
         const size_t nc2 = (B2 + chunk - 1) / chunk;
-        pb_on_pool(ctx, nc2, [&](size_t c) { const size_t lo = c * chunk, hi = std::min(B2, lo + chunk); pb_to_aff<C>(pts2.data() + 3 * lo, 3 * (hi - lo), aff2.data() + 3 * lo); });
+        pb_on_pool(ctx, nc2, [&](size_t c) { const size_t lo = c * chunk, hi = std::min(B2, lo + chunk); to_aff_many<C>(pts2.data() + 3 * lo, 3 * (hi - lo), aff2.data() + 3 * lo); });
     }
     pb_on_pool(ctx, B, [&](size_t j) {
         PfMember<C>& m = *part[j];
@@ -549,23 +482,14 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
         const bool has2 = m.n > m.n1;
         pf.A_I1 = m.c1[0]; pf.A_O1 = m.c1[1]; pf.S1 = m.c1[2];
         pf.A_I2 = has2 ? aff2[3 * job2_of[j]] : G::aff_inf(); pf.A_O2 = has2 ? aff2[3 * job2_of[j] + 1] : G::aff_inf(); pf.S2 = has2 ? aff2[3 * job2_of[j] + 2] : G::aff_inf();
-        TP::append_point(tr, "A_I2", pf.A_I2); TP::append_point(tr, "A_O2", pf.A_O2); TP::append_point(tr, "S2", pf.S2);
+        host::prove_append_phase<C>(tr, 2, pf.A_I2, pf.A_O2, pf.S2);
         m.y = TP::challenge_scalar(tr, "y"); m.z = TP::challenge_scalar(tr, "z");
         F4* u2 = (F4*)(hs + s_u2) + j * 96;
-        { F4 c = m.z; for (int i = 0; i < 32; i++) { m.ztab[i] = c; u2[i] = to_resident<FrP>(c); c = S::sqr(c); } }
-        { F4 c = m.y, ci = S::inv(m.y); for (int i = 0; i < 32; i++) { u2[32 + i] = to_resident<FrP>(c); u2[64 + i] = to_resident<FrP>(ci); c = S::sqr(c); ci = S::sqr(ci); } }
-        // wV on the host: the few terms on committed variables, z^(q+1) carried from term to term (as r1cs_prove)
-        m.wV.assign(m.cs->v.size(), S::zero());
-        auto pow_z = [&](u32 e) { F4 r = S::one(); for (u32 i = 0; e; e >>= 1, i++) if (e & 1) r = S::mul(r, m.ztab[i]); return r; };
-        F4 zq = S::one(), zstep = S::one();
-        u32 cur = 0, last_d = 0;
-        for (const auto& t2 : m.csc->vterms) {
-            const u32 q1 = t2.q + 1;
-            if (cur == 0) zq = pow_z(q1);
-            else if (q1 != cur) { const u32 d = q1 - cur; if (d != last_d) { zstep = pow_z(d); last_d = d; } zq = S::mul(zq, zstep); }
-            cur = q1;
-            m.wV[t2.j] = S::sub(m.wV[t2.j], S::mul(zq, t2.c));
-        }
+        F4 ztab[32], ypw[64];
+        host::prove_pow_tables<C>(m.z, m.y, ztab, ypw);
+        for (int i = 0; i < 32; i++) u2[i] = to_resident<FrP>(ztab[i]);
+        for (int i = 0; i < 64; i++) u2[32 + i] = to_resident<FrP>(ypw[i]);
+        host::prove_wv<C>(*m.csc, ztab, m.cs->v.size(), m.wV);
     });
     HIPCHK(hipMemcpyAsync(ax + a_u2, hs + s_u2, B * 96 * 32, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_r1cs_ztables_multi<C>, dim3((u32)((std::max<size_t>(256, nzmax) + 255) / 256), (u32)B), dim3(256), 0, st, (u32*)ax, (const PfDesc*)ax);
@@ -592,7 +516,7 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     PfXu* hxu = (PfXu*)(hs + s_xu);
     pb_on_pool(ctx, nchunks, [&](size_t c) {
         const size_t lo = c * chunk, hi = std::min(B, lo + chunk);
-        pb_to_aff<C>(ptsT.data() + 5 * lo, 5 * (hi - lo), affT.data() + 5 * lo);
+        to_aff_many<C>(ptsT.data() + 5 * lo, 5 * (hi - lo), affT.data() + 5 * lo);
         for (size_t j = lo; j < hi; j++) {
             PfMember<C>& m = *part[j];
             host::Transcript& tr = *m.cs->tr;
@@ -602,22 +526,9 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
             memcpy(tco, hs + s_ts + j * 192, 192);
             const A4* Tc = affT.data() + 5 * j;
             pf.T_1 = Tc[0]; pf.T_3 = Tc[1]; pf.T_4 = Tc[2]; pf.T_5 = Tc[3]; pf.T_6 = Tc[4];
-            TP::append_point(tr, "T_1", Tc[0]); TP::append_point(tr, "T_3", Tc[1]); TP::append_point(tr, "T_4", Tc[2]); TP::append_point(tr, "T_5", Tc[3]);
-            TP::append_point(tr, "T_6", Tc[4]);
-            const F4 u = TP::challenge_scalar(tr, "u"), x = TP::challenge_scalar(tr, "x");
-            F4 t2b = S::zero();
-            for (size_t i = 0; i < m.wV.size(); i++) t2b = S::add(t2b, S::mul(m.cs->v_blinding[i], m.wV[i]));
-            auto poly6 = [&](const F4& c1, const F4& c2, const F4& c3, const F4& c4, const F4& c5, const F4& c6) {  // util.rs:107-109
-                F4 acc = S::add(S::mul(x, c6), c5);
-                acc = S::add(S::mul(acc, x), c4); acc = S::add(S::mul(acc, x), c3); acc = S::add(S::mul(acc, x), c2); acc = S::add(S::mul(acc, x), c1);
-                return S::mul(acc, x);
-            };
-            pf.t_x = poly6(tco[0], tco[1], tco[2], tco[3], tco[4], tco[5]);
-            pf.t_x_blinding = poly6(m.tb[0], t2b, m.tb[1], m.tb[2], m.tb[3], m.tb[4]);
-            const F4 i_b = S::add(pre.i_b1, S::mul(u, m.bl2[0])), o_b = S::add(pre.o_b1, S::mul(u, m.bl2[1])), s_b = S::add(pre.s_b1, S::mul(u, m.bl2[2]));
-            pf.e_blinding = S::mul(x, S::add(i_b, S::mul(x, S::add(o_b, S::mul(x, s_b)))));
-            TP::append_scalar(tr, "t_x", pf.t_x); TP::append_scalar(tr, "t_x_blinding", pf.t_x_blinding); TP::append_scalar(tr, "e_blinding", pf.e_blinding);
-            m.w = TP::challenge_scalar(tr, "w");
+            const F4 b1[3] = {pre.i_b1, pre.o_b1, pre.s_b1};
+            F4 u, x;
+            host::prove_t_tail<C>(tr, Tc, tco, m.tb, m.wV, m.cs->v_blinding, b1, m.bl2, u, x, pf.t_x, pf.t_x_blinding, pf.e_blinding, m.w);
             memcpy(hxu[j].x, x.v, 32); memcpy(hxu[j].u, u.v, 32);
             TP::innerproduct_domain_sep(tr, N);
             pf.L_vec.resize(pb_lg(N)); pf.R_vec.resize(pb_lg(N));

@@ -29,14 +29,7 @@ template <class C> static int upload_scalars(bp_ctx* ctx, u32* dst, const F4* sr
 // (168 MB per 2^20 proof) capped the whole pipeline.  Here the host thread copies into the ctx's pinned slab (parallel across the
 // proofs' threads, ~10 GB/s each) and the DMA from pinned memory is asynchronous.  `slot` picks one of the ctx's slabs: each is
 // used at most once per prove() call, and the previous call's copies are long complete.
-static int upload_slab_ensure(bp_ctx* ctx, size_t bytes) {
-    if (ctx->h_upload_cap >= bytes) return BP_OK;
-    if (ctx->h_upload) HIPCHK(hipHostFree(ctx->h_upload));
-    ctx->h_upload = nullptr; ctx->h_upload_cap = 0;
-    HIPCHK(hipHostMalloc(&ctx->h_upload, bytes + 4096));
-    ctx->h_upload_cap = bytes + 4096;
-    return BP_OK;
-}
+static int upload_slab_ensure(bp_ctx* ctx, size_t bytes) { return pinned_ensure(ctx->h_upload, ctx->h_upload_cap, bytes, 4096); }
 template <class C> static int upload_scalars_pinned(bp_ctx* ctx, u32* dst, const F4* src, size_t cnt, size_t slab_offset_bytes) {
     if (!cnt) return BP_OK;
     char* stage = (char*)ctx->h_upload + slab_offset_bytes;
@@ -274,70 +267,45 @@ template <class C> static int commit_msm(bp_ctx* ctx, const F4& blind, const u32
     return BP_OK;
 }
 
-// the commitments of one phase (A_I, A_O, S: prover.rs:516-559 / 604-649) in ONE launch over the direct window tables (small.cuh); the
-// blinding factors ride in the launch
-template <class C> static int commit_direct(bp_ctx* ctx, int nout, const F4* blinds, const u32* const* xs, const u32* const* ys, size_t off, size_t cnt, A4* outs) {
-    DtJobs jobs; memset(&jobs, 0, sizeof jobs);
-    for (int o = 0; o < nout; o++) {
-        DtJob& jb = jobs.job[o];
+// ---- jobs over the direct window tables (small.cuh) that both prover routes build ---------------------------------------------------
+// The blinding term of a table sum, blind * B_blinding: the value rides in the job as its immediate term (`imm`: one proof on the
+// ctx's workspaces), or is read as ark words where it lies on the device (`dev`: a group's arena), then as the job's last run.
+template <class C> static void dt_job_blind(DtJob& jb, const F4* imm, const u32* dev) {
+    if (imm) {
         uint64_t cw[4];
-        host::Fld<typename C::Fr>::to_canon(cw, blinds[o]);
+        host::Fld<typename C::Fr>::to_canon(cw, *imm);
         memcpy(jb.imm, cw, 32);
         jb.has_imm = 1; jb.imm_base = dt_base_pc(1);
-        jb.nseg = ys[o] ? 2 : 1; jb.terms = (u32)(1 + cnt * (ys[o] ? 2 : 1));
-        jb.seg[0] = DtSeg{xs[o], dt_base_G(ctx, off), (u32)cnt, 1};
-        if (ys[o]) jb.seg[1] = DtSeg{ys[o], dt_base_H(ctx, off), (u32)cnt, 1};
+    } else jb.seg[jb.nseg++] = DtSeg{dev, dt_base_pc(1), 1, 2, 0, 0};
+    jb.terms++;
+}
+// A_I, A_O, S of one phase (prover.rs:516-559 / 604-649): <xs, G[off ..]> (+ <ys, H[off ..]>) + blind * B_blinding, cnt resident
+// scalars per run.  imm: the three blinding factors, or null and dev: 3 x 8 words on the device
+template <class C> static void dt_commit_jobs(bp_ctx* ctx, DtJob jobs[3], const u32* const xs[3], const u32* const ys[3], size_t off, size_t cnt, const F4* imm, const u32* dev) {
+    for (int o = 0; o < 3; o++) {
+        DtJob& jb = jobs[o];
+        memset(&jb, 0, sizeof jb);
+        jb.seg[jb.nseg++] = DtSeg{xs[o], dt_base_G(ctx, off), (u32)cnt, 1, 0, 0};
+        if (ys[o]) jb.seg[jb.nseg++] = DtSeg{ys[o], dt_base_H(ctx, off), (u32)cnt, 1, 0, 0};
+        jb.terms = (u32)(cnt * (ys[o] ? 2 : 1));
+        dt_job_blind<C>(jb, imm ? imm + o : nullptr, dev ? dev + 8 * o : nullptr);
     }
-    J4 r[DT_MAXOUT];
-    BPCHK(msm_direct<C>(ctx, jobs, nout, r));
-    to_aff_batch<C>(r, nout, outs);
-    return BP_OK;
+}
+// T_i = t_i * B + blinding_i * B_blinding for i = 1, 3 .. 6: t_i read as ark words where the t(x) kernels leave the six sums (tsum)
+template <class C> static void dt_t_jobs(DtJob jobs[5], const u32* tsum, const F4* imm, const u32* dev) {
+    const int slot[5] = {0, 2, 3, 4, 5};
+    for (int o = 0; o < 5; o++) {
+        DtJob& jb = jobs[o];
+        memset(&jb, 0, sizeof jb);
+        jb.seg[jb.nseg++] = DtSeg{tsum + slot[o] * 8, dt_base_pc(0), 1, 2, 0, 0};
+        jb.terms = 1;
+        dt_job_blind<C>(jb, imm ? imm + o : nullptr, dev ? dev + 8 * o : nullptr);
+    }
 }
 
 // The host-only head of prove() (prover.rs:466-513): `m`, the TranscriptRng and the phase-1 blinding draws — the strictly
 // sequential Keccak chain (8 permutations per multiplier).  It needs no GPU, so a service runs it for proof k+1 on another
 // core while proof k occupies the GPU; prove() continues from the stored rng state.
-// Merged CSC of a recorded constraint system (see k_r1cs_flatten): built on the host, once per statement — with the statement for
-// single-phase circuits (outside prove()), after the randomized phase otherwise.
-struct HostCsc {
-    size_t n = 0, q = 0;
-    std::vector<u32> moff, ment, mc;   // n+1 offsets; (vector << 30) | constraint; coefficient id with the +-1 flags in bits 31 / 30
-    std::vector<F4> coefs;
-    std::vector<host::VTerm> vterms;   // committed-variable terms in constraint order: feed wV (t_2's blinding, prover.rs:716-721)
-};
-template <class C> static bool build_host_csc(const host::ConstraintSystem<C>& cs, HostCsc& h) {
-    typedef host::Fld<typename C::Fr> S;
-    const size_t n = cs.num_vars, Q = cs.num_constraints();
-    if (!cs.deferred.empty() || cs.base || Q >= ((size_t)1 << 30) || n >= ((size_t)1 << 31)) return false;
-    h.n = n; h.q = Q;
-    host::reserve_huge(h.moff, n + 1);
-    h.moff.assign(n + 1, 0);
-    auto vec_of = [](int k) { return k == host::VK_LEFT ? 0 : k == host::VK_RIGHT ? 1 : k == host::VK_OUT ? 2 : -1; };
-    for (const host::Term& t : cs.cs_terms) if (vec_of(t.v.k) >= 0) h.moff[t.v.i + 1]++;
-    for (size_t i = 0; i < n; i++) h.moff[i + 1] += h.moff[i];
-    host::reserve_huge(h.ment, h.moff[n]); host::reserve_huge(h.mc, h.moff[n]);
-    h.ment.resize(h.moff[n]); h.mc.resize(h.moff[n]);
-    std::vector<u32> cur;
-    host::reserve_huge(cur, n + 1);
-    cur.assign(h.moff.begin(), h.moff.end() - 1);
-    const F4 one = S::one(), mone = S::neg(S::one());
-    host::CanonState st;
-    bool ok = true;
-    // constraints in order: every column's run comes out sorted by q
-    st.walk(cs.cs_terms.data(), cs.cs_off.data(), Q, 0, one, mone, [&](size_t q, const host::Term& t, u32 cid) {
-        const int v = vec_of(t.v.k);
-        if (t.v.k == host::VK_COMMITTED) h.vterms.push_back(host::VTerm{t.v.i, (u32)q, t.c});
-        if (v < 0) return;   // (the constant terms enter wc, which the prover does not use)
-        if (!(cid & (host::CID_ONE | host::CID_MONE)) && cid >= (1u << 30)) ok = false;
-        const u32 pos = cur[t.v.i]++;
-        h.ment[pos] = ((u32)v << 30) | (u32)q;
-        h.mc[pos] = cid;
-    });
-    h.coefs.swap(st.coefs);
-    if (h.coefs.empty()) h.coefs.push_back(one);
-    return ok;
-}
-
 template <class C> struct ProvePre {
     std::unique_ptr<host::TranscriptRng> rng;
     F4 i_b1, o_b1, s_b1;
@@ -446,351 +414,280 @@ struct IpaDefer {
     F4 w;
 };
 
-// Prover::prove_and_return_transcript (src/r1cs/prover.rs:454-831)
-template <class C>
-static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8* rng_bytes, host::ProofData& proof, StageTimes& tm,
-                      ProvePre<C>* pre_in = nullptr, const HostCsc* csc = nullptr /* constraint index built with the statement (single-phase) */,
-                      IpaDefer* defer = nullptr,
-                      const A4* resume1 = nullptr /* bp_prover_prove_batch, a member that leaves its front group after the randomized phase: A_I1, A_O1,
-                      S1 are in the transcript and the phase has run — neither happens again; the whole witness goes up to the workspaces here */) {
-    typedef typename C::Fr FrP;
-    typedef host::Fld<FrP> S;
-    typedef host::Grp<C> G;
-    typedef host::TP<C> TP;
-    host::Transcript& tr = *cs.tr;
-    hipStream_t st = ctx->stream;
-    const double t_begin = now_s();
-    double t0;
-    host::PedersenGens<C> pc; pc.B = ctx->pc_B; pc.B_blinding = ctx->pc_Bb;
-
-    // ARKBP_PROVE_TRACE=1: microseconds between the marks of one prove() on stderr (where a SMALL proof's latency goes)
-    static const bool trace = getenv("ARKBP_PROVE_TRACE") != nullptr;
+// ---- Prover::prove_and_return_transcript (src/r1cs/prover.rs:454-831) as stages over one state struct -------------------------------
+// ARKBP_PROVE_TRACE=1: microseconds between the marks of one prove() on stderr (where a SMALL proof's latency goes)
+struct ProveTrace {
+    bool on;
     std::vector<std::pair<const char*, double>> marks;
-    auto mark = [&](const char* what) { if (trace) marks.emplace_back(what, now_s()); };
-    mark("begin");
-    ProvePre<C> pre_local;
-    ProvePre<C>& pre = pre_in && pre_in->rng ? *pre_in : pre_local;
-    if (pre_in) pre_local.mode = pre_in->mode;
-    const bool expanded = pre.mode == BP_BLINDING_EXPANDED;
-    if (!pre.rng) prove_precompute<C>(cs, rng_bytes, pre);
-    host::TranscriptRng& rng = *pre.rng;
-    tm.rng += pre.t_rng;
-    const size_t n1 = resume1 ? cs.n1 : cs.a_L.size();
-    if (ctx->gens_cap < n1) return BP_E_GENS_LENGTH;
-    const F4 i_b1 = pre.i_b1, o_b1 = pre.o_b1, s_b1 = pre.s_b1;
-    std::vector<F4>& s_L = pre.s_L;
-    std::vector<F4>& s_R = pre.s_R;
-
-    // device vectors are sized for the final padded length lazily: phase 1 first
-    auto ensure_vecs = [&](size_t cap) -> int {
-        DevBuf* bs[] = {&ctx->r_aL, &ctx->r_aR, &ctx->r_aO, &ctx->r_sL, &ctx->r_sR};
-        for (auto b : bs) {
-            if (b->cap >= cap * 32) continue;
-            DevBuf nb;
-            BPCHK(nb.ensure(cap * 32));
-            if (b->p && b->cap) { HIPCHK(hipMemcpyAsync(nb.p, b->p, std::min(b->cap, nb.cap), hipMemcpyDeviceToDevice, st)); HIPCHK(ctx_stream_wait(ctx)); }
-            b->release(); *b = nb;
-        }
-        return BP_OK;
-    };
-    t0 = now_s();
-    BPCHK(ensure_vecs(host::next_pow2(std::max<size_t>(n1, 1))));
-    HIPCHK(ctx_stream_wait(ctx));   // (the slab's previous use — the last proof of this ctx — is complete)
-    BPCHK(upload_slab_ensure(ctx, 5 * n1 * 32));
-    {
-        u32* const dst[5] = {ctx->r_aL.as<u32>(), ctx->r_aR.as<u32>(), ctx->r_aO.as<u32>(), ctx->r_sL.as<u32>(), ctx->r_sR.as<u32>()};
-        const F4* const src[5] = {cs.a_L.data(), cs.a_R.data(), cs.a_O.data(), s_L.data(), s_R.data()};
-        BPCHK(upload_witness5<C>(ctx, dst, src, n1, expanded ? 3 : 5));
-        if (expanded) BPCHK(blind_expand_launch<C>(ctx, pre.kappa1, 0, n1, dst[3], dst[4]));
+    void mark(const char* what) { if (on) marks.emplace_back(what, now_s()); }
+    void print(size_t n) {
+        if (!on) return;
+        mark("end");
+        std::string line = "prove n=" + std::to_string(n) + ":";
+        for (size_t i = 1; i < marks.size(); i++) { char b[96]; snprintf(b, sizeof b, "  %s %.0f", marks[i].first, (marks[i].second - marks[i - 1].second) * 1e6); line += b; }
+        fprintf(stderr, "%s us\n", line.c_str());
     }
-    tm.upload += now_s() - t0;
-    mark("head + upload");
-    t0 = now_s();
-    A4 A_I1, A_O1, S1;
-    bool direct1 = false;
-    if (n1 && !resume1) BPCHK(dt_ensure<C>(ctx, host::next_pow2(n1), direct1));
-    if (resume1) { A_I1 = resume1[0]; A_O1 = resume1[1]; S1 = resume1[2]; }
-    else if (n1 == 0) {   // no multipliers in this phase (a k-shuffle's phase 1): three single Pedersen terms on the host's tables, one inversion
-        const J4 j3[3] = {pc.commit_jac(S::zero(), i_b1), pc.commit_jac(S::zero(), o_b1), pc.commit_jac(S::zero(), s_b1)};
-        A4 o3[3];
-        to_aff_batch<C>(j3, 3, o3);
-        A_I1 = o3[0]; A_O1 = o3[1]; S1 = o3[2];
-    } else if (direct1) {
-        const F4 bl[3] = {i_b1, o_b1, s_b1};
-        const u32* xs[3] = {ctx->r_aL.as<u32>(), ctx->r_aO.as<u32>(), ctx->r_sL.as<u32>()};
-        const u32* ys[3] = {ctx->r_aR.as<u32>(), nullptr, ctx->r_sR.as<u32>()};
-        A4 o3[3];
-        BPCHK(commit_direct<C>(ctx, 3, bl, xs, ys, 0, n1, o3));
-        A_I1 = o3[0]; A_O1 = o3[1]; S1 = o3[2];
-    } else {
-    BPCHK(commit_msm<C>(ctx, i_b1, ctx->r_aL.as<u32>(), ctx->r_aR.as<u32>(), 0, n1, A_I1));
-    BPCHK(commit_msm<C>(ctx, o_b1, ctx->r_aO.as<u32>(), nullptr, 0, n1, A_O1));
-    BPCHK(commit_msm<C>(ctx, s_b1, ctx->r_sL.as<u32>(), ctx->r_sR.as<u32>(), 0, n1, S1));
-    }
-    tm.commit_msm += now_s() - t0;
-    mark("commit phase 1");
-    if (!resume1) {
-        TP::append_point(tr, "A_I1", A_I1); TP::append_point(tr, "A_O1", A_O1); TP::append_point(tr, "S1", S1);
-        int rc = cs.run_randomized();
-        if (rc) return rc;
-    }
-
-    mark("randomized phase");
-    const size_t n = cs.a_L.size(), n2 = n - n1, N = host::next_pow2(n);
-    if (ctx->gens_cap < N) return BP_E_GENS_LENGTH;
-    const bool has2 = n2 > 0;
-    F4 i_b2 = S::zero(), o_b2 = S::zero(), s_b2 = S::zero();
-    t0 = now_s();
-    if (has2) { i_b2 = host::rand_fe<FrP>(rng); o_b2 = host::rand_fe<FrP>(rng); s_b2 = host::rand_fe<FrP>(rng); }
-    F4 kappa2 = S::zero();
-    if (expanded) { if (has2) kappa2 = host::rand_fe<FrP>(rng); }
-    else {
-        s_L.resize(n); s_R.resize(n);
-        for (size_t i = n1; i < n; i++) s_L[i] = host::rand_fe<FrP>(rng);
-        for (size_t i = n1; i < n; i++) s_R[i] = host::rand_fe<FrP>(rng);
-    }
-    tm.rng += now_s() - t0;
-    A4 A_I2 = G::aff_inf(), A_O2 = G::aff_inf(), S2 = G::aff_inf();
-    if (has2) {
-        t0 = now_s();
-        BPCHK(ensure_vecs(N));
-        HIPCHK(ctx_stream_wait(ctx));   // phase 1's copies out of the slab are done (the commitment MSMs above synchronised anyway)
-        BPCHK(upload_slab_ensure(ctx, 5 * std::max(n1, n2) * 32));
-        {
-            u32* const dst[5] = {ctx->r_aL.as<u32>() + n1 * 8, ctx->r_aR.as<u32>() + n1 * 8, ctx->r_aO.as<u32>() + n1 * 8, ctx->r_sL.as<u32>() + n1 * 8, ctx->r_sR.as<u32>() + n1 * 8};
-            const F4* const src[5] = {cs.a_L.data() + n1, cs.a_R.data() + n1, cs.a_O.data() + n1, expanded ? nullptr : s_L.data() + n1, expanded ? nullptr : s_R.data() + n1};
-            BPCHK(upload_witness5<C>(ctx, dst, src, n2, expanded ? 3 : 5));
-            if (expanded) BPCHK(blind_expand_launch<C>(ctx, kappa2, 0, n2, dst[3], dst[4]));
-            kappa2 = S::zero();
-        }
-        tm.upload += now_s() - t0;
-        t0 = now_s();
-        bool direct2 = false;
-        BPCHK(dt_ensure<C>(ctx, N, direct2));
-        if (direct2) {
-            const F4 bl[3] = {i_b2, o_b2, s_b2};
-            const u32* xs[3] = {ctx->r_aL.as<u32>() + n1 * 8, ctx->r_aO.as<u32>() + n1 * 8, ctx->r_sL.as<u32>() + n1 * 8};
-            const u32* ys[3] = {ctx->r_aR.as<u32>() + n1 * 8, nullptr, ctx->r_sR.as<u32>() + n1 * 8};
-            A4 o3[3];
-            BPCHK(commit_direct<C>(ctx, 3, bl, xs, ys, n1, n2, o3));
-            A_I2 = o3[0]; A_O2 = o3[1]; S2 = o3[2];
-        } else {
-        BPCHK(commit_msm<C>(ctx, i_b2, ctx->r_aL.as<u32>() + n1 * 8, ctx->r_aR.as<u32>() + n1 * 8, n1, n2, A_I2));
-        BPCHK(commit_msm<C>(ctx, o_b2, ctx->r_aO.as<u32>() + n1 * 8, nullptr, n1, n2, A_O2));
-        BPCHK(commit_msm<C>(ctx, s_b2, ctx->r_sL.as<u32>() + n1 * 8, ctx->r_sR.as<u32>() + n1 * 8, n1, n2, S2));
-        }
-        tm.commit_msm += now_s() - t0;
-    }
-    mark("commit phase 2");
-    TP::append_point(tr, "A_I2", A_I2); TP::append_point(tr, "A_O2", A_O2); TP::append_point(tr, "S2", S2);
-
-    const F4 y = TP::challenge_scalar(tr, "y"), z = TP::challenge_scalar(tr, "z");
-    F4 ypw[64];
-    bool ypw_early = false;   // (a small statement sends the y tables up together with the coefficient table)
-    t0 = now_s();
-    BPCHK(ctx->r_wL.ensure(N * 32)); BPCHK(ctx->r_wR.ensure(N * 32)); BPCHK(ctx->r_wO.ensure(N * 32));
+};
+// What one prove() carries from stage to stage
+template <class C> struct ProveJob {
+    bp_ctx* ctx;
+    host::ConstraintSystem<C>& cs;
+    ProvePre<C>& pre;            // the head: rng, phase 1's blinding factors, s_L / s_R (or kappa1)
+    StageTimes& tm;
+    host::PedersenGens<C> pc;
+    ProveTrace trace;
+    bool expanded = false;       // BP_BLINDING_EXPANDED
+    size_t n1 = 0, n = 0, N = 0; // phase-1 multipliers, all multipliers, padded
+    F4 b1[3], bl2[3], tb[5];     // i_b, o_b, s_b of the two phases; the blinding factors of T_1, T_3 .. T_6
+    A4 c1[3], c2[3], Tc[5];      // A_I, A_O, S of the two phases; T_1, T_3 .. T_6
+    F4 y, z, u, x, w;
+    F4 ypw[64], tco[6];          // y^(2^k) | y^-(2^k); t_1 .. t_6
+    const HostCsc* csc = nullptr;
+    HostCsc csc_late;            // a two-phase statement's index, built after its randomized phase
     std::vector<F4> wV;
-    HostCsc csc_late;
+    F4 t_x, t_x_blinding, e_blinding;
+    bool cyclic = false, direct = false, in_place = false, deferred = false;   // how the inner-product argument runs (prove_eval, prove_ipa)
+    bool secrets_up = false;     // from the first upload on: every way out wipes
+};
+
+// device vectors are sized for the final padded length lazily: phase 1 first
+static int prove_ensure_vecs(bp_ctx* ctx, size_t cap) {
+    DevBuf* bs[] = {&ctx->r_aL, &ctx->r_aR, &ctx->r_aO, &ctx->r_sL, &ctx->r_sR};
+    for (auto b : bs) {
+        if (b->cap >= cap * 32) continue;
+        DevBuf nb;
+        BPCHK(nb.ensure(cap * 32));
+        if (b->p && b->cap) { HIPCHK(hipMemcpyAsync(nb.p, b->p, std::min(b->cap, nb.cap), hipMemcpyDeviceToDevice, ctx->stream)); HIPCHK(ctx_stream_wait(ctx)); }
+        b->release(); *b = nb;
+    }
+    return BP_OK;
+}
+
+// the witness of one phase — multipliers [off, off + cnt) — to the device; kappa: the phase's key (BP_BLINDING_EXPANDED)
+template <class C> static int prove_upload_phase(ProveJob<C>& j, size_t off, size_t cnt, const F4& kappa) {
+    bp_ctx* ctx = j.ctx;
+    const double t0 = now_s();
+    BPCHK(prove_ensure_vecs(ctx, host::next_pow2(std::max<size_t>(off + cnt, 1))));
+    HIPCHK(ctx_stream_wait(ctx));   // (the slab's previous use — the last proof of this ctx, or phase 1's copies — is complete)
+    BPCHK(upload_slab_ensure(ctx, 5 * std::max(off, cnt) * 32));
+    u32* const dst[5] = {ctx->r_aL.as<u32>() + off * 8, ctx->r_aR.as<u32>() + off * 8, ctx->r_aO.as<u32>() + off * 8, ctx->r_sL.as<u32>() + off * 8, ctx->r_sR.as<u32>() + off * 8};
+    const F4* const src[5] = {j.cs.a_L.data() + off, j.cs.a_R.data() + off, j.cs.a_O.data() + off, j.expanded ? nullptr : j.pre.s_L.data() + off, j.expanded ? nullptr : j.pre.s_R.data() + off};
+    j.secrets_up = true;
+    BPCHK(upload_witness5<C>(ctx, dst, src, cnt, j.expanded ? 3 : 5));
+    if (j.expanded) BPCHK(blind_expand_launch<C>(ctx, kappa, 0, cnt, dst[3], dst[4]));
+    j.tm.upload += now_s() - t0;
+    return BP_OK;
+}
+
+// A_I, A_O, S of one phase (prover.rs:516-559 / 604-649) over the uploaded multipliers [off, off + cnt)
+template <class C> static int prove_commit_phase(ProveJob<C>& j, size_t off, size_t cnt, const F4 blinds[3], A4 out[3]) {
+    typedef host::Fld<typename C::Fr> S;
+    bp_ctx* ctx = j.ctx;
+    const double t0 = now_s();
+    const u32* xs[3] = {ctx->r_aL.as<u32>() + off * 8, ctx->r_aO.as<u32>() + off * 8, ctx->r_sL.as<u32>() + off * 8};
+    const u32* ys[3] = {ctx->r_aR.as<u32>() + off * 8, nullptr, ctx->r_sR.as<u32>() + off * 8};
+    bool direct = false;
+    if (cnt) BPCHK(dt_ensure<C>(ctx, host::next_pow2(off + cnt), direct));
+    if (cnt == 0) {   // no multipliers in this phase (a k-shuffle's phase 1): three single Pedersen terms on the host's tables, one inversion
+        const J4 j3[3] = {j.pc.commit_jac(S::zero(), blinds[0]), j.pc.commit_jac(S::zero(), blinds[1]), j.pc.commit_jac(S::zero(), blinds[2])};
+        to_aff_many<C>(j3, 3, out);
+    } else if (direct) {   // ONE launch over the direct window tables (small.cuh); the blinding factors ride in the launch
+        DtJobs jobs; memset(&jobs, 0, sizeof jobs);
+        dt_commit_jobs<C>(ctx, jobs.job, xs, ys, off, cnt, blinds, nullptr);
+        J4 r[3];
+        BPCHK(msm_direct<C>(ctx, jobs, 3, r));
+        to_aff_many<C>(r, 3, out);
+    } else {
+        for (int o = 0; o < 3; o++) BPCHK(commit_msm<C>(ctx, blinds[o], xs[o], ys[o], off, cnt, out[o]));
+    }
+    j.tm.commit_msm += now_s() - t0;
+    return BP_OK;
+}
+
+// the constraint index to the device (36 MB at 2^20 instead of 96 MB of flattened vectors) through pinned memory like the witness (a
+// pageable H2D copy serialises across the proofs in flight); a small statement's kernels read the pinned staging memory themselves
+struct CscPtrs { const u32 *moff, *ment, *mc; };
+static int prove_csc_stage(bp_ctx* ctx, const HostCsc& csc, bool small_stmt, CscPtrs& k) {
+    const size_t n = csc.n, nnz = csc.ment.size();
+    BPCHK(ctx->p_moff.ensure((n + 1) * 4)); BPCHK(ctx->p_ment.ensure(std::max<size_t>(nnz, 1) * 4)); BPCHK(ctx->p_mc.ensure(std::max<size_t>(nnz, 1) * 4));
+    k = CscPtrs{ctx->p_moff.as<u32>(), ctx->p_ment.as<u32>(), ctx->p_mc.as<u32>()};
+    const size_t b_off = (n + 1) * 4, b_nz = nnz * 4, a_nz = (b_off + 63) / 64 * 64, a_mc = a_nz + (b_nz + 63) / 64 * 64;
+    BPCHK(pinned_ensure(ctx->h_csc, ctx->h_csc_cap, a_mc + b_nz + 64, 4096 - 64));
+    char* hs = (char*)ctx->h_csc;
+    memcpy(hs, csc.moff.data(), b_off);
+    if (nnz) { memcpy(hs + a_nz, csc.ment.data(), b_nz); memcpy(hs + a_mc, csc.mc.data(), b_nz); }
+    if (small_stmt) { k = CscPtrs{(const u32*)hs, (const u32*)(hs + a_nz), (const u32*)(hs + a_mc)}; return BP_OK; }
+    HIPCHK(hipMemcpyAsync(ctx->p_moff.p, hs, b_off, hipMemcpyHostToDevice, ctx->stream));
+    if (nnz) {
+        HIPCHK(hipMemcpyAsync(ctx->p_ment.p, hs + a_nz, b_nz, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->p_mc.p, hs + a_mc, b_nz, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return BP_OK;
+}
+
+// w_L, w_R, w_O on the device, wV on the host, the y tables on the device (prover.rs:354-397, 651-698)
+template <class C> static int prove_flatten(ProveJob<C>& j) {
+    typedef typename C::Fr FrP;
+    bp_ctx* ctx = j.ctx;
+    hipStream_t st = ctx->stream;
+    const size_t n = j.n, N = j.N;
+    bool ypw_early = false;   // (a small statement sends the y tables up together with the coefficient table)
+    double t0 = now_s();
+    BPCHK(ctx->r_wL.ensure(N * 32)); BPCHK(ctx->r_wR.ensure(N * 32)); BPCHK(ctx->r_wO.ensure(N * 32));
     static const bool host_flatten = getenv("ARKBP_HOST_FLATTEN") != nullptr;   // A/B: the host pass over all terms + 3 uploads
-    if (!(csc && csc->n == n && csc->q == cs.num_constraints()) && n > 0 && !host_flatten) {
+    auto fits = [&](const HostCsc* c) { return c && c->n == n && c->q == j.cs.num_constraints(); };
+    if (!fits(j.csc) && n > 0 && !host_flatten) {
         // randomized (two-phase) statements: the constraints exist only now (prover.rs:418-441) — index them here, then the
         // same kernel evaluates them
-        csc = build_host_csc<C>(cs, csc_late) ? &csc_late : nullptr;
+        j.csc = build_host_csc<C>(j.cs, j.csc_late) ? &j.csc_late : nullptr;
     }
-    if (csc && csc->n == n && csc->q == cs.num_constraints() && n > 0) {
-        // the constraint index goes up (36 MB at 2^20 instead of 96 MB of flattened vectors), z^e tables, one launch
-        const size_t nnz = csc->ment.size();
-        const u32 nzhi = (u32)((csc->q + 1) >> 8) + 1;
-        BPCHK(ctx->p_moff.ensure((n + 1) * 4)); BPCHK(ctx->p_ment.ensure(std::max<size_t>(nnz, 1) * 4)); BPCHK(ctx->p_mc.ensure(std::max<size_t>(nnz, 1) * 4));
-        BPCHK(ctx->p_coefs.ensure((csc->coefs.size() + 32) * 32)); BPCHK(ctx->p_ztab.ensure((size_t)(256 + nzhi) * 32));
-        const bool small_stmt = n <= UPLOAD_FUSED_MAX && csc->coefs.size() <= UPLOAD_FUSED_MAX;   // a small statement: the kernels read the pinned staging memory themselves
-        const u32 *k_moff = ctx->p_moff.as<u32>(), *k_ment = ctx->p_ment.as<u32>(), *k_mc = ctx->p_mc.as<u32>();
-        {   // 36 MB at 2^20: through pinned memory like the witness (a pageable H2D copy serialises across the proofs in flight)
-            const size_t b_off = (n + 1) * 4, b_nz = nnz * 4, a_nz = (b_off + 63) / 64 * 64, a_mc = a_nz + (b_nz + 63) / 64 * 64;
-            if (ctx->h_csc_cap < a_mc + b_nz + 64) {
-                if (ctx->h_csc) HIPCHK(hipHostFree(ctx->h_csc));
-                ctx->h_csc = nullptr; ctx->h_csc_cap = 0;
-                HIPCHK(hipHostMalloc(&ctx->h_csc, a_mc + b_nz + 4096));
-                ctx->h_csc_cap = a_mc + b_nz + 4096;
-            }
-            char* hs = (char*)ctx->h_csc;
-            memcpy(hs, csc->moff.data(), b_off);
-            if (nnz) { memcpy(hs + a_nz, csc->ment.data(), b_nz); memcpy(hs + a_mc, csc->mc.data(), b_nz); }
-            if (small_stmt) { k_moff = (const u32*)hs; k_ment = (const u32*)(hs + a_nz); k_mc = (const u32*)(hs + a_mc); }
-            else {
-            HIPCHK(hipMemcpyAsync(ctx->p_moff.p, hs, b_off, hipMemcpyHostToDevice, st));
-            if (nnz) {
-                HIPCHK(hipMemcpyAsync(ctx->p_ment.p, hs + a_nz, b_nz, hipMemcpyHostToDevice, st));
-                HIPCHK(hipMemcpyAsync(ctx->p_mc.p, hs + a_mc, b_nz, hipMemcpyHostToDevice, st));
-            }
-            }
-        }
+    if (fits(j.csc) && n > 0) {   // the constraint index goes up, z^e tables, one launch
+        const HostCsc& csc = *j.csc;
+        const size_t nc = csc.coefs.size();
+        const u32 nzhi = (u32)((csc.q + 1) >> 8) + 1;
+        BPCHK(ctx->p_coefs.ensure((nc + 32) * 32)); BPCHK(ctx->p_ztab.ensure((size_t)(256 + nzhi) * 32));
+        const bool small_stmt = n <= UPLOAD_FUSED_MAX && nc <= UPLOAD_FUSED_MAX;
+        CscPtrs k;
+        BPCHK(prove_csc_stage(ctx, csc, small_stmt, k));
         F4 ztab[32];
-        { F4 c = z; for (int j = 0; j < 32; j++) { ztab[j] = c; c = S::sqr(c); } }
-        u32* d_ztab = ctx->p_coefs.as<u32>() + csc->coefs.size() * 8;
+        host::prove_pow_tables<C>(j.z, j.y, ztab, small_stmt ? j.ypw : nullptr);
+        u32* d_ztab = ctx->p_coefs.as<u32>() + nc * 8;
         if (small_stmt) {   // coefficient table, powers of z and the y tables (needed by the t(x) kernels below) in one launch, read from the pinned slab
             ypw_early = true;
-            { F4 c = y, ci = S::inv(y); for (int k = 0; k < 32; k++) { ypw[k] = c; ypw[32 + k] = ci; c = S::sqr(c); ci = S::sqr(ci); } }
             BPCHK(ctx->r_ypow.ensure(64 * 32));
-            const size_t nc = csc->coefs.size();
             BPCHK(upload_slab_ensure(ctx, (nc + 96) * 32));
             char* stage = (char*)ctx->h_upload;
-            memcpy(stage, csc->coefs.data(), nc * 32); memcpy(stage + nc * 32, ztab, 32 * 32); memcpy(stage + (nc + 32) * 32, ypw, 64 * 32);
+            memcpy(stage, csc.coefs.data(), nc * 32); memcpy(stage + nc * 32, ztab, 32 * 32); memcpy(stage + (nc + 32) * 32, j.ypw, 64 * 32);
             ImportList il; memset(&il, 0, sizeof il);
             il.nseg = 3;
             il.dst[0] = ctx->p_coefs.as<u32>(); il.cnt[0] = (u32)nc; il.dst[1] = d_ztab; il.cnt[1] = 32; il.dst[2] = ctx->r_ypow.as<u32>(); il.cnt[2] = 64;
             hipLaunchKernelGGL(k_scalars_import_multi<FrP>, dim3((u32)((nc + 96 + 255) / 256)), dim3(256), 0, st, (const u32*)stage, il);
         } else {
-        BPCHK(upload_scalars<C>(ctx, ctx->p_coefs.as<u32>(), csc->coefs.data(), csc->coefs.size()));
-        BPCHK(upload_scalars<C>(ctx, d_ztab, ztab, 32));
+            BPCHK(upload_scalars<C>(ctx, ctx->p_coefs.as<u32>(), csc.coefs.data(), nc));
+            BPCHK(upload_scalars<C>(ctx, d_ztab, ztab, 32));
         }
         hipLaunchKernelGGL(k_r1cs_ztables<C>, dim3((std::max(256u, nzhi) + 255) / 256), dim3(256), 0, st, d_ztab, nzhi, ctx->p_ztab.as<u32>());
-        hipLaunchKernelGGL(k_r1cs_flatten<C>, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, k_moff, k_ment, k_mc,
+        hipLaunchKernelGGL(k_r1cs_flatten<C>, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, k.moff, k.ment, k.mc,
                            ctx->p_coefs.as<u32>(), ctx->p_ztab.as<u32>(), (u32)n, ctx->r_wL.as<u32>(), ctx->r_wR.as<u32>(), ctx->r_wO.as<u32>());
         HIPCHK(hipGetLastError());
-        // wV on the host: the few terms on committed variables, z^(q+1) carried from term to term
-        wV.assign(cs.v.size(), S::zero());
-        {
-            auto pow_z = [&](u32 e) { F4 r = S::one(); for (u32 j = 0; e; e >>= 1, j++) if (e & 1) r = S::mul(r, ztab[j]); return r; };
-            F4 zq = S::one(), zstep = S::one();
-            u32 cur = 0, last_d = 0;
-            for (const auto& tm2 : csc->vterms) {
-                const u32 q1 = tm2.q + 1;
-                if (cur == 0) zq = pow_z(q1);
-                else if (q1 != cur) { const u32 d = q1 - cur; if (d != last_d) { zstep = pow_z(d); last_d = d; } zq = S::mul(zq, zstep); }
-                cur = q1;
-                wV[tm2.j] = S::sub(wV[tm2.j], S::mul(zq, tm2.c));
-            }
-        }
-        tm.flatten += now_s() - t0;
+        host::prove_wv<C>(csc, ztab, j.cs.v.size(), j.wV);
+        j.tm.flatten += now_s() - t0;
         t0 = now_s();
     } else {
         std::vector<F4> wL, wR, wO; F4 wc;
-        cs.flatten(z, wL, wR, wO, wV, wc, cs.v.size());
-        tm.flatten += now_s() - t0;
+        j.cs.flatten(j.z, wL, wR, wO, j.wV, wc, j.cs.v.size());
+        j.tm.flatten += now_s() - t0;
         t0 = now_s();
         BPCHK(upload_scalars<C>(ctx, ctx->r_wL.as<u32>(), wL.data(), n));
         BPCHK(upload_scalars<C>(ctx, ctx->r_wR.as<u32>(), wR.data(), n));
         BPCHK(upload_scalars<C>(ctx, ctx->r_wO.as<u32>(), wO.data(), n));
         HIPCHK(ctx_stream_wait(ctx));   // wL, wR, wO are locals of this branch
     }
-    mark("flatten");
-    // y^(2^k), y^-(2^k) tables
+    j.trace.mark("flatten");
     if (!ypw_early) {
-        { F4 c = y, ci = S::inv(y); for (int k = 0; k < 32; k++) { ypw[k] = c; ypw[32 + k] = ci; c = S::sqr(c); ci = S::sqr(ci); } }
+        host::prove_pow_tables<C>(j.z, j.y, nullptr, j.ypw);
         BPCHK(ctx->r_ypow.ensure(64 * 32));
-        BPCHK(upload_scalars<C>(ctx, ctx->r_ypow.as<u32>(), ypw, 64));
+        BPCHK(upload_scalars<C>(ctx, ctx->r_ypow.as<u32>(), j.ypw, 64));
     }
-    tm.upload += now_s() - t0;
+    j.tm.upload += now_s() - t0;
+    return BP_OK;
+}
 
-    // the blinding factors of T_1, T_3 .. T_6 (prover.rs:700-707) are the next draws whatever t(x) turns out to be: drawn first, so that
-    // a small statement's T commitments can follow the t(x) kernels on the GPU without a host round trip in between
-    t0 = now_s();
-    const F4 t1b = host::rand_fe<FrP>(rng), t3b = host::rand_fe<FrP>(rng), t4b = host::rand_fe<FrP>(rng), t5b = host::rand_fe<FrP>(rng),
-             t6b = host::rand_fe<FrP>(rng);
-    tm.rng += now_s() - t0;
-    t0 = now_s();
-    F4 tco[6];
-    bool t_direct = false;   // T_i = t_i * B + blinding_i * B_blinding over the direct window tables, behind k_r1cs_sum in the stream
+// t_1 .. t_6 (prover.rs:651-698) and T_1, T_3 .. T_6 (prover.rs:709-714): a small statement's T commitments follow the t(x) kernels
+// over the direct window tables, behind k_r1cs_sum in the stream, without a host round trip in between
+template <class C> static int prove_poly_t(ProveJob<C>& j) {
+    typedef host::Fld<typename C::Fr> S;
+    bp_ctx* ctx = j.ctx;
+    hipStream_t st = ctx->stream;
+    const size_t n = j.n;
+    const double t0 = now_s();
+    bool t_direct = false;
     J4 Tj[5];
     if (n > 0) {
         const u32 gb = (u32)((n + 255) / 256);
         BPCHK(ctx->r_part.ensure((size_t)gb * 6 * 32)); BPCHK(ctx->r_small.ensure(6 * 32));
-        BPCHK(dt_ensure<C>(ctx, N, t_direct));
+        BPCHK(dt_ensure<C>(ctx, j.N, t_direct));
         ScopedK tk(ctx, BP_K_R1CS_POLY);
         hipLaunchKernelGGL(k_r1cs_poly_t<C>, dim3(gb), dim3(256), 0, st, ctx->r_aL.as<u32>(), ctx->r_aR.as<u32>(), ctx->r_aO.as<u32>(), ctx->r_sL.as<u32>(),
                            ctx->r_sR.as<u32>(), ctx->r_wL.as<u32>(), ctx->r_wR.as<u32>(), ctx->r_wO.as<u32>(), ctx->r_ypow.as<u32>(), (u32)n, ctx->r_part.as<u32>(),
                            gb == 1 ? ctx->r_small.as<u32>() : (u32*)nullptr);
         if (gb > 1) hipLaunchKernelGGL(k_r1cs_sum<C>, dim3(1), dim3(256), 0, st, ctx->r_part.as<u32>(), gb, 6u, ctx->r_small.as<u32>());
         tk.stop();
-        HIPCHK(hipMemcpyAsync(tco, ctx->r_small.p, 6 * 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(j.tco, ctx->r_small.p, 6 * 32, hipMemcpyDeviceToHost, st));
         if (t_direct) {
             DtJobs jobs; memset(&jobs, 0, sizeof jobs);
-            const F4* bl[5] = {&t1b, &t3b, &t4b, &t5b, &t6b};
-            const int slot[5] = {0, 2, 3, 4, 5};
-            for (int o = 0; o < 5; o++) {
-                DtJob& jb = jobs.job[o];
-                uint64_t cw[4];
-                S::to_canon(cw, *bl[o]);
-                memcpy(jb.imm, cw, 32);
-                jb.has_imm = 1; jb.imm_base = dt_base_pc(1);
-                jb.nseg = 1; jb.terms = 2;
-                jb.seg[0] = DtSeg{ctx->r_small.as<u32>() + slot[o] * 8, dt_base_pc(0), 1, 2 /* k_r1cs_sum writes ark words */, 0, 0};
-            }
+            dt_t_jobs<C>(jobs.job, ctx->r_small.as<u32>() /* k_r1cs_sum writes ark words */, j.tb, nullptr);
             BPCHK(msm_direct_launch<C>(ctx, jobs, 5));
         }
         HIPCHK(ctx_stream_wait(ctx));
         HIPCHK(hipGetLastError());
         if (t_direct) msm_direct_collect<C>(ctx, 5, Tj);
     } else {
-        for (auto& t : tco) t = S::zero();
+        for (auto& t : j.tco) t = S::zero();
     }
-    tm.poly += now_s() - t0;
-    mark("poly t");
-    const F4 &t1 = tco[0], &t2 = tco[1], &t3 = tco[2], &t4 = tco[3], &t5 = tco[4], &t6 = tco[5];
+    j.tm.poly += now_s() - t0;
+    j.trace.mark("poly t");
+    const int slot[5] = {0, 2, 3, 4, 5};
+    if (t_direct) to_aff_many<C>(Tj, 5, j.Tc);
+    else for (int o = 0; o < 5; o++) j.Tc[o] = j.pc.commit(j.tco[slot[o]], j.tb[o]);
+    return BP_OK;
+}
 
-    A4 Tc[5];
-    if (t_direct) to_aff_batch<C>(Tj, 5, Tc);
-    else { Tc[0] = pc.commit(t1, t1b); Tc[1] = pc.commit(t3, t3b); Tc[2] = pc.commit(t4, t4b); Tc[3] = pc.commit(t5, t5b); Tc[4] = pc.commit(t6, t6b); }
-    const A4 &T_1 = Tc[0], &T_3 = Tc[1], &T_4 = Tc[2], &T_5 = Tc[3], &T_6 = Tc[4];
-    TP::append_point(tr, "T_1", T_1); TP::append_point(tr, "T_3", T_3); TP::append_point(tr, "T_4", T_4); TP::append_point(tr, "T_5", T_5);
-    TP::append_point(tr, "T_6", T_6);
-    mark("T commitments");
-    const F4 u = TP::challenge_scalar(tr, "u"), x = TP::challenge_scalar(tr, "x");
-    F4 t2b = S::zero();
-    for (size_t j = 0; j < wV.size(); j++) t2b = S::add(t2b, S::mul(cs.v_blinding[j], wV[j]));
-    auto poly6 = [&](const F4& c1, const F4& c2, const F4& c3, const F4& c4, const F4& c5, const F4& c6) {  // util.rs:107-109
-        F4 acc = S::add(S::mul(x, c6), c5);
-        acc = S::add(S::mul(acc, x), c4); acc = S::add(S::mul(acc, x), c3); acc = S::add(S::mul(acc, x), c2); acc = S::add(S::mul(acc, x), c1);
-        return S::mul(acc, x);
-    };
-    const F4 t_x = poly6(t1, t2, t3, t4, t5, t6), t_x_blinding = poly6(t1b, t2b, t3b, t4b, t5b, t6b);
-    const F4 i_b = S::add(i_b1, S::mul(u, i_b2)), o_b = S::add(o_b1, S::mul(u, o_b2)), s_b = S::add(s_b1, S::mul(u, s_b2));
-    const F4 e_blinding = S::mul(x, S::add(i_b, S::mul(x, S::add(o_b, S::mul(x, s_b)))));
-    TP::append_scalar(tr, "t_x", t_x); TP::append_scalar(tr, "t_x_blinding", t_x_blinding); TP::append_scalar(tr, "e_blinding", e_blinding);
-    const F4 w = TP::challenge_scalar(tr, "w");
-    mark("t_x .. w");
-
-    // l(x), r(x), G_factors, H_factors on the device; working copies of the generator tables
-    t0 = now_s();
+// l(x), r(x), G_factors, H_factors on the device (prover.rs:723-789); working copies of the generator tables; Q
+template <class C> static int prove_eval(ProveJob<C>& j) {
+    typedef host::Fld<typename C::Fr> S;
+    typedef host::Grp<C> G;
+    bp_ctx* ctx = j.ctx;
+    hipStream_t st = ctx->stream;
+    const size_t N = j.N;
+    const double t0 = now_s();
     BPCHK(ctx->ipa_a.ensure(N * 32)); BPCHK(ctx->ipa_b.ensure(N * 32)); BPCHK(ctx->ipa_Gf.ensure(N * 32)); BPCHK(ctx->ipa_Hf.ensure(N * 32));
     if (!ipa_cyclic_applies(ctx, N)) { BPCHK(ctx->ipa_G.ensure(N * 64)); BPCHK(ctx->ipa_H.ensure(N * 64)); }
     BPCHK(ctx->ipa_Q.ensure(64));
-    BPCHK(ensure_vecs(N));
+    BPCHK(prove_ensure_vecs(ctx, N));
     {
         ScopedK tk(ctx, BP_K_R1CS_POLY);
         hipLaunchKernelGGL(k_r1cs_poly_eval<C>, dim3((u32)((N + 255) / 256)), dim3(256), 0, st, ctx->r_aL.as<u32>(), ctx->r_aR.as<u32>(), ctx->r_aO.as<u32>(),
-                           ctx->r_sL.as<u32>(), ctx->r_sR.as<u32>(), ctx->r_wL.as<u32>(), ctx->r_wR.as<u32>(), ctx->r_wO.as<u32>(), ctx->r_ypow.as<u32>(), (u32)n,
-                           (u32)n1, (u32)N, words_of<S>(x), words_of<S>(u), ctx->ipa_a.as<u32>(), ctx->ipa_b.as<u32>(), ctx->ipa_Gf.as<u32>(),
+                           ctx->r_sL.as<u32>(), ctx->r_sR.as<u32>(), ctx->r_wL.as<u32>(), ctx->r_wR.as<u32>(), ctx->r_wO.as<u32>(), ctx->r_ypow.as<u32>(), (u32)j.n,
+                           (u32)j.n1, (u32)N, words_of<S>(j.x), words_of<S>(j.u), ctx->ipa_a.as<u32>(), ctx->ipa_b.as<u32>(), ctx->ipa_Gf.as<u32>(),
                            ctx->ipa_Hf.as<u32>());
     }
-    const bool cyclic = ipa_cyclic_applies(ctx, N);   // sharded prover: the IPA's vectors partitioned index-cyclically across the ranks
-    bool direct = false;   // small statements: no folding of G and H at all, every round over the direct window tables
-    if (!cyclic && N >= 2) BPCHK(dt_ensure<C>(ctx, N, direct));
+    j.cyclic = ipa_cyclic_applies(ctx, N);   // sharded prover: the IPA's vectors partitioned index-cyclically across the ranks
+    j.direct = false;   // small statements: no folding of G and H at all, every round over the direct window tables
+    if (!j.cyclic && N >= 2) BPCHK(dt_ensure<C>(ctx, N, j.direct));
     // with first-round fold tables the round reads the resident generator tables in place: no working copy (2 x 64 B x N)
-    const bool in_place = !cyclic && !direct && N >= 128 && (ctx->ftab_n >= N / 2 || ctx->fb_cap >= N);
-    if (!cyclic && !in_place && !direct) {
+    j.in_place = !j.cyclic && !j.direct && N >= 128 && (ctx->ftab_n >= N / 2 || ctx->fb_cap >= N);
+    if (!j.cyclic && !j.in_place && !j.direct) {
         HIPCHK(hipMemcpyAsync(ctx->ipa_G.p, ctx->d_G.p, N * 64, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(ctx->ipa_H.p, ctx->d_H.p, N * 64, hipMemcpyDeviceToDevice, st));
     }
-    if (!direct) {   // Q = w * B as a point (prover.rs:779); over the direct tables c * Q is (c * w) * B and Q itself is never formed
-        const A4 Q = G::to_aff(pc.mul_B_jac(w));   // (the host's fixed-base tables of the ctx's pair)
+    if (!j.direct) {   // Q = w * B as a point (prover.rs:779); over the direct tables c * Q is (c * w) * B and Q itself is never formed
+        const A4 Q = G::to_aff(j.pc.mul_B_jac(j.w));   // (the host's fixed-base tables of the ctx's pair)
         uint64_t Qw[8]; memcpy(Qw, Q.x.v, 32); memcpy(Qw + 4, Q.y.v, 32);
         HIPCHK(hipMemcpyAsync(ctx->ipa_Q.p, Qw, 64, hipMemcpyHostToDevice, st));
         BPCHK(bp_points_import(ctx, ctx->ipa_Q.p, ctx->ipa_Q.p, 1));
     }
-    tm.poly += now_s() - t0;
-    mark("l(x), r(x), Q");
+    j.tm.poly += now_s() - t0;
+    return BP_OK;
+}
 
-    t0 = now_s();
+// The inner-product argument (prover.rs:791-803) — here, or handed to a lockstep group (defer) — into `proof`
+template <class C> static int prove_ipa(ProveJob<C>& j, IpaDefer* defer, host::ProofData& proof) {
+    typedef host::Fld<typename C::Fr> S;
+    typedef host::TP<C> TP;
+    bp_ctx* ctx = j.ctx;
+    hipStream_t st = ctx->stream;
+    host::Transcript& tr = *j.cs.tr;
+    const size_t N = j.N, n1 = j.n1;
+    const double t0 = now_s();
     IpaDeferSlot dslot;
-    const bool deferred = defer && direct && !cyclic && N >= 2 && ctx->dt_cap >= N && defer->take(N, dslot);
-    if (deferred) {   // (the same copies ipa_create_dev's direct path makes of the factor vectors)
+    j.deferred = defer && j.direct && !j.cyclic && N >= 2 && ctx->dt_cap >= N && defer->take(N, dslot);
+    if (j.deferred) {   // (the same copies ipa_create_dev's direct path makes of the factor vectors)
         HIPCHK(hipMemcpyAsync(dslot.a, ctx->ipa_a.p, N * 32, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(dslot.b, ctx->ipa_b.p, N * 32, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(dslot.cG, ctx->ipa_Gf.p, N * 32, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(dslot.cH, ctx->ipa_Hf.p, N * 32, hipMemcpyDeviceToDevice, st));
-        defer->taken = true; defer->N = N; defer->w = w;
+        defer->taken = true; defer->N = N; defer->w = j.w;
     }
     TP::innerproduct_domain_sep(tr, N);
     size_t lg = 0; while (((size_t)1 << lg) < N) lg++;
@@ -798,31 +695,30 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     uint64_t aw[4], bw[4];
     ChallengeFn fn = [&](const uint64_t* L, const uint64_t* R, uint64_t* uo) {
         A4 Lp, Rp; memcpy(Lp.x.v, L, 32); memcpy(Lp.y.v, L + 4, 32); memcpy(Rp.x.v, R, 32); memcpy(Rp.y.v, R + 4, 32);
-        TP::append_point(tr, "L", Lp); TP::append_point(tr, "R", Rp);
-        F4 uu = TP::challenge_scalar(tr, "u");
+        const F4 uu = host::prove_round_challenge<C>(tr, Lp, Rp);
         memcpy(uo, uu.v, 32);
         return 0;
     };
     // G_factors = [1]*n1 ++ [u]*(N-n1) (prover.rs:781-784): constant on each half of the first fold iff n1 is 0, N/2 or >= N
-    F4 gfh[2] = {n1 >= N / 2 ? S::one() : u, n1 >= N ? S::one() : u};
+    F4 gfh[2] = {n1 >= N / 2 ? S::one() : j.u, n1 >= N ? S::one() : j.u};
     const bool gf_const_halves = N >= 2 && (n1 == 0 || n1 == N / 2 || n1 >= N);
-    if (deferred) {}
-    else if (cyclic)
+    if (j.deferred) {}
+    else if (j.cyclic)
         BPCHK(ipa_create_cyclic<C>(ctx, ctx->ipa_Q.as<u32>(), ctx->ipa_Gf.as<u32>(), ctx->ipa_Hf.as<u32>(), ctx->d_G.as<u32>(), ctx->d_H.as<u32>(), ctx->ipa_a.as<u32>(),
-                                   ctx->ipa_b.as<u32>(), N, fn, Lw.data(), Rw.data(), aw, bw, gf_const_halves ? gfh : nullptr, gf_const_halves ? ypw : nullptr,
-                                   gf_const_halves ? ctx->r_ypow.as<u32>() + 32 * 8 : nullptr, &w));
+                                   ctx->ipa_b.as<u32>(), N, fn, Lw.data(), Rw.data(), aw, bw, gf_const_halves ? gfh : nullptr, gf_const_halves ? j.ypw : nullptr,
+                                   gf_const_halves ? ctx->r_ypow.as<u32>() + 32 * 8 : nullptr, &j.w));
     else
-    BPCHK(ipa_create_dev<C>(ctx, ctx->ipa_Q.as<u32>(), ctx->ipa_Gf.as<u32>(), ctx->ipa_Hf.as<u32>(), ctx->ipa_G.as<u32>(), ctx->ipa_H.as<u32>(),
-                            ctx->ipa_a.as<u32>(), ctx->ipa_b.as<u32>(), N, fn, Lw.data(), Rw.data(), aw, bw, gf_const_halves ? gfh : nullptr,
-                            // H_factors[i] = y^-i * G_factors[i] (prover.rs:785-789): rho = y^-1; ypw[k] = y^(2^k) = rho^-(2^k), ypw[32+k] = rho^(2^k)
-                            gf_const_halves ? ypw : nullptr, gf_const_halves ? ctx->r_ypow.as<u32>() + 32 * 8 : nullptr, true, in_place, &w, direct));
-    tm.ipa += now_s() - t0;
-    mark("inner-product argument");
+        BPCHK(ipa_create_dev<C>(ctx, ctx->ipa_Q.as<u32>(), ctx->ipa_Gf.as<u32>(), ctx->ipa_Hf.as<u32>(), ctx->ipa_G.as<u32>(), ctx->ipa_H.as<u32>(),
+                                ctx->ipa_a.as<u32>(), ctx->ipa_b.as<u32>(), N, fn, Lw.data(), Rw.data(), aw, bw, gf_const_halves ? gfh : nullptr,
+                                // H_factors[i] = y^-i * G_factors[i] (prover.rs:785-789): rho = y^-1; ypw[k] = y^(2^k) = rho^-(2^k), ypw[32+k] = rho^(2^k)
+                                gf_const_halves ? j.ypw : nullptr, gf_const_halves ? ctx->r_ypow.as<u32>() + 32 * 8 : nullptr, true, j.in_place, &j.w, j.direct));
+    j.tm.ipa += now_s() - t0;
+    j.trace.mark("inner-product argument");
 
-    proof.A_I1 = A_I1; proof.A_O1 = A_O1; proof.S1 = S1; proof.A_I2 = A_I2; proof.A_O2 = A_O2; proof.S2 = S2;
-    proof.T_1 = T_1; proof.T_3 = T_3; proof.T_4 = T_4; proof.T_5 = T_5; proof.T_6 = T_6;
-    proof.t_x = t_x; proof.t_x_blinding = t_x_blinding; proof.e_blinding = e_blinding;
-    if (!deferred) {
+    proof.A_I1 = j.c1[0]; proof.A_O1 = j.c1[1]; proof.S1 = j.c1[2]; proof.A_I2 = j.c2[0]; proof.A_O2 = j.c2[1]; proof.S2 = j.c2[2];
+    proof.T_1 = j.Tc[0]; proof.T_3 = j.Tc[1]; proof.T_4 = j.Tc[2]; proof.T_5 = j.Tc[3]; proof.T_6 = j.Tc[4];
+    proof.t_x = j.t_x; proof.t_x_blinding = j.t_x_blinding; proof.e_blinding = j.e_blinding;
+    if (!j.deferred) {
         proof.L_vec.resize(lg); proof.R_vec.resize(lg);
         for (size_t i = 0; i < lg; i++) {
             memcpy(proof.L_vec[i].x.v, &Lw[8 * i], 32); memcpy(proof.L_vec[i].y.v, &Lw[8 * i + 4], 32);
@@ -830,32 +726,110 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
         }
         memcpy(proof.a.v, aw, 32); memcpy(proof.b.v, bw, 32);
     }
-    // secret hygiene (prover.rs:74-94, 805-812): wipe the witness-derived device vectors
+    return BP_OK;
+}
+
+// secret hygiene (prover.rs:74-94, 805-812): the witness-derived device vectors, the host copies of s_L / s_R, the key
+template <class C> static int prove_wipe(ProveJob<C>& j) {
+    typedef host::Fld<typename C::Fr> S;
+    bp_ctx* ctx = j.ctx;
+    j.secrets_up = false;
+    for (auto& s : j.pre.s_L) s = S::zero();
+    for (auto& s : j.pre.s_R) s = S::zero();
+    j.pre.kappa1 = S::zero();
     DevBuf* wipe[] = {&ctx->r_aL, &ctx->r_aR, &ctx->r_aO, &ctx->r_sL, &ctx->r_sR, &ctx->ipa_a, &ctx->ipa_b, &ctx->cyc_a, &ctx->cyc_b, &ctx->dt_a2, &ctx->dt_b2};
-    {
-        size_t total = 0;
-        int live = 0;
-        for (auto b : wipe) if (b->p) { total += b->cap; live++; }
-        if (live && live <= ZERO_MAX && total <= ((size_t)64 << 20)) {   // a small proof: one launch instead of eleven memsets
-            ZeroList zl; memset(&zl, 0, sizeof zl);
-            for (auto b : wipe) if (b->p) { zl.p[zl.count] = (uint4*)b->p; zl.n16[zl.count] = (u32)(b->cap / 16); zl.count++; }   // (allocations are 256-byte multiples + 256: cap / 16 units cover all but < 16 trailing bytes that no kernel addresses)
-            hipLaunchKernelGGL(k_zero_many, dim3((u32)std::min<size_t>(1024, (total / 16 + 255) / 256)), dim3(256), 0, st, zl);
-            HIPCHK(hipGetLastError());
-        } else {
-            for (auto b : wipe) if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->cap, st));
-        }
+    size_t total = 0;
+    int live = 0;
+    for (auto b : wipe) if (b->p) { total += b->cap; live++; }
+    if (live && live <= ZERO_MAX && total <= ((size_t)64 << 20)) {   // a small proof: one launch instead of eleven memsets
+        ZeroList zl; memset(&zl, 0, sizeof zl);
+        for (auto b : wipe) if (b->p) { zl.p[zl.count] = (uint4*)b->p; zl.n16[zl.count] = (u32)(b->cap / 16); zl.count++; }   // (allocations are 256-byte multiples + 256: cap / 16 units cover all but < 16 trailing bytes that no kernel addresses)
+        hipLaunchKernelGGL(k_zero_many, dim3((u32)std::min<size_t>(1024, (total / 16 + 255) / 256)), dim3(256), 0, ctx->stream, zl);
+        HIPCHK(hipGetLastError());
+    } else {
+        for (auto b : wipe) if (b->p) HIPCHK(hipMemsetAsync(b->p, 0, b->cap, ctx->stream));
     }
-    for (auto& s : s_L) s = S::zero();
-    for (auto& s : s_R) s = S::zero();
-    pre.kappa1 = S::zero();
+    return BP_OK;
+}
+// ... on every way out once something secret is on the device: a stage that fails returns through this
+template <class C> struct ProveWipeScope {
+    ProveJob<C>& j;
+    ~ProveWipeScope() { if (j.secrets_up) (void)prove_wipe<C>(j); }
+};
+
+template <class C>
+static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8* rng_bytes, host::ProofData& proof, StageTimes& tm,
+                      ProvePre<C>* pre_in = nullptr, const HostCsc* csc = nullptr /* constraint index built with the statement (single-phase) */,
+                      IpaDefer* defer = nullptr,
+                      const A4* resume1 = nullptr /* bp_prover_prove_batch, a member that leaves its front group after the randomized phase: A_I1, A_O1,
+                      S1 are in the transcript and the phase has run — neither happens again; the whole witness goes up to the workspaces here */) {
+    typedef host::Fld<typename C::Fr> S;
+    typedef host::Grp<C> G;
+    typedef host::TP<C> TP;
+    host::Transcript& tr = *cs.tr;
+    const double t_begin = now_s();
+    static const bool trace = getenv("ARKBP_PROVE_TRACE") != nullptr;
+    ProvePre<C> pre_local;
+    ProvePre<C>& pre = pre_in && pre_in->rng ? *pre_in : pre_local;
+    if (pre_in) pre_local.mode = pre_in->mode;
+    ProveJob<C> j{ctx, cs, pre, tm};
+    j.pc.B = ctx->pc_B; j.pc.B_blinding = ctx->pc_Bb;
+    j.trace.on = trace;
+    j.csc = csc;
+    j.trace.mark("begin");
+    j.expanded = pre.mode == BP_BLINDING_EXPANDED;
+    if (!pre.rng) prove_precompute<C>(cs, rng_bytes, pre);
+    host::TranscriptRng& rng = *pre.rng;
+    tm.rng += pre.t_rng;
+    const size_t n1 = j.n1 = resume1 ? cs.n1 : cs.a_L.size();
+    if (ctx->gens_cap < n1) return BP_E_GENS_LENGTH;
+    j.b1[0] = pre.i_b1; j.b1[1] = pre.o_b1; j.b1[2] = pre.s_b1;
+
+    ProveWipeScope<C> wipe_on_exit{j};
+    BPCHK(prove_upload_phase<C>(j, 0, n1, pre.kappa1));
+    j.trace.mark("head + upload");
+    if (resume1) for (int o = 0; o < 3; o++) j.c1[o] = resume1[o];
+    else BPCHK(prove_commit_phase<C>(j, 0, n1, j.b1, j.c1));
+    j.trace.mark("commit phase 1");
+    if (!resume1) {
+        host::prove_append_phase<C>(tr, 1, j.c1[0], j.c1[1], j.c1[2]);
+        int rc = cs.run_randomized();
+        if (rc) return rc;
+    }
+    j.trace.mark("randomized phase");
+
+    const size_t n = j.n = cs.a_L.size(), N = j.N = host::next_pow2(n);
+    if (ctx->gens_cap < N) return BP_E_GENS_LENGTH;
+    const bool has2 = n > n1;
+    double t0 = now_s();
+    F4 kappa2;
+    host::prove_draw_phase2<C>(rng, has2, j.expanded, n1, n, j.bl2, kappa2, pre.s_L, pre.s_R);
+    tm.rng += now_s() - t0;
+    j.c2[0] = j.c2[1] = j.c2[2] = G::aff_inf();
+    if (has2) {
+        const int rc = prove_upload_phase<C>(j, n1, n - n1, kappa2);
+        kappa2 = S::zero();
+        BPCHK(rc);
+        BPCHK(prove_commit_phase<C>(j, n1, n - n1, j.bl2, j.c2));
+    }
+    j.trace.mark("commit phase 2");
+    host::prove_append_phase<C>(tr, 2, j.c2[0], j.c2[1], j.c2[2]);
+    j.y = TP::challenge_scalar(tr, "y"); j.z = TP::challenge_scalar(tr, "z");
+    BPCHK(prove_flatten<C>(j));
+    t0 = now_s();
+    host::prove_draw_t<C>(rng, j.tb);   // (drawn before t(x): a small statement's T commitments then follow its kernels on the GPU)
+    tm.rng += now_s() - t0;
+    BPCHK(prove_poly_t<C>(j));
+    j.trace.mark("T commitments");
+    host::prove_t_tail<C>(tr, j.Tc, j.tco, j.tb, j.wV, cs.v_blinding, j.b1, j.bl2, j.u, j.x, j.t_x, j.t_x_blinding, j.e_blinding, j.w);
+    j.trace.mark("t_x .. w");
+    BPCHK(prove_eval<C>(j));
+    j.trace.mark("l(x), r(x), Q");
+    BPCHK(prove_ipa<C>(j, defer, proof));
+    BPCHK(prove_wipe<C>(j));
     tm.total = now_s() - t_begin + (pre_in && pre_in->rng ? pre.t_rng : 0.0);
     if (ctx->profiling) collect_timers(ctx);
-    if (trace) {
-        mark("end");
-        std::string line = "prove n=" + std::to_string(n) + ":";
-        for (size_t i = 1; i < marks.size(); i++) { char b[96]; snprintf(b, sizeof b, "  %s %.0f", marks[i].first, (marks[i].second - marks[i - 1].second) * 1e6); line += b; }
-        fprintf(stderr, "%s us\n", line.c_str());
-    }
+    j.trace.print(n);
     return BP_OK;
 }
 
@@ -920,8 +894,6 @@ template <class C> static int pedersen_commit_batch(bp_ctx* ctx, const uint64_t*
     if (!m) return BP_OK;
     BPCHK(pedersen_ensure<C>(ctx));
     if (m <= PC_LATENCY_MAX) {
-        typedef host::Grp<C> G;
-        typedef host::Fld<typename C::Fq> F;
         BPCHK(ctx->io_scal.ensure(m * 64)); BPCHK(ctx->io_pts.ensure(m * 96));
         BPCHK(upload_slab_ensure(ctx, m * 160));
         char* slab = (char*)ctx->h_upload;
@@ -933,18 +905,7 @@ template <class C> static int pedersen_commit_batch(bp_ctx* ctx, const uint64_t*
         const J4* jac = (const J4*)(slab + m * 64);
         HIPCHK(hipMemcpyAsync((void*)jac, ctx->io_pts.p, m * 96, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx_stream_wait(ctx));
-        // one inversion for the whole batch (Montgomery's trick); the identity (v = blind = 0) stays all-zero words
-        std::vector<F4> pref(m);
-        F4 run = F::one();
-        for (size_t i = 0; i < m; i++) { pref[i] = run; if (!jac[i].Z.is_zero()) run = F::mul(run, jac[i].Z); }
-        F4 inv = F::inv(run);
-        A4* out = (A4*)out_xy;
-        for (size_t i = m; i-- > 0;) {
-            if (jac[i].Z.is_zero()) { out[i] = G::aff_inf(); continue; }
-            const F4 zi = F::mul(inv, pref[i]), zi2 = F::sqr(zi);
-            inv = F::mul(inv, jac[i].Z);
-            out[i] = A4{F::mul(jac[i].X, zi2), F::mul(jac[i].Y, F::mul(zi2, zi))};
-        }
+        to_aff_many<C>(jac, m, (A4*)out_xy);   // one inversion for the whole batch; the identity (v = blind = 0) stays all-zero words
         return BP_OK;
     }
     const size_t CHUNK = (size_t)1 << 20;   // bounds the staging buffers (128 MiB) for very wide statements
@@ -1426,22 +1387,14 @@ template <class C> static int decompress_points(bp_ctx* ctx, const F4* xs, const
 // pinned staging memory of the batch-verify pipeline (two alternating halves, an event each)
 static int vfy_stage_ensure(bp_ctx* ctx, int which, size_t bytes) {
     if (ctx->h_vstage_cap[which] >= bytes) return BP_OK;
-    if (ctx->h_vstage[which]) HIPCHK(hipHostFree(ctx->h_vstage[which]));
-    ctx->h_vstage[which] = nullptr; ctx->h_vstage_cap[which] = 0;
-    HIPCHK(hipHostMalloc(&ctx->h_vstage[which], bytes + bytes / 4 + 4096));
-    ctx->h_vstage_cap[which] = bytes + bytes / 4 + 4096;
+    BPCHK(pinned_ensure(ctx->h_vstage[which], ctx->h_vstage_cap[which], bytes, bytes / 4 + 4096));
     if (!ctx->vstage_ev[which]) HIPCHK(hipEventCreateWithFlags(&ctx->vstage_ev[which], hipEventDisableTiming));
     return BP_OK;
 }
 // second pinned buffer per half: the block's launch order and the coefficient tables of instances that carry their own values
 // (sized after the replay, when the staging half already holds the block's parameter blocks and tails)
 static int vfy_aux_ensure(bp_ctx* ctx, int which, size_t bytes) {
-    if (ctx->h_vaux_cap[which] >= bytes) return BP_OK;
-    if (ctx->h_vaux[which]) HIPCHK(hipHostFree(ctx->h_vaux[which]));
-    ctx->h_vaux[which] = nullptr; ctx->h_vaux_cap[which] = 0;
-    HIPCHK(hipHostMalloc(&ctx->h_vaux[which], bytes + bytes / 4 + 4096));
-    ctx->h_vaux_cap[which] = bytes + bytes / 4 + 4096;
-    return BP_OK;
+    return pinned_ensure(ctx->h_vaux[which], ctx->h_vaux_cap[which], bytes, bytes / 4 + 4096);
 }
 
 // One (Verifier, &R1CSProof) pair of batch_verify (verifier.rs:604-612) as the core sees it: a recorded verifier whose transcript

@@ -285,7 +285,7 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
             if (points) jpts.resize(P);
             BPCHK(ve_run_group<C>(ctx, t, own, live.data() + lo, P, ngroups & 1, flags.data(), points ? jpts.data() : nullptr, wait_s));
             ngroups++;
-            if (points) { apts.resize(P); pb_to_aff<C>(jpts.data(), P, apts.data()); }   // one inversion for the group's points
+            if (points) { apts.resize(P); to_aff_many<C>(jpts.data(), P, apts.data()); }   // one inversion for the group's points
             for (size_t j = 0; j < P; j++) {
                 const size_t k = live[lo + j]->k;
                 stv[k] = flags[j] ? BP_OK : BP_E_VERIFICATION;
@@ -409,7 +409,7 @@ static int msm_each_entry(bp_ctx* ctx, size_t count, const size_t* offsets, cons
     std::vector<J4> jp(count);
     std::vector<A4> ap(count);
     pf_points_in(res.data(), count, jp.data());
-    pb_to_aff<C>(jp.data(), count, ap.data());
+    to_aff_many<C>(jp.data(), count, ap.data());
     for (size_t j = 0; j < count; j++) { memcpy(out_xy + 8 * j, ap[j].x.v, 32); memcpy(out_xy + 8 * j + 4, ap[j].y.v, 32); }
     if (ctx->profiling) collect_timers(ctx);
     return BP_OK;
