@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ARKBP_LIB_PATH") or os.path.join(_HERE, "libarkbp_hip.so")   # (the override: sanitizer builds of the same sources, tools/sanitize/)
 _lib = None
 
-BP_OK, BP_E_ARG, BP_E_HIP, BP_E_NO_DEVICE, BP_E_VERIFICATION, BP_E_GENS_LENGTH, BP_E_FORMAT, BP_E_MISSING = 0, -1, -2, -3, -4, -5, -6, -7
+BP_OK, BP_E_ARG, BP_E_HIP, BP_E_NO_DEVICE, BP_E_VERIFICATION, BP_E_GENS_LENGTH, BP_E_FORMAT, BP_E_MISSING, BP_E_UNSATISFIED = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/arkbp.h declares (tests check the library exports all of them)
 EXPORTS = [
@@ -36,6 +36,8 @@ EXPORTS = [
     "bp_pedersen_gens_install", "bp_ctx_pedersen_gens", "bp_prover_new_gens",
     # blinding vectors from a key
     "bp_prover_set_blinding", "bp_prover_blinding", "bp_host_blind_expand", "bp_debug_blind_expand", "bp_ctx_blinding_stats",
+    # witness check
+    "bp_witness_check_piece", "bp_prover_check", "bp_prover_check_batch", "bp_prover_set_check", "bp_prover_checking", "bp_ctx_last_unsatisfied", "bp_debug_prover_poke_witness",
 ]
 
 
@@ -60,12 +62,21 @@ def lib():
         _lib.bp_transcript_clone.restype = C.c_void_p
         _lib.bp_cs_transcript.restype = C.c_void_p
         _lib.bp_stmt_as_prover.restype = C.c_void_p
+        if hasattr(_lib, "bp_witness_check_piece"):   # (an older build named by ARKBP_LIB_PATH has no witness check: tools/exp_witness_check.py)
+            _lib.bp_witness_check_piece.restype = C.c_size_t
     return _lib
+
+
+class UnsatisfiedError(ArkbpError):
+    """BP_E_UNSATISFIED: a guarded prover's witness violates a gate or a constraint (Engine.last_unsatisfied() has the report)"""
+
+
+_ERRORS = {BP_E_UNSATISFIED: UnsatisfiedError}   # status -> exception class (every other code: ArkbpError)
 
 
 def check(rc, where):
     if rc != BP_OK:
-        raise ArkbpError(rc, where)
+        raise _ERRORS.get(rc, ArkbpError)(rc, where)
 
 
 def ptr(a):

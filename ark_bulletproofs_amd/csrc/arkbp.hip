@@ -30,6 +30,7 @@
 #include "small.cuh"
 #include "small_batch.cuh"
 #include "small_batch_front.cuh"
+#include "witness_check.cuh"
 #include "vfy_each.cuh"
 #include "msm_batch.cuh"
 #include "vfe.hpp"
@@ -42,6 +43,8 @@ using arkbp::host::F4;
 using arkbp::host::J4;
 using arkbp::host::HostCsc;
 using arkbp::host::build_host_csc;
+using arkbp::host::HostRowIndex;
+using arkbp::host::build_row_index;
 using arkbp::host::jac_from_words;
 using arkbp::host::to_aff_many;
 
@@ -361,6 +364,11 @@ struct bp_ctx {
     void* h_pf = nullptr;            // pinned: witness staging, the aux block, results
     size_t h_pf_cap = 0;
     uint64_t pf_instances = 0, pf_groups = 0, pf_waits = 0;
+    // witness check (witness_check.cuh): its index block on the device, the pinned staging, and the instances the most recent proving call refused
+    DevBuf wc_dev;
+    void* h_wc = nullptr;            // pinned: [the flags as they come back | the image of wc_dev]
+    size_t h_wc_cap = 0;
+    std::vector<std::pair<uint64_t, bp_witness_report>> unsat;
     uint64_t bx_scalars = 0, bx_launches = 0;   // BP_BLINDING_EXPANDED: scalars the expansion kernels wrote / their launches (bp_ctx_blinding_stats)
     // bp_verifier_verify_batch (verify_each.inc): its device arena and counters
     size_t tune_verify_each = 0;     // BP_TUNE_VERIFY_EACH: most instances per group (0 = what VE_ARENA_BUDGET holds, at most VE_GROUP_MAX)
@@ -2686,6 +2694,7 @@ struct bp_cs {
     bool have_rng = false;
     bool consumed = false;                          // prove(self) / verify(self)
     bool running = false;                           // inside prove / verify: the randomized-phase callbacks may still record
+    bool check = false;                             // prover: the witness-check guard (bp_prover_set_check)
     std::vector<A4> commitments;                    // V points in commit order (both modes)
     A4 pc_B, pc_Bb;                                 // prover: the pc_gens of Prover::new when they are not PedersenGens::default() (bp_prover_new_gens)
     bool pc_custom = false;
@@ -2758,12 +2767,46 @@ template <class C> static int cs_prove(bp_ctx* c, bp_cs* s, uint8_t* proof_out, 
         if (!build_host_csc<C>(*s->cs<C>(), *s->csc)) s->csc.reset();
         s->csc_tried = true;
     }
-    int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pf, tm, pre, s->csc.get());
+    WcGuard guard; guard.on = s->check;
+    c->unsat.clear();
+    int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pf, tm, pre, s->csc.get(), nullptr, nullptr, s->check ? &guard : nullptr);
+    if (rc == BP_E_UNSATISFIED) c->unsat.emplace_back((uint64_t)0, guard.report);
     if (rc) return rc;
     std::vector<host::u8> bytes = host::proof_to_bytes<C>(pf);
     if (bytes.size() > *proof_len) { g_err = "prove: output buffer too small"; return BP_E_ARG; }
     memcpy(proof_out, bytes.data(), bytes.size()); *proof_len = bytes.size();
     if (timing) { timing[0] = tm.total; timing[1] = 0; timing[2] = tm.rng; timing[3] = tm.upload; timing[4] = tm.commit_msm; timing[5] = tm.flatten; timing[6] = tm.poly; timing[7] = tm.ipa; }
+    return BP_OK;
+}
+// `count` live provers of one curve: the host twin without a device, else one index upload, one launch sequence and one wait for all
+template <class C> static int cs_check_batch(bp_ctx* c, size_t count, bp_cs* const* hs, bp_witness_report* out) {
+    if (!c || c->host_only) {
+        for (size_t k = 0; k < count; k++) host::witness_check_host<C>(*hs[k]->cs<C>(), out[k]);
+        return BP_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(ctx_stream_wait(c));   // (the staging's previous use is complete)
+    WcRun<C> wc;
+    wc.own.resize(count);
+    std::vector<char> ok(count, 1);
+    host_pool_ensure(c, count);
+    if (count == 1) { if (hs[0]->cs<C>()->cs_terms.size() > ((size_t)1 << 16)) host_pool_ensure(c, 2); ok[0] = build_row_index<C>(*hs[0]->cs<C>(), WC_PIECE, wc.own[0], [&](size_t cnt, const std::function<void(size_t)>& fn) { pool_range(c, 0, cnt, fn); }) ? 1 : 0; }
+    else pool_range(c, 0, count, [&](size_t k) { ok[k] = build_row_index<C>(*hs[k]->cs<C>(), WC_PIECE, wc.own[k]) ? 1 : 0; });
+    for (size_t k = 0; k < count; k++) {
+        if (!ok[k]) { g_err = "prover_check: the constraints of instance " + std::to_string(k) + " cannot be indexed"; return BP_E_ARG; }
+        WcItem<C> it; it.cs = hs[k]->cs<C>(); it.idx = &wc.own[k];
+        wc.items.push_back(it);
+    }
+    int rc = wc_enqueue<C>(c, wc, nullptr);
+    if (!rc) rc = wc_fetch<C>(c, wc);
+    const int rcw = wc_wipe_dev<C>(c, wc);
+    const hipError_t e = ctx_stream_wait(c);
+    wc_wipe_host<C>(c, wc);
+    if (!rc) rc = rcw;
+    if (!rc && e != hipSuccess) { g_err = std::string("prover_check: ") + hipGetErrorString(e); rc = BP_E_HIP; }
+    if (rc) return rc;
+    for (size_t k = 0; k < count; k++) host::witness_report_from_flags<C>(*hs[k]->cs<C>(), wc.flags(c, k), out[k]);
+    if (c->profiling) collect_timers(c);
     return BP_OK;
 }
 template <class C> static int cs_precompute_batch(bp_cs** hs, size_t count) {
@@ -3602,6 +3645,8 @@ void bp_ctx_destroy(bp_ctx* c) {
     c->dt_tab.release(); c->dt_part.release(); c->pc_dt.release(); c->dt_a2.release(); c->dt_b2.release(); c->dt_ticket.release();
     c->pb_arena.release();
     c->pf_aux.release();
+    c->wc_dev.release();
+    if (c->h_wc) (void)hipHostFree(c->h_wc);
     if (c->h_pf) (void)hipHostFree(c->h_pf);
     if (c->h_pb) (void)hipHostFree(c->h_pb);
     if (c->h_dt) (void)hipHostFree(c->h_dt);
@@ -4390,6 +4435,61 @@ int bp_prover_prove(bp_ctx* c, bp_cs* h, const uint8_t rng_bytes[32], uint8_t* p
     h->running = false;
     return rc;
 }
+// ---- witness check (include/arkbp.h) ----------------------------------------------------------------------------------------------
+size_t bp_witness_check_piece(void) { return WC_PIECE; }
+static bool wc_prover_ok(const bp_cs* h) { return h && h->proving && !h->consumed; }
+int bp_prover_check(bp_ctx* c, bp_cs* h, bp_witness_report* out) {
+    if (!wc_prover_ok(h) || !out || (c && c->curve != h->curve)) { g_err = "prover_check: needs a live prover handle of the ctx's curve and a report"; return BP_E_ARG; }
+    bp_witness_report r;
+    const int rc = h->curve == 0 ? cs_check_batch<Secq>(c, 1, &h, &r) : cs_check_batch<Zorro>(c, 1, &h, &r);
+    if (!rc) *out = r;
+    return rc;
+}
+int bp_prover_check_batch(bp_ctx* c, size_t count, bp_cs* const* provers, bp_witness_report* out) {
+    if (!c) return BP_E_ARG;
+    if (count == 0) return BP_OK;
+    if (!provers || !out) return BP_E_ARG;
+    for (size_t k = 0; k < count; k++)
+        if (!wc_prover_ok(provers[k]) || provers[k]->curve != c->curve) { g_err = "prover_check_batch: every instance needs a live prover of the ctx's curve"; return BP_E_ARG; }
+    {
+        std::vector<const void*> hv(provers, provers + count);
+        std::sort(hv.begin(), hv.end());
+        if (std::adjacent_find(hv.begin(), hv.end()) != hv.end()) { g_err = "prover_check_batch: a prover appears twice"; return BP_E_ARG; }
+    }
+    std::vector<bp_witness_report> r(count);
+    const int rc = c->curve == 0 ? cs_check_batch<Secq>(c, count, provers, r.data()) : cs_check_batch<Zorro>(c, count, provers, r.data());
+    if (!rc) memcpy(out, r.data(), count * sizeof(bp_witness_report));
+    return rc;
+}
+int bp_prover_set_check(bp_cs* h, int on) {
+    if (!wc_prover_ok(h)) { g_err = "set_check: needs a live prover handle"; return BP_E_ARG; }
+    h->check = on != 0;
+    return BP_OK;
+}
+int bp_prover_checking(bp_cs* h, int* on_out) {
+    if (!h || !h->proving || !on_out) return BP_E_ARG;
+    *on_out = h->check ? 1 : 0;
+    return BP_OK;
+}
+int bp_ctx_last_unsatisfied(bp_ctx* c, size_t cap, uint64_t* instance, bp_witness_report* reports, size_t* count) {
+    if (!c || !count || (cap && (!instance || !reports))) return BP_E_ARG;
+    *count = c->unsat.size();
+    for (size_t i = 0; i < c->unsat.size() && i < cap; i++) { instance[i] = c->unsat[i].first; reports[i] = c->unsat[i].second; }
+    return BP_OK;
+}
+int bp_debug_prover_poke_witness(bp_cs* h, int vec, size_t index, const uint64_t value[4]) {
+    if (!wc_prover_ok(h) || !value || vec < 0 || vec > 3) return BP_E_ARG;
+    F4 x; memcpy(x.v, value, 32);
+    if (h->curve == 0 ? host::Fld<SecqFr>::geq_p(x.v) : host::Fld<ZorroFr>::geq_p(x.v)) { g_err = "poke_witness: the value is not a reduced scalar"; return BP_E_ARG; }
+    auto poke = [&](auto* cs) -> int {
+        std::vector<F4>& t = vec == 0 ? cs->a_L : vec == 1 ? cs->a_R : vec == 2 ? cs->a_O : cs->v;
+        if (index >= t.size()) return BP_E_ARG;
+        t[index] = x;
+        return BP_OK;
+    };
+    return h->curve == 0 ? poke(h->cs0.get()) : poke(h->cs1.get());
+}
+
 int bp_r1cs_batch_verify(bp_ctx* c, size_t count, bp_cs* const* verifiers, const uint8_t* proofs, const size_t* proof_lens, const uint64_t* alphas, double* timing,
                          uint64_t* check_point_xy) {
     if (!c) return BP_E_ARG;

@@ -209,6 +209,9 @@ template <class C> struct PfMember {
     std::vector<F4> wV;
     F4 w;
     bool csc_ok = true;
+    std::unique_ptr<HostRowIndex> widx; // a guarded member's row index (bp_prover_set_check)
+    bool unsat = false;                 // ... and what the check found
+    bp_witness_report report;
 };
 
 static int pf_stage_ensure(bp_ctx* c, size_t bytes) { return pinned_ensure(c->h_pf, c->h_pf_cap, bytes, bytes / 4 + 4096); }
@@ -337,6 +340,7 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     pb_on_pool(ctx, part.size(), [&](size_t j) {
         PfMember<C>& m = *part[j];
         const HostCsc* have = m.s->csc.get();
+        if (m.s->check) { m.widx.reset(new HostRowIndex()); if (!build_row_index<C>(*m.cs, WC_PIECE, *m.widx)) { m.csc_ok = false; return; } }   // (r1cs_prove reports it)
         if (have && have->n == m.n && have->q == m.cs->num_constraints()) { m.csc = have; return; }
         m.csc_late.reset(new HostCsc());
         m.csc_ok = build_host_csc<C>(*m.cs, *m.csc_late);
@@ -357,9 +361,10 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     std::vector<PfDesc> descs(B);
     const bool expanded = part[0]->pre->mode == BP_BLINDING_EXPANDED;   // (all members alike: they come from one front group)
     const size_t nv = expanded ? 3 : 5;
-    size_t nmax = 0, nzmax = 0, B2 = 0, in_words = 0;
+    size_t nmax = 0, nzmax = 0, B2 = 0, in_words = 0, NG = 0;   // NG: guarded members (bp_prover_set_check); their flags lie behind the T results
     const size_t a_jobs2 = pb_align(B * sizeof(PfDesc));
     for (size_t j = 0; j < B; j++) if (part[j]->n > part[j]->n1) B2++;
+    for (size_t j = 0; j < B; j++) if (part[j]->widx) NG++;
     const size_t a_jobsT = a_jobs2 + pb_align(3 * B2 * sizeof(DtJob)), a_data = a_jobsT + pb_align(5 * B * sizeof(DtJob));
     size_t at = a_data;
     for (size_t j = 0; j < B; j++) {
@@ -383,11 +388,11 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
         descs[j].Z = (u32)(at / 4); at += (256 + (size_t)descs[j].nzhi) * 32;
     }
     const size_t nblk2 = B2 ? pf_nblk(2 * (nmax - part[0]->n1) + 1, 3 * B2) : 1;
-    const size_t a_acc2 = pb_align(at), a_res2 = a_acc2 + pb_align(3 * B2 * nblk2 * 96), a_resT = a_res2 + pb_align(3 * B2 * 96), a_end = a_resT + 5 * B * 96;
+    const size_t a_acc2 = pb_align(at), a_res2 = a_acc2 + pb_align(3 * B2 * nblk2 * 96), a_resT = a_res2 + pb_align(3 * B2 * 96), a_flags = a_resT + 5 * B * 96, a_end = a_flags + NG * 16;
     if (a_end >= ((size_t)1 << 34)) { g_err = "prove_batch: a front group's tables exceed 16 GB"; return BP_E_ARG; }
     BPCHK(ctx->pf_aux.ensure(a_end));
     const size_t s_bl = in_words * 4, s_bd = s_bl + B * 256, s_u1 = s_bd + (expanded ? pb_align(B * 2 * sizeof(BlindDesc)) : 0), s_u2 = s_u1 + a_u2, s_xu = s_u2 + B * 96 * 32, s_res2 = s_xu + pb_align(B * sizeof(PfXu)),
-                 s_ts = s_res2 + pb_align(3 * B2 * 96), s_resT = s_ts + pb_align(B * 192), s_end = s_resT + 5 * B * 96;
+                 s_ts = s_res2 + pb_align(3 * B2 * 96), s_resT = s_ts + pb_align(B * 192), s_end = s_resT + 5 * B * 96 + NG * 16;
     BPCHK(pf_stage_ensure(ctx, s_end));
     secret_stage_bytes = s_u1;   // the witness, the blinding factors and the keys, in front of everything public
     char* hs = (char*)ctx->h_pf;
@@ -458,6 +463,15 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
         ctx->bx_scalars += total; ctx->bx_launches++;
     }
     HIPCHK(hipGetLastError());
+    // the guard: gates and constraints of every guarded member over its arena slices, ONE launch sequence; no wait of its own
+    WcRun<C> wc;
+    std::vector<size_t> wc_member;
+    for (size_t j = 0; j < B; j++) {
+        if (!part[j]->widx) continue;
+        WcItem<C> it; it.cs = part[j]->cs; it.idx = part[j]->widx.get(); it.aL = wit(j, L.o_waL); it.aR = wit(j, L.o_waR); it.aO = wit(j, L.o_waO);
+        wc.items.push_back(it); wc_member.push_back(j);
+    }
+    if (NG) { BPCHK(wc_enqueue<C>(ctx, wc, (u32*)(ax + a_flags))); BPCHK(wc_wipe_dev<C>(ctx, wc)); }
     std::vector<A4> aff2(3 * B2);
     if (B2) {
         BPCHK((pf_accum<C>(ctx, (const DtJob*)(ax + a_jobs2), 3 * B2, nblk2, (u32*)(ax + a_acc2), (u32*)(ax + a_res2))));
@@ -505,10 +519,17 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     HIPCHK(hipGetLastError());
     BPCHK((pf_accum<C>(ctx, (const DtJob*)(ax + a_jobsT), 5 * B, 1, (u32*)nullptr, (u32*)(ax + a_resT))));
     HIPCHK(hipMemcpyAsync(hs + s_ts, ar + L.ts_off, B * 192, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hs + s_resT, ax + a_resT, 5 * B * 96, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hs + s_resT, ax + a_resT, 5 * B * 96 + NG * 16, hipMemcpyDeviceToHost, st));   // (the guard's flags ride behind the T results)
     HIPCHK(ctx_stream_wait(ctx));
     HIPCHK(hipGetLastError());
     ctx->pf_waits++;
+    // a member whose witness fails stays in the group to the end (no other member's launches change) and is refused by the caller
+    wc_wipe_host<C>(ctx, wc);
+    for (size_t g = 0; g < NG; g++) {
+        const u32* f = (const u32*)(hs + s_resT + 5 * B * 96) + 4 * g;
+        PfMember<C>& m = *part[wc_member[g]];
+        if (wc_flags_bad(f)) { m.unsat = true; host::witness_report_from_flags<C>(*m.cs, f, m.report); }
+    }
     // T appends, u, x, t_x, t_x_blinding, e_blinding, w
     std::vector<J4> ptsT(5 * B);
     std::vector<A4> affT(5 * B);
@@ -579,6 +600,7 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
     std::vector<host::ProofData> pfs(count);
     std::vector<char> grouped(count, 0);
     StageTimes tm;
+    std::vector<std::pair<uint64_t, bp_witness_report>> unsat;   // the instances the guard refuses (bp_ctx_last_unsatisfied)
     // 1. TranscriptRng heads: same-shaped statements eight at a time in lockstep (prove_precompute_batch)
     {
         std::vector<bp_cs*> need;
@@ -633,8 +655,10 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
             return true;
         };
         s->consumed = true; s->running = true;
-        const int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pfs[k], tm, pre, s->csc.get(), &defer, resume1);
+        WcGuard guard; guard.on = s->check;
+        const int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pfs[k], tm, pre, s->csc.get(), &defer, resume1, s->check ? &guard : nullptr);
         s->running = false;
+        if (rc == BP_E_UNSATISFIED) unsat.emplace_back((uint64_t)k, guard.report);
         if (defer.taken) {
             grp.mem.push_back(PbMember<C>{k, s->cs<C>()->tr, &pfs[k], defer.w});
             pfs[k].L_vec.resize(pb_lg(defer.N)); pfs[k].R_vec.resize(pb_lg(defer.N));
@@ -712,6 +736,7 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
                     if (std::find(leavers.begin(), leavers.end(), m) != leavers.end()) continue;
                     grouped[m->k] = 1;
                     if (r) st[m->k] = r;
+                    else if (m->unsat) { st[m->k] = BP_E_UNSATISFIED; unsat.emplace_back((uint64_t)m->k, m->report); }
                 }
             }
         }
@@ -720,6 +745,8 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
         for (auto* m : leavers) prove_single(m->k, 1, m->c1);
     }
     flush();
+    std::sort(unsat.begin(), unsat.end(), [](const std::pair<uint64_t, bp_witness_report>& a, const std::pair<uint64_t, bp_witness_report>& b) { return a.first < b.first; });
+    c->unsat.swap(unsat);
     // 3. serialisation, per-instance status
     int first = BP_OK;
     for (size_t k = 0; k < count; k++) {

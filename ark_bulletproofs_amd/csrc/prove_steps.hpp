@@ -50,6 +50,114 @@ template <class C> static bool build_host_csc(const ConstraintSystem<C>& cs, Hos
     return ok;
 }
 
+// ---- witness check (include/arkbp.h: bp_prover_check; the kernels: witness_check.cuh) -----------------------------------------------
+// The constraints by ROW, the recorder's own order (cs_terms / cs_off), for the device: every row cut into pieces of at most `piece`
+// terms.  poff: npieces + 1 term offsets; pinfo[p]: the row a one-piece row's piece belongs to, or ROW_LONG | partial slot for a piece
+// of a longer row; tvar: (kind << 29) | index; tcid: coefficient id in HostCsc's convention (a de-duplicated table, +-1 as flags, no
+// product for them); lrow: (row, first partial slot, pieces) per long row.
+struct HostRowIndex {
+    static constexpr u32 ROW_LONG = 0x80000000u;
+    size_t n = 0, q = 0, m = 0;
+    std::vector<u32> poff, pinfo, tvar, tcid, lrow;
+    std::vector<F4> coefs;
+    size_t nslots = 0;       // partial sums of all long rows
+    u32 max_pieces = 0;      // most pieces of one row
+    size_t nlong() const { return lrow.size() / 3; }
+    size_t npieces() const { return pinfo.size(); }
+};
+// par(count, fn): fn(0) .. fn(count - 1) in any order, possibly on several threads (null: here, one after the other).  The result does
+// not depend on it: coefficients other than +-1 are numbered in a second, sequential pass, in order of first occurrence.
+typedef std::function<void(size_t, const std::function<void(size_t)>&)> RowIndexPar;
+template <class C> static bool build_row_index(const ConstraintSystem<C>& cs, size_t piece, HostRowIndex& h, const RowIndexPar& par = nullptr) {
+    typedef Fld<typename C::Fr> S;
+    const size_t n = cs.a_L.size(), Q = cs.cs_off.size() - 1, m = cs.v.size(), nt = cs.cs_terms.size();
+    if (cs.base || piece < 2 || n >= ((size_t)1 << 29) || m >= ((size_t)1 << 29) || Q >= ((size_t)1 << 30) || nt >= ((size_t)1 << 31)) return false;
+    if (cs.a_R.size() != n || cs.a_O.size() != n) return false;
+    h = HostRowIndex();
+    h.n = n; h.q = Q; h.m = m;
+    auto run = [&](size_t count, const std::function<void(size_t)>& fn) { if (par && count > 1) par(count, fn); else for (size_t c = 0; c < count; c++) fn(c); };
+    reserve_huge(h.tvar, nt); reserve_huge(h.tcid, nt);
+    h.tvar.resize(nt); h.tcid.resize(nt);
+    const F4 one = S::one(), mone = S::neg(S::one());
+    static constexpr size_t CHUNK = (size_t)1 << 16;
+    static constexpr u32 GENERAL = 0x3fffffffu;   // pass 1's mark of a coefficient that still needs its number (never a valid id: ids stay below 2^30 - 1)
+    const size_t tchunks = (nt + CHUNK - 1) / CHUNK, qchunks = (Q + CHUNK - 1) / CHUNK;
+    std::vector<u8> bad(tchunks, 0), general(tchunks, 0), longrow(qchunks, 0);
+    run(tchunks, [&](size_t c) {
+        for (size_t k = c * CHUNK, hi = std::min(nt, k + CHUNK); k < hi; k++) {
+            const Term& t = cs.cs_terms[k];
+            const size_t lim = t.v.k == VK_COMMITTED ? m : t.v.k <= VK_OUT ? n : 0;
+            if (t.v.k != VK_ONE && t.v.i >= lim) bad[c] = 1;   // a variable the recorder never handed out
+            h.tvar[k] = ((u32)t.v.k << 29) | (t.v.k == VK_ONE ? 0u : t.v.i);
+            if (t.c == one) h.tcid[k] = CID_ONE; else if (t.c == mone) h.tcid[k] = CID_MONE; else { h.tcid[k] = GENERAL; general[c] = 1; }
+        }
+    });
+    CanonState st;   // (its coefficient numbering only)
+    for (size_t c = 0; c < tchunks; c++) {
+        if (bad[c]) return false;
+        if (!general[c]) continue;
+        for (size_t k = c * CHUNK, hi = std::min(nt, k + CHUNK); k < hi; k++) {
+            if (h.tcid[k] != GENERAL) continue;
+            const u32 id = st.id_of(cs.cs_terms[k].c);
+            if (id >= GENERAL) return false;
+            h.tcid[k] = id;
+        }
+    }
+    run(qchunks, [&](size_t c) { for (size_t q = c * CHUNK, hi = std::min(Q, q + CHUNK); q < hi; q++) if (cs.cs_off[q + 1] - cs.cs_off[q] > piece) longrow[c] = 1; });
+    bool any_long = false;
+    for (size_t c = 0; c < qchunks; c++) any_long |= longrow[c] != 0;
+    if (!any_long) {   // every row is one piece (an empty row is one empty piece: sum 0, satisfied)
+        reserve_huge(h.poff, Q + 1); reserve_huge(h.pinfo, Q);
+        h.poff.resize(Q + 1); h.pinfo.resize(Q);
+        h.poff[0] = 0;
+        run(qchunks, [&](size_t c) { for (size_t q = c * CHUNK, hi = std::min(Q, q + CHUNK); q < hi; q++) { h.pinfo[q] = (u32)q; h.poff[q + 1] = (u32)cs.cs_off[q + 1]; } });
+    } else {
+        reserve_huge(h.poff, Q + nt / piece + 2); reserve_huge(h.pinfo, Q + nt / piece + 1);
+        h.poff.push_back(0);
+        for (size_t q = 0; q < Q; q++) {
+            const size_t lo = cs.cs_off[q], hi = cs.cs_off[q + 1], len = hi - lo;
+            const size_t np = len <= piece ? 1 : (len + piece - 1) / piece;
+            if (np == 1) { h.pinfo.push_back((u32)q); h.poff.push_back((u32)hi); continue; }
+            if (h.nslots + np >= HostRowIndex::ROW_LONG) return false;
+            h.lrow.push_back((u32)q); h.lrow.push_back((u32)h.nslots); h.lrow.push_back((u32)np);
+            for (size_t p = 0; p < np; p++) { h.pinfo.push_back(HostRowIndex::ROW_LONG | (u32)(h.nslots + p)); h.poff.push_back((u32)std::min(hi, lo + (p + 1) * piece)); }
+            h.nslots += np;
+            h.max_pieces = std::max<u32>(h.max_pieces, (u32)np);
+        }
+    }
+    h.coefs.swap(st.coefs);
+    if (h.coefs.empty()) h.coefs.push_back(one);
+    return true;
+}
+// the value of row q's combination (ark words)
+template <class C> static F4 witness_row_value(const ConstraintSystem<C>& cs, size_t q) {
+    return cs.eval(cs.cs_terms.data() + cs.cs_off[q], cs.cs_off[q + 1] - cs.cs_off[q]);
+}
+// The host twin: plain loops over the recorder with the host field.  What the kernels are tested against, and what a NULL or host-only
+// ctx runs.
+template <class C> static void witness_check_host(const ConstraintSystem<C>& cs, bp_witness_report& r) {
+    typedef Fld<typename C::Fr> S;
+    memset(&r, 0, sizeof r);
+    const size_t n = cs.a_L.size(), Q = cs.cs_off.size() - 1;
+    r.gates_checked = n; r.constraints_checked = Q; r.deferred_callbacks = cs.deferred.size();
+    r.first_bad_gate = r.first_bad_constraint = ~(uint64_t)0;
+    for (size_t i = 0; i < n; i++)
+        if (!(S::mul(cs.a_L[i], cs.a_R[i]) == cs.a_O[i])) { if (!r.bad_gates++) r.first_bad_gate = i; }
+    for (size_t q = 0; q < Q; q++) {
+        const F4 s = witness_row_value<C>(cs, q);
+        if (s.is_zero()) continue;
+        if (!r.bad_constraints++) { r.first_bad_constraint = q; memcpy(r.first_bad_residual, s.v, 32); }
+    }
+}
+// a device result (bad gates, first, bad constraints, first) as a report; the residual comes from the recorder
+template <class C> static void witness_report_from_flags(const ConstraintSystem<C>& cs, const u32 res[4], bp_witness_report& r) {
+    memset(&r, 0, sizeof r);
+    r.gates_checked = cs.a_L.size(); r.constraints_checked = cs.cs_off.size() - 1; r.deferred_callbacks = cs.deferred.size();
+    r.bad_gates = res[0]; r.first_bad_gate = res[0] ? res[1] : ~(uint64_t)0;
+    r.bad_constraints = res[2]; r.first_bad_constraint = res[2] ? res[3] : ~(uint64_t)0;
+    if (res[2] && res[3] < cs.cs_off.size() - 1) { const F4 s = witness_row_value<C>(cs, res[3]); memcpy(r.first_bad_residual, s.v, 32); }
+}
+
 // ztab[j] = z^(2^j); ypw[k] = y^(2^k), ypw[32 + k] = y^-(2^k): ONE inversion.  A null table is left out.
 template <class C> static void prove_pow_tables(const F4& z, const F4& y, F4* ztab /* [32] */, F4* ypw /* [64] */) {
     typedef Fld<typename C::Fr> S;

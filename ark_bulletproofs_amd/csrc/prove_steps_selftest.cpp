@@ -3,6 +3,7 @@
 // statements with host::ConstraintSystem — single-phase with 3 multipliers and 2 committed variables, a k = 2 shuffle (no phase-1
 // multipliers), two-phase with 3 + 2 multipliers — and compares each shared step with an independent path.
 #include <cstdio>
+#include <cstring>
 #include "host_proto.hpp"
 #include "prove_steps.hpp"
 
@@ -178,7 +179,69 @@ template <class C> static void check_t_tail_and_draws() {
     CHECK(TP<C>::challenge_scalar(p1, "c") == TP<C>::challenge_scalar(p2, "c"));
 }
 
+// Witness check: the host twin (plain loops over the recorder) against the row index walked the way the kernels walk it: one sum
+// per piece, a one-piece row decided there, the partial sums of a longer row added afterwards.  Piece lengths 2, 4 and 256 over a
+// statement with rows of 0, 1, 3 and 11 terms; the gadget's own rows are not satisfied, one gate is spoiled on top.
+template <class C> static void index_walk(const ConstraintSystem<C>& cs, const HostRowIndex& h, u32 res[4]) {
+    typedef Fld<typename C::Fr> S;
+    res[0] = res[2] = 0; res[1] = res[3] = 0xFFFFFFFFu;
+    for (size_t i = 0; i < h.n; i++) if (!(S::mul(cs.a_L[i], cs.a_R[i]) == cs.a_O[i])) { res[0]++; res[1] = std::min<u32>(res[1], (u32)i); }
+    std::vector<F4> partial(h.nslots, S::zero());
+    CHECK(h.poff.size() == h.npieces() + 1 && h.tvar.size() == cs.cs_terms.size() && h.tcid.size() == h.tvar.size());
+    for (size_t p = 0; p < h.npieces(); p++) {
+        F4 acc = S::zero();
+        for (u32 e = h.poff[p]; e < h.poff[p + 1]; e++) {
+            const u32 kind = h.tvar[e] >> 29, idx = h.tvar[e] & ((1u << 29) - 1), cid = h.tcid[e];
+            const F4 val = kind == VK_COMMITTED ? cs.v[idx] : kind == VK_LEFT ? cs.a_L[idx] : kind == VK_RIGHT ? cs.a_R[idx] : kind == VK_OUT ? cs.a_O[idx] : S::one();
+            acc = S::add(acc, (cid & CID_ONE) ? val : (cid & CID_MONE) ? S::neg(val) : S::mul(val, h.coefs[cid]));
+        }
+        if (h.pinfo[p] & HostRowIndex::ROW_LONG) partial[h.pinfo[p] & ~HostRowIndex::ROW_LONG] = acc;
+        else if (!acc.is_zero()) { res[2]++; res[3] = std::min(res[3], h.pinfo[p]); }
+    }
+    for (size_t r = 0; r < h.nlong(); r++) {
+        F4 acc = S::zero();
+        CHECK(h.lrow[3 * r + 2] <= h.max_pieces && h.lrow[3 * r + 1] + h.lrow[3 * r + 2] <= h.nslots);
+        for (u32 j = 0; j < h.lrow[3 * r + 2]; j++) acc = S::add(acc, partial[h.lrow[3 * r + 1] + j]);
+        if (!acc.is_zero()) { res[2]++; res[3] = std::min(res[3], h.lrow[3 * r]); }
+    }
+}
+template <class C> static void check_witness() {
+    typedef Fld<typename C::Fr> S;
+    Stmt<C> s;
+    record_gadget<C>(s, false);
+    const Var v0{VK_COMMITTED, 0}, one{VK_ONE, 0};
+    const F4 m1 = S::neg(S::one());
+    s.cs.constrain(LinComb{});
+    s.cs.constrain(LinComb{Term{one, S::zero()}});
+    LinComb row;
+    for (int i = 0; i < 10; i++) row.push_back(Term{v0, i % 2 ? m1 : S::one()});   // cancels
+    row.push_back(Term{one, S::zero()});
+    s.cs.constrain(row);          // 11 terms, satisfied
+    row.back().c = S::from_u64(3);
+    s.cs.constrain(row);          // 11 terms, residual 3
+    s.cs.a_O[1] = S::add(s.cs.a_O[1], S::one());
+    bp_witness_report twin;
+    witness_check_host<C>(s.cs, twin);
+    CHECK(twin.gates_checked == 3 && twin.constraints_checked == s.cs.cs_off.size() - 1 && twin.bad_gates == 1 && twin.first_bad_gate == 1 && twin.deferred_callbacks == 0);
+    CHECK(twin.bad_constraints >= 1);
+    for (size_t piece : {(size_t)2, (size_t)4, (size_t)256}) {
+        HostRowIndex h;
+        CHECK(build_row_index<C>(s.cs, piece, h, [](size_t count, const std::function<void(size_t)>& fn) { for (size_t c = count; c-- > 0;) fn(c); }));
+        CHECK((piece == 256) == (h.nlong() == 0));
+        u32 res[4];
+        index_walk<C>(s.cs, h, res);
+        bp_witness_report dev;
+        witness_report_from_flags<C>(s.cs, res, dev);
+        CHECK(memcmp(&dev, &twin, sizeof dev) == 0);
+    }
+    HostRowIndex h;
+    CHECK(!build_row_index<C>(s.cs, 1, h));
+    s.cs.cs_terms[0].v.i = 99;    // a variable nobody handed out: refused, not indexed
+    CHECK(!build_row_index<C>(s.cs, 4, h));
+}
+
 template <class C> static void run_curve() {
+    check_witness<C>();
     { Stmt<C> s; record_gadget<C>(s, false); check_wv<C>(s, 3, 3); }
     { Stmt<C> s; record_shuffle2<C>(s); check_wv<C>(s, 0, 2); }
     { Stmt<C> s; record_gadget<C>(s, true); check_wv<C>(s, 3, 5); }

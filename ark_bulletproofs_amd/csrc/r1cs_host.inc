@@ -414,6 +414,151 @@ struct IpaDefer {
     F4 w;
 };
 
+// ---- witness check (witness_check.cuh; include/arkbp.h bp_prover_check / bp_prover_set_check) -----------------------------------------
+// One call's statements share ONE block: the device buffer ctx->wc_dev and its image in the pinned staging ctx->h_wc (behind the
+// area the flags return to).  Image: [descriptors | flags | per statement: poff, pinfo, tvar, tcid, lrow, coefs || the witnesses (ark
+// words, bp_prover_check only) | per statement: v || partial sums (device only)].  Everything from the witnesses on derives from
+// secrets and is wiped after use.
+struct WcGuard { bool on = false; bp_witness_report report; };   // r1cs_prove's guard: the report of a refused proof
+static size_t wc_align(size_t x) { return (x + 255) & ~(size_t)255; }
+template <class C> struct WcItem {
+    const host::ConstraintSystem<C>* cs = nullptr;
+    const HostRowIndex* idx = nullptr;
+    const u32 *aL = nullptr, *aR = nullptr, *aO = nullptr;   // the resident witness; all null: the run uploads it itself
+};
+template <class C> struct WcRun {
+    std::vector<WcItem<C>> items;
+    std::vector<HostRowIndex> own;           // the indices (built by the caller into here)
+    size_t back = 0, o_res = 0, o_secret = 0, o_wit = 0, wit_scalars = 0, end_up = 0, total = 0;
+    bool enqueued = false;
+    bp_ctx* staged_on = nullptr;             // set while the staging holds this run's secrets (wc_enqueue .. wc_wipe_host)
+    const u32* flags(const bp_ctx* ctx, size_t j) const { return (const u32*)ctx->h_wc + 4 * j; }
+    // a way out that skips wc_wipe_host (a stage failed in between): the stream may still read the staging, so wait, then wipe
+    ~WcRun() {
+        if (!staged_on) return;
+        (void)hipStreamSynchronize(staged_on->stream);
+        if (staged_on->h_wc && end_up > o_secret) memset((char*)staged_on->h_wc + back + o_secret, 0, end_up - o_secret);
+    }
+};
+// Index upload and the check launches of a run on the ctx's stream.  res_dev: where the flags live on the device (a front group keeps
+// them next to results it copies back anyway), null: in the block.
+template <class C> static int wc_enqueue(bp_ctx* ctx, WcRun<C>& r, u32* res_dev) {
+    typedef typename C::Fr FrP;
+    const size_t B = r.items.size();
+    if (!B) return BP_OK;
+    hipStream_t st = ctx->stream;
+    const bool upload_witness = !r.items[0].aL;
+    std::vector<size_t> at(B), v_at(B), wit_at(B), part_at(B);
+    size_t o = wc_align(B * sizeof(WcDesc));
+    r.o_res = o; o += wc_align(B * 16);
+    for (size_t j = 0; j < B; j++) {
+        const HostRowIndex& h = *r.items[j].idx;
+        at[j] = o;
+        o += wc_align((h.npieces() + 1) * 4) + wc_align(h.npieces() * 4) + 2 * wc_align(h.tvar.size() * 4) + wc_align(h.lrow.size() * 4) + wc_align(h.coefs.size() * 32);
+    }
+    r.o_secret = r.o_wit = o;
+    r.wit_scalars = 0;
+    if (upload_witness) for (size_t j = 0; j < B; j++) { wit_at[j] = o; o += 3 * r.items[j].idx->n * 32; r.wit_scalars += 3 * r.items[j].idx->n; }
+    o = wc_align(o);
+    for (size_t j = 0; j < B; j++) { v_at[j] = o; o += wc_align(r.items[j].idx->m * 32); }
+    r.end_up = o;
+    for (size_t j = 0; j < B; j++) { part_at[j] = o; o += wc_align(r.items[j].idx->nslots * 32); }
+    r.total = o;
+    r.back = wc_align(B * 16);
+    if (r.wit_scalars >= ((size_t)1 << 32)) { g_err = "witness check: more than 2^32 witness scalars in one call"; return BP_E_ARG; }
+    BPCHK(ctx->wc_dev.ensure(r.total));
+    BPCHK(pinned_ensure(ctx->h_wc, ctx->h_wc_cap, r.back + r.end_up, (r.back + r.end_up) / 4 + 4096));
+    char* img = (char*)ctx->h_wc + r.back;
+    char* dev = (char*)ctx->wc_dev.p;
+    WcDesc* descs = (WcDesc*)img;
+    u32 gx = 0, gl = 0, max_pieces = 0;
+    host_pool_ensure(ctx, B);
+    struct Copy { char* dst; const char* src; size_t bytes; };
+    std::vector<std::vector<Copy>> big(B);   // the long arrays go over in slices, on the pool (a 2^20 statement stages 48 MB)
+    static constexpr size_t SLICE = (size_t)4 << 20;
+    pool_range(ctx, 0, B, [&](size_t j) {
+        const WcItem<C>& it = r.items[j];
+        const HostRowIndex& h = *it.idx;
+        size_t p = at[j];
+        auto put = [&](const void* src, size_t bytes) {
+            const size_t here = p;
+            if (bytes > SLICE) for (size_t o2 = 0; o2 < bytes; o2 += SLICE) big[j].push_back(Copy{img + p + o2, (const char*)src + o2, std::min(SLICE, bytes - o2)});
+            else if (bytes) memcpy(img + p, src, bytes);
+            p += wc_align(bytes);
+            return (const u32*)(dev + here);
+        };
+        WcDesc& d = descs[j];
+        memset(&d, 0, sizeof d);
+        d.poff = put(h.poff.data(), h.poff.size() * 4);
+        d.pinfo = put(h.pinfo.data(), h.pinfo.size() * 4);
+        d.tvar = put(h.tvar.data(), h.tvar.size() * 4);
+        d.tcid = put(h.tcid.data(), h.tcid.size() * 4);
+        d.lrow = put(h.lrow.data(), h.lrow.size() * 4);
+        d.coefs = (const u32*)(dev + p);
+        F4* co = (F4*)(img + p);
+        for (size_t i = 0; i < h.coefs.size(); i++) co[i] = to_resident<FrP>(h.coefs[i]);
+        d.v = (const u32*)(dev + v_at[j]);
+        F4* vv = (F4*)(img + v_at[j]);
+        for (size_t i = 0; i < h.m; i++) vv[i] = to_resident<FrP>(it.cs->v[i]);
+        if (upload_witness) {
+            char* w = img + wit_at[j];
+            memcpy(w, it.cs->a_L.data(), h.n * 32); memcpy(w + h.n * 32, it.cs->a_R.data(), h.n * 32); memcpy(w + 2 * h.n * 32, it.cs->a_O.data(), h.n * 32);
+            d.aL = (const u32*)(dev + wit_at[j]); d.aR = d.aL + h.n * 8; d.aO = d.aR + h.n * 8;
+        } else { d.aL = it.aL; d.aR = it.aR; d.aO = it.aO; }
+        d.partial = (u32*)(dev + part_at[j]);
+        d.res = res_dev ? res_dev + 4 * j : (u32*)(dev + r.o_res) + 4 * j;
+        d.n = (u32)h.n; d.npieces = (u32)h.npieces(); d.nlong = (u32)h.nlong();
+        u32* init = (u32*)(img + r.o_res) + 4 * j;
+        init[0] = 0; init[1] = 0xFFFFFFFFu; init[2] = 0; init[3] = 0xFFFFFFFFu;
+    });
+    {
+        std::vector<Copy> all;
+        for (auto& v : big) all.insert(all.end(), v.begin(), v.end());
+        host_pool_ensure(ctx, all.size());
+        pool_range(ctx, 0, all.size(), [&](size_t i) { memcpy(all[i].dst, all[i].src, all[i].bytes); });
+    }
+    for (size_t j = 0; j < B; j++) {
+        const HostRowIndex& h = *r.items[j].idx;
+        gx = std::max<u32>(gx, (u32)((std::max(h.n, h.npieces()) + 255) / 256)); gl = std::max<u32>(gl, (u32)h.nlong()); max_pieces = std::max(max_pieces, h.max_pieces);
+    }
+    r.enqueued = true; r.staged_on = ctx;
+    HIPCHK(hipMemcpyAsync(dev, img, r.end_up, hipMemcpyHostToDevice, st));
+    if (res_dev) HIPCHK(hipMemcpyAsync(res_dev, img + r.o_res, B * 16, hipMemcpyHostToDevice, st));
+    if (upload_witness && r.wit_scalars)
+        hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((r.wit_scalars + 255) / 256)), dim3(256), 0, st, (const u32*)(dev + r.o_wit), (u32*)(dev + r.o_wit), (u32)r.wit_scalars);
+    {
+        ScopedK tk(ctx, BP_K_WITNESS_CHECK);
+        if (B == 1) {
+            if (gx) hipLaunchKernelGGL(k_r1cs_check<C>, dim3(gx), dim3(256), 0, st, descs[0]);
+            if (gl) hipLaunchKernelGGL(k_r1cs_check_long<C>, dim3(gl), dim3(256), 0, st, descs[0], max_pieces);
+        } else {
+            for (size_t lo = 0; lo < B; lo += 32768) {   // (grid.y stays below 65536)
+                const u32 cnt = (u32)std::min<size_t>(32768, B - lo);
+                if (gx) hipLaunchKernelGGL(k_r1cs_check_multi<C>, dim3(gx, cnt), dim3(256), 0, st, (const WcDesc*)dev + lo);
+                if (gl) hipLaunchKernelGGL(k_r1cs_check_long_multi<C>, dim3(gl, cnt), dim3(256), 0, st, (const WcDesc*)dev + lo, max_pieces);
+            }
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return BP_OK;
+}
+// the flags of a run whose flags live in the block, on their way to the front of the pinned staging (valid after the next wait)
+template <class C> static int wc_fetch(bp_ctx* ctx, WcRun<C>& r) {
+    HIPCHK(hipMemcpyAsync(ctx->h_wc, (char*)ctx->wc_dev.p + r.o_res, r.items.size() * 16, hipMemcpyDeviceToHost, ctx->stream));
+    return BP_OK;
+}
+// secret hygiene: the witnesses, the committed values and the partial sums on the device (enqueued), ...
+template <class C> static int wc_wipe_dev(bp_ctx* ctx, const WcRun<C>& r) {
+    if (r.enqueued && r.total > r.o_secret) HIPCHK(hipMemsetAsync((char*)ctx->wc_dev.p + r.o_secret, 0, r.total - r.o_secret, ctx->stream));
+    return BP_OK;
+}
+// ... and their image in the staging, once the stream has read it (after a wait)
+template <class C> static void wc_wipe_host(bp_ctx* ctx, WcRun<C>& r) {
+    if (r.enqueued && ctx->h_wc && r.end_up > r.o_secret) memset((char*)ctx->h_wc + r.back + r.o_secret, 0, r.end_up - r.o_secret);
+    r.staged_on = nullptr;
+}
+static bool wc_flags_bad(const u32* f) { return f[0] != 0 || f[2] != 0; }
+
 // ---- Prover::prove_and_return_transcript (src/r1cs/prover.rs:454-831) as stages over one state struct -------------------------------
 // ARKBP_PROVE_TRACE=1: microseconds between the marks of one prove() on stderr (where a SMALL proof's latency goes)
 struct ProveTrace {
@@ -762,7 +907,8 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
                       ProvePre<C>* pre_in = nullptr, const HostCsc* csc = nullptr /* constraint index built with the statement (single-phase) */,
                       IpaDefer* defer = nullptr,
                       const A4* resume1 = nullptr /* bp_prover_prove_batch, a member that leaves its front group after the randomized phase: A_I1, A_O1,
-                      S1 are in the transcript and the phase has run — neither happens again; the whole witness goes up to the workspaces here */) {
+                      S1 are in the transcript and the phase has run — neither happens again; the whole witness goes up to the workspaces here */,
+                      WcGuard* guard = nullptr /* bp_prover_set_check: refuse an unsatisfying witness with BP_E_UNSATISFIED and its report */) {
     typedef host::Fld<typename C::Fr> S;
     typedef host::Grp<C> G;
     typedef host::TP<C> TP;
@@ -813,6 +959,24 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
         BPCHK(prove_commit_phase<C>(j, n1, n - n1, j.bl2, j.c2));
     }
     j.trace.mark("commit phase 2");
+    // the guard: the whole witness is resident and every constraint exists.  The check is enqueued here and its flags are read after
+    // the wait prove_poly_t makes anyway; a statement without multipliers has no such wait and few rows: the host twin decides it.
+    WcRun<C> wc;
+    if (guard && guard->on) {
+        if (n == 0) {
+            host::witness_check_host<C>(cs, guard->report);
+            if (guard->report.bad_gates || guard->report.bad_constraints) { g_err = "prove: the witness does not satisfy the constraint system"; return BP_E_UNSATISFIED; }
+        } else {
+            wc.own.resize(1);
+            if (cs.cs_terms.size() > ((size_t)1 << 16)) host_pool_ensure(ctx, 2);   // (a large statement's index is built on the pool)
+            if (!build_row_index<C>(cs, WC_PIECE, wc.own[0], [&](size_t cnt, const std::function<void(size_t)>& fn) { pool_range(ctx, 0, cnt, fn); })) { g_err = "prove: the constraints cannot be indexed for the witness check"; return BP_E_ARG; }
+            WcItem<C> it; it.cs = &cs; it.idx = &wc.own[0]; it.aL = ctx->r_aL.as<u32>(); it.aR = ctx->r_aR.as<u32>(); it.aO = ctx->r_aO.as<u32>();
+            wc.items.push_back(it);
+            BPCHK(wc_enqueue<C>(ctx, wc, nullptr));
+            BPCHK(wc_fetch<C>(ctx, wc));
+            BPCHK(wc_wipe_dev<C>(ctx, wc));
+        }
+    }
     host::prove_append_phase<C>(tr, 2, j.c2[0], j.c2[1], j.c2[2]);
     j.y = TP::challenge_scalar(tr, "y"); j.z = TP::challenge_scalar(tr, "z");
     BPCHK(prove_flatten<C>(j));
@@ -821,6 +985,14 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     tm.rng += now_s() - t0;
     BPCHK(prove_poly_t<C>(j));
     j.trace.mark("T commitments");
+    if (wc.enqueued) {
+        wc_wipe_host<C>(ctx, wc);
+        if (wc_flags_bad(wc.flags(ctx, 0))) {
+            host::witness_report_from_flags<C>(cs, wc.flags(ctx, 0), guard->report);
+            g_err = "prove: the witness does not satisfy the constraint system";
+            return BP_E_UNSATISFIED;
+        }
+    }
     host::prove_t_tail<C>(tr, j.Tc, j.tco, j.tb, j.wV, cs.v_blinding, j.b1, j.bl2, j.u, j.x, j.t_x, j.t_x_blinding, j.e_blinding, j.w);
     j.trace.mark("t_x .. w");
     BPCHK(prove_eval<C>(j));

@@ -506,6 +506,66 @@ def host_points_sum(curve, pts_xy):
     return out
 
 
+# ---- witness check (include/arkbp.h: bp_prover_check, bp_prover_set_check) ------------------------------------------------------
+NONE_BAD = (1 << 64) - 1             # first_bad_gate / first_bad_constraint of a report without one (UINT64_MAX)
+
+
+class _WitnessReportC(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("gates_checked", "constraints_checked", "bad_gates", "first_bad_gate", "bad_constraints", "first_bad_constraint", "deferred_callbacks")] + [("first_bad_residual", C.c_uint64 * 4)]
+
+
+class WitnessReport:
+    """bp_witness_report: what was examined, how many gates / constraints are violated and the smallest index of each (NONE_BAD when
+    none), the randomized-phase callbacks that have not run (their constraints are not covered), and the value of the first violated
+    constraint's combination (4 ark words)."""
+
+    def __init__(self, c):
+        for n, _ in _WitnessReportC._fields_[:-1]:
+            setattr(self, n, int(getattr(c, n)))
+        self.first_bad_residual = np.array(list(c.first_bad_residual), dtype=np.uint64)
+
+    @property
+    def satisfied(self):
+        return self.bad_gates == 0 and self.bad_constraints == 0
+
+    def astuple(self):
+        return (self.gates_checked, self.constraints_checked, self.bad_gates, self.first_bad_gate, self.bad_constraints, self.first_bad_constraint,
+                self.deferred_callbacks, tuple(int(x) for x in self.first_bad_residual))
+
+    def __eq__(self, other):
+        return isinstance(other, WitnessReport) and self.astuple() == other.astuple()
+
+    def __repr__(self):
+        return "WitnessReport(gates=%d, constraints=%d, bad_gates=%d, first_bad_gate=%d, bad_constraints=%d, first_bad_constraint=%d, deferred_callbacks=%d)" % self.astuple()[:7]
+
+
+def witness_check_piece():
+    """most terms one lane of the constraint check walks (bp_witness_check_piece)"""
+    return int(lib().bp_witness_check_piece())
+
+
+def _witness_check(handle, engine):
+    r = _WitnessReportC()
+    check(lib().bp_prover_check(engine.ctx if engine is not None else None, handle, C.byref(r)), "bp_prover_check")
+    return WitnessReport(r)
+
+
+def _set_check(handle, on):
+    check(lib().bp_prover_set_check(handle, 1 if on else 0), "bp_prover_set_check")
+
+
+def _checking(handle):
+    on = C.c_int(-1)
+    check(lib().bp_prover_checking(handle, C.byref(on)), "bp_prover_checking")
+    return bool(on.value)
+
+
+def debug_poke_witness(prover, vec, index, value):
+    """test hook (bp_debug_prover_poke_witness): overwrite one recorded assignment; vec 0 a_L, 1 a_R, 2 a_O, 3 v; value: 4 ark words"""
+    v = np.ascontiguousarray(value, dtype=np.uint64).reshape(4)
+    check(lib().bp_debug_prover_poke_witness(_prover_handle(prover), int(vec), C.c_size_t(index), ptr(v)), "bp_debug_prover_poke_witness")
+
+
 # ---- statements (setup separated from prove(), several proofs in flight) -----------------------------------
 class Statement:
     """Prover::new + commits + gadget for a scenario.  Host only by default; with `engine` the statement's Pedersen
@@ -541,6 +601,17 @@ class Statement:
         m = C.c_int(-1)
         check(lib().bp_prover_blinding(C.c_void_p(lib().bp_stmt_as_prover(self.h)), C.byref(m)), "bp_prover_blinding")
         return m.value
+
+    def check(self, engine=None):
+        """WitnessReport of this statement's witness (bp_prover_check): on the GPU with an engine, the host twin without; consumes nothing"""
+        return _witness_check(C.c_void_p(lib().bp_stmt_as_prover(self.h)), engine)
+
+    def set_check(self, on):
+        """the guard: prove() refuses an unsatisfying witness with UnsatisfiedError instead of emitting a proof no verifier accepts"""
+        _set_check(C.c_void_p(lib().bp_stmt_as_prover(self.h)), on)
+
+    def checking(self):
+        return _checking(C.c_void_p(lib().bp_stmt_as_prover(self.h)))
 
     def prove(self, eng):
         buf = C.create_string_buffer(1 << 16)
@@ -801,6 +872,20 @@ class ProverCS(_ConstraintSystem):
         check(lib().bp_prover_blinding(self.h, C.byref(m)), "bp_prover_blinding")
         return m.value
 
+    def check(self, engine=None):
+        """WitnessReport of what has been recorded so far (bp_prover_check): gates and constraints evaluated on the GPU with an
+        engine, by the host twin without.  Consumes nothing and touches no transcript; pending randomized-phase callbacks are
+        counted in deferred_callbacks and their constraints are not covered."""
+        return _witness_check(self.h, engine)
+
+    def set_check(self, on):
+        """the guard (bp_prover_set_check): every proving route evaluates the whole witness after the randomized phase and refuses a
+        violating one with BP_E_UNSATISFIED (UnsatisfiedError; in a batch: the instance's status) — no proof bytes.  Default off."""
+        _set_check(self.h, on)
+
+    def checking(self):
+        return _checking(self.h)
+
     def precompute(self, rng_bytes=None):
         """the host-only head of prove() (bp_prover_precompute)"""
         check(lib().bp_prover_precompute(self.h, bytes(rng_bytes) if rng_bytes is not None else None), "bp_prover_precompute")
@@ -1019,6 +1104,7 @@ def _gens_tables_check(self):
 
 TABLES_DIRECT, TABLES_PC_DIRECT, TABLES_PC_WIDE, TABLES_RESIDENT, TABLES_KINDS = 0, 1, 2, 3, 4   # include/arkbp.h BP_TABLES_*
 K_DT_CHECK = 17                          # BP_K_DT_CHECK (Engine.kernel_time)
+K_WITNESS_CHECK = 18                     # BP_K_WITNESS_CHECK: the witness-check kernels
 
 
 def _gens_direct_tables_check(self):
@@ -1406,7 +1492,33 @@ def _prove_batch_front_stats(self):
     return a.value, g.value, w.value
 
 
+def _check_batch(self, provers):
+    """bp_prover_check_batch: the WitnessReports of several provers (ProverCS and / or Statements) from one launch sequence and one wait"""
+    n = len(provers)
+    if n == 0:
+        return []
+    hs = (C.c_void_p * n)(*[_prover_handle(p) for p in provers])
+    out = (_WitnessReportC * n)()
+    check(lib().bp_prover_check_batch(self.ctx, C.c_size_t(n), hs, out), "bp_prover_check_batch")
+    return [WitnessReport(r) for r in out]
+
+
+def _last_unsatisfied(self):
+    """[(instance index, WitnessReport)] of the instances this engine's most recent proving call refused with BP_E_UNSATISFIED"""
+    cnt = C.c_size_t(0)
+    check(lib().bp_ctx_last_unsatisfied(self.ctx, C.c_size_t(0), None, None, C.byref(cnt)), "bp_ctx_last_unsatisfied")
+    n = cnt.value
+    if n == 0:
+        return []
+    inst = (C.c_uint64 * n)()
+    out = (_WitnessReportC * n)()
+    check(lib().bp_ctx_last_unsatisfied(self.ctx, C.c_size_t(n), inst, out, C.byref(cnt)), "bp_ctx_last_unsatisfied")
+    return [(int(inst[i]), WitnessReport(out[i])) for i in range(min(n, cnt.value))]
+
+
 Engine.prove_batch = _prove_batch
+Engine.check_batch = _check_batch
+Engine.last_unsatisfied = _last_unsatisfied
 Engine.prover_commit_batch = _prover_commit_batch
 Engine.prove_batch_stats = _prove_batch_stats
 Engine.prove_batch_front_stats = _prove_batch_front_stats

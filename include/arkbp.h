@@ -33,6 +33,7 @@ extern "C" {
 #define BP_E_GENS_LENGTH (-5)  /* R1CSError::InvalidGeneratorsLength */
 #define BP_E_FORMAT (-6)       /* R1CSError::FormatError */
 #define BP_E_MISSING (-7)      /* R1CSError::MissingAssignment */
+#define BP_E_UNSATISFIED (-8)  /* the witness violates a gate or a constraint; no proof was produced */
 
 typedef struct bp_ctx bp_ctx;
 
@@ -613,6 +614,56 @@ int bp_prover_commit_batch(bp_ctx* ctx, size_t count, bp_cs* const* provers, con
                            bp_var* vars_out);
 int bp_ctx_prove_batch_stats(bp_ctx* ctx, uint64_t* lockstep_instances, uint64_t* single_instances, uint64_t* groups);
 int bp_ctx_prove_batch_front_stats(bp_ctx* ctx, uint64_t* front_instances, uint64_t* front_groups, uint64_t* front_waits);
+/* Witness check: does the recorded assignment satisfy the recorded constraint system?  (The reference has no such call: a prover
+ * handed an unsatisfying witness runs the whole proof and returns bytes that no verifier accepts.)
+ *   gate i (i < multipliers):  a_L[i] * a_R[i] == a_O[i]  (mod r)
+ *   constraint k:              sum of coefficient * variable over its terms == 0  (mod r), with Committed(i) = v[i],
+ *                              MultiplierLeft / Right / Output(i) = a_L / a_R / a_O[i] and One = 1.
+ * Constraints are numbered in the order of the constrain calls, the two of every bp_cs_multiply included, the randomized phase
+ * continuing where phase 1 stopped (the `constraints` of bp_cs_metrics count the same rows).
+ * bp_witness_report: n and q examined; the number of violated gates and the smallest violated gate index (UINT64_MAX when none);
+ * the same for constraints; deferred_callbacks = randomized-phase callbacks that have not run yet — their constraints do not exist
+ * and are NOT covered, so a report with deferred_callbacks > 0 speaks about phase 1 only; first_bad_residual = the value of
+ * first_bad_constraint's combination (ark words), re-evaluated on the host from the recorder (all zero when none).
+ * With a device ctx the gates and the constraints are evaluated on the GPU (csrc/witness_check.cuh): one lane per gate, and the
+ * constraints row by row, every row cut into pieces of at most bp_witness_check_piece() terms — one lane per piece, a second launch
+ * summing the pieces of the rows that have several.  With a NULL or host-only ctx the host twin runs: plain loops over the recorder.
+ * Both give the same report.
+ * bp_prover_check: a diagnostic.  It uploads the witness itself, consumes nothing, touches no transcript and checks everything
+ * recorded so far.  It returns BP_OK whatever the report says (the return value is about the call; the caller reads the counts);
+ * BP_E_ARG for a null handle or report, a verifier handle, a consumed prover, or a ctx of another curve.
+ * bp_prover_check_batch: the same for `count` provers (out[k] is prover k's report) with one launch sequence and one host wait for
+ * all of them.  Up-front checks as in bp_prover_prove_batch: every prover live, of the ctx's curve, given once; BP_E_ARG otherwise,
+ * and no report is written.  Nothing is consumed either way.  A host-only ctx runs the host twin per prover.
+ * bp_prover_set_check(prover, 1): the GUARD.  Every proving route (bp_prover_prove over the direct tables or the folding path, after
+ * bp_prover_precompute[_batch], bp_stmt_prove, bp_prover_prove_batch with and without front groups; both blinding modes) evaluates
+ * the gates and ALL constraints once the whole witness is resident, after the randomized phase.  An instance with any violation
+ * returns BP_E_UNSATISFIED, writes no proof bytes (proof_len 0 in a batch), and is consumed; its transcript is left unspecified.  In
+ * a batch it is one more way for an instance to fail on its own: no other instance's bytes, status or transcript changes.  The guard
+ * adds no host wait: the flags come back with a copy the route already waits for.  It changes no TranscriptRng draw, so a satisfied
+ * statement proves to the same bytes with the guard on or off.  It may be set any time before the proof starts; the default is off,
+ * and with it off nothing changes: not a byte, not a launch, not a wait.  BP_E_ARG for a null, verifier or consumed handle.
+ * bp_prover_checking reads the flag back.
+ * bp_ctx_last_unsatisfied: the reports of the instances the ctx's most recent proving call (bp_prover_prove, bp_stmt_prove,
+ * bp_prover_prove_batch) refused with BP_E_UNSATISFIED, in instance order, with their instance indices (0 for a single proof).  *count
+ * receives how many there are; at most `cap` are written (instance / reports may be NULL when cap is 0).  0 after a call that refused none.
+ * bp_debug_prover_poke_witness (test hook): overwrites one recorded assignment — vec 0: a_L, 1: a_R, 2: a_O, 3: v; value: ark words
+ * of a reduced scalar.  The only way to produce a violated gate (the recorder computes a_O itself), and the easy way to spoil a
+ * satisfiable program.  Commitments already made are not recomputed.  BP_E_ARG for a bad handle, vector, index or value. */
+typedef struct bp_witness_report {
+    uint64_t gates_checked, constraints_checked;      /* n and q examined */
+    uint64_t bad_gates, first_bad_gate;               /* UINT64_MAX when none */
+    uint64_t bad_constraints, first_bad_constraint;   /* index = order of constrain calls, multiply's two included, phase 2 continuing */
+    uint64_t deferred_callbacks;                      /* randomized-phase callbacks not yet run: their constraints are NOT covered */
+    uint64_t first_bad_residual[4];                   /* value of first_bad_constraint's combination (ark words), re-evaluated on the host; zero when none */
+} bp_witness_report;
+size_t bp_witness_check_piece(void);
+int bp_prover_check(bp_ctx* ctx_or_null, bp_cs* prover, bp_witness_report* out);
+int bp_prover_check_batch(bp_ctx* ctx, size_t count, bp_cs* const* provers, bp_witness_report* out);
+int bp_prover_set_check(bp_cs* prover, int on);
+int bp_prover_checking(bp_cs* prover, int* on_out);
+int bp_ctx_last_unsatisfied(bp_ctx* ctx, size_t cap, uint64_t* instance, bp_witness_report* reports, size_t* count);
+int bp_debug_prover_poke_witness(bp_cs* prover, int vec /* 0 a_L, 1 a_R, 2 a_O, 3 v */, size_t index, const uint64_t value[4]);
 /* `verifier.verify(&proof, &pc_gens, &bp_gens)` (verifier.rs:549-557): consumes the verifier */
 int bp_verifier_verify(bp_ctx* ctx, bp_cs* verifier, const uint8_t* proof, size_t proof_len);
 /* `batch_verify(prng, instances, &pc_gens, &bp_gens)` (verifier.rs:604-691): instance k = (verifiers[k], the k-th of the
@@ -780,7 +831,8 @@ int bp_r1cs_batch_verify_scenarios(bp_ctx* ctx, size_t count, const int* scenari
 #define BP_K_VE_TAIL 15     /* k_ve_tail: the per-proof variable-base sums of bp_verifier_verify_batch */
 #define BP_K_MSM_BATCH 16   /* k_msb_accum + k_msb_combine: the bucketed route of bp_msm_batch, one region per group */
 #define BP_K_DT_CHECK 17    /* k_dt_check over table 4: the direct window tables' part of bp_gens_direct_tables_check */
-#define BP_K_COUNT 18
+#define BP_K_WITNESS_CHECK 18 /* k_r1cs_check* : gates and constraints of the witness check */
+#define BP_K_COUNT 19
 int bp_ctx_set_profiling(bp_ctx* ctx, int enabled);
 /* accumulated milliseconds and launch count since the last reset */
 int bp_ctx_kernel_time(bp_ctx* ctx, int which, double* ms_total, uint64_t* launches);
