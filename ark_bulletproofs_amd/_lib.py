@@ -38,6 +38,8 @@ EXPORTS = [
     "bp_prover_set_blinding", "bp_prover_blinding", "bp_host_blind_expand", "bp_debug_blind_expand", "bp_ctx_blinding_stats",
     # witness check
     "bp_witness_check_piece", "bp_prover_check", "bp_prover_check_batch", "bp_prover_set_check", "bp_prover_checking", "bp_ctx_last_unsatisfied", "bp_debug_prover_poke_witness",
+    # many witnesses of one recorded gadget
+    "bp_prover_new_like", "bp_prover_assign_multipliers", "bp_ctx_prover_like_stats",
 ]
 
 

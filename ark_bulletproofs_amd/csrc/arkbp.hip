@@ -198,6 +198,23 @@ static int pinned_ensure(void*& p, size_t& cap, size_t bytes, size_t slack) {
     return BP_OK;
 }
 
+// Device copies of ONE shared recording's constraint indices (bp_prover_new_like; r1cs_host.inc pl_entry): the column index with its
+// imported coefficient table, and — once a guarded proof has used it — the row index.  The key is the recording itself, held weakly:
+// an entry whose recording is gone is purged before the next lookup, and a live recording's address cannot have been reused.
+static constexpr size_t PL_CACHE_MAX = 8;
+struct PlResident {
+    std::weak_ptr<const host::FrozenRecording> key;
+    DevBuf csc;    // [moff | ment | mc | coefs]
+    size_t o_ment = 0, o_mc = 0, o_coefs = 0;
+    bool have_csc = false;
+    DevBuf row;    // [poff | pinfo | tvar | tcid | lrow | coefs]
+    size_t r_pinfo = 0, r_tvar = 0, r_tcid = 0, r_lrow = 0, r_coefs = 0;
+    const host::HostRowIndex* row_of = nullptr;   // the host index the row block was made from (owned by the recording)
+    uint64_t used = 0;
+    size_t bytes() const { return csc.cap + row.cap; }
+    ~PlResident() { csc.release(); row.release(); }
+};
+
 struct KTimer {
     double ms = 0;
     uint64_t launches = 0;
@@ -370,6 +387,11 @@ struct bp_ctx {
     size_t h_wc_cap = 0;
     std::vector<std::pair<uint64_t, bp_witness_report>> unsat;
     uint64_t bx_scalars = 0, bx_launches = 0;   // BP_BLINDING_EXPANDED: scalars the expansion kernels wrote / their launches (bp_ctx_blinding_stats)
+    // like-provers (bp_prover_new_like): device copies of their recordings' constraint indices, and the counters of bp_ctx_prover_like_stats
+    std::vector<std::unique_ptr<PlResident>> pl_cache;   // at most PL_CACHE_MAX, the least recently used goes first
+    uint64_t pl_clock = 0;
+    uint64_t pl_uploads = 0, pl_hits = 0, pl_gates_dev = 0, pl_gates_host = 0;
+    DevBuf pl_ztab;                  // the z^(2^j) of the proof in flight, when the coefficient table it would share a buffer with is resident
     // bp_verifier_verify_batch (verify_each.inc): its device arena and counters
     size_t tune_verify_each = 0;     // BP_TUNE_VERIFY_EACH: most instances per group (0 = what VE_ARENA_BUDGET holds, at most VE_GROUP_MAX)
     DevBuf ve_arena;
@@ -2690,6 +2712,7 @@ struct bp_cs {
     ProvePre<Zorro> pre1;
     std::unique_ptr<HostCsc> csc;                   // constraint index of a single-phase statement (built on first need, outside prove())
     bool csc_tried = false;
+    std::shared_ptr<const HostCsc> csc_shared;      // ... or the index of the recording it shares (bp_prover_new_like), owned by the recording
     host::u8 rng32[32] = {0};                       // what prove() draws from the external rng
     bool have_rng = false;
     bool consumed = false;                          // prove(self) / verify(self)
@@ -2758,18 +2781,44 @@ template <class C> static int stmt_build(bp_stmt* s, const uint64_t* params, con
     s->csc_tried = true;
     return BP_OK;
 }
+// The constraint index of a single-phase statement (null: two-phase, or not indexable): statement construction, not prove().  Built on
+// first need; a prover that shares a recording and recorded nothing itself gets the recording's own, built once for all of them.
+template <class C> static const HostCsc* cs_index(bp_cs* s) {
+    const host::ConstraintSystem<C>& cs = *s->cs<C>();
+    if (cs.base && cs.own_empty() && cs.deferred.empty()) {
+        if (!s->csc_shared) s->csc_shared = host::shared_host_csc<C>(*cs.base);
+        return s->csc_shared.get();
+    }
+    if (!s->csc_tried) {
+        s->csc.reset(new HostCsc());
+        if (!build_host_csc<C>(cs, *s->csc)) s->csc.reset();
+        s->csc_tried = true;
+    }
+    return s->csc.get();
+}
+// what a like-prover (bp_prover_new_like) must hold before anything of it is consumed: its witness, and every commitment the shared
+// constraints name
+template <class C> static bool cs_like_ready_t(const bp_cs* s, std::string& why) {
+    const host::ConstraintSystem<C>& cs = *const_cast<bp_cs*>(s)->cs<C>();
+    if (!cs.like) return true;
+    if (!cs.assigned) { why = "a like-prover has no witness (bp_prover_assign_multipliers)"; return false; }
+    if (cs.base) for (const host::VTerm& t : cs.base->vterms) if (t.j >= cs.v.size()) { why = "a like-prover holds fewer commitments than the shared constraints name"; return false; }
+    return true;
+}
+static int cs_like_ready(const char* who, const bp_cs* s, size_t instance) {
+    std::string why;
+    if (s->curve == 0 ? cs_like_ready_t<Secq>(s, why) : cs_like_ready_t<Zorro>(s, why)) return BP_OK;
+    g_err = std::string(who) + ": instance " + std::to_string(instance) + ": " + why;
+    return BP_E_ARG;
+}
 template <class C> static int cs_prove(bp_ctx* c, bp_cs* s, uint8_t* proof_out, size_t* proof_len, double* timing) {
     host::ProofData pf;
     StageTimes tm;
     auto* pre = C::ID == 0 ? (ProvePre<C>*)&s->pre0 : (ProvePre<C>*)&s->pre1;
-    if (!s->csc_tried) {   // single-phase circuits: the constraint index is statement construction, not prove()
-        s->csc.reset(new HostCsc());
-        if (!build_host_csc<C>(*s->cs<C>(), *s->csc)) s->csc.reset();
-        s->csc_tried = true;
-    }
+    const HostCsc* csc = cs_index<C>(s);
     WcGuard guard; guard.on = s->check;
     c->unsat.clear();
-    int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pf, tm, pre, s->csc.get(), nullptr, nullptr, s->check ? &guard : nullptr);
+    int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pf, tm, pre, csc, nullptr, nullptr, s->check ? &guard : nullptr);
     if (rc == BP_E_UNSATISFIED) c->unsat.emplace_back((uint64_t)0, guard.report);
     if (rc) return rc;
     std::vector<host::u8> bytes = host::proof_to_bytes<C>(pf);
@@ -2780,6 +2829,7 @@ template <class C> static int cs_prove(bp_ctx* c, bp_cs* s, uint8_t* proof_out, 
 }
 // `count` live provers of one curve: the host twin without a device, else one index upload, one launch sequence and one wait for all
 template <class C> static int cs_check_batch(bp_ctx* c, size_t count, bp_cs* const* hs, bp_witness_report* out) {
+    for (size_t k = 0; k < count; k++) prove_need_aO<C>(c, *hs[k]->cs<C>());   // (the host twin and this call's own upload read a_O on the host)
     if (!c || c->host_only) {
         for (size_t k = 0; k < count; k++) host::witness_check_host<C>(*hs[k]->cs<C>(), out[k]);
         return BP_OK;
@@ -2790,11 +2840,19 @@ template <class C> static int cs_check_batch(bp_ctx* c, size_t count, bp_cs* con
     wc.own.resize(count);
     std::vector<char> ok(count, 1);
     host_pool_ensure(c, count);
-    if (count == 1) { if (hs[0]->cs<C>()->cs_terms.size() > ((size_t)1 << 16)) host_pool_ensure(c, 2); ok[0] = build_row_index<C>(*hs[0]->cs<C>(), WC_PIECE, wc.own[0], [&](size_t cnt, const std::function<void(size_t)>& fn) { pool_range(c, 0, cnt, fn); }) ? 1 : 0; }
-    else pool_range(c, 0, count, [&](size_t k) { ok[k] = build_row_index<C>(*hs[k]->cs<C>(), WC_PIECE, wc.own[k]) ? 1 : 0; });
+    // (a prover that shares a recording and recorded nothing itself: the recording's index, built once, resident on this ctx)
+    std::vector<std::shared_ptr<const HostRowIndex>> shared(count);
+    auto index = [&](size_t k, const host::RowIndexPar& par) {
+        const host::ConstraintSystem<C>& cs = *hs[k]->cs<C>();
+        if (cs.base && cs.own_empty()) shared[k] = host::shared_row_index<C>(*cs.base, cs.v.size(), WC_PIECE, par);
+        ok[k] = shared[k] || build_row_index<C>(cs, WC_PIECE, wc.own[k], par) ? 1 : 0;
+    };
+    if (count == 1) { if (hs[0]->cs<C>()->num_terms() > ((size_t)1 << 16)) host_pool_ensure(c, 2); index(0, [&](size_t cnt, const std::function<void(size_t)>& fn) { pool_range(c, 0, cnt, fn); }); }
+    else pool_range(c, 0, count, [&](size_t k) { index(k, nullptr); });
     for (size_t k = 0; k < count; k++) {
         if (!ok[k]) { g_err = "prover_check: the constraints of instance " + std::to_string(k) + " cannot be indexed"; return BP_E_ARG; }
-        WcItem<C> it; it.cs = hs[k]->cs<C>(); it.idx = &wc.own[k];
+        WcItem<C> it; it.cs = hs[k]->cs<C>(); it.idx = shared[k] ? shared[k].get() : &wc.own[k];
+        if (shared[k] && count == 1 && c->shard_world <= 1) BPCHK(pl_row<C>(c, it.cs->base, *shared[k], it.dev));   // (one call's items never outnumber the cache: a single one)
         wc.items.push_back(it);
     }
     int rc = wc_enqueue<C>(c, wc, nullptr);
@@ -3201,6 +3259,26 @@ template <class C> static int verifier_new_like(bp_cs* of, host::Transcript* tr,
     return BP_OK;
 }
 
+template <class C> static int prover_new_like(bp_cs* of, host::Transcript* tr, bp_cs** out) {
+    host::ConstraintSystem<C>& src = *of->cs<C>();
+    BPCHK(src.freeze(true));
+    of->csc.reset(); of->csc_tried = false;   // (its index is the recording's from here)
+    bp_cs* h = new bp_cs();
+    cs_handle_init<C>(h, true, tr);
+    h->cs<C>()->init_like_prover(src);
+    h->pc_custom = of->pc_custom; h->pc_B = of->pc_B; h->pc_Bb = of->pc_Bb;
+    *out = h;
+    return BP_OK;
+}
+template <class C> static int prover_assign_multipliers(bp_cs* h, const uint64_t* left, const uint64_t* right, size_t count) {
+    host::ConstraintSystem<C>& cs = *h->cs<C>();
+    if (!cs.like || cs.assigned || cs.phase2 || !cs.base || count != cs.base->num_vars) { g_err = "assign_multipliers: needs a like-prover (bp_prover_new_like) without a witness, and as many values as the recording has multipliers"; return BP_E_ARG; }
+    for (size_t i = 0; i < 4 * count; i += 4)
+        if (host::Fld<typename C::Fr>::geq_p(left + i) || host::Fld<typename C::Fr>::geq_p(right + i)) { g_err = "assign_multipliers: a value is not a reduced scalar"; return BP_E_ARG; }
+    cs.assign_multipliers((const F4*)left, (const F4*)right, count);
+    return BP_OK;
+}
+
 template <class C> static int prover_commit(bp_cs* h, bp_ctx* ctx, const uint64_t* v, const uint64_t* blind, size_t count, uint64_t* V_xy, bp_var* vars) {
     host::ConstraintSystem<C>& cs = *h->cs<C>();
     if (cs.phase2) return BP_E_ARG;
@@ -3297,7 +3375,7 @@ template <class C> static int cs_specify_t(bp_cs* h, bp_randomize_cb cb, void* u
     h->cs<C>()->specify_randomized_constraints([cb, user](host::ConstraintSystem<C>& cs) -> int { return cb(user, (bp_cs*)cs.owner); });
     return BP_OK;
 }
-#define CS_RECORD_GUARD(h) do { if (!cs_live(h)) return BP_E_ARG; if (!CS_DISPATCH(h, cs_can_record<Secq>(h), cs_can_record<Zorro>(h))) { g_err = "this verifier shares its phase-1 constraints (bp_verifier_new_like): only commits and randomized constraints can be added"; return BP_E_ARG; } } while (0)
+#define CS_RECORD_GUARD(h) do { if (!cs_live(h)) return BP_E_ARG; if (!CS_DISPATCH(h, cs_can_record<Secq>(h), cs_can_record<Zorro>(h))) { g_err = (h)->proving ? "this prover shares its phase-1 constraints (bp_prover_new_like): only commits and randomized constraints can be added" : "this verifier shares its phase-1 constraints (bp_verifier_new_like): only commits and randomized constraints can be added"; return BP_E_ARG; } } while (0)
 
 // ---- C ABI ----------------------------------------------------------------------------------------
 #if defined(__x86_64__)
@@ -3637,6 +3715,8 @@ void bp_ctx_destroy(bp_ctx* c) {
                       &c->r_ypow, &c->r_part, &c->r_small, &c->r_g, &c->r_h, &c->r_chal, &c->r_tail, &c->v_params, &c->v_gpart, &c->v_hpart, &c->v_alpha, &c->v_tables, &c->v_dec, &c->ve_arena, &c->cyc_a, &c->cyc_b, &c->cyc_Gf, &c->cyc_Hf, &c->ftab_G, &c->ftab_H, &c->fb_G, &c->fb_H, &c->fb_pc, &c->p_moff, &c->p_ment, &c->p_mc, &c->p_coefs, &c->p_ztab, &c->fs_bcnt, &c->fs_loff, &c->fs_binch, &c->fs_sums};
     c->templates.clear();
     c->vfe_classes.clear();
+    c->pl_cache.clear();
+    c->pl_ztab.release();
     for (auto b : bufs) b->release();
     DevBuf* vbufs[] = {&c->vfe_in, &c->vfe_msg, &c->vfe_chal, &c->vfe_ws, &c->vfe_small, &c->vfe_flags, &c->vfe2_sched, &c->vfe2_voff, &c->vfe2_vq, &c->vfe2_vcid, &c->vfe2_gch, &c->vfe2_coef};
     for (auto b : vbufs) b->release();
@@ -4248,6 +4328,26 @@ int bp_verifier_new_like(bp_cs* of, void* transcript, bp_cs** out) {
     if (!cs_live(of) || of->proving || !transcript || !out) { g_err = "bp_verifier_new_like: needs a live verifier handle"; return BP_E_ARG; }
     return CS_DISPATCH(of, verifier_new_like<Secq>(of, (host::Transcript*)transcript, out), verifier_new_like<Zorro>(of, (host::Transcript*)transcript, out));
 }
+int bp_prover_new_like(bp_cs* of, void* transcript, bp_cs** out) {
+    if (!of || !of->proving || of->consumed || of->running || !transcript || !out) { g_err = "bp_prover_new_like: needs a live prover handle that is not inside prove"; return BP_E_ARG; }
+    if (of->pre0.rng || of->pre1.rng) { g_err = "bp_prover_new_like: the head of prove() has run on this prover"; return BP_E_ARG; }
+    if (CS_DISPATCH(of, of->cs0->phase2, of->cs1->phase2)) { g_err = "bp_prover_new_like: inside the randomized phase"; return BP_E_ARG; }
+    return CS_DISPATCH(of, prover_new_like<Secq>(of, (host::Transcript*)transcript, out), prover_new_like<Zorro>(of, (host::Transcript*)transcript, out));
+}
+int bp_prover_assign_multipliers(bp_cs* h, const uint64_t* left, const uint64_t* right, size_t count) {
+    if (!h || !h->proving || h->consumed || h->running || (count && (!left || !right))) { g_err = "assign_multipliers: needs a live like-prover and both vectors"; return BP_E_ARG; }
+    if (h->pre0.rng || h->pre1.rng) { g_err = "assign_multipliers: the head of prove() has run on this prover"; return BP_E_ARG; }
+    return CS_DISPATCH(h, prover_assign_multipliers<Secq>(h, left, right, count), prover_assign_multipliers<Zorro>(h, left, right, count));
+}
+int bp_ctx_prover_like_stats(bp_ctx* c, uint64_t* index_uploads, uint64_t* index_hits, uint64_t* resident_bytes, uint64_t* gates_on_device, uint64_t* gates_on_host) {
+    if (!c) return BP_E_ARG;
+    if (index_uploads) *index_uploads = c->pl_uploads;
+    if (index_hits) *index_hits = c->pl_hits;
+    if (resident_bytes) *resident_bytes = pl_resident_bytes(c);
+    if (gates_on_device) *gates_on_device = c->pl_gates_dev;
+    if (gates_on_host) *gates_on_host = c->pl_gates_host;
+    return BP_OK;
+}
 void bp_cs_free(bp_cs* h) { delete h; }
 void* bp_cs_transcript(bp_cs* h) { return h ? h->tr : nullptr; }
 int bp_cs_metrics(bp_cs* h, size_t* multipliers, size_t* constraints, size_t* commitments) {
@@ -4367,6 +4467,7 @@ int bp_cs_challenge_scalar(bp_cs* h, const char* label, uint64_t out[4]) {
 }
 int bp_prover_precompute(bp_cs* h, const uint8_t rng_bytes[32]) {
     if (!cs_live(h) || !h->proving) return BP_E_ARG;
+    BPCHK(cs_like_ready("precompute", h, 0));
     if (rng_bytes) { memcpy(h->rng32, rng_bytes, 32); h->have_rng = true; }
     if (!h->have_rng) { g_err = "prove: the external rng bytes are missing"; return BP_E_ARG; }
     if (h->curve == 0) { if (!h->pre0.rng) prove_precompute<Secq>(*h->cs0, h->rng32, h->pre0); }
@@ -4377,6 +4478,7 @@ int bp_prover_precompute(bp_cs* h, const uint8_t rng_bytes[32]) {
 int bp_prover_precompute_batch(bp_cs** hs, size_t count) {
     if (!hs) return BP_E_ARG;
     for (size_t i = 0; i < count; i++) if (!cs_live(hs[i]) || !hs[i]->proving || !hs[i]->have_rng || hs[i]->curve != hs[0]->curve) return BP_E_ARG;
+    for (size_t i = 0; i < count; i++) BPCHK(cs_like_ready("precompute_batch", hs[i], i));
     if (!count) return BP_OK;
     return hs[0]->curve == 0 ? cs_precompute_batch<Secq>(hs, count) : cs_precompute_batch<Zorro>(hs, count);
 }
@@ -4427,6 +4529,7 @@ int bp_prover_prove(bp_ctx* c, bp_cs* h, const uint8_t rng_bytes[32], uint8_t* p
         memcpy(h->rng32, rng_bytes, 32); h->have_rng = true;
     }
     if (!h->have_rng) { g_err = "prove: the external rng bytes are missing"; return BP_E_ARG; }
+    BPCHK(cs_like_ready("prove", h, 0));
     BPCHK(cs_pair_check("prove", c, h, 0));   // (before the prover is consumed)
     HIPCHK(hipSetDevice(c->device));
     if (!c->gens_cap) { g_err = "prove: generators not installed (bp_gens_derive / bp_gens_upload / bp_gens_share)"; return BP_E_GENS_LENGTH; }
@@ -4440,6 +4543,7 @@ size_t bp_witness_check_piece(void) { return WC_PIECE; }
 static bool wc_prover_ok(const bp_cs* h) { return h && h->proving && !h->consumed; }
 int bp_prover_check(bp_ctx* c, bp_cs* h, bp_witness_report* out) {
     if (!wc_prover_ok(h) || !out || (c && c->curve != h->curve)) { g_err = "prover_check: needs a live prover handle of the ctx's curve and a report"; return BP_E_ARG; }
+    BPCHK(cs_like_ready("prover_check", h, 0));
     bp_witness_report r;
     const int rc = h->curve == 0 ? cs_check_batch<Secq>(c, 1, &h, &r) : cs_check_batch<Zorro>(c, 1, &h, &r);
     if (!rc) *out = r;
@@ -4451,6 +4555,7 @@ int bp_prover_check_batch(bp_ctx* c, size_t count, bp_cs* const* provers, bp_wit
     if (!provers || !out) return BP_E_ARG;
     for (size_t k = 0; k < count; k++)
         if (!wc_prover_ok(provers[k]) || provers[k]->curve != c->curve) { g_err = "prover_check_batch: every instance needs a live prover of the ctx's curve"; return BP_E_ARG; }
+    for (size_t k = 0; k < count; k++) BPCHK(cs_like_ready("prover_check_batch", provers[k], k));
     {
         std::vector<const void*> hv(provers, provers + count);
         std::sort(hv.begin(), hv.end());
@@ -4482,6 +4587,7 @@ int bp_debug_prover_poke_witness(bp_cs* h, int vec, size_t index, const uint64_t
     F4 x; memcpy(x.v, value, 32);
     if (h->curve == 0 ? host::Fld<SecqFr>::geq_p(x.v) : host::Fld<ZorroFr>::geq_p(x.v)) { g_err = "poke_witness: the value is not a reduced scalar"; return BP_E_ARG; }
     auto poke = [&](auto* cs) -> int {
+        if (vec == 2) prove_need_aO(nullptr, *cs);   // (a like-prover's a_O exists on the host from here: the poked value is the truth)
         std::vector<F4>& t = vec == 0 ? cs->a_L : vec == 1 ? cs->a_R : vec == 2 ? cs->a_O : cs->v;
         if (index >= t.size()) return BP_E_ARG;
         t[index] = x;

@@ -596,7 +596,11 @@ struct CanonState {
 };
 struct VTerm { u32 j, q; F4 c; };   // committed variable j in constraint q with coefficient c: feeds wV (verifier.rs:334-338, prover.rs:385-387)
 
-// A phase-1 recording that several verifier instances share (bp_verifier_new_like): immutable once frozen.
+// A phase-1 recording that several verifier instances (bp_verifier_new_like) or several provers (bp_prover_new_like) share: immutable
+// once frozen.  The prover's constraint indices of the recording alone (prove_steps.hpp: HostCsc, HostRowIndex) hang off it, each built
+// once on first need: like-provers of one recording prove concurrently on several ctxs and threads.
+struct HostCsc;
+struct HostRowIndex;
 struct FrozenRecording {
     std::vector<Term> terms;
     std::vector<size_t> off{0};
@@ -605,6 +609,10 @@ struct FrozenRecording {
     CanonState canon;              // state after walking every constraint of this part
     std::vector<VTerm> vterms;     // in constraint order
     size_t nq() const { return off.size() - 1; }
+    mutable std::once_flag csc_once, row_once;
+    mutable std::shared_ptr<const HostCsc> csc;        // null after csc_once: the recording cannot be indexed
+    mutable std::shared_ptr<const HostRowIndex> row;   // (pieces of WC_PIECE terms, m = row_m commitments)
+    mutable size_t row_m = 0;
 };
 
 // The recorder shared by prover and verifier: the verifier records the same constraints without
@@ -626,6 +634,9 @@ template <class C> struct ConstraintSystem {
     std::vector<std::function<int(ConstraintSystem&)>> deferred;
     // prover secrets
     std::vector<F4> v, v_blinding, a_L, a_R, a_O;
+    // a like-prover (bp_prover_new_like): its witness arrives as two flat vectors (assigned) and a_O = a_L * a_R is formed only when
+    // somebody reads it on the host (aO_lazy: a_O is still empty; the routes that never need it take the product on the device)
+    bool like = false, assigned = false, aO_lazy = false;
     // verifier commitments
     std::vector<A4> V;
 
@@ -740,6 +751,13 @@ template <class C> struct ConstraintSystem {
         preset = nullptr; preset_labels = nullptr; preset_at = 0; preset_bad = false; chal_log = nullptr;
     }
     size_t base_nq() const { return base ? base->nq() : 0; }
+    bool own_empty() const { return cs_off.size() == 1; }
+    // constraint q of the whole recording: its terms
+    void row(size_t q, const Term*& p, size_t& cnt) const {
+        const size_t q0 = base_nq();
+        if (q < q0) { p = base->terms.data() + base->off[q]; cnt = base->off[q + 1] - base->off[q]; }
+        else { p = cs_terms.data() + cs_off[q - q0]; cnt = cs_off[q - q0 + 1] - cs_off[q - q0]; }
+    }
     size_t num_constraints() const { return base_nq() + cs_off.size() - 1; }
     size_t num_terms() const { return (base ? base->terms.size() : 0) + cs_terms.size(); }
     // fn(q, term) over every recorded term, the shared part first
@@ -749,8 +767,8 @@ template <class C> struct ConstraintSystem {
         for (size_t q = 0; q + 1 < cs_off.size(); q++) for (size_t k = cs_off[q]; k < cs_off[q + 1]; k++) fn(q0 + q, cs_terms[k]);
     }
     // Freezes what has been recorded so far (phase 1) into a shareable part; this instance continues on top of it.
-    int freeze() {
-        if (phase2 || proving) return BP_E_ARG;
+    int freeze(bool prover = false) {
+        if (phase2 || proving != prover) return BP_E_ARG;
         if (base && cs_terms.empty() && cs_off.size() == 1 && num_vars == base->num_vars) return BP_OK;   // already frozen, nothing new
         if (base) return BP_E_ARG;                         // (a second layer is not needed: like-instances record nothing in phase 1)
         auto f = std::make_shared<FrozenRecording>();
@@ -766,6 +784,28 @@ template <class C> struct ConstraintSystem {
     // a fresh verifier instance of the same gadget: shares `src`'s frozen phase-1 recording and its deferred closures
     void init_like(const ConstraintSystem& src) {
         base = src.base; num_vars = src.num_vars; has_pending = src.has_pending; pending = src.pending; deferred = src.deferred; proving = false;
+    }
+    // a fresh prover of the same gadget: the same sharing; its witness comes through assign_multipliers
+    void init_like_prover(const ConstraintSystem& src) {
+        base = src.base; num_vars = src.num_vars; has_pending = src.has_pending; pending = src.pending; deferred = src.deferred; proving = true; like = true;
+    }
+    // a_L = left, a_R = right for the shared multipliers (exactly once, words below r: the caller has checked)
+    void assign_multipliers(const F4* left, const F4* right, size_t count) {
+        reserve_huge(a_L, count); reserve_huge(a_R, count);
+        a_L.assign(left, left + count); a_R.assign(right, right + count);
+        assigned = true; aO_lazy = true;
+    }
+    // a_O on the host, on first need; par(count, fn) may spread the products over threads
+    void materialise_aO(const std::function<void(size_t, const std::function<void(size_t)>&)>& par = nullptr) {
+        if (!aO_lazy) return;
+        const size_t n = a_L.size();
+        reserve_huge(a_O, n);
+        a_O.resize(n);
+        static constexpr size_t CHUNK = (size_t)1 << 14;
+        const size_t chunks = (n + CHUNK - 1) / CHUNK;
+        auto work = [&](size_t c) { for (size_t i = c * CHUNK, hi = std::min(n, i + CHUNK); i < hi; i++) a_O[i] = S::mul(a_L[i], a_R[i]); };
+        if (par && chunks > 1) par(chunks, work); else for (size_t c = 0; c < chunks; c++) work(c);
+        aO_lazy = false;
     }
     // Canonical form of the whole recording (shared part + own part).  st_own is scratch for instances that recorded something
     // themselves; the returned state is the base's cached one otherwise (no copy).  own_vterms: committed-variable terms of the own part.

@@ -210,6 +210,8 @@ template <class C> struct PfMember {
     F4 w;
     bool csc_ok = true;
     std::unique_ptr<HostRowIndex> widx; // a guarded member's row index (bp_prover_set_check)
+    std::shared_ptr<const HostRowIndex> widx_shared;   // ... or the one of the recording it shares
+    const HostRowIndex* row() const { return widx_shared ? widx_shared.get() : widx.get(); }
     bool unsat = false;                 // ... and what the check found
     bp_witness_report report;
 };
@@ -339,8 +341,11 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     // the constraint index of the two-phase members
     pb_on_pool(ctx, part.size(), [&](size_t j) {
         PfMember<C>& m = *part[j];
-        const HostCsc* have = m.s->csc.get();
-        if (m.s->check) { m.widx.reset(new HostRowIndex()); if (!build_row_index<C>(*m.cs, WC_PIECE, *m.widx)) { m.csc_ok = false; return; } }   // (r1cs_prove reports it)
+        const HostCsc* have = m.cs->own_empty() && m.s->csc_shared ? m.s->csc_shared.get() : m.s->csc.get();
+        if (m.s->check) {   // (a like-prover that recorded nothing itself: the recording's index, built once)
+            if (m.cs->base && m.cs->own_empty()) m.widx_shared = host::shared_row_index<C>(*m.cs->base, m.cs->v.size(), WC_PIECE);
+            if (!m.widx_shared) { m.widx.reset(new HostRowIndex()); if (!build_row_index<C>(*m.cs, WC_PIECE, *m.widx)) { m.csc_ok = false; return; } }   // (r1cs_prove reports it)
+        }
         if (have && have->n == m.n && have->q == m.cs->num_constraints()) { m.csc = have; return; }
         m.csc_late.reset(new HostCsc());
         m.csc_ok = build_host_csc<C>(*m.cs, *m.csc_late);
@@ -364,9 +369,11 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     size_t nmax = 0, nzmax = 0, B2 = 0, in_words = 0, NG = 0;   // NG: guarded members (bp_prover_set_check); their flags lie behind the T results
     const size_t a_jobs2 = pb_align(B * sizeof(PfDesc));
     for (size_t j = 0; j < B; j++) if (part[j]->n > part[j]->n1) B2++;
-    for (size_t j = 0; j < B; j++) if (part[j]->widx) NG++;
+    for (size_t j = 0; j < B; j++) if (part[j]->row()) NG++;
     const size_t a_jobsT = a_jobs2 + pb_align(3 * B2 * sizeof(DtJob)), a_data = a_jobsT + pb_align(5 * B * sizeof(DtJob));
     size_t at = a_data;
+    std::map<const HostCsc*, size_t> first_of;   // like-provers of one recording point at ONE copy of its index and coefficient table
+    std::vector<char> owns(B, 1);
     for (size_t j = 0; j < B; j++) {
         const PfMember<C>& m = *part[j];
         PfDesc& d = descs[j];
@@ -374,11 +381,14 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
         const size_t nnz = m.csc->ment.size(), nc = m.csc->coefs.size();
         d.n = (u32)m.n; d.n1 = (u32)m.n1; d.nzhi = (u32)((m.csc->q + 1) >> 8) + 1;
         d.in_off = in_words; in_words += nv * m.n * 8;
+        nmax = std::max(nmax, m.n); nzmax = std::max<size_t>(nzmax, d.nzhi);
+        const auto seen = first_of.find(m.csc);
+        if (seen != first_of.end()) { const PfDesc& f = descs[seen->second]; d.moff = f.moff; d.ment = f.ment; d.mc = f.mc; d.coefs = f.coefs; owns[j] = 0; continue; }
+        first_of[m.csc] = j;
         d.moff = (u32)(at / 4); at += pb_align((m.n + 1) * 4);
         d.ment = (u32)(at / 4); at += pb_align(std::max<size_t>(nnz, 1) * 4);
         d.mc = (u32)(at / 4); at += pb_align(std::max<size_t>(nnz, 1) * 4);
         d.coefs = (u32)(at / 4); at += pb_align(nc * 32);
-        nmax = std::max(nmax, m.n); nzmax = std::max<size_t>(nzmax, d.nzhi);
     }
     const size_t a_u2 = at;                       // [B][96] scalars: z^(2^j) (32), y^(2^k) | y^-(2^k) (64)
     const size_t a_xu = a_u2 + B * 96 * 32;
@@ -446,6 +456,7 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
         char* u1 = hs + s_u1;
         memcpy(u1 + j * sizeof(PfDesc), &descs[j], sizeof(PfDesc));
         const HostCsc& cc = *m.csc;
+        if (!owns[j]) return;
         memcpy(u1 + (size_t)descs[j].moff * 4, cc.moff.data(), (n + 1) * 4);
         if (!cc.ment.empty()) { memcpy(u1 + (size_t)descs[j].ment * 4, cc.ment.data(), cc.ment.size() * 4); memcpy(u1 + (size_t)descs[j].mc * 4, cc.mc.data(), cc.mc.size() * 4); }
         F4* co = (F4*)(u1 + (size_t)descs[j].coefs * 4);
@@ -467,8 +478,8 @@ template <class C> static int pf_run_part_stages(bp_ctx* ctx, std::vector<PfMemb
     WcRun<C> wc;
     std::vector<size_t> wc_member;
     for (size_t j = 0; j < B; j++) {
-        if (!part[j]->widx) continue;
-        WcItem<C> it; it.cs = part[j]->cs; it.idx = part[j]->widx.get(); it.aL = wit(j, L.o_waL); it.aR = wit(j, L.o_waR); it.aO = wit(j, L.o_waO);
+        if (!part[j]->row()) continue;
+        WcItem<C> it; it.cs = part[j]->cs; it.idx = part[j]->row(); it.aL = wit(j, L.o_waL); it.aR = wit(j, L.o_waR); it.aO = wit(j, L.o_waO);
         wc.items.push_back(it); wc_member.push_back(j);
     }
     if (NG) { BPCHK(wc_enqueue<C>(ctx, wc, (u32*)(ax + a_flags))); BPCHK(wc_wipe_dev<C>(ctx, wc)); }
@@ -633,11 +644,7 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
     auto prove_single = [&](size_t k, size_t left, const A4* resume1) {
         bp_cs* s = hs[k];
         auto* pre = C::ID == 0 ? (ProvePre<C>*)&s->pre0 : (ProvePre<C>*)&s->pre1;
-        if (!s->csc_tried) {
-            s->csc.reset(new HostCsc());
-            if (!build_host_csc<C>(*s->cs<C>(), *s->csc)) s->csc.reset();
-            s->csc_tried = true;
-        }
+        const HostCsc* csc = cs_index<C>(s);
         IpaDefer defer;
         defer.take = [&](size_t N, IpaDeferSlot& slot) -> bool {
             if (grp.open && (grp.lay.N != N || grp.mem.size() >= grp.lay.cap)) flush();
@@ -656,7 +663,7 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
         };
         s->consumed = true; s->running = true;
         WcGuard guard; guard.on = s->check;
-        const int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pfs[k], tm, pre, s->csc.get(), &defer, resume1, s->check ? &guard : nullptr);
+        const int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pfs[k], tm, pre, csc, &defer, resume1, s->check ? &guard : nullptr);
         s->running = false;
         if (rc == BP_E_UNSATISFIED) unsat.emplace_back((uint64_t)k, guard.report);
         if (defer.taken) {
@@ -678,7 +685,7 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
     auto qualifies = [&](size_t k) -> bool {
         bp_cs* s = hs[k];
         const host::ConstraintSystem<C>& cs = *s->cs<C>();
-        if (reach_max < 2 || cs.base || cs.a_L.size() > reach_max) return false;
+        if (reach_max < 2 || cs.a_L.size() > reach_max) return false;
         if (cs.deferred.empty() && (cs.a_L.size() < 2 || host::next_pow2(cs.a_L.size()) > reach_max)) return false;
         if (!dt_tried) {
             dt_tried = true;
@@ -689,12 +696,8 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
         if (!cs.deferred.empty()) return true;   // two-phase: its padded size and its constraint index exist after the randomized phase
         const size_t N = host::next_pow2(cs.a_L.size());
         if (cs.a_L.size() == 0 || N < 2 || N > reach) return false;
-        if (!s->csc_tried) {
-            s->csc.reset(new HostCsc());
-            if (!build_host_csc<C>(cs, *s->csc)) s->csc.reset();
-            s->csc_tried = true;
-        }
-        return s->csc && s->csc->n == cs.a_L.size() && s->csc->q == cs.num_constraints();
+        const HostCsc* csc = cs_index<C>(s);
+        return csc && csc->n == cs.a_L.size() && csc->q == cs.num_constraints();
     };
     for (size_t oi = 0; oi < count;) {
         if (!qualifies(order[oi])) { prove_single(order[oi], count - oi, nullptr); oi++; continue; }
@@ -708,6 +711,7 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
             bp_cs* sk = hs[order[oi]];
             m.k = order[oi]; m.s = sk; m.cs = sk->cs<C>(); m.pre = C::ID == 0 ? (ProvePre<C>*)&sk->pre0 : (ProvePre<C>*)&sk->pre1; m.n1 = n1;
             sk->consumed = true; sk->running = true;
+            prove_need_aO<C>(c, *m.cs);   // (the group's staging copies a_O from the host)
             mem.push_back(std::move(m));
             oi++;
         }
@@ -722,7 +726,7 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
             if (r) { st[m.k] = r; continue; }
             m.n = m.cs->a_L.size(); m.N = host::next_pow2(m.n);
             if (c->gens_cap < m.N) { st[m.k] = BP_E_GENS_LENGTH; continue; }
-            if (m.n == 0 || m.N < 2 || m.N > reach || m.cs->base) { leavers.push_back(&m); continue; }
+            if (m.n == 0 || m.N < 2 || m.N > reach) { leavers.push_back(&m); continue; }
             parts[m.N].push_back(&m);
         }
         for (auto& pr : parts) {
@@ -779,6 +783,7 @@ int bp_prover_prove_batch(bp_ctx* c, size_t count, bp_cs* const* provers, const 
             if (h->have_rng && (h->pre0.rng || h->pre1.rng) && memcmp(h->rng32, rng_bytes + 32 * k, 32)) { g_err = "prove_batch: rng bytes differ from the precomputed ones"; return BP_E_ARG; }
         } else if (!h->have_rng) { g_err = "prove_batch: the external rng bytes are missing"; return BP_E_ARG; }
         BPCHK(cs_pair_check("prove_batch", c, h, k));
+        BPCHK(cs_like_ready("prove_batch", h, k));
     }
     {
         std::vector<const void*> hv(provers, provers + count), tv(count);

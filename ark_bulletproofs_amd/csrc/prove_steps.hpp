@@ -17,15 +17,21 @@ struct HostCsc {
     std::vector<F4> coefs;
     std::vector<VTerm> vterms;   // committed-variable terms in constraint order: feed wV (t_2's blinding, prover.rs:716-721)
 };
-template <class C> static bool build_host_csc(const ConstraintSystem<C>& cs, HostCsc& h) {
+// The index of `base` (a shared phase-1 recording, may be null) followed by the Q own constraints of (terms, off): what the same
+// constraints recorded flat give, entry by entry.  n: multipliers.
+template <class C> static bool build_host_csc_parts(const FrozenRecording* base, const Term* terms, const size_t* off, size_t Qown, size_t n, HostCsc& h) {
     typedef Fld<typename C::Fr> S;
-    const size_t n = cs.num_vars, Q = cs.num_constraints();
-    if (!cs.deferred.empty() || cs.base || Q >= ((size_t)1 << 30) || n >= ((size_t)1 << 31)) return false;
+    const size_t Qb = base ? base->nq() : 0, Q = Qb + Qown;
+    if (Q >= ((size_t)1 << 30) || n >= ((size_t)1 << 31)) return false;
     h.n = n; h.q = Q;
     reserve_huge(h.moff, n + 1);
     h.moff.assign(n + 1, 0);
     auto vec_of = [](int k) { return k == VK_LEFT ? 0 : k == VK_RIGHT ? 1 : k == VK_OUT ? 2 : -1; };
-    for (const Term& t : cs.cs_terms) if (vec_of(t.v.k) >= 0) h.moff[t.v.i + 1]++;
+    bool ok = true;
+    auto count = [&](const Term* t, size_t cnt) { for (size_t k = 0; k < cnt; k++) if (vec_of(t[k].v.k) >= 0) { if (t[k].v.i < n) h.moff[t[k].v.i + 1]++; else ok = false; } };
+    if (base) count(base->terms.data(), base->terms.size());
+    count(terms, off[Qown]);
+    if (!ok) return false;
     for (size_t i = 0; i < n; i++) h.moff[i + 1] += h.moff[i];
     reserve_huge(h.ment, h.moff[n]); reserve_huge(h.mc, h.moff[n]);
     h.ment.resize(h.moff[n]); h.mc.resize(h.moff[n]);
@@ -34,9 +40,8 @@ template <class C> static bool build_host_csc(const ConstraintSystem<C>& cs, Hos
     cur.assign(h.moff.begin(), h.moff.end() - 1);
     const F4 one = S::one(), mone = S::neg(S::one());
     CanonState st;
-    bool ok = true;
     // constraints in order: every column's run comes out sorted by q
-    st.walk(cs.cs_terms.data(), cs.cs_off.data(), Q, 0, one, mone, [&](size_t q, const Term& t, u32 cid) {
+    auto put = [&](size_t q, const Term& t, u32 cid) {
         const int v = vec_of(t.v.k);
         if (t.v.k == VK_COMMITTED) h.vterms.push_back(VTerm{t.v.i, (u32)q, t.c});
         if (v < 0) return;   // (the constant terms enter wc, which the prover does not use)
@@ -44,10 +49,25 @@ template <class C> static bool build_host_csc(const ConstraintSystem<C>& cs, Hos
         const u32 pos = cur[t.v.i]++;
         h.ment[pos] = ((u32)v << 30) | (u32)q;
         h.mc[pos] = cid;
-    });
+    };
+    if (base) st.walk(base->terms.data(), base->off.data(), Qb, 0, one, mone, put);
+    st.walk(terms, off, Qown, Qb, one, mone, put);
     h.coefs.swap(st.coefs);
     if (h.coefs.empty()) h.coefs.push_back(one);
     return ok;
+}
+template <class C> static bool build_host_csc(const ConstraintSystem<C>& cs, HostCsc& h) {
+    if (!cs.deferred.empty()) return false;
+    return build_host_csc_parts<C>(cs.base.get(), cs.cs_terms.data(), cs.cs_off.data(), cs.cs_off.size() - 1, cs.num_vars, h);
+}
+// the index of a shared recording alone: built by the first prover that asks, under the recording's once-flag (null: cannot be indexed)
+template <class C> static std::shared_ptr<const HostCsc> shared_host_csc(const FrozenRecording& f) {
+    std::call_once(f.csc_once, [&] {
+        auto h = std::make_shared<HostCsc>();
+        const size_t none[1] = {0};
+        if (build_host_csc_parts<C>(&f, nullptr, none, 0, f.num_vars, *h)) f.csc = h;
+    });
+    return f.csc;
 }
 
 // ---- witness check (include/arkbp.h: bp_prover_check; the kernels: witness_check.cuh) -----------------------------------------------
@@ -68,11 +88,11 @@ struct HostRowIndex {
 // par(count, fn): fn(0) .. fn(count - 1) in any order, possibly on several threads (null: here, one after the other).  The result does
 // not depend on it: coefficients other than +-1 are numbered in a second, sequential pass, in order of first occurrence.
 typedef std::function<void(size_t, const std::function<void(size_t)>&)> RowIndexPar;
-template <class C> static bool build_row_index(const ConstraintSystem<C>& cs, size_t piece, HostRowIndex& h, const RowIndexPar& par = nullptr) {
+// (the core: Q constraints flat in (terms, off), n multipliers, m committed variables)
+template <class C> static bool build_row_index_flat(const Term* terms, const size_t* off, size_t Q, size_t n, size_t m, size_t piece, HostRowIndex& h, const RowIndexPar& par) {
     typedef Fld<typename C::Fr> S;
-    const size_t n = cs.a_L.size(), Q = cs.cs_off.size() - 1, m = cs.v.size(), nt = cs.cs_terms.size();
-    if (cs.base || piece < 2 || n >= ((size_t)1 << 29) || m >= ((size_t)1 << 29) || Q >= ((size_t)1 << 30) || nt >= ((size_t)1 << 31)) return false;
-    if (cs.a_R.size() != n || cs.a_O.size() != n) return false;
+    const size_t nt = off[Q];
+    if (piece < 2 || n >= ((size_t)1 << 29) || m >= ((size_t)1 << 29) || Q >= ((size_t)1 << 30) || nt >= ((size_t)1 << 31)) return false;
     h = HostRowIndex();
     h.n = n; h.q = Q; h.m = m;
     auto run = [&](size_t count, const std::function<void(size_t)>& fn) { if (par && count > 1) par(count, fn); else for (size_t c = 0; c < count; c++) fn(c); };
@@ -85,7 +105,7 @@ template <class C> static bool build_row_index(const ConstraintSystem<C>& cs, si
     std::vector<u8> bad(tchunks, 0), general(tchunks, 0), longrow(qchunks, 0);
     run(tchunks, [&](size_t c) {
         for (size_t k = c * CHUNK, hi = std::min(nt, k + CHUNK); k < hi; k++) {
-            const Term& t = cs.cs_terms[k];
+            const Term& t = terms[k];
             const size_t lim = t.v.k == VK_COMMITTED ? m : t.v.k <= VK_OUT ? n : 0;
             if (t.v.k != VK_ONE && t.v.i >= lim) bad[c] = 1;   // a variable the recorder never handed out
             h.tvar[k] = ((u32)t.v.k << 29) | (t.v.k == VK_ONE ? 0u : t.v.i);
@@ -98,24 +118,24 @@ template <class C> static bool build_row_index(const ConstraintSystem<C>& cs, si
         if (!general[c]) continue;
         for (size_t k = c * CHUNK, hi = std::min(nt, k + CHUNK); k < hi; k++) {
             if (h.tcid[k] != GENERAL) continue;
-            const u32 id = st.id_of(cs.cs_terms[k].c);
+            const u32 id = st.id_of(terms[k].c);
             if (id >= GENERAL) return false;
             h.tcid[k] = id;
         }
     }
-    run(qchunks, [&](size_t c) { for (size_t q = c * CHUNK, hi = std::min(Q, q + CHUNK); q < hi; q++) if (cs.cs_off[q + 1] - cs.cs_off[q] > piece) longrow[c] = 1; });
+    run(qchunks, [&](size_t c) { for (size_t q = c * CHUNK, hi = std::min(Q, q + CHUNK); q < hi; q++) if (off[q + 1] - off[q] > piece) longrow[c] = 1; });
     bool any_long = false;
     for (size_t c = 0; c < qchunks; c++) any_long |= longrow[c] != 0;
     if (!any_long) {   // every row is one piece (an empty row is one empty piece: sum 0, satisfied)
         reserve_huge(h.poff, Q + 1); reserve_huge(h.pinfo, Q);
         h.poff.resize(Q + 1); h.pinfo.resize(Q);
         h.poff[0] = 0;
-        run(qchunks, [&](size_t c) { for (size_t q = c * CHUNK, hi = std::min(Q, q + CHUNK); q < hi; q++) { h.pinfo[q] = (u32)q; h.poff[q + 1] = (u32)cs.cs_off[q + 1]; } });
+        run(qchunks, [&](size_t c) { for (size_t q = c * CHUNK, hi = std::min(Q, q + CHUNK); q < hi; q++) { h.pinfo[q] = (u32)q; h.poff[q + 1] = (u32)off[q + 1]; } });
     } else {
         reserve_huge(h.poff, Q + nt / piece + 2); reserve_huge(h.pinfo, Q + nt / piece + 1);
         h.poff.push_back(0);
         for (size_t q = 0; q < Q; q++) {
-            const size_t lo = cs.cs_off[q], hi = cs.cs_off[q + 1], len = hi - lo;
+            const size_t lo = off[q], hi = off[q + 1], len = hi - lo;
             const size_t np = len <= piece ? 1 : (len + piece - 1) / piece;
             if (np == 1) { h.pinfo.push_back((u32)q); h.poff.push_back((u32)hi); continue; }
             if (h.nslots + np >= HostRowIndex::ROW_LONG) return false;
@@ -129,16 +149,43 @@ template <class C> static bool build_row_index(const ConstraintSystem<C>& cs, si
     if (h.coefs.empty()) h.coefs.push_back(one);
     return true;
 }
+// An instance's index: its own constraints; behind a shared recording (ConstraintSystem::base) the recording's rows first — copied in
+// front of the own ones, so that the result is what the same constraints recorded flat give.  (A like-prover that recorded nothing
+// itself uses the recording's own index instead: shared_row_index, no copy.)
+template <class C> static bool build_row_index(const ConstraintSystem<C>& cs, size_t piece, HostRowIndex& h, const RowIndexPar& par = nullptr) {
+    const size_t n = cs.a_L.size();
+    if (cs.a_R.size() != n || (!cs.aO_lazy && cs.a_O.size() != n)) return false;
+    if (!cs.base) return build_row_index_flat<C>(cs.cs_terms.data(), cs.cs_off.data(), cs.cs_off.size() - 1, n, cs.v.size(), piece, h, par);
+    const FrozenRecording& f = *cs.base;
+    std::vector<Term> terms;
+    std::vector<size_t> off;
+    reserve_huge(terms, f.terms.size() + cs.cs_terms.size()); reserve_huge(off, f.off.size() + cs.cs_off.size());
+    terms.insert(terms.end(), f.terms.begin(), f.terms.end()); terms.insert(terms.end(), cs.cs_terms.begin(), cs.cs_terms.end());
+    off.insert(off.end(), f.off.begin(), f.off.end());
+    for (size_t q = 1; q < cs.cs_off.size(); q++) off.push_back(f.terms.size() + cs.cs_off[q]);
+    return build_row_index_flat<C>(terms.data(), off.data(), off.size() - 1, n, cs.v.size(), piece, h, par);
+}
+// the index of a shared recording alone for provers that hold m commitments (like-provers of one recording hold the same number: one
+// that differs gets null and builds its own): once per recording
+template <class C> static std::shared_ptr<const HostRowIndex> shared_row_index(const FrozenRecording& f, size_t m, size_t piece, const RowIndexPar& par = nullptr) {
+    std::call_once(f.row_once, [&] {
+        auto h = std::make_shared<HostRowIndex>();
+        if (build_row_index_flat<C>(f.terms.data(), f.off.data(), f.nq(), f.num_vars, m, piece, *h, par)) { f.row = h; f.row_m = m; }
+    });
+    return f.row && f.row_m == m && f.row->n == f.num_vars ? f.row : nullptr;
+}
 // the value of row q's combination (ark words)
 template <class C> static F4 witness_row_value(const ConstraintSystem<C>& cs, size_t q) {
-    return cs.eval(cs.cs_terms.data() + cs.cs_off[q], cs.cs_off[q + 1] - cs.cs_off[q]);
+    const Term* p; size_t cnt;
+    cs.row(q, p, cnt);
+    return cs.eval(p, cnt);
 }
 // The host twin: plain loops over the recorder with the host field.  What the kernels are tested against, and what a NULL or host-only
 // ctx runs.
 template <class C> static void witness_check_host(const ConstraintSystem<C>& cs, bp_witness_report& r) {
     typedef Fld<typename C::Fr> S;
     memset(&r, 0, sizeof r);
-    const size_t n = cs.a_L.size(), Q = cs.cs_off.size() - 1;
+    const size_t n = cs.a_L.size(), Q = cs.num_constraints();
     r.gates_checked = n; r.constraints_checked = Q; r.deferred_callbacks = cs.deferred.size();
     r.first_bad_gate = r.first_bad_constraint = ~(uint64_t)0;
     for (size_t i = 0; i < n; i++)
@@ -152,10 +199,10 @@ template <class C> static void witness_check_host(const ConstraintSystem<C>& cs,
 // a device result (bad gates, first, bad constraints, first) as a report; the residual comes from the recorder
 template <class C> static void witness_report_from_flags(const ConstraintSystem<C>& cs, const u32 res[4], bp_witness_report& r) {
     memset(&r, 0, sizeof r);
-    r.gates_checked = cs.a_L.size(); r.constraints_checked = cs.cs_off.size() - 1; r.deferred_callbacks = cs.deferred.size();
+    r.gates_checked = cs.a_L.size(); r.constraints_checked = cs.num_constraints(); r.deferred_callbacks = cs.deferred.size();
     r.bad_gates = res[0]; r.first_bad_gate = res[0] ? res[1] : ~(uint64_t)0;
     r.bad_constraints = res[2]; r.first_bad_constraint = res[2] ? res[3] : ~(uint64_t)0;
-    if (res[2] && res[3] < cs.cs_off.size() - 1) { const F4 s = witness_row_value<C>(cs, res[3]); memcpy(r.first_bad_residual, s.v, 32); }
+    if (res[2] && res[3] < cs.num_constraints()) { const F4 s = witness_row_value<C>(cs, res[3]); memcpy(r.first_bad_residual, s.v, 32); }
 }
 
 // ztab[j] = z^(2^j); ypw[k] = y^(2^k), ypw[32 + k] = y^-(2^k): ONE inversion.  A null table is left out.

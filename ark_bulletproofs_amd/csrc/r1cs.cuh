@@ -127,6 +127,17 @@ k_r1cs_poly_eval(const u32* __restrict__ aL, const u32* __restrict__ aR, const u
     r1cs_poly_eval_body<C>(aL, aR, aO, sL, sR, wL, wR, wO, ypow, n, n1, N, xw.w, uw.w, lvec, rvec, Gf, Hf);
 }
 
+// Gate outputs of a like-prover (bp_prover_new_like): a_O[i] = a_L[i] * a_R[i] for i < n, resident words in and out, one lane per
+// multiplier behind the import of a_L, a_R.  64 bytes in and 32 out per product: bound by memory, one fe_mul per lane; nothing beyond n
+// is touched (the routes' padding stays theirs).
+template <class F> __global__ void __launch_bounds__(256)
+k_r1cs_gate_out(const u32* __restrict__ aL, const u32* __restrict__ aR, u32* __restrict__ aO, u32 n) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t o = (size_t)i * 8;
+    store_fe_dev<F>(aO + o, fe_mul<F>(load_fe_dev<F>(aL + o), load_fe_dev<F>(aR + o)));
+}
+
 // Verifier scalars.  chal: u_sq[k] (resident words, creation order); consts: resident words
 // [allinv, x, a, b, u, alpha]; ypow as above (only the inverse half is used).
 // g[i] = u_or_1 * (x * y^-i * wR[i] - a * s[i]),  h[i] = u_or_1 * (y^-i * (x*wL[i] + wO[i] - b*s[N-1-i]) - 1)

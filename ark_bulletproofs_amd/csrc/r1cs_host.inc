@@ -414,6 +414,83 @@ struct IpaDefer {
     F4 w;
 };
 
+// ---- like-provers (include/arkbp.h bp_prover_new_like) ---------------------------------------------------------------------------------
+// a_O of a like-prover on the host: THE place where it is formed there (randomized-phase callbacks read it through eval, the host twin
+// of the witness check, the staging of front groups, bp_prover_check's own upload, a poke of a_O) — on the ctx's pool when there is one.
+// Once formed the host vector is the truth and goes up like a recorded prover's.
+template <class C> static void prove_need_aO(bp_ctx* ctx, host::ConstraintSystem<C>& cs) {
+    if (!cs.aO_lazy) return;
+    const size_t n = cs.a_L.size();
+    if (ctx && n > ((size_t)1 << 14)) host_pool_ensure(ctx, 2);
+    cs.materialise_aO([&](size_t cnt, const std::function<void(size_t)>& fn) { pool_range(ctx, 0, cnt, fn); });
+    if (ctx) ctx->pl_gates_host += n;
+}
+// the ctx's entry of a recording: expired entries go first, then the least recently used one when PL_CACHE_MAX are kept
+static PlResident* pl_entry(bp_ctx* ctx, const std::shared_ptr<const host::FrozenRecording>& rec) {
+    auto& cache = ctx->pl_cache;
+    cache.erase(std::remove_if(cache.begin(), cache.end(), [](const std::unique_ptr<PlResident>& e) { return e->key.expired(); }), cache.end());
+    for (auto& e : cache) if (e->key.lock() == rec) { e->used = ++ctx->pl_clock; return e.get(); }
+    if (cache.size() >= PL_CACHE_MAX) cache.erase(std::min_element(cache.begin(), cache.end(), [](const std::unique_ptr<PlResident>& a, const std::unique_ptr<PlResident>& b) { return a->used < b->used; }));
+    cache.emplace_back(new PlResident());
+    cache.back()->key = rec; cache.back()->used = ++ctx->pl_clock;
+    return cache.back().get();
+}
+static size_t pl_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// the recording's column index on the device: uploaded by the first proof of the recording on this ctx, found there by every later one
+struct CscPtrs { const u32 *moff, *ment, *mc; };
+template <class C> static int pl_csc(bp_ctx* ctx, const std::shared_ptr<const host::FrozenRecording>& rec, const HostCsc& csc, CscPtrs& k, const u32*& coefs) {
+    PlResident* e = pl_entry(ctx, rec);
+    if (!e->have_csc) {
+        const size_t n = csc.n, nnz = csc.ment.size(), nc = csc.coefs.size();
+        e->o_ment = pl_align((n + 1) * 4); e->o_mc = e->o_ment + pl_align(nnz * 4); e->o_coefs = e->o_mc + pl_align(nnz * 4);
+        const size_t total = e->o_coefs + nc * 32;
+        BPCHK(e->csc.ensure_exact(total));
+        BPCHK(pinned_ensure(ctx->h_csc, ctx->h_csc_cap, total, 4096));
+        char* hs = (char*)ctx->h_csc;
+        memcpy(hs, csc.moff.data(), (n + 1) * 4);
+        if (nnz) { memcpy(hs + e->o_ment, csc.ment.data(), nnz * 4); memcpy(hs + e->o_mc, csc.mc.data(), nnz * 4); }
+        memcpy(hs + e->o_coefs, csc.coefs.data(), nc * 32);
+        HIPCHK(hipMemcpyAsync(e->csc.p, hs, total, hipMemcpyHostToDevice, ctx->stream));
+        u32* dc = (u32*)((char*)e->csc.p + e->o_coefs);
+        hipLaunchKernelGGL(k_scalars_import<typename C::Fr>, dim3((u32)((nc + 255) / 256)), dim3(256), 0, ctx->stream, dc, dc, (u32)nc);
+        HIPCHK(hipGetLastError());
+        HIPCHK(ctx_stream_wait(ctx));   // (once per recording and ctx: the staging is free again)
+        e->have_csc = true;
+        ctx->pl_uploads++;
+    } else ctx->pl_hits++;
+    const char* d = (const char*)e->csc.p;
+    k = CscPtrs{(const u32*)d, (const u32*)(d + e->o_ment), (const u32*)(d + e->o_mc)};
+    coefs = (const u32*)(d + e->o_coefs);
+    return BP_OK;
+}
+// ... and its row index, for the guard's check kernels (the first guarded proof of the recording on this ctx uploads it)
+template <class C> static int pl_row(bp_ctx* ctx, const std::shared_ptr<const host::FrozenRecording>& rec, const HostRowIndex& h, const PlResident*& out) {
+    typedef typename C::Fr FrP;
+    PlResident* e = pl_entry(ctx, rec);
+    if (e->row_of != &h) {
+        e->r_pinfo = pl_align(h.poff.size() * 4); e->r_tvar = e->r_pinfo + pl_align(h.pinfo.size() * 4); e->r_tcid = e->r_tvar + pl_align(h.tvar.size() * 4);
+        e->r_lrow = e->r_tcid + pl_align(h.tcid.size() * 4); e->r_coefs = e->r_lrow + pl_align(h.lrow.size() * 4);
+        const size_t total = e->r_coefs + h.coefs.size() * 32;
+        BPCHK(e->row.ensure_exact(total));
+        BPCHK(pinned_ensure(ctx->h_csc, ctx->h_csc_cap, total, 4096));
+        char* hs = (char*)ctx->h_csc;
+        auto put = [&](size_t at, const std::vector<u32>& v) { if (!v.empty()) memcpy(hs + at, v.data(), v.size() * 4); };
+        put(0, h.poff); put(e->r_pinfo, h.pinfo); put(e->r_tvar, h.tvar); put(e->r_tcid, h.tcid); put(e->r_lrow, h.lrow);
+        F4* co = (F4*)(hs + e->r_coefs);
+        for (size_t i = 0; i < h.coefs.size(); i++) co[i] = to_resident<FrP>(h.coefs[i]);   // (as wc_enqueue stages an instance's own table)
+        HIPCHK(hipMemcpyAsync(e->row.p, hs, total, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx_stream_wait(ctx));
+        e->row_of = &h;
+    }
+    out = e;
+    return BP_OK;
+}
+static size_t pl_resident_bytes(const bp_ctx* ctx) {
+    size_t b = 0;
+    for (auto& e : ctx->pl_cache) if (!e->key.expired()) b += e->bytes();
+    return b;
+}
+
 // ---- witness check (witness_check.cuh; include/arkbp.h bp_prover_check / bp_prover_set_check) -----------------------------------------
 // One call's statements share ONE block: the device buffer ctx->wc_dev and its image in the pinned staging ctx->h_wc (behind the
 // area the flags return to).  Image: [descriptors | flags | per statement: poff, pinfo, tvar, tcid, lrow, coefs || the witnesses (ark
@@ -425,6 +502,7 @@ template <class C> struct WcItem {
     const host::ConstraintSystem<C>* cs = nullptr;
     const HostRowIndex* idx = nullptr;
     const u32 *aL = nullptr, *aR = nullptr, *aO = nullptr;   // the resident witness; all null: the run uploads it itself
+    const PlResident* dev = nullptr;                        // idx is a shared recording's and lives on the device already (pl_row): nothing of it is staged
 };
 template <class C> struct WcRun {
     std::vector<WcItem<C>> items;
@@ -454,6 +532,7 @@ template <class C> static int wc_enqueue(bp_ctx* ctx, WcRun<C>& r, u32* res_dev)
     for (size_t j = 0; j < B; j++) {
         const HostRowIndex& h = *r.items[j].idx;
         at[j] = o;
+        if (r.items[j].dev) continue;
         o += wc_align((h.npieces() + 1) * 4) + wc_align(h.npieces() * 4) + 2 * wc_align(h.tvar.size() * 4) + wc_align(h.lrow.size() * 4) + wc_align(h.coefs.size() * 32);
     }
     r.o_secret = r.o_wit = o;
@@ -489,14 +568,20 @@ template <class C> static int wc_enqueue(bp_ctx* ctx, WcRun<C>& r, u32* res_dev)
         };
         WcDesc& d = descs[j];
         memset(&d, 0, sizeof d);
-        d.poff = put(h.poff.data(), h.poff.size() * 4);
-        d.pinfo = put(h.pinfo.data(), h.pinfo.size() * 4);
-        d.tvar = put(h.tvar.data(), h.tvar.size() * 4);
-        d.tcid = put(h.tcid.data(), h.tcid.size() * 4);
-        d.lrow = put(h.lrow.data(), h.lrow.size() * 4);
-        d.coefs = (const u32*)(dev + p);
-        F4* co = (F4*)(img + p);
-        for (size_t i = 0; i < h.coefs.size(); i++) co[i] = to_resident<FrP>(h.coefs[i]);
+        if (it.dev) {
+            const char* rb = (const char*)it.dev->row.p;
+            d.poff = (const u32*)rb; d.pinfo = (const u32*)(rb + it.dev->r_pinfo); d.tvar = (const u32*)(rb + it.dev->r_tvar); d.tcid = (const u32*)(rb + it.dev->r_tcid);
+            d.lrow = (const u32*)(rb + it.dev->r_lrow); d.coefs = (const u32*)(rb + it.dev->r_coefs);
+        } else {
+            d.poff = put(h.poff.data(), h.poff.size() * 4);
+            d.pinfo = put(h.pinfo.data(), h.pinfo.size() * 4);
+            d.tvar = put(h.tvar.data(), h.tvar.size() * 4);
+            d.tcid = put(h.tcid.data(), h.tcid.size() * 4);
+            d.lrow = put(h.lrow.data(), h.lrow.size() * 4);
+            d.coefs = (const u32*)(dev + p);
+            F4* co = (F4*)(img + p);
+            for (size_t i = 0; i < h.coefs.size(); i++) co[i] = to_resident<FrP>(h.coefs[i]);
+        }
         d.v = (const u32*)(dev + v_at[j]);
         F4* vv = (F4*)(img + v_at[j]);
         for (size_t i = 0; i < h.m; i++) vv[i] = to_resident<FrP>(it.cs->v[i]);
@@ -618,7 +703,18 @@ template <class C> static int prove_upload_phase(ProveJob<C>& j, size_t off, siz
     u32* const dst[5] = {ctx->r_aL.as<u32>() + off * 8, ctx->r_aR.as<u32>() + off * 8, ctx->r_aO.as<u32>() + off * 8, ctx->r_sL.as<u32>() + off * 8, ctx->r_sR.as<u32>() + off * 8};
     const F4* const src[5] = {j.cs.a_L.data() + off, j.cs.a_R.data() + off, j.cs.a_O.data() + off, j.expanded ? nullptr : j.pre.s_L.data() + off, j.expanded ? nullptr : j.pre.s_R.data() + off};
     j.secrets_up = true;
-    BPCHK(upload_witness5<C>(ctx, dst, src, cnt, j.expanded ? 3 : 5));
+    if (j.cs.aO_lazy) {   // a like-prover whose a_O nobody has read on the host: two witness vectors go up, the products are taken here
+        u32* const d4[4] = {dst[0], dst[1], dst[3], dst[4]};
+        const F4* const s4[4] = {src[0], src[1], src[3], src[4]};
+        BPCHK(upload_witness5<C>(ctx, d4, s4, cnt, j.expanded ? 2 : 4));
+        if (cnt) {
+            hipLaunchKernelGGL(k_r1cs_gate_out<typename C::Fr>, dim3((u32)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, (const u32*)dst[0], (const u32*)dst[1], dst[2], (u32)cnt);
+            HIPCHK(hipGetLastError());
+            ctx->pl_gates_dev += cnt;
+        }
+    } else {
+        BPCHK(upload_witness5<C>(ctx, dst, src, cnt, j.expanded ? 3 : 5));
+    }
     if (j.expanded) BPCHK(blind_expand_launch<C>(ctx, kappa, 0, cnt, dst[3], dst[4]));
     j.tm.upload += now_s() - t0;
     return BP_OK;
@@ -651,7 +747,6 @@ template <class C> static int prove_commit_phase(ProveJob<C>& j, size_t off, siz
 
 // the constraint index to the device (36 MB at 2^20 instead of 96 MB of flattened vectors) through pinned memory like the witness (a
 // pageable H2D copy serialises across the proofs in flight); a small statement's kernels read the pinned staging memory themselves
-struct CscPtrs { const u32 *moff, *ment, *mc; };
 static int prove_csc_stage(bp_ctx* ctx, const HostCsc& csc, bool small_stmt, CscPtrs& k) {
     const size_t n = csc.n, nnz = csc.ment.size();
     BPCHK(ctx->p_moff.ensure((n + 1) * 4)); BPCHK(ctx->p_ment.ensure(std::max<size_t>(nnz, 1) * 4)); BPCHK(ctx->p_mc.ensure(std::max<size_t>(nnz, 1) * 4));
@@ -690,14 +785,30 @@ template <class C> static int prove_flatten(ProveJob<C>& j) {
         const HostCsc& csc = *j.csc;
         const size_t nc = csc.coefs.size();
         const u32 nzhi = (u32)((csc.q + 1) >> 8) + 1;
-        BPCHK(ctx->p_coefs.ensure((nc + 32) * 32)); BPCHK(ctx->p_ztab.ensure((size_t)(256 + nzhi) * 32));
+        // a like-prover that recorded nothing itself proves from the recording's index, resident on this ctx: no staging, no copy
+        const bool resident = j.cs.base && j.cs.own_empty() && j.csc == j.cs.base->csc.get() && ctx->shard_world <= 1;
+        if (!resident) BPCHK(ctx->p_coefs.ensure((nc + 32) * 32));
+        else BPCHK(ctx->pl_ztab.ensure(32 * 32));
+        BPCHK(ctx->p_ztab.ensure((size_t)(256 + nzhi) * 32));
         const bool small_stmt = n <= UPLOAD_FUSED_MAX && nc <= UPLOAD_FUSED_MAX;
         CscPtrs k;
-        BPCHK(prove_csc_stage(ctx, csc, small_stmt, k));
+        const u32* d_coefs = ctx->p_coefs.as<u32>();
+        if (resident) BPCHK(pl_csc<C>(ctx, j.cs.base, csc, k, d_coefs));
+        else BPCHK(prove_csc_stage(ctx, csc, small_stmt, k));
         F4 ztab[32];
         host::prove_pow_tables<C>(j.z, j.y, ztab, small_stmt ? j.ypw : nullptr);
-        u32* d_ztab = ctx->p_coefs.as<u32>() + nc * 8;
-        if (small_stmt) {   // coefficient table, powers of z and the y tables (needed by the t(x) kernels below) in one launch, read from the pinned slab
+        u32* d_ztab = resident ? ctx->pl_ztab.as<u32>() : ctx->p_coefs.as<u32>() + nc * 8;
+        if (small_stmt && resident) {   // the per-proof tables alone: powers of z and the y tables, one launch from the pinned slab
+            ypw_early = true;
+            BPCHK(ctx->r_ypow.ensure(64 * 32));
+            BPCHK(upload_slab_ensure(ctx, 96 * 32));
+            char* stage = (char*)ctx->h_upload;
+            memcpy(stage, ztab, 32 * 32); memcpy(stage + 32 * 32, j.ypw, 64 * 32);
+            ImportList il; memset(&il, 0, sizeof il);
+            il.nseg = 2;
+            il.dst[0] = d_ztab; il.cnt[0] = 32; il.dst[1] = ctx->r_ypow.as<u32>(); il.cnt[1] = 64;
+            hipLaunchKernelGGL(k_scalars_import_multi<FrP>, dim3(1), dim3(256), 0, st, (const u32*)stage, il);
+        } else if (small_stmt) {   // coefficient table, powers of z and the y tables (needed by the t(x) kernels below) in one launch, read from the pinned slab
             ypw_early = true;
             BPCHK(ctx->r_ypow.ensure(64 * 32));
             BPCHK(upload_slab_ensure(ctx, (nc + 96) * 32));
@@ -708,12 +819,12 @@ template <class C> static int prove_flatten(ProveJob<C>& j) {
             il.dst[0] = ctx->p_coefs.as<u32>(); il.cnt[0] = (u32)nc; il.dst[1] = d_ztab; il.cnt[1] = 32; il.dst[2] = ctx->r_ypow.as<u32>(); il.cnt[2] = 64;
             hipLaunchKernelGGL(k_scalars_import_multi<FrP>, dim3((u32)((nc + 96 + 255) / 256)), dim3(256), 0, st, (const u32*)stage, il);
         } else {
-            BPCHK(upload_scalars<C>(ctx, ctx->p_coefs.as<u32>(), csc.coefs.data(), nc));
+            if (!resident) BPCHK(upload_scalars<C>(ctx, ctx->p_coefs.as<u32>(), csc.coefs.data(), nc));
             BPCHK(upload_scalars<C>(ctx, d_ztab, ztab, 32));
         }
         hipLaunchKernelGGL(k_r1cs_ztables<C>, dim3((std::max(256u, nzhi) + 255) / 256), dim3(256), 0, st, d_ztab, nzhi, ctx->p_ztab.as<u32>());
         hipLaunchKernelGGL(k_r1cs_flatten<C>, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, k.moff, k.ment, k.mc,
-                           ctx->p_coefs.as<u32>(), ctx->p_ztab.as<u32>(), (u32)n, ctx->r_wL.as<u32>(), ctx->r_wR.as<u32>(), ctx->r_wO.as<u32>());
+                           d_coefs, ctx->p_ztab.as<u32>(), (u32)n, ctx->r_wL.as<u32>(), ctx->r_wR.as<u32>(), ctx->r_wO.as<u32>());
         HIPCHK(hipGetLastError());
         host::prove_wv<C>(csc, ztab, j.cs.v.size(), j.wV);
         j.tm.flatten += now_s() - t0;
@@ -927,6 +1038,7 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     if (!pre.rng) prove_precompute<C>(cs, rng_bytes, pre);
     host::TranscriptRng& rng = *pre.rng;
     tm.rng += pre.t_rng;
+    if (!cs.deferred.empty() || resume1) prove_need_aO<C>(ctx, cs);   // (a like-prover's randomized callbacks read and extend a_O on the host)
     const size_t n1 = j.n1 = resume1 ? cs.n1 : cs.a_L.size();
     if (ctx->gens_cap < n1) return BP_E_GENS_LENGTH;
     j.b1[0] = pre.i_b1; j.b1[1] = pre.o_b1; j.b1[2] = pre.s_b1;
@@ -964,13 +1076,25 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     WcRun<C> wc;
     if (guard && guard->on) {
         if (n == 0) {
+            prove_need_aO<C>(ctx, cs);
             host::witness_check_host<C>(cs, guard->report);
             if (guard->report.bad_gates || guard->report.bad_constraints) { g_err = "prove: the witness does not satisfy the constraint system"; return BP_E_UNSATISFIED; }
         } else {
             wc.own.resize(1);
-            if (cs.cs_terms.size() > ((size_t)1 << 16)) host_pool_ensure(ctx, 2);   // (a large statement's index is built on the pool)
-            if (!build_row_index<C>(cs, WC_PIECE, wc.own[0], [&](size_t cnt, const std::function<void(size_t)>& fn) { pool_range(ctx, 0, cnt, fn); })) { g_err = "prove: the constraints cannot be indexed for the witness check"; return BP_E_ARG; }
-            WcItem<C> it; it.cs = &cs; it.idx = &wc.own[0]; it.aL = ctx->r_aL.as<u32>(); it.aR = ctx->r_aR.as<u32>(); it.aO = ctx->r_aO.as<u32>();
+            if (cs.num_terms() > ((size_t)1 << 16)) host_pool_ensure(ctx, 2);   // (a large statement's index is built on the pool)
+            const host::RowIndexPar par = [&](size_t cnt, const std::function<void(size_t)>& fn) { pool_range(ctx, 0, cnt, fn); };
+            WcItem<C> it; it.cs = &cs;
+            // a like-prover that recorded nothing itself: the recording's index, built once and resident on this ctx
+            std::shared_ptr<const HostRowIndex> shared;
+            if (cs.base && cs.own_empty()) shared = host::shared_row_index<C>(*cs.base, cs.v.size(), WC_PIECE, par);
+            if (shared) {
+                it.idx = shared.get();
+                if (ctx->shard_world <= 1) BPCHK(pl_row<C>(ctx, cs.base, *shared, it.dev));
+            } else {
+                if (!build_row_index<C>(cs, WC_PIECE, wc.own[0], par)) { g_err = "prove: the constraints cannot be indexed for the witness check"; return BP_E_ARG; }
+                it.idx = &wc.own[0];
+            }
+            it.aL = ctx->r_aL.as<u32>(); it.aR = ctx->r_aR.as<u32>(); it.aO = ctx->r_aO.as<u32>();
             wc.items.push_back(it);
             BPCHK(wc_enqueue<C>(ctx, wc, nullptr));
             BPCHK(wc_fetch<C>(ctx, wc));
@@ -988,6 +1112,7 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     if (wc.enqueued) {
         wc_wipe_host<C>(ctx, wc);
         if (wc_flags_bad(wc.flags(ctx, 0))) {
+            prove_need_aO<C>(ctx, cs);   // (the residual of the failing row may read a_O)
             host::witness_report_from_flags<C>(cs, wc.flags(ctx, 0), guard->report);
             g_err = "prove: the witness does not satisfy the constraint system";
             return BP_E_UNSATISFIED;

@@ -853,6 +853,24 @@ class ProverCS(_ConstraintSystem):
             B, Bb = [np.ascontiguousarray(x, dtype=np.uint64).reshape(8) for x in pc_gens]
             check(lib().bp_prover_new_gens(curve, transcript.h, ptr(B), ptr(Bb), C.byref(self.h)), "bp_prover_new_gens")
 
+    def new_like(self, transcript):
+        """the next prover of this gadget without recording it again (bp_prover_new_like): freezes what this prover has recorded into
+        a recording both share, and returns a prover on `transcript` with this one's Pedersen pair, no commitments and no witness.
+        From here both accept only commits and, inside their randomized phase, recording calls."""
+        p = ProverCS.__new__(ProverCS)
+        _ConstraintSystem.__init__(p, self.curve, transcript)
+        check(lib().bp_prover_new_like(self.h, transcript.h, C.byref(p.h)), "bp_prover_new_like")
+        p._like = self   # its callbacks (ctypes thunks) serve this instance too
+        return p
+
+    def assign_multipliers(self, left, right):
+        """the witness of a like-prover: a_L = left, a_R = right, (count, 4) ark words each, count = the recording's multipliers;
+        a_O is their product and is not passed (bp_prover_assign_multipliers).  Exactly once, before proving or checking."""
+        l, r = u64arr(left, 4), u64arr(right, 4)
+        if len(l) != len(r):
+            raise ValueError("assign_multipliers: left and right differ in length")
+        check(lib().bp_prover_assign_multipliers(self.h, ptr(l), ptr(r), C.c_size_t(len(l))), "bp_prover_assign_multipliers")
+
     def commit(self, v, v_blinding, engine=None):
         """Prover::commit for one value or for arrays of values: returns (V points (count, 8), variables)"""
         v, b = u64arr(v, 4), u64arr(v_blinding, 4)
@@ -897,6 +915,9 @@ class ProverCS(_ConstraintSystem):
         rc = lib().bp_prover_prove(engine.ctx, self.h, bytes(rng_bytes), buf, C.byref(plen), None)
         if self._cb_errors:
             raise self._cb_errors[0]
+        src = getattr(self, "_like", None)
+        if src is not None and src._cb_errors:
+            raise src._cb_errors[0]
         check(rc, "bp_prover_prove")
         return buf.raw[: plen.value]
 
@@ -1063,6 +1084,15 @@ def _blinding_stats(self):
     return a.value, b.value
 
 
+def _prover_like_stats(self):
+    """like-provers on this engine since it was created (bp_ctx_prover_like_stats): (uploads of a recording's constraint index, proofs
+    that found it resident, bytes resident now, gate outputs formed by the GPU kernel, gate outputs formed on the host)"""
+    v = [C.c_uint64(0) for _ in range(5)]
+    check(lib().bp_ctx_prover_like_stats(self.ctx, *[C.byref(x) for x in v]), "bp_ctx_prover_like_stats")
+    return tuple(x.value for x in v)
+
+
+Engine.prover_like_stats = _prover_like_stats
 Engine.debug_blind_expand = _debug_blind_expand
 Engine.blinding_stats = _blinding_stats
 Engine.debug_inner_product = _debug_inner_product

@@ -664,6 +664,37 @@ int bp_prover_set_check(bp_cs* prover, int on);
 int bp_prover_checking(bp_cs* prover, int* on_out);
 int bp_ctx_last_unsatisfied(bp_ctx* ctx, size_t cap, uint64_t* instance, bp_witness_report* reports, size_t* count);
 int bp_debug_prover_poke_witness(bp_cs* prover, int vec /* 0 a_L, 1 a_R, 2 a_O, 3 v */, size_t index, const uint64_t value[4]);
+
+/* ---- Many witnesses of one recorded gadget (an addition the reference lacks; the prover's counterpart of bp_verifier_new_like) ----
+ * bp_prover_new_like: `of` must be a live prover that is not consumed, not inside prove, and on which the head of prove()
+ * (bp_prover_precompute*) has not run; BP_E_ARG otherwise — also for a verifier handle or a null pointer — and nothing is frozen.
+ * The call freezes `of`'s phase-1 constraints, its multiplier count and its randomized-constraint callbacks into ONE recording that
+ * `of` and every like-prover share.  From then on they accept only commits and, inside their randomized phase, recording calls;
+ * anything else is BP_E_ARG.  `of` keeps its witness and proves to the bytes it would have produced unfrozen.  The new handle
+ * appends the r1cs domain separator to `transcript` (Prover::new), inherits `of`'s Pedersen pair and curve, and starts with no
+ * commitments, no witness, the default blinding mode and the guard off.  bp_cs_metrics reports the shared counts.
+ *
+ * bp_prover_assign_multipliers: the witness of a like-prover, a_L = left, a_R = right, count x 4 ark Montgomery words each.  count
+ * must be the recording's multiplier count; words at or above r, a second call, a handle that is no like-prover: BP_E_ARG, nothing
+ * changed.  a_O is NOT passed: it is the product, taken by a kernel on the GPU when the witness goes up (a single-phase like-prover
+ * on bp_prover_prove) and on the host, once, wherever the host reads it (randomized callbacks, the host witness check, the staging
+ * of bp_prover_prove_batch's front groups, bp_prover_check's own upload, bp_debug_prover_poke_witness on a_O).  Proving,
+ * precomputing or checking a like-prover without an assignment, or with fewer commitments than the shared constraints name, is
+ * BP_E_ARG before anything is consumed (bp_prover_prove_batch: a failed up-front check, no prover consumed).
+ *
+ * A like-prover proves to the bytes of a prover that recorded the gadget itself with the same witness, commitments, transcript
+ * state, rng bytes and blinding mode, on every route, and leaves its transcript in the same state.  The constraint index of a
+ * single-phase recording is built once per recording and kept on the device per ctx (at most 8 recordings, least recently used
+ * first out; an entry whose recording was freed is dropped at the next lookup): only the first proof of a recording on a ctx
+ * uploads it.  Two-phase like-provers share the recording; their full index depends on the instance's challenges and is built per
+ * proof.  On a sharded ctx nothing is kept resident.
+ *
+ * bp_ctx_prover_like_stats, since ctx creation: uploads of a recording's index / proofs that found it resident / bytes resident
+ * now / multipliers whose product the GPU kernel took / multipliers whose product the host took.  Any pointer may be NULL. */
+int bp_prover_new_like(bp_cs* of, void* transcript, bp_cs** out);
+int bp_prover_assign_multipliers(bp_cs* prover, const uint64_t* left, const uint64_t* right, size_t count);
+int bp_ctx_prover_like_stats(bp_ctx* ctx, uint64_t* index_uploads, uint64_t* index_hits, uint64_t* resident_bytes, uint64_t* gates_on_device, uint64_t* gates_on_host);
+
 /* `verifier.verify(&proof, &pc_gens, &bp_gens)` (verifier.rs:549-557): consumes the verifier */
 int bp_verifier_verify(bp_ctx* ctx, bp_cs* verifier, const uint8_t* proof, size_t proof_len);
 /* `batch_verify(prng, instances, &pc_gens, &bp_gens)` (verifier.rs:604-691): instance k = (verifiers[k], the k-th of the
