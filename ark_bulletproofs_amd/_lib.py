@@ -40,6 +40,8 @@ EXPORTS = [
     "bp_witness_check_piece", "bp_prover_check", "bp_prover_check_batch", "bp_prover_set_check", "bp_prover_checking", "bp_ctx_last_unsatisfied", "bp_debug_prover_poke_witness",
     # many witnesses of one recorded gadget
     "bp_prover_new_like", "bp_prover_assign_multipliers", "bp_ctx_prover_like_stats",
+    # a like-prover's witness from device memory
+    "bp_prover_assign_multipliers_dev", "bp_witness_range_bits_dev", "bp_ctx_witness_dev_stats",
 ]
 
 

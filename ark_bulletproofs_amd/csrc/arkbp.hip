@@ -31,6 +31,7 @@
 #include "small_batch.cuh"
 #include "small_batch_front.cuh"
 #include "witness_check.cuh"
+#include "witness_dev.cuh"
 #include "vfy_each.cuh"
 #include "msm_batch.cuh"
 #include "vfe.hpp"
@@ -391,6 +392,11 @@ struct bp_ctx {
     std::vector<std::unique_ptr<PlResident>> pl_cache;   // at most PL_CACHE_MAX, the least recently used goes first
     uint64_t pl_clock = 0;
     uint64_t pl_uploads = 0, pl_hits = 0, pl_gates_dev = 0, pl_gates_host = 0;
+    // witnesses assigned from device memory (bp_prover_assign_multipliers_dev): the flag words of k_wit_take, their pinned landing place, and the counters of bp_ctx_witness_dev_stats
+    DevBuf wd_res;
+    void* h_wd = nullptr;
+    size_t h_wd_cap = 0;
+    uint64_t wd_assigns = 0, wd_gates_dev = 0, wd_gates_down = 0;
     DevBuf pl_ztab;                  // the z^(2^j) of the proof in flight, when the coefficient table it would share a buffer with is resident
     // bp_verifier_verify_batch (verify_each.inc): its device arena and counters
     size_t tune_verify_each = 0;     // BP_TUNE_VERIFY_EACH: most instances per group (0 = what VE_ARENA_BUDGET holds, at most VE_GROUP_MAX)
@@ -2811,6 +2817,19 @@ static int cs_like_ready(const char* who, const bp_cs* s, size_t instance) {
     g_err = std::string(who) + ": instance " + std::to_string(instance) + ": " + why;
     return BP_E_ARG;
 }
+// a prover whose witness lies in device memory (bp_prover_assign_multipliers_dev) proves, checks and joins a batch only on a ctx of
+// that device: asked before anything is consumed
+static int cs_dev_witness_check(const char* who, const bp_ctx* c, const bp_cs* s, size_t instance) {
+    const host::DevWitness& w = s->curve == 0 ? s->cs0->dev : s->cs1->dev;
+    if (!w.held() || (c && !c->host_only && c->device == w.device)) return BP_OK;
+    g_err = std::string(who) + ": instance " + std::to_string(instance) + ": its witness lies in the memory of device " + std::to_string(w.device) + ", which is not this ctx's";
+    return BP_E_ARG;
+}
+// ... and to the host with it, where a route reads it there (a host-assigned prover is left alone)
+static int cs_dev_witness_to_host(bp_ctx* c, bp_cs* s) {
+    if (!(s->curve == 0 ? s->cs0->dev : s->cs1->dev).held()) return BP_OK;
+    return s->curve == 0 ? prove_need_aO<Secq>(c, *s->cs0) : prove_need_aO<Zorro>(c, *s->cs1);
+}
 template <class C> static int cs_prove(bp_ctx* c, bp_cs* s, uint8_t* proof_out, size_t* proof_len, double* timing) {
     host::ProofData pf;
     StageTimes tm;
@@ -2819,6 +2838,7 @@ template <class C> static int cs_prove(bp_ctx* c, bp_cs* s, uint8_t* proof_out, 
     WcGuard guard; guard.on = s->check;
     c->unsat.clear();
     int rc = r1cs_prove<C>(c, *s->cs<C>(), s->rng32, pf, tm, pre, csc, nullptr, nullptr, s->check ? &guard : nullptr);
+    s->cs<C>()->drop_dev_witness(c);   // (the prover is consumed: a witness still in device memory is wiped and freed)
     if (rc == BP_E_UNSATISFIED) c->unsat.emplace_back((uint64_t)0, guard.report);
     if (rc) return rc;
     std::vector<host::u8> bytes = host::proof_to_bytes<C>(pf);
@@ -2829,7 +2849,7 @@ template <class C> static int cs_prove(bp_ctx* c, bp_cs* s, uint8_t* proof_out, 
 }
 // `count` live provers of one curve: the host twin without a device, else one index upload, one launch sequence and one wait for all
 template <class C> static int cs_check_batch(bp_ctx* c, size_t count, bp_cs* const* hs, bp_witness_report* out) {
-    for (size_t k = 0; k < count; k++) prove_need_aO<C>(c, *hs[k]->cs<C>());   // (the host twin and this call's own upload read a_O on the host)
+    for (size_t k = 0; k < count; k++) BPCHK(prove_need_aO<C>(c, *hs[k]->cs<C>()));   // (the host twin and this call's own upload read the witness and a_O on the host)
     if (!c || c->host_only) {
         for (size_t k = 0; k < count; k++) host::witness_check_host<C>(*hs[k]->cs<C>(), out[k]);
         return BP_OK;
@@ -3727,6 +3747,8 @@ void bp_ctx_destroy(bp_ctx* c) {
     c->pf_aux.release();
     c->wc_dev.release();
     if (c->h_wc) (void)hipHostFree(c->h_wc);
+    c->wd_res.release();
+    if (c->h_wd) (void)hipHostFree(c->h_wd);
     if (c->h_pf) (void)hipHostFree(c->h_pf);
     if (c->h_pb) (void)hipHostFree(c->h_pb);
     if (c->h_dt) (void)hipHostFree(c->h_dt);
@@ -4348,6 +4370,34 @@ int bp_ctx_prover_like_stats(bp_ctx* c, uint64_t* index_uploads, uint64_t* index
     if (gates_on_host) *gates_on_host = c->pl_gates_host;
     return BP_OK;
 }
+int bp_prover_assign_multipliers_dev(bp_cs* h, bp_ctx* c, const void* d_left, const void* d_right, size_t count) {
+    // the handle's rules first, those of bp_prover_assign_multipliers: the ctx is looked at only for a handle that could take a witness
+    if (!h || !h->proving || h->consumed || h->running) { g_err = "assign_multipliers_dev: needs a live like-prover"; return BP_E_ARG; }
+    if (h->pre0.rng || h->pre1.rng) { g_err = "assign_multipliers_dev: the head of prove() has run on this prover"; return BP_E_ARG; }
+    auto fits = [&](auto* cs) { return cs->like && !cs->assigned && !cs->phase2 && cs->base && count == cs->base->num_vars; };
+    if (!(h->curve == 0 ? fits(h->cs0.get()) : fits(h->cs1.get()))) { g_err = "assign_multipliers_dev: needs a like-prover (bp_prover_new_like) without a witness, and as many values as the recording has multipliers"; return BP_E_ARG; }
+    if (!c || (count && (!d_left || !d_right))) { g_err = "assign_multipliers_dev: needs a ctx and both vectors"; return BP_E_ARG; }
+    if (c->host_only) { g_err = "assign_multipliers_dev: a host-only ctx has no device memory"; return BP_E_NO_DEVICE; }
+    if (c->curve != h->curve) { g_err = "assign_multipliers_dev: the ctx is of the other curve"; return BP_E_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    return h->curve == 0 ? wd_assign<Secq>(c, *h->cs0, d_left, d_right, count) : wd_assign<Zorro>(c, *h->cs1, d_left, d_right, count);
+}
+int bp_witness_range_bits_dev(bp_ctx* c, const void* d_values, size_t count, unsigned nbits, void* d_left, void* d_right) {
+    if (!c || nbits < 1 || nbits > 64) { g_err = "witness_range_bits_dev: needs a ctx and 1 to 64 bits per value"; return BP_E_ARG; }
+    if (count >= ((size_t)1 << 31) || count * nbits >= ((size_t)1 << 31)) { g_err = "witness_range_bits_dev: count * nbits reaches 2^31"; return BP_E_ARG; }
+    if (c->host_only) { g_err = "witness_range_bits_dev: a host-only ctx has no device to build on"; return BP_E_NO_DEVICE; }
+    if (count && (!d_values || !d_left || !d_right)) { g_err = "witness_range_bits_dev: needs the values and both outputs"; return BP_E_ARG; }
+    if (!count) return BP_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return c->curve == 0 ? wd_range_bits<Secq>(c, d_values, count * nbits, nbits, d_left, d_right) : wd_range_bits<Zorro>(c, d_values, count * nbits, nbits, d_left, d_right);
+}
+int bp_ctx_witness_dev_stats(bp_ctx* c, uint64_t* assigns, uint64_t* gates_from_device, uint64_t* gates_downloaded) {
+    if (!c) return BP_E_ARG;
+    if (assigns) *assigns = c->wd_assigns;
+    if (gates_from_device) *gates_from_device = c->wd_gates_dev;
+    if (gates_downloaded) *gates_downloaded = c->wd_gates_down;
+    return BP_OK;
+}
 void bp_cs_free(bp_cs* h) { delete h; }
 void* bp_cs_transcript(bp_cs* h) { return h ? h->tr : nullptr; }
 int bp_cs_metrics(bp_cs* h, size_t* multipliers, size_t* constraints, size_t* commitments) {
@@ -4530,6 +4580,7 @@ int bp_prover_prove(bp_ctx* c, bp_cs* h, const uint8_t rng_bytes[32], uint8_t* p
     }
     if (!h->have_rng) { g_err = "prove: the external rng bytes are missing"; return BP_E_ARG; }
     BPCHK(cs_like_ready("prove", h, 0));
+    BPCHK(cs_dev_witness_check("prove", c, h, 0));
     BPCHK(cs_pair_check("prove", c, h, 0));   // (before the prover is consumed)
     HIPCHK(hipSetDevice(c->device));
     if (!c->gens_cap) { g_err = "prove: generators not installed (bp_gens_derive / bp_gens_upload / bp_gens_share)"; return BP_E_GENS_LENGTH; }
@@ -4544,6 +4595,7 @@ static bool wc_prover_ok(const bp_cs* h) { return h && h->proving && !h->consume
 int bp_prover_check(bp_ctx* c, bp_cs* h, bp_witness_report* out) {
     if (!wc_prover_ok(h) || !out || (c && c->curve != h->curve)) { g_err = "prover_check: needs a live prover handle of the ctx's curve and a report"; return BP_E_ARG; }
     BPCHK(cs_like_ready("prover_check", h, 0));
+    BPCHK(cs_dev_witness_check("prover_check", c, h, 0));
     bp_witness_report r;
     const int rc = h->curve == 0 ? cs_check_batch<Secq>(c, 1, &h, &r) : cs_check_batch<Zorro>(c, 1, &h, &r);
     if (!rc) *out = r;
@@ -4556,6 +4608,7 @@ int bp_prover_check_batch(bp_ctx* c, size_t count, bp_cs* const* provers, bp_wit
     for (size_t k = 0; k < count; k++)
         if (!wc_prover_ok(provers[k]) || provers[k]->curve != c->curve) { g_err = "prover_check_batch: every instance needs a live prover of the ctx's curve"; return BP_E_ARG; }
     for (size_t k = 0; k < count; k++) BPCHK(cs_like_ready("prover_check_batch", provers[k], k));
+    for (size_t k = 0; k < count; k++) BPCHK(cs_dev_witness_check("prover_check_batch", c, provers[k], k));
     {
         std::vector<const void*> hv(provers, provers + count);
         std::sort(hv.begin(), hv.end());
@@ -4587,7 +4640,8 @@ int bp_debug_prover_poke_witness(bp_cs* h, int vec, size_t index, const uint64_t
     F4 x; memcpy(x.v, value, 32);
     if (h->curve == 0 ? host::Fld<SecqFr>::geq_p(x.v) : host::Fld<ZorroFr>::geq_p(x.v)) { g_err = "poke_witness: the value is not a reduced scalar"; return BP_E_ARG; }
     auto poke = [&](auto* cs) -> int {
-        if (vec == 2) prove_need_aO(nullptr, *cs);   // (a like-prover's a_O exists on the host from here: the poked value is the truth)
+        if (vec != 3 && cs->dev.held()) BPCHK(prove_need_aO(nullptr, *cs));   // (a witness in device memory comes to the host to be poked)
+        if (vec == 2) BPCHK(prove_need_aO(nullptr, *cs));   // (a like-prover's a_O exists on the host from here: the poked value is the truth)
         std::vector<F4>& t = vec == 0 ? cs->a_L : vec == 1 ? cs->a_R : vec == 2 ? cs->a_O : cs->v;
         if (index >= t.size()) return BP_E_ARG;
         t[index] = x;

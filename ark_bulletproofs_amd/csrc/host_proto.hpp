@@ -615,6 +615,19 @@ struct FrozenRecording {
     mutable size_t row_m = 0;
 };
 
+// A like-prover's witness in device memory (bp_prover_assign_multipliers_dev): a_L and a_R as count x 4 ark Montgomery words each, in
+// two plain allocations on `device` that the HANDLE owns (no ctx arena: they outlive the ctx that assigned them).  The two operations
+// that need the device's runtime are installed by whoever made the copy, so that this header stays host-only: fetch brings the words
+// to the host (0: done), drop wipes and frees.  ctx: the ctx whose stream does the work (null: the device's default stream).
+struct DevWitness {
+    void *aL = nullptr, *aR = nullptr;
+    size_t count = 0;
+    int device = -1;
+    int (*fetch)(const DevWitness& w, void* ctx, F4* left, F4* right) = nullptr;
+    void (*drop)(DevWitness& w, void* ctx) = nullptr;
+    bool held() const { return drop != nullptr; }
+};
+
 // The recorder shared by prover and verifier: the verifier records the same constraints without
 // assignments.  Constraints are stored flat (CSR-like) because circuits reach 2^22 multipliers.
 template <class C> struct ConstraintSystem {
@@ -637,6 +650,12 @@ template <class C> struct ConstraintSystem {
     // a like-prover (bp_prover_new_like): its witness arrives as two flat vectors (assigned) and a_O = a_L * a_R is formed only when
     // somebody reads it on the host (aO_lazy: a_O is still empty; the routes that never need it take the product on the device)
     bool like = false, assigned = false, aO_lazy = false;
+    // ... or stays in device memory (dev.held(): a_L, a_R and a_O are all empty on the host) until witness_to_host brings it over
+    DevWitness dev;
+    ConstraintSystem() = default;
+    ConstraintSystem(const ConstraintSystem&) = delete;
+    ConstraintSystem& operator=(const ConstraintSystem&) = delete;
+    ~ConstraintSystem() { drop_dev_witness(nullptr); }
     // verifier commitments
     std::vector<A4> V;
 
@@ -794,6 +813,32 @@ template <class C> struct ConstraintSystem {
         reserve_huge(a_L, count); reserve_huge(a_R, count);
         a_L.assign(left, left + count); a_R.assign(right, right + count);
         assigned = true; aO_lazy = true;
+    }
+    // multipliers of the assignment, wherever it lies
+    size_t mults() const { return dev.held() ? dev.count : a_L.size(); }
+    // the witness stays where `w` says (exactly once, in place of assign_multipliers; the words are below r: the caller has checked)
+    void assign_multipliers_dev(const DevWitness& w) { dev = w; assigned = true; }
+    void drop_dev_witness(void* ctx) {
+        if (!dev.held()) return;
+        dev.drop(dev, ctx);
+        dev = DevWitness();
+    }
+    // A device witness to the host: from here on this is a host-assigned like-prover (a_O still to be formed), and the device copy is
+    // wiped and freed.  A copy that fails leaves the handle as it was.
+    int witness_to_host(void* ctx) {
+        if (!dev.held()) return BP_OK;
+        const size_t count = dev.count;
+        reserve_huge(a_L, count); reserve_huge(a_R, count);
+        a_L.resize(count); a_R.resize(count);
+        const int rc = count ? dev.fetch(dev, ctx, a_L.data(), a_R.data()) : BP_OK;
+        if (rc) {
+            if (count) { memset((void*)a_L.data(), 0, count * sizeof(F4)); memset((void*)a_R.data(), 0, count * sizeof(F4)); }
+            a_L.clear(); a_R.clear();
+            return rc;
+        }
+        drop_dev_witness(ctx);
+        aO_lazy = true;
+        return BP_OK;
     }
     // a_O on the host, on first need; par(count, fn) may spread the products over threads
     void materialise_aO(const std::function<void(size_t, const std::function<void(size_t)>&)>& par = nullptr) {

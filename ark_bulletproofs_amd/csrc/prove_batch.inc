@@ -711,7 +711,7 @@ static int cs_prove_batch(bp_ctx* c, size_t count, bp_cs* const* hs, uint8_t* pr
             bp_cs* sk = hs[order[oi]];
             m.k = order[oi]; m.s = sk; m.cs = sk->cs<C>(); m.pre = C::ID == 0 ? (ProvePre<C>*)&sk->pre0 : (ProvePre<C>*)&sk->pre1; m.n1 = n1;
             sk->consumed = true; sk->running = true;
-            prove_need_aO<C>(c, *m.cs);   // (the group's staging copies a_O from the host)
+            (void)prove_need_aO<C>(c, *m.cs);   // (the group's staging copies a_O from the host; a device witness came over at the entry)
             mem.push_back(std::move(m));
             oi++;
         }
@@ -784,6 +784,7 @@ int bp_prover_prove_batch(bp_ctx* c, size_t count, bp_cs* const* provers, const 
         } else if (!h->have_rng) { g_err = "prove_batch: the external rng bytes are missing"; return BP_E_ARG; }
         BPCHK(cs_pair_check("prove_batch", c, h, k));
         BPCHK(cs_like_ready("prove_batch", h, k));
+        BPCHK(cs_dev_witness_check("prove_batch", c, h, k));
     }
     {
         std::vector<const void*> hv(provers, provers + count), tv(count);
@@ -797,6 +798,8 @@ int bp_prover_prove_batch(bp_ctx* c, size_t count, bp_cs* const* provers, const 
     if (c->host_only) { g_err = "prove_batch: a host-only ctx has no device to prove on"; return BP_E_NO_DEVICE; }
     HIPCHK(hipSetDevice(c->device));
     for (size_t k = 0; k < count; k++) if (rng_bytes) { memcpy(provers[k]->rng32, rng_bytes + 32 * k, 32); provers[k]->have_rng = true; }
+    // (a witness in device memory comes to the host first: the front groups stage from host vectors, and no route of a batch keeps it resident)
+    for (size_t k = 0; k < count; k++) BPCHK(cs_dev_witness_to_host(c, provers[k]));
     return c->curve == 0 ? cs_prove_batch<Secq>(c, count, provers, proofs_out, proof_stride, proof_lens, status, timing)
                          : cs_prove_batch<Zorro>(c, count, provers, proofs_out, proof_stride, proof_lens, status, timing);
 }

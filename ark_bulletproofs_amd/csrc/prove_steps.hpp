@@ -153,8 +153,8 @@ template <class C> static bool build_row_index_flat(const Term* terms, const siz
 // front of the own ones, so that the result is what the same constraints recorded flat give.  (A like-prover that recorded nothing
 // itself uses the recording's own index instead: shared_row_index, no copy.)
 template <class C> static bool build_row_index(const ConstraintSystem<C>& cs, size_t piece, HostRowIndex& h, const RowIndexPar& par = nullptr) {
-    const size_t n = cs.a_L.size();
-    if (cs.a_R.size() != n || (!cs.aO_lazy && cs.a_O.size() != n)) return false;
+    const size_t n = cs.mults();
+    if (!cs.dev.held() && (cs.a_R.size() != n || (!cs.aO_lazy && cs.a_O.size() != n))) return false;
     if (!cs.base) return build_row_index_flat<C>(cs.cs_terms.data(), cs.cs_off.data(), cs.cs_off.size() - 1, n, cs.v.size(), piece, h, par);
     const FrozenRecording& f = *cs.base;
     std::vector<Term> terms;

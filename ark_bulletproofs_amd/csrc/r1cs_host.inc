@@ -325,7 +325,7 @@ template <class C> static void prove_precompute(host::ConstraintSystem<C>& cs, c
     pre.rng.reset(new host::TranscriptRng(tr));
     for (auto& vb : cs.v_blinding) { host::u8 b[32]; S::to_bytes(b, vb); pre.rng->rekey("v_blinding", b, 32); }
     pre.rng->finalize_bytes(rng_bytes);
-    const size_t n1 = cs.a_L.size();
+    const size_t n1 = cs.mults();
     pre.i_b1 = host::rand_fe<FrP>(*pre.rng); pre.o_b1 = host::rand_fe<FrP>(*pre.rng); pre.s_b1 = host::rand_fe<FrP>(*pre.rng);
     if (pre.mode == BP_BLINDING_EXPANDED) {   // one draw instead of 2 n1: the vectors come from it on the device
         if (n1) pre.kappa1 = host::rand_fe<FrP>(*pre.rng);
@@ -347,7 +347,7 @@ template <class C> static void prove_precompute_batch(host::ConstraintSystem<C>*
     typedef host::Fld<FrP> S;
     bool ok = count == 8 && host::cpu_has_avx512();
     for (size_t j = 0; ok && j < count; j++)
-        ok = !pres[j]->rng && pres[j]->mode == BP_BLINDING_TRANSCRIPT /* (an expanded head is four draws: the scalar path) */ && css[j]->a_L.size() == css[0]->a_L.size() && css[j]->v.size() == css[0]->v.size() && css[0]->a_L.size() >= 64;
+        ok = !pres[j]->rng && pres[j]->mode == BP_BLINDING_TRANSCRIPT /* (an expanded head is four draws: the scalar path) */ && css[j]->mults() == css[0]->mults() && css[j]->v.size() == css[0]->v.size() && css[0]->mults() >= 64;
 #if !defined(__x86_64__)
     ok = false;
 #endif
@@ -357,7 +357,7 @@ template <class C> static void prove_precompute_batch(host::ConstraintSystem<C>*
     }
 #if defined(__x86_64__)
     const double t0 = now_s();
-    const size_t n1 = css[0]->a_L.size();
+    const size_t n1 = css[0]->mults();
     host::TranscriptRng* rngs[8];
     for (size_t j = 0; j < 8; j++) {
         host::Transcript& tr = *css[j]->tr;
@@ -418,12 +418,103 @@ struct IpaDefer {
 // a_O of a like-prover on the host: THE place where it is formed there (randomized-phase callbacks read it through eval, the host twin
 // of the witness check, the staging of front groups, bp_prover_check's own upload, a poke of a_O) — on the ctx's pool when there is one.
 // Once formed the host vector is the truth and goes up like a recorded prover's.
-template <class C> static void prove_need_aO(bp_ctx* ctx, host::ConstraintSystem<C>& cs) {
-    if (!cs.aO_lazy) return;
+// A witness assigned from device memory (bp_prover_assign_multipliers_dev) comes to the host HERE and nowhere else, in front of the
+// products: one D2H copy of the ark words per vector, no kernel; the handle's device copy is wiped and freed, and from then on the
+// handle is a host-assigned like-prover.  Its other readers on the host (a sharded ctx, bp_prover_check, a poke, the front groups of
+// prove_batch) call this too.
+template <class C> static int prove_need_aO(bp_ctx* ctx, host::ConstraintSystem<C>& cs) {
+    if (cs.dev.held()) {
+        const size_t cnt = cs.dev.count;
+        BPCHK(cs.witness_to_host(ctx));
+        if (ctx) ctx->wd_gates_down += cnt;
+    }
+    if (!cs.aO_lazy) return BP_OK;
     const size_t n = cs.a_L.size();
     if (ctx && n > ((size_t)1 << 14)) host_pool_ensure(ctx, 2);
     cs.materialise_aO([&](size_t cnt, const std::function<void(size_t)>& fn) { pool_range(ctx, 0, cnt, fn); });
     if (ctx) ctx->pl_gates_host += n;
+    return BP_OK;
+}
+
+// ---- a like-prover's witness from device memory (include/arkbp.h bp_prover_assign_multipliers_dev; the kernels: witness_dev.cuh) -------
+// the stream that works on a handle's device copy: the given ctx's when it lives on the copy's device, else that device's default one
+static hipStream_t wd_stream(const host::DevWitness& w, void* ctxv) {
+    bp_ctx* c = (bp_ctx*)ctxv;
+    return c && !c->host_only && c->device == w.device ? c->stream : (hipStream_t) nullptr;
+}
+static hipError_t wd_wait(const host::DevWitness& w, void* ctxv) {
+    hipStream_t st = wd_stream(w, ctxv);
+    return st ? ctx_stream_wait((bp_ctx*)ctxv) : hipStreamSynchronize(st);
+}
+// host::DevWitness::fetch: both vectors to the host, ark words as they lie there
+static int wd_fetch(const host::DevWitness& w, void* ctxv, F4* left, F4* right) {
+    if (!w.count) return BP_OK;
+    HIPCHK(hipSetDevice(w.device));
+    hipStream_t st = wd_stream(w, ctxv);
+    HIPCHK(hipMemcpyAsync(left, w.aL, w.count * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(right, w.aR, w.count * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(wd_wait(w, ctxv));
+    return BP_OK;
+}
+// host::DevWitness::drop: zeroes behind whatever the stream still reads, a wait, then the memory goes back (as prove_wipe treats r_aL
+// and the others).  Runs from destructors too: errors have nowhere to go, and the caller's current device is put back.
+static void wd_drop(host::DevWitness& w, void* ctxv) {
+    if (w.aL || w.aR) {
+        int prev = -1;
+        (void)hipGetDevice(&prev);
+        if (hipSetDevice(w.device) == hipSuccess) {
+            hipStream_t st = wd_stream(w, ctxv);
+            if (w.aL) (void)hipMemsetAsync(w.aL, 0, std::max<size_t>(w.count, 1) * 32, st);
+            if (w.aR) (void)hipMemsetAsync(w.aR, 0, std::max<size_t>(w.count, 1) * 32, st);
+            (void)wd_wait(w, ctxv);
+            if (w.aL) (void)hipFree(w.aL);
+            if (w.aR) (void)hipFree(w.aR);
+        }
+        if (prev >= 0 && prev != w.device) (void)hipSetDevice(prev);
+    }
+    w.aL = w.aR = nullptr;
+}
+// bp_prover_assign_multipliers_dev behind its argument checks: the handle's copy and the range check in ONE kernel, one copy back,
+// one wait.  Nothing of the handle changes unless every word is below r.
+template <class C> static int wd_assign(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const void* d_left, const void* d_right, size_t count) {
+    host::DevWitness w;
+    w.count = count; w.device = ctx->device; w.fetch = wd_fetch; w.drop = wd_drop;
+    if (count) {
+        if (count >= ((size_t)1 << 31)) { g_err = "assign_multipliers_dev: 2^31 multipliers or more"; return BP_E_ARG; }
+        BPCHK(ctx->wd_res.ensure(16));
+        BPCHK(pinned_ensure(ctx->h_wd, ctx->h_wd_cap, 16, 48));
+        hipError_t e = hipMalloc(&w.aL, count * 32);
+        if (e == hipSuccess) e = hipMalloc(&w.aR, count * 32);
+        if (e != hipSuccess) { if (w.aL) (void)hipFree(w.aL); g_err = std::string("assign_multipliers_dev: hipMalloc: ") + hipGetErrorString(e); return BP_E_HIP; }
+        u32* res = ctx->wd_res.as<u32>();
+        u32* back = (u32*)ctx->h_wd;
+        int rc = BP_OK;
+        auto step = [&](hipError_t he, const char* what) { if (!rc && he != hipSuccess) { g_err = std::string("assign_multipliers_dev: ") + what + ": " + hipGetErrorString(he); rc = BP_E_HIP; } };
+        step(hipMemsetAsync(res, 0, 8, ctx->stream), "hipMemsetAsync");
+        step(hipMemsetAsync(res + 2, 0xff, 8, ctx->stream), "hipMemsetAsync");
+        if (!rc) {
+            hipLaunchKernelGGL(k_wit_take<typename C::Fr>, dim3((u32)((count + 255) / 256)), dim3(256), 0, ctx->stream, (const u32*)d_left, (const u32*)d_right, (u32*)w.aL, (u32*)w.aR, (u32)count, res);
+            step(hipGetLastError(), "k_wit_take");
+        }
+        if (!rc) step(hipMemcpyAsync(back, res, 16, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
+        if (!rc) step(ctx_stream_wait(ctx), "wait");
+        if (!rc && (back[0] || back[1])) {
+            const bool left_first = back[0] && (!back[1] || back[2] <= back[3]);
+            g_err = std::string("assign_multipliers_dev: ") + (left_first ? "left" : "right") + "[" + std::to_string(left_first ? back[2] : back[3]) + "] is not a reduced scalar";
+            rc = BP_E_ARG;
+        }
+        if (rc) { wd_drop(w, ctx); return rc; }
+    }
+    cs.assign_multipliers_dev(w);
+    ctx->wd_assigns++;
+    return BP_OK;
+}
+// the builder of the range gadget's witness (bp_witness_range_bits_dev): one launch on the ctx's stream, and a wait
+template <class C> static int wd_range_bits(bp_ctx* ctx, const void* d_values, size_t total, unsigned nbits, void* d_left, void* d_right) {
+    hipLaunchKernelGGL(k_wit_range_bits<typename C::Fr>, dim3((u32)((total + 255) / 256)), dim3(256), 0, ctx->stream, (const u64*)d_values, (u32)total, (u32)nbits, (u32*)d_left, (u32*)d_right);
+    HIPCHK(hipGetLastError());
+    HIPCHK(ctx_stream_wait(ctx));
+    return BP_OK;
 }
 // the ctx's entry of a recording: expired entries go first, then the least recently used one when PL_CACHE_MAX are kept
 static PlResident* pl_entry(bp_ctx* ctx, const std::shared_ptr<const host::FrozenRecording>& rec) {
@@ -703,7 +794,17 @@ template <class C> static int prove_upload_phase(ProveJob<C>& j, size_t off, siz
     u32* const dst[5] = {ctx->r_aL.as<u32>() + off * 8, ctx->r_aR.as<u32>() + off * 8, ctx->r_aO.as<u32>() + off * 8, ctx->r_sL.as<u32>() + off * 8, ctx->r_sR.as<u32>() + off * 8};
     const F4* const src[5] = {j.cs.a_L.data() + off, j.cs.a_R.data() + off, j.cs.a_O.data() + off, j.expanded ? nullptr : j.pre.s_L.data() + off, j.expanded ? nullptr : j.pre.s_R.data() + off};
     j.secrets_up = true;
-    if (j.cs.aO_lazy) {   // a like-prover whose a_O nobody has read on the host: two witness vectors go up, the products are taken here
+    if (j.cs.dev.held()) {   // a witness assigned from device memory: no staging and no copy; ONE kernel imports a_L, a_R from the handle's ark words and takes the products
+        const char* wl = (const char*)j.cs.dev.aL + off * 32;
+        const char* wr = (const char*)j.cs.dev.aR + off * 32;
+        if (off + cnt > j.cs.dev.count) { g_err = "prove: the device witness is shorter than the phase"; return BP_E_ARG; }
+        if (cnt) {
+            hipLaunchKernelGGL(k_r1cs_import_gate<typename C::Fr>, dim3((u32)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, (const u32*)wl, (const u32*)wr, dst[0], dst[1], dst[2], (u32)cnt);
+            HIPCHK(hipGetLastError());
+            ctx->wd_gates_dev += cnt; ctx->pl_gates_dev += cnt;
+        }
+        if (!j.expanded) BPCHK(upload_witness5<C>(ctx, dst + 3, src + 3, cnt, 2));
+    } else if (j.cs.aO_lazy) {   // a like-prover whose a_O nobody has read on the host: two witness vectors go up, the products are taken here
         u32* const d4[4] = {dst[0], dst[1], dst[3], dst[4]};
         const F4* const s4[4] = {src[0], src[1], src[3], src[4]};
         BPCHK(upload_witness5<C>(ctx, d4, s4, cnt, j.expanded ? 2 : 4));
@@ -1038,8 +1139,10 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     if (!pre.rng) prove_precompute<C>(cs, rng_bytes, pre);
     host::TranscriptRng& rng = *pre.rng;
     tm.rng += pre.t_rng;
-    if (!cs.deferred.empty() || resume1) prove_need_aO<C>(ctx, cs);   // (a like-prover's randomized callbacks read and extend a_O on the host)
-    const size_t n1 = j.n1 = resume1 ? cs.n1 : cs.a_L.size();
+    // (a like-prover's randomized callbacks read and extend a_O on the host; a witness in device memory stays there only for a
+    // single-phase proof on a ctx that is not sharded)
+    if (!cs.deferred.empty() || resume1 || (cs.dev.held() && ctx->shard_world > 1)) BPCHK(prove_need_aO<C>(ctx, cs));
+    const size_t n1 = j.n1 = resume1 ? cs.n1 : cs.mults();
     if (ctx->gens_cap < n1) return BP_E_GENS_LENGTH;
     j.b1[0] = pre.i_b1; j.b1[1] = pre.o_b1; j.b1[2] = pre.s_b1;
 
@@ -1056,7 +1159,7 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     }
     j.trace.mark("randomized phase");
 
-    const size_t n = j.n = cs.a_L.size(), N = j.N = host::next_pow2(n);
+    const size_t n = j.n = cs.mults(), N = j.N = host::next_pow2(n);
     if (ctx->gens_cap < N) return BP_E_GENS_LENGTH;
     const bool has2 = n > n1;
     double t0 = now_s();
@@ -1076,7 +1179,7 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     WcRun<C> wc;
     if (guard && guard->on) {
         if (n == 0) {
-            prove_need_aO<C>(ctx, cs);
+            BPCHK(prove_need_aO<C>(ctx, cs));
             host::witness_check_host<C>(cs, guard->report);
             if (guard->report.bad_gates || guard->report.bad_constraints) { g_err = "prove: the witness does not satisfy the constraint system"; return BP_E_UNSATISFIED; }
         } else {
@@ -1112,7 +1215,7 @@ static int r1cs_prove(bp_ctx* ctx, host::ConstraintSystem<C>& cs, const host::u8
     if (wc.enqueued) {
         wc_wipe_host<C>(ctx, wc);
         if (wc_flags_bad(wc.flags(ctx, 0))) {
-            prove_need_aO<C>(ctx, cs);   // (the residual of the failing row may read a_O)
+            BPCHK(prove_need_aO<C>(ctx, cs));   // (the residual of the failing row may read a_O)
             host::witness_report_from_flags<C>(cs, wc.flags(ctx, 0), guard->report);
             g_err = "prove: the witness does not satisfy the constraint system";
             return BP_E_UNSATISFIED;

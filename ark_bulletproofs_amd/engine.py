@@ -871,6 +871,13 @@ class ProverCS(_ConstraintSystem):
             raise ValueError("assign_multipliers: left and right differ in length")
         check(lib().bp_prover_assign_multipliers(self.h, ptr(l), ptr(r), C.c_size_t(len(l))), "bp_prover_assign_multipliers")
 
+    def assign_multipliers_dev(self, engine, left, right, count):
+        """the same witness from device memory (bp_prover_assign_multipliers_dev): left and right are DeviceBuffers of `engine` (or
+        None with count == 0) holding count x 4 ark words each, complete before the call.  The handle takes its own copy: the
+        buffers are unread afterwards.  Proving, checking and batches then need an engine of the same device."""
+        check(lib().bp_prover_assign_multipliers_dev(self.h, engine.ctx if engine is not None else None, left.ptr if left is not None else None,
+                                                     right.ptr if right is not None else None, C.c_size_t(count)), "bp_prover_assign_multipliers_dev")
+
     def commit(self, v, v_blinding, engine=None):
         """Prover::commit for one value or for arrays of values: returns (V points (count, 8), variables)"""
         v, b = u64arr(v, 4), u64arr(v_blinding, 4)
@@ -1092,6 +1099,34 @@ def _prover_like_stats(self):
     return tuple(x.value for x in v)
 
 
+def _witness_range_bits(self, values, nbits=64):
+    """the witness of the range gadget built on the GPU (bp_witness_range_bits_dev): uploads the 64-bit `values` (8 bytes each) and
+    returns two DeviceBuffers (left, right) of len(values) * nbits ark scalars: element j * nbits + i is 1 - bit i of value j on the
+    left and the bit on the right.  A helper: any kernel that writes ark words serves assign_multipliers_dev equally well."""
+    v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+    total = len(v) * int(nbits)
+    d_v = DeviceBuffer(self, max(v.nbytes, 8)).upload(v)
+    left, right = DeviceBuffer(self, max(total * 32, 32)), DeviceBuffer(self, max(total * 32, 32))
+    try:
+        check(lib().bp_witness_range_bits_dev(self.ctx, d_v.ptr, C.c_size_t(len(v)), C.c_uint(int(nbits)), left.ptr, right.ptr), "bp_witness_range_bits_dev")
+    except Exception:
+        left.free(); right.free()
+        raise
+    finally:
+        d_v.free()
+    return left, right
+
+
+def _witness_dev_stats(self):
+    """witnesses assigned from device memory on this engine since it was created (bp_ctx_witness_dev_stats): (assignments accepted,
+    multipliers the import kernel read from device memory, multipliers taken to the host instead)"""
+    v = [C.c_uint64(0) for _ in range(3)]
+    check(lib().bp_ctx_witness_dev_stats(self.ctx, *[C.byref(x) for x in v]), "bp_ctx_witness_dev_stats")
+    return tuple(x.value for x in v)
+
+
+Engine.witness_range_bits = _witness_range_bits
+Engine.witness_dev_stats = _witness_dev_stats
 Engine.prover_like_stats = _prover_like_stats
 Engine.debug_blind_expand = _debug_blind_expand
 Engine.blinding_stats = _blinding_stats

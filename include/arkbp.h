@@ -695,6 +695,45 @@ int bp_prover_new_like(bp_cs* of, void* transcript, bp_cs** out);
 int bp_prover_assign_multipliers(bp_cs* prover, const uint64_t* left, const uint64_t* right, size_t count);
 int bp_ctx_prover_like_stats(bp_ctx* ctx, uint64_t* index_uploads, uint64_t* index_hits, uint64_t* resident_bytes, uint64_t* gates_on_device, uint64_t* gates_on_host);
 
+/* ---- A like-prover's witness from device memory (an addition the reference lacks; the prover's counterpart of bp_msm_dev) ----
+ * bp_prover_assign_multipliers_dev: bp_prover_assign_multipliers with a_L = d_left and a_R = d_right in the memory of ctx's device
+ * (bp_dev_alloc, or a host that links the same HIP runtime): count x 4 ark Montgomery words each, the public data convention, complete
+ * before the call (the caller has synchronised its own producer).  The handle's rules are the host form's and are checked first,
+ * before ctx is looked at: a live like-prover without an assignment, on which the head of prove() has not run, count = the
+ * recording's multiplier count; anything else is BP_E_ARG and nothing changes.  Then: a null ctx, a ctx of the other curve, or a
+ * null vector with count > 0: BP_E_ARG; a host-only ctx: BP_E_NO_DEVICE; nothing changes.  count == 0 with null vectors is allowed.
+ *
+ * The call takes a copy that the HANDLE owns: a plain allocation on that device, still ark words, from no ctx arena — it survives
+ * bp_ctx_destroy of the assigning ctx.  One kernel copies both vectors and compares every word with r in the same pass; one copy
+ * back, one host wait.  A word at or above r: BP_E_ARG, bp_last_error() names the vector and the smallest failing index (of both
+ * vectors: the one with the smaller index, left on a tie), the copy is wiped and freed, and the handle is unchanged: a later valid
+ * assignment by either entry point succeeds.  After return the caller's buffers are unread and may be reused.  The copy is wiped
+ * (zeroes on the stream, then a wait) and freed when the prover is consumed, freed, or its witness is taken to the host.
+ *
+ * A prover with a device witness proves, checks and joins a batch only on a ctx of the same device: BP_E_ARG otherwise, before
+ * anything is consumed (bp_prover_prove_batch: a failed up-front check, no prover consumed).  bp_prover_prove of a single-phase
+ * like-prover on a ctx that is not sharded keeps the witness on the device: no staging and no H2D copy of a_L, a_R; one kernel
+ * imports them from the handle's copy and forms a_O = a_L * a_R in the same pass.  Every other reader takes the witness to the host
+ * once — a D2H copy of the ark words, then the products there — and from then on the handle is a host-assigned like-prover:
+ * randomized callbacks of a two-phase like-prover, the host twin of the witness check, bp_prover_check's own upload, every route of
+ * bp_prover_prove_batch (at its entry, after the up-front checks), a sharded ctx, bp_debug_prover_poke_witness, the residual of a
+ * refused proof.  Proof bytes and the final transcript state are those of the same like-prover assigned through
+ * bp_prover_assign_multipliers with the same words, on every route, with the guard on or off.
+ *
+ * bp_witness_range_bits_dev: a helper, not part of the prover's contract (any kernel that writes ark words serves equally well):
+ * the witness of the reference's range gadget (tests/r1cs_secq256k1.rs:361-445) built on the GPU.  d_values: count 64-bit
+ * integers; for value j and bit i < nbits, element j * nbits + i of d_left is 1 - bit and of d_right is the bit, as ark
+ * Montgomery words: count * nbits x 32 bytes per vector.  nbits from 1 to 64 and count * nbits below 2^31, else BP_E_ARG (checked
+ * before any device use); a host-only ctx: BP_E_NO_DEVICE.  Only the low nbits bits are decomposed: a value out of range is the
+ * gadget's sum constraint's business (with the guard on: BP_E_UNSATISFIED).  One launch on the ctx's stream; returns after a wait.
+ *
+ * bp_ctx_witness_dev_stats, since ctx creation: device assignments accepted / multipliers the import kernel read from device
+ * memory (they also count in gates_on_device of bp_ctx_prover_like_stats) / multipliers taken to the host instead.  Any pointer
+ * may be NULL. */
+int bp_prover_assign_multipliers_dev(bp_cs* prover, bp_ctx* ctx, const void* d_left, const void* d_right, size_t count);
+int bp_witness_range_bits_dev(bp_ctx* ctx, const void* d_values, size_t count, unsigned nbits, void* d_left, void* d_right);
+int bp_ctx_witness_dev_stats(bp_ctx* ctx, uint64_t* assigns, uint64_t* gates_from_device, uint64_t* gates_downloaded);
+
 /* `verifier.verify(&proof, &pc_gens, &bp_gens)` (verifier.rs:549-557): consumes the verifier */
 int bp_verifier_verify(bp_ctx* ctx, bp_cs* verifier, const uint8_t* proof, size_t proof_len);
 /* `batch_verify(prng, instances, &pc_gens, &bp_gens)` (verifier.rs:604-691): instance k = (verifiers[k], the k-th of the
