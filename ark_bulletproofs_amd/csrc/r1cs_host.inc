@@ -2373,8 +2373,21 @@ static int vfy_dev_launch(bp_ctx* ctx, VfyDevJob<C>& J, const VfyDevTotals& tot,
     ok = true;
     return BP_OK;
 }
+// The mega-check of the host replay and of the device front end alike: the two head scalars up, then ONE MSM over
+// [B, B_blinding | G[0..Nmax) | H[0..Nmax) | tails] with the scalars resident in r_g (accumulators and tails in canonical form by now)
+template <class C> static int vfy_mega_check(bp_ctx* ctx, size_t Nmax, size_t Ttot, const F4& sB, const F4& sBb, J4& r) {
+    u32* sc = ctx->r_g.as<u32>();
+    uint64_t head[8];
+    canon_words<typename C::Fr>(head, sB); canon_words<typename C::Fr>(head + 4, sBb);
+    HIPCHK(hipMemcpyAsync(sc, head, 64, hipMemcpyHostToDevice, ctx->stream));
+    BaseSegs sg; memset(&sg, 0, sizeof sg);
+    sg.nseg = 4;
+    sg.ptr[0] = ctx->d_pc.as<u32>(); sg.ptr[1] = ctx->d_G.as<u32>(); sg.ptr[2] = ctx->d_H.as<u32>(); sg.ptr[3] = ctx->r_tail.as<u32>();
+    sg.start[0] = 0; sg.start[1] = 2; sg.start[2] = (u32)(2 + Nmax); sg.start[3] = (u32)(2 + 2 * Nmax); sg.start[4] = (u32)(2 + 2 * Nmax + Ttot);
+    return msm_run<C>(ctx, sg, sc, 2 + 2 * Nmax + Ttot, 0, r);
+}
 // After the last job: the accumulators to canonical integers, ONE copy back, ONE polled wait, the head scalars summed on the host,
-// ONE MSM over [pc | G[0..Nmax) | H[0..Nmax) | every job's tails].  flagged: a kernel raised a reject bit (no MSM then; the
+// the mega-check over every job's tails.  flagged: a kernel raised a reject bit (no MSM then; the
 // per-instance flag words are in pinned memory, vfy_dev_flagged reads them).
 template <class C>
 static int vfy_dev_finish(bp_ctx* ctx, VfyDevJob<C>* const* jobs, size_t nj, const VfyDevTotals& tot, VfyDrain& drain, double* timing, J4& r, bool& flagged) {
@@ -2385,7 +2398,7 @@ static int vfy_dev_finish(bp_ctx* ctx, VfyDevJob<C>* const* jobs, size_t nj, con
     u32* sc = ctx->r_g.as<u32>();
     const u32* d_status = ctx->vfe_small.as<u32>();
     uint8_t* h_small = (uint8_t*)ctx->h_vfe + ctx->h_vfe_cap - 4096;
-    const size_t Nmax = tot.Nmax, Ttot = tot.tail;
+    const size_t Nmax = tot.Nmax;
     hipLaunchKernelGGL(k_scalars_to_canon<FrP>, dim3((u32)((2 * Nmax + 255) / 256)), dim3(256), 0, st, sc + 2 * 8, (u32)(2 * Nmax));
     HIPCHK(hipMemcpyAsync(h_small, ctx->r_small.p, tot.blocks * 32, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(h_small + VFY_HS_SUMS, d_status + 64, nj * 64, hipMemcpyDeviceToHost, st));
@@ -2403,15 +2416,8 @@ static int vfy_dev_finish(bp_ctx* ctx, VfyDevJob<C>* const* jobs, size_t nj, con
     F4 sB = S::zero(), sBb = S::zero();
     for (size_t c = 0; c < nj; c++) { F4 a, b; memcpy(a.v, h_small + VFY_HS_SUMS + c * 64, 32); memcpy(b.v, h_small + VFY_HS_SUMS + c * 64 + 32, 32); sB = S::add(sB, a); sBb = S::add(sBb, b); }
     for (size_t j = 0; j < tot.blocks; j++) { F4 d; memcpy(d.v, h_small + j * 32, 32); sB = S::add(sB, d); }
-    uint64_t head[8];
-    canon_words<FrP>(head, sB); canon_words<FrP>(head + 4, sBb);
-    HIPCHK(hipMemcpyAsync(sc, head, 64, hipMemcpyHostToDevice, st));
     const double t_msm = now_s();
-    BaseSegs sg; memset(&sg, 0, sizeof sg);
-    sg.nseg = 4;
-    sg.ptr[0] = ctx->d_pc.as<u32>(); sg.ptr[1] = ctx->d_G.as<u32>(); sg.ptr[2] = ctx->d_H.as<u32>(); sg.ptr[3] = ctx->r_tail.as<u32>();
-    sg.start[0] = 0; sg.start[1] = 2; sg.start[2] = (u32)(2 + Nmax); sg.start[3] = (u32)(2 + 2 * Nmax); sg.start[4] = (u32)(2 + 2 * Nmax + Ttot);
-    BPCHK(msm_run<C>(ctx, sg, sc, 2 + 2 * Nmax + Ttot, 0, r));
+    BPCHK(vfy_mega_check<C>(ctx, Nmax, tot.tail, sB, sBb, r));
     const double t_end = now_s(), t_entry = jobs[0]->t_entry;
     if (timing) { timing[0] = t_end - t_entry; timing[1] = 0; timing[2] = t_msm - t_drain; timing[3] = t_end - t_msm; }
     if (ctx->profiling) collect_timers(ctx);
@@ -2444,424 +2450,15 @@ static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& 
     bool bad = false;
     BPCHK(vfy_dev_finish<C>(ctx, jobs, 1, tot, drain, timing, r, bad));
     if (bad) { ctx->vfe_fallbacks++; if (flagged) vfy_dev_flagged<C>(ctx, jobs, 1, tot, *flagged); return BP_OK; }
-    if (point_out) { A4 pt = host::Grp<C>::to_aff(r); memcpy(point_out, pt.x.v, 32); memcpy(point_out + 4, pt.y.v, 32); }
+    if (point_out) aff_out<C>(point_out, host::Grp<C>::to_aff(r));
     ctx->vfe_batches++;
     if (J.wire) ctx->cw_front_end += count * J.m;
     handled = true;
     return host::Grp<C>::is_inf(r) ? BP_OK : BP_E_VERIFICATION;
 }
 
-// batch_verify (src/r1cs/verifier.rs:604-691); Verifier::verify (:559-600) is a batch of one with alpha = 1.
-//
-// Pipeline.  Decode: framing on the host, every compressed point of the batch decompressed on the GPU, one block ahead.  The
-// instances go through in blocks of VFY_BLOCK: the host threads replay the transcripts of a block (commitments, proof points,
-// the instance's randomized constraints, challenges; verify_prepare) and stage parameter blocks, coefficient tables and tail
-// scalars / points in pinned memory while the GPU evaluates the previous block (k_vfy_batch: flattened constraints from the
-// circuit template, the 2N g/h scalars of every proof, alpha-weighted accumulation).  Instances are grouped by the template their
-// recording canonicalises to — single-phase and randomized statements alike; one launch per (template, block).  The alpha-scaling
-// of the tails and the canonical forms are GPU work; the host keeps only the two head scalars.  One MSM at the end.
-//
-// inst_status (count ints, optional; bp_r1cs_batch_verify_locate): the call then does not stop at the first instance that fails
-// before the mega-check (framing, decompression, verify_prepare).  EVERY such instance of the batch gets its own status — what a
-// batch of that instance alone returns — the others stay BP_OK, and the call returns the first of them in instance order without
-// a mega-check verdict.  When no instance fails that way the statuses are all BP_OK and the return value is the mega-check's.
-//
-// checked (optional): set when the call reached its mega-check, i.e. no instance failed before it.
-template <class C>
-static int batch_verify_host(bp_ctx* ctx, size_t count, const VfyProvider<C>& prov, const uint8_t* proofs, const size_t* poff /* count + 1 */, const F4* alphas,
-                             double* timing, uint64_t* point_out, int* inst_status, bool* checked) {
-    typedef typename C::Fr FrP;
-    typedef host::Fld<FrP> S;
-    hipStream_t st = ctx->stream;
-    const double t_entry = now_s();
-    if (checked) *checked = false;
-    if (point_out) memset(point_out, 0, 64);   // every early exit leaves a defined (identity) check point
-    if (inst_status) std::fill(inst_status, inst_status + count, BP_OK);
-    static const bool vtrace = getenv("ARKBP_VFY_TRACE") != nullptr;
-    double t_last = t_entry;
-    auto mark = [&](const char* what) { if (vtrace) { double t = now_s(); fprintf(stderr, "[vfy] %-28s %8.3f ms\n", what, (t - t_last) * 1e3); t_last = t; } };
-    host_pool_ensure(ctx, count);
-    if (prov.prologue) {   // pending wire commitments: a rejected encoding is reported before anything the proof bytes would give
-        std::vector<int> pst(count, BP_OK);
-        BPCHK(prov.prologue(nullptr, count, pst.data()));
-        int first = BP_OK;
-        for (size_t k = 0; k < count && !first; k++) first = pst[k];
-        if (first) {
-            if (inst_status) std::copy(pst.begin(), pst.end(), inst_status);
-            g_err = "batch_verify: a commitment's encoding was rejected";
-            return first;
-        }
-    }
-    // decode: framing + x coordinates on the host, the square roots of all compressed points on the GPU
-    std::vector<int> rcs(count, BP_OK);
-    std::vector<host::LazyProof> lps(count);
-    pool_range(ctx, 0, count, [&](size_t k) { rcs[k] = host::proof_parse_lazy<C>(lps[k], proofs + poff[k], poff[k + 1] - poff[k]); });
-    for (size_t k = 0; k < count; k++) if (rcs[k]) {
-        if (!inst_status) return rcs[k];
-        lps[k].xs.clear(); lps[k].flags.clear(); lps[k].k = (size_t)-1;   // no points of its own; it dooms the batch below
-    }
-    std::vector<size_t> xoff(count + 1, 0);
-    for (size_t k = 0; k < count; k++) xoff[k + 1] = xoff[k] + lps[k].xs.size();
-    // compressed points: x words and flag bytes gathered in pinned memory; the square roots run on a second stream, block by
-    // block, one block ahead of the replay that consumes them
-    const size_t xtot = xoff[count];
-    {
-        const size_t need = xtot * (32 + 4 + 64 + 4) + 64;
-        if (ctx->h_dec_cap < need) {
-            if (ctx->h_dec) HIPCHK(hipHostFree(ctx->h_dec));
-            ctx->h_dec = nullptr; ctx->h_dec_cap = 0;
-            HIPCHK(hipHostMalloc(&ctx->h_dec, need + (need >> 2)));
-            ctx->h_dec_cap = need + (need >> 2);
-        }
-        if (!ctx->aux_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) if (!ctx->dec_ev[i]) HIPCHK(hipEventCreateWithFlags(&ctx->dec_ev[i], hipEventDisableTiming));
-        BPCHK(ctx->v_dec.ensure(xtot * (32 + 4 + 64 + 4) + 64));
-    }
-    F4* all_x = (F4*)ctx->h_dec;
-    A4* all_pts = (A4*)((char*)ctx->h_dec + xtot * 32);
-    u32* all_f = (u32*)((char*)ctx->h_dec + xtot * 96);
-    u32* all_ok = all_f + xtot;
-    u32* d_x = ctx->v_dec.as<u32>();
-    u32* d_pts = d_x + xtot * 8;
-    u32* d_f = d_pts + xtot * 16;
-    u32* d_ok = d_f + xtot;
-    pool_range(ctx, 0, count, [&](size_t k) { std::copy(lps[k].xs.begin(), lps[k].xs.end(), all_x + xoff[k]); std::copy(lps[k].flags.begin(), lps[k].flags.end(), all_f + xoff[k]); });
-    mark("parse + gather x");
-    size_t decoded_upto = 0;   // instances [0, decoded_upto) have their decode enqueued on the aux stream
-    auto issue_decode = [&](size_t k_hi, int ev) -> int {   // enqueue the decode of instances [decoded_upto, k_hi)
-        const size_t x0 = xoff[decoded_upto], x1 = xoff[k_hi];
-        if (x1 > x0 && ctx->host_only) {
-            // dry run without a device: the square roots on the host pool (what k_points_decompress computes)
-            pool_range(ctx, x0, x1, [&](size_t j) {
-                A4 pt{}; bool good = true;
-                const u32 fl = all_f[j];
-                if (!(fl & 0x40)) good = host::Grp<C>::from_x(pt, all_x[j], (fl & 0x80) != 0);
-                all_pts[j] = good ? pt : A4{}; all_ok[j] = good ? 1u : 0u;
-            });
-        } else if (x1 > x0) {
-            hipStream_t as = ctx->aux_stream;
-            const size_t cnt = x1 - x0;
-            HIPCHK(hipMemcpyAsync(d_x + x0 * 8, all_x + x0, cnt * 32, hipMemcpyHostToDevice, as));
-            HIPCHK(hipMemcpyAsync(d_f + x0, all_f + x0, cnt * 4, hipMemcpyHostToDevice, as));
-            hipLaunchKernelGGL(k_points_decompress<C>, dim3((u32)((cnt + 255) / 256)), dim3(256), 0, as, d_x + x0 * 8, d_f + x0, d_pts + x0 * 16, d_ok + x0, (u32)cnt);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(all_pts + x0, d_pts + x0 * 16, cnt * 64, hipMemcpyDeviceToHost, as));
-            HIPCHK(hipMemcpyAsync(all_ok + x0, d_ok + x0, cnt * 4, hipMemcpyDeviceToHost, as));
-        }
-        HIPCHK(hipEventRecord(ctx->dec_ev[ev], ctx->aux_stream));
-        decoded_upto = k_hi;
-        return BP_OK;
-    };
-    auto check_decoded = [&](size_t k_lo, size_t k_hi) -> int {   // x not on the curve -> FormatError, first in instance order
-        for (size_t k = k_lo; k < k_hi; k++) for (size_t j = xoff[k]; j < xoff[k + 1]; j++) if (!all_ok[j]) return BP_E_FORMAT;
-        return BP_OK;
-    };
-    // layout of the mega-check MSM: [B, B_blinding | G[..maxN] | H[..maxN] | tails of instance 0, 1, ...].  A valid proof carries
-    // lg N points in L_vec (checked against the recording in verify_prepare), so the proofs themselves size the layout.  A proof
-    // whose claim cannot hold on this ctx (L/R lengths differ, k >= 32, 2^k above the installed generators) dooms the batch: the
-    // instances are then replayed without any GPU work, only to report the reference's first error in instance order.
-    size_t maxN = 1;
-    bool doomed = false;
-    std::vector<size_t> toff(count + 1, 0);
-    for (size_t k = 0; k < count; k++) {
-        const size_t kk = lps[k].k;
-        if (kk == (size_t)-1 || kk >= 32 || ((size_t)1 << kk) > ctx->gens_cap) { doomed = true; toff[k + 1] = toff[k]; continue; }
-        maxN = std::max(maxN, (size_t)1 << kk);
-        toff[k + 1] = toff[k] + 6 + prov.m_of(k) + 5 + 2 * kk;
-    }
-    {
-        const size_t first_hi = doomed ? count : std::min(count, VFY_BLOCK);
-        BPCHK(issue_decode(first_hi, 0));
-        HIPCHK(event_wait(ctx, ctx->dec_ev[0]));
-        if (!inst_status) BPCHK(check_decoded(0, first_hi));
-    }
-    mark("gpu decompress (first block)");
-    if (timing) timing[4] = now_s() - t_entry;
-    struct Replayed { VfyInstance<C> inst; host::ProofData pf; VerifyPrep<C> vp; int rc = BP_OK; };
-    auto replay = [&](size_t k, Replayed& r) -> int {
-        host::proof_finish_lazy(r.pf, lps[k], all_pts + xoff[k]);
-        int rc = prov.get(k, r.inst);
-        if (rc) return rc;
-        return verify_prepare<C>(*r.inst.cs, r.pf, ctx->gens_cap, r.vp);
-    };
-    // inst_status: instances [from, count) each on their own — framing, its points, its replay — with no GPU work but the decode
-    auto report_each = [&](size_t from) -> int {
-        if (decoded_upto < count) BPCHK(issue_decode(count, 0));
-        HIPCHK(hipStreamSynchronize(ctx->aux_stream));
-        std::vector<int> erc(count, BP_OK);
-        std::vector<const char*> emsg(count, nullptr);
-        pool_range(ctx, from, count, [&](size_t k) {
-            if (rcs[k]) { erc[k] = rcs[k]; return; }
-            for (size_t j = xoff[k]; j < xoff[k + 1]; j++) if (!all_ok[j]) { erc[k] = BP_E_FORMAT; return; }
-            Replayed r;
-            erc[k] = replay(k, r); emsg[k] = r.vp.err;
-            const size_t kk = lps[k].k;
-            if (!erc[k] && (kk == (size_t)-1 || kk >= 32 || ((size_t)1 << kk) > ctx->gens_cap)) erc[k] = BP_E_VERIFICATION;   // (not reached, as below)
-        });
-        for (size_t k = from; k < count; k++) inst_status[k] = erc[k];
-        for (size_t k = 0; k < count; k++) if (inst_status[k]) { if (k >= from && emsg[k]) g_err = emsg[k]; return inst_status[k]; }
-        return BP_OK;
-    };
-    if (inst_status && (doomed || check_decoded(0, std::min(count, VFY_BLOCK)))) return report_each(0);
-    if (doomed) {
-        std::vector<int> erc(count, BP_OK);
-        std::vector<const char*> emsg(count, nullptr);
-        pool_range(ctx, 0, count, [&](size_t k) { Replayed r; erc[k] = replay(k, r); emsg[k] = r.vp.err; });
-        for (size_t k = 0; k < count; k++) if (erc[k]) { if (emsg[k]) g_err = emsg[k]; return erc[k]; }
-        return BP_E_VERIFICATION;   // (not reached: a doomed instance fails its own replay)
-    }
-    const size_t Ttot = toff[count];
-    BPCHK(ctx->r_g.ensure((2 + 2 * maxN + Ttot) * 32));
-    BPCHK(ctx->r_tail.ensure(std::max<size_t>(Ttot, 1) * 64));
-    const size_t nblocks = (count + VFY_BLOCK - 1) / VFY_BLOCK;
-    BPCHK(ctx->r_small.ensure((count + 8) * 32));               // one (wc + delta) slot per launched group: at most one per instance
-    BPCHK(ctx->v_alpha.ensure(count * 32 + (count + 1) * 4));
-    u32* sc = ctx->r_g.as<u32>();
-    u32* acc_g = sc + 2 * 8;
-    u32* acc_h = sc + (2 + maxN) * 8;
-    u32* d_tail_sc = sc + (2 + 2 * maxN) * 8;
-    u32* d_alpha = ctx->v_alpha.as<u32>();
-    u32* d_toff = d_alpha + count * 8;
-    HIPCHK(hipMemsetAsync(sc, 0, (2 + 2 * maxN) * 32, st));
-    BPCHK(upload_scalars<C>(ctx, d_alpha, alphas, count));
-    std::vector<u32> toff32(toff.begin(), toff.end());
-    HIPCHK(hipMemcpyAsync(d_toff, toff32.data(), (count + 1) * 4, hipMemcpyHostToDevice, st));
-    F4 sB = S::zero(), sBb = S::zero();
-    size_t nslots = 0;
-    mark("layout + alphas");
-    double host_busy = 0;
-    int first_err = BP_OK;
-    size_t err_from = 0;   // inst_status: the instances from here on have no status yet when first_err stops the blocks
-    uint64_t dry_sum = 0xcbf29ce484222325ULL;
-    for (size_t blk = 0; blk < nblocks && !first_err; blk++) {
-        const size_t lo = blk * VFY_BLOCK, hi = std::min(count, lo + VFY_BLOCK), nb = hi - lo;
-        const int half = (int)(blk & 1);
-        if (hi > decoded_upto) BPCHK(issue_decode(hi, half));            // (only when block 0 was shorter than expected: not reached)
-        if (blk > 0) {
-            HIPCHK(event_wait(ctx, ctx->dec_ev[half]));              // this block's points are in host memory
-            const int frc = check_decoded(lo, hi);
-            if (frc) { first_err = frc; err_from = lo; break; }
-        }
-        if (decoded_upto < count) BPCHK(issue_decode(std::min(count, decoded_upto + VFY_BLOCK), half ^ 1));   // next block's decode runs beside this block
-        // staging layout of this block: [parameter blocks (block order) | tail scalars | tail points | perm | coefficient tables]
-        const size_t t_lo = toff[lo], t_hi = toff[hi];
-        const size_t bytes_pb = nb * VFY_PB_SCALARS * 32, bytes_ts = (t_hi - t_lo) * 32, bytes_tp = (t_hi - t_lo) * 64, bytes_perm = (nb * 4 + 31) / 32 * 32;
-        if (blk >= 2 && ctx->vstage_ev[half]) HIPCHK(event_wait(ctx, ctx->vstage_ev[half]));   // the copies out of this half (two blocks ago) are done
-        if (blk >= 2 && ctx->vtail_ev[half]) HIPCHK(event_wait(ctx, ctx->vtail_ev[half]));
-        BPCHK(vfy_stage_ensure(ctx, half, bytes_pb + bytes_ts + bytes_tp));   // (may reallocate: only after those copies)
-        F4* st_pb = (F4*)ctx->h_vstage[half];
-        F4* st_ts = (F4*)((char*)ctx->h_vstage[half] + bytes_pb);
-        A4* st_tp = (A4*)((char*)ctx->h_vstage[half] + bytes_pb + bytes_ts);
-        std::vector<Replayed> rep(nb);
-        std::vector<F4> part_sB(nb), part_sBb(nb);
-        const double th0 = now_s();
-        auto prep = [&](size_t p) {      // the proof's points in place, the instance's recording at hand
-            const size_t k = lo + p;
-            Replayed& r = rep[p];
-            host::proof_finish_lazy(r.pf, lps[k], all_pts + xoff[k]);
-            r.rc = prov.get(k, r.inst);
-        };
-        auto one = [&](size_t p, const F4* chal, const F4* inv_acc_y) {   // chal: the proof's challenges from the lockstep replay, or nullptr (its own transcript)
-            const size_t k = lo + p;
-            Replayed& r = rep[p];
-            if (r.rc) return;
-            if (chal) { PrecompTr T{chal, inv_acc_y}; r.rc = verify_prepare_t<C>(*r.inst.cs, r.pf, ctx->gens_cap, r.vp, T); }
-            else r.rc = verify_prepare<C>(*r.inst.cs, r.pf, ctx->gens_cap, r.vp);
-            if (r.rc) return;
-            const VerifyPrep<C>& vp = r.vp;
-            if (vp.tail_scalars.size() != toff[k + 1] - toff[k]) { r.rc = BP_E_VERIFICATION; return; }
-            F4* b = st_pb + p * VFY_PB_SCALARS;
-            for (u32 j = 0; j < VFY_PB_SCALARS; j++) b[j] = S::zero();
-            for (int j = 0; j < 32; j++) { b[j] = vp.ztab[j]; b[32 + j] = vp.ypw[32 + j]; }
-            b[64] = vp.allinv; b[65] = vp.x; b[66] = vp.a; b[67] = vp.b; b[68] = vp.u; b[69] = alphas[k]; b[70] = S::mul(alphas[k], vp.coefD); b[71] = vp.rx;
-            for (size_t j = 0; j < vp.k; j++) b[72 + j] = vp.u_sq[j];
-            if (!vp.tail_scalars.empty()) {
-                memcpy(st_ts + (toff[k] - t_lo), vp.tail_scalars.data(), vp.tail_scalars.size() * 32);
-                memcpy(st_tp + (toff[k] - t_lo), vp.tail_points.data(), vp.tail_points.size() * 64);
-            }
-            part_sB[p] = S::mul(alphas[k], vp.sB); part_sBb[p] = S::mul(alphas[k], vp.sBb);
-            // the recording is only needed again if its template does not exist yet (the map is not modified during the replay):
-            // release it here, in the thread that allocated it
-            if (r.inst.owned_cs && ctx->templates.count(std::string((const char*)&vp.digest, sizeof vp.digest))) { r.inst.owned_cs.reset(); r.inst.owned_tr.reset(); r.inst.cs = nullptr; r.inst.released = true; }
-            std::vector<F4>().swap(r.vp.tail_scalars); std::vector<A4>().swap(r.vp.tail_points);
-            r.pf = host::ProofData();
-        };
-        // groups of eight: their transcripts take the commitments in lockstep where the provider can do that (AVX-512 Keccak x8)
-        pool_range(ctx, 0, (nb + 7) / 8, [&](size_t g) {
-            const size_t p0 = g * 8, cnt = std::min<size_t>(8, nb - p0);
-            if (prov.head8) {
-                std::unique_ptr<host::Transcript> heads[8];
-                prov.head8(lo + p0, cnt, heads);
-                for (size_t j = 0; j < cnt; j++) rep[p0 + j].inst.owned_tr = std::move(heads[j]);
-            }
-            for (size_t j = 0; j < cnt; j++) prep(p0 + j);
-#if defined(__x86_64__)
-            static const bool no_x8 = getenv("ARKBP_VFY_NOX8") != nullptr;   // A/B switch
-            if (cnt == 8 && !no_x8 && host::cpu_has_avx512()) {
-                // the eight transcripts in lockstep through the rest of the replay (replay_challenges_x8); the arithmetic per proof after
-                host::ConstraintSystem<C>* csp[8];
-                const host::ProofData* pfp[8];
-                bool ok = true;
-                for (size_t j = 0; j < 8; j++) { const Replayed& r = rep[p0 + j]; if (r.rc || !r.inst.cs) { ok = false; break; } csp[j] = r.inst.cs; pfp[j] = &r.pf; }
-                std::vector<F4> chal[8];
-                if (ok && replay_challenges_x8<C>(csp, pfp, chal)) {
-                    // the eight proofs' inversions as one (every challenge is known: y = chal[0], u_i = chal[5 + i])
-                    F4 prod[8], pre[8], both[8];
-                    F4 run = S::one();
-                    for (size_t j = 0; j < 8; j++) {
-                        const size_t kk = chal[j].size() - 6;
-                        F4 acc = S::one();
-                        for (size_t i = 0; i < kk; i++) if (!chal[j][5 + i].is_zero()) acc = S::mul(acc, chal[j][5 + i]);
-                        prod[j] = chal[j][0].is_zero() ? acc : S::mul(acc, chal[j][0]);
-                        pre[j] = run; run = S::mul(run, prod[j]);          // (never zero: products of non-zero scalars)
-                    }
-                    F4 inv = S::inv(run);
-                    for (size_t j = 8; j-- > 0;) { both[j] = S::mul(inv, pre[j]); inv = S::mul(inv, prod[j]); }
-                    for (size_t j = 0; j < 8; j++) one(p0 + j, chal[j].data(), &both[j]);
-                    return;
-                }
-            }
-#endif
-            for (size_t j = 0; j < cnt; j++) one(p0 + j, nullptr, nullptr);
-        });
-        host_busy += now_s() - th0;
-        mark("  block: replay");
-        if (ctx->host_only) {   // dry run: what the host staged for this block, folded into a checksum (compared across thread counts / replay modes)
-            auto fold = [&](const void* p, size_t nbytes) { const uint64_t* w = (const uint64_t*)p; for (size_t i = 0; i < nbytes / 8; i++) { dry_sum = (dry_sum ^ w[i]) * 0x100000001b3ULL; dry_sum ^= dry_sum >> 31; } };
-            bool all_ok_blk = true;
-            for (size_t p = 0; p < nb; p++) if (rep[p].rc) all_ok_blk = false;
-            if (all_ok_blk) { fold(st_pb, bytes_pb); fold(st_ts, bytes_ts); fold(st_tp, bytes_tp); fold(part_sB.data(), nb * 32); fold(part_sBb.data(), nb * 32); }
-        }
-        for (size_t p = 0; p < nb; p++) if (rep[p].rc) { first_err = rep[p].rc; if (rep[p].vp.err) g_err = rep[p].vp.err; break; }   // the first error in instance order (`?` at :619)
-        if (first_err && inst_status) { for (size_t p = 0; p < nb; p++) inst_status[lo + p] = rep[p].rc; err_from = hi; }
-        if (first_err) break;
-        for (size_t p = 0; p < nb; p++) { sB = S::add(sB, part_sB[p]); sBb = S::add(sBb, part_sBb[p]); }
-        // templates: look up by structure digest; a miss records the matrices from this instance (upload + sync, once per gadget)
-        std::vector<const VTemplate<C>*> tm(nb, nullptr);
-        std::vector<std::shared_ptr<void>> keep(nb);
-        std::vector<char> own_tab(nb, 0);
-        bool uniform = true;   // every instance of the block resolved like the first (the common case: one gadget, shared values)
-        // Bounded cache.  The replay workers above released the recordings of instances whose template was cached at that moment, so
-        // nothing this block refers to may leave the cache before the loop below is through: eviction happens HERE, once per block,
-        // and only takes entries no instance of this block resolves to (the bound is soft: a block of > 64 new shapes grows it).
-        if (ctx->templates.size() >= VFY_TEMPLATE_CACHE) {
-            std::set<std::string> used;
-            for (size_t p = 0; p < nb; p++) used.insert(vfy_template_key(rep[p].vp.digest));
-            BPCHK(vfy_templates_trim(ctx, used));
-        }
-        for (size_t p = 0; p < nb; p++) {
-            const VerifyPrep<C>& vp = rep[p].vp;
-            if (p > 0 && vp.digest == rep[p - 1].vp.digest && vp.coef_ptr == rep[p - 1].vp.coef_ptr && vp.n == rep[p - 1].vp.n && vp.n1 == rep[p - 1].vp.n1) {
-                tm[p] = tm[p - 1]; keep[p] = keep[p - 1]; own_tab[p] = own_tab[p - 1];   // same gadget, same table as the previous instance
-                continue;
-            }
-            if (p > 0) uniform = false;
-            // (a miss means the template was not cached during the replay either — entries only leave the cache above, and never one
-            // this block uses — so the worker kept this instance's recording: inst.cs is null only for a template that is found)
-            BPCHK(vfy_template_get<C>(ctx, vp.digest, rep[p].inst.cs, vp.n, vp.n1, vp.nq, vp.ncoef, "batch_verify", keep[p], tm[p]));
-            own_tab[p] = vfy_own_table<C>(*tm[p], vp);
-        }
-        mark("  block: templates");
-        // groups: same template, same kind of coefficient table; instance order inside a group
-        std::vector<u32> order(nb);
-        for (size_t p = 0; p < nb; p++) order[p] = (u32)p;
-        if (!uniform) std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return tm[x] != tm[y] ? std::less<const void*>()(tm[x], tm[y]) : own_tab[x] < own_tab[y]; });
-        size_t coef_scalars = 0;
-        for (size_t p = 0; p < nb; p++) if (own_tab[p]) coef_scalars += tm[p]->ncoef;
-        BPCHK(vfy_aux_ensure(ctx, half, bytes_perm + coef_scalars * 32));
-        u32* st_perm = (u32*)ctx->h_vaux[half];
-        F4* st_coef = (F4*)((char*)st_perm + bytes_perm);
-        memcpy(st_perm, order.data(), nb * 4);
-        {
-            size_t at = 0;
-            for (size_t j = 0; j < nb; j++) { const u32 p = order[j]; if (own_tab[p]) { memcpy(st_coef + at, rep[p].vp.coef_ptr, tm[p]->ncoef * 32); at += tm[p]->ncoef; } }
-        }
-        BPCHK(ctx->v_params.ensure(bytes_pb + bytes_perm + coef_scalars * 32 + 64));
-        u32* d_pb = ctx->v_params.as<u32>();
-        u32* d_perm = d_pb + nb * VFY_PB_WORDS;
-        u32* d_coef = d_perm + bytes_perm / 4;
-        HIPCHK(hipMemcpyAsync(d_pb, st_pb, bytes_pb, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_perm, st_perm, bytes_perm + coef_scalars * 32, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((nb * VFY_PB_SCALARS + 255) / 256)), dim3(256), 0, st, d_pb, d_pb, (u32)(nb * VFY_PB_SCALARS));
-        if (coef_scalars) hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((coef_scalars + 255) / 256)), dim3(256), 0, st, d_coef, d_coef, (u32)coef_scalars);
-        {
-            size_t coef_at = 0;
-            for (size_t j0 = 0; j0 < nb;) {
-                size_t j1 = j0 + 1;
-                while (j1 < nb && tm[order[j1]] == tm[order[j0]] && own_tab[order[j1]] == own_tab[order[j0]]) j1++;
-                const VTemplate<C>& t = *tm[order[j0]];
-                const bool own = own_tab[order[j0]] != 0;
-                BPCHK(verify_launch_template_group<C>(ctx, t, d_pb, d_perm + j0, own ? d_coef + coef_at * 8 : nullptr, j1 - j0, rep[order[j0]].vp.N, rep[order[j0]].vp.k,
-                                                      acc_g, acc_h, ctx->r_small.as<u32>() + nslots * 8));
-                if (own) coef_at += (j1 - j0) * t.ncoef;
-                nslots++;
-                j0 = j1;
-            }
-        }
-        // the block's tails (96 B per tail term: 14.5 MB per block of cfg4) go up on the second stream: on the main stream the copy
-        // would sit behind k_vfy_batch and lengthen the GPU's chain per block by ~0.6 ms; nothing reads them before the drain
-        HIPCHK(hipMemcpyAsync(d_tail_sc + t_lo * 8, st_ts, bytes_ts, hipMemcpyHostToDevice, ctx->aux_stream));
-        HIPCHK(hipMemcpyAsync(ctx->r_tail.as<u32>() + t_lo * 16, st_tp, bytes_tp, hipMemcpyHostToDevice, ctx->aux_stream));
-        if (!ctx->vtail_ev[half]) HIPCHK(hipEventCreateWithFlags(&ctx->vtail_ev[half], hipEventDisableTiming));
-        HIPCHK(hipEventRecord(ctx->vtail_ev[half], ctx->aux_stream));
-        HIPCHK(hipEventRecord(ctx->vstage_ev[half], st));
-        mark("  block: launches");
-        {   // recordings that were kept for a template build: rare, but then there may be hundreds (a new gadget's first block)
-            size_t kept = 0;
-            for (size_t p = 0; p < nb; p++) kept += rep[p].inst.owned_cs ? 1 : 0;
-            if (kept > 8) pool_range(ctx, 0, nb, [&](size_t p) { rep[p].inst.owned_cs.reset(); rep[p].inst.owned_tr.reset(); });
-        }
-        mark("  block: release");
-    }
-    if (first_err) {
-        (void)hipStreamSynchronize(st);
-        if (inst_status) return report_each(err_from);   // the blocks before passed their replay; the rest is decided one by one
-        if (first_err != BP_E_FORMAT) {   // the reference decodes every proof before batch_verify runs: a malformed later proof wins
-            if (decoded_upto < count) BPCHK(issue_decode(count, 0));
-            HIPCHK(hipStreamSynchronize(ctx->aux_stream));
-            if (check_decoded(0, count)) return BP_E_FORMAT;
-        } else (void)hipStreamSynchronize(ctx->aux_stream);
-        return first_err;
-    }
-    if (checked) *checked = true;
-    if (ctx->host_only) {   // dry run: no mega-check; the checksum of everything the host staged comes back in the check point's words
-        if (point_out) { memset(point_out, 0, 64); point_out[0] = dry_sum; point_out[1] = count; point_out[2] = nslots; }
-        if (timing) { timing[0] = now_s() - t_entry; timing[1] = host_busy; }
-        return BP_OK;
-    }
-    const double t_drain = now_s();
-    HIPCHK(ctx_aux_stream_wait(ctx));   // every block's tails have arrived (the main stream's kernels below read them)
-    // tails: alpha-scaling + canonical form on the GPU; points to the resident layout; accumulators to canonical integers
-    if (Ttot) {
-        hipLaunchKernelGGL(k_vfy_tail_scale<FrP>, dim3((u32)((Ttot + 255) / 256)), dim3(256), 0, st, d_tail_sc, d_alpha, d_toff, (u32)count, (u32)Ttot);
-        BPCHK(bp_points_import(ctx, ctx->r_tail.p, ctx->r_tail.p, Ttot));
-    }
-    hipLaunchKernelGGL(k_scalars_to_canon<FrP>, dim3((u32)((2 * maxN + 255) / 256)), dim3(256), 0, st, sc + 2 * 8, (u32)(2 * maxN));
-    std::vector<F4> deltas(std::max<size_t>(nslots, 1));
-    if (nslots) HIPCHK(hipMemcpyAsync(deltas.data(), ctx->r_small.p, nslots * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx_stream_wait(ctx));
-    HIPCHK(hipGetLastError());
-    for (size_t j = 0; j < nslots; j++) sB = S::add(sB, deltas[j]);   // sum_p alpha_p * r_p * x_p^2 * (wc_p + delta_p) of the groups
-    uint64_t head[8];
-    canon_words<FrP>(head, sB); canon_words<FrP>(head + 4, sBb);
-    HIPCHK(hipMemcpyAsync(sc, head, 64, hipMemcpyHostToDevice, st));
-    mark("pipeline (replay | k_vfy_batch)");
-    const double t_msm = now_s();
-    // the mega-check MSM over [B, B_blinding, G[..maxN], H[..maxN], tails...]
-    BaseSegs sg; memset(&sg, 0, sizeof sg);
-    sg.nseg = 4;
-    sg.ptr[0] = ctx->d_pc.as<u32>(); sg.ptr[1] = ctx->d_G.as<u32>(); sg.ptr[2] = ctx->d_H.as<u32>(); sg.ptr[3] = ctx->r_tail.as<u32>();
-    sg.start[0] = 0; sg.start[1] = 2; sg.start[2] = (u32)(2 + maxN); sg.start[3] = (u32)(2 + 2 * maxN); sg.start[4] = (u32)(2 + 2 * maxN + Ttot);
-    J4 r;
-    BPCHK(msm_run<C>(ctx, sg, sc, 2 + 2 * maxN + Ttot, 0, r));
-    const bool ok = host::Grp<C>::is_inf(r);  // `mega_check.is_zero()` (verifier.rs:595)
-    if (point_out) { A4 pt = host::Grp<C>::to_aff(r); memcpy(point_out, pt.x.v, 32); memcpy(point_out + 4, pt.y.v, 32); }
-    mark("mega-check msm");
-    const double t_end = now_s();
-    if (timing) { timing[0] = t_end - t_entry; timing[1] = host_busy; timing[2] = t_msm - t_drain; timing[3] = t_end - t_msm; }
-    if (ctx->profiling) collect_timers(ctx);
-    return ok ? BP_OK : BP_E_VERIFICATION;
-}
+// batch_verify on the host-replay route: batch_verify_host, a short sequence of steps over one VfyHostJob
+#include "verify_steps.inc"
 
 // ---- batches of several gadgets --------------------------------------------------------------------------------------------------
 // The partition of a batch into device classes: the one place the rule lives (bp_debug_vfy_class_plan is this function).  keys[k]
@@ -3032,7 +2629,7 @@ static int batch_verify_classes(bp_ctx* ctx, size_t count, const VfyProvider<C>&
         memcpy(p.x.v, pt, 32); memcpy(p.y.v, pt + 4, 32);
         r = host::Grp<C>::madd(r, p);
     }
-    if (point_out) { A4 pt = host::Grp<C>::to_aff(r); memcpy(point_out, pt.x.v, 32); memcpy(point_out + 4, pt.y.v, 32); }
+    if (point_out) aff_out<C>(point_out, host::Grp<C>::to_aff(r));
     return host::Grp<C>::is_inf(r) ? BP_OK : BP_E_VERIFICATION;
 }
 

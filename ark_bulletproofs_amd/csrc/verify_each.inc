@@ -60,16 +60,7 @@ struct VeLayout {
     }
 };
 
-template <class C> struct VeRep {
-    size_t k = 0, kk = 0;              // instance index in the call; lg N as the proof claims it
-    VfyInstance<C> inst;
-    host::ProofData pf;
-    VerifyPrep<C> vp;
-    int rc = BP_OK;
-    const VTemplate<C>* tm = nullptr;
-    std::shared_ptr<void> keep;
-    bool own_tab = false;
-};
+template <class C> struct VeRep : VfyReplayed<C> { size_t k = 0, kk = 0; };   // + instance index in the call; lg N as the proof claims it
 
 // One group: P proofs of one template.  flags_out[j] = 1 iff member j's check is the identity; pts_out (may be null): the checks.
 template <class C>
@@ -178,19 +169,15 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
     typedef typename C::Fr FrP;
     typedef host::Fld<FrP> S;
     const double t_entry = now_s();
-    static const bool vtrace = getenv("ARKBP_VFY_TRACE") != nullptr;
-    double t_last = t_entry;
-    auto mark = [&](const char* what) { if (vtrace) { double t = now_s(); fprintf(stderr, "[vfy-each] %-28s %8.3f ms\n", what, (t - t_last) * 1e3); t_last = t; } };
+    VfyMark mark{"vfy-each", t_entry};
     if (points) memset(points, 0, count * 64);
     std::vector<int> stv(count, BP_OK);
     host_pool_ensure(ctx, count);
     // 0. pending wire commitments: decoded and committed first; an instance with a rejected encoding is left out with BP_E_FORMAT
-    std::vector<int> pst(count, BP_OK);
-    if (prov.prologue) BPCHK(prov.prologue(nullptr, count, pst.data()));
     // 1. framing; the proof's claim decides the route
-    std::vector<host::LazyProof> lps(count);
-    std::vector<int> prc(count, BP_OK);
-    pool_range(ctx, 0, count, [&](size_t k) { prc[k] = host::proof_parse_lazy<C>(lps[k], proofs + poff[k], poff[k + 1] - poff[k]); });
+    std::vector<host::LazyProof> lps;
+    std::vector<int> pst, prc;
+    BPCHK(vfy_parse<C>(ctx, prov, count, proofs, poff, pst, lps, prc));
     const size_t reach_max = ctx->shard_world <= 1 && ctx->tune_direct_max >= 2 ? std::min(ctx->gens_cap, ctx->tune_direct_max) : 0;
     auto claim = [&](size_t k) -> size_t {   // the padded size the proof claims, 0 when it cannot take the grouped path
         const size_t kk = lps[k].k;
@@ -214,12 +201,11 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
     ctx->ve_grouped += ng;
     mark("parse + route");
     // 2. the grouped instances' points: one decompression launch, one wait
-    std::vector<size_t> xoff(ng + 1, 0);
-    for (size_t j = 0; j < ng; j++) xoff[j + 1] = xoff[j] + lps[gl[j]].xs.size();
+    const std::vector<size_t> xoff = vfy_xoff(lps, gl.data(), ng);
     std::vector<F4> all_x(xoff[ng]);
     std::vector<u32> all_f(xoff[ng]), all_ok;
     std::vector<A4> all_pts;
-    pool_range(ctx, 0, ng, [&](size_t j) { const host::LazyProof& lp = lps[gl[j]]; std::copy(lp.xs.begin(), lp.xs.end(), all_x.begin() + xoff[j]); std::copy(lp.flags.begin(), lp.flags.end(), all_f.begin() + xoff[j]); });
+    vfy_gather(ctx, lps, gl.data(), ng, xoff, all_x.data(), all_f.data());
     BPCHK(decompress_points<C>(ctx, all_x.data(), all_f.data(), xoff[ng], all_pts, all_ok));
     const double t_dec = now_s();
     mark("gpu decompress");
@@ -228,12 +214,8 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
     pool_range(ctx, 0, ng, [&](size_t j) {
         VeRep<C>& r = rep[j];
         r.k = gl[j]; r.kk = lps[r.k].k;
-        for (size_t x = xoff[j]; x < xoff[j + 1]; x++) if (!all_ok[x]) { r.rc = BP_E_FORMAT; return; }   // x not on the curve: FormatError
-        host::proof_finish_lazy(r.pf, lps[r.k], all_pts.data() + xoff[j]);
-        r.rc = prov.get(r.k, r.inst);
-        if (r.rc) return;
-        r.rc = verify_prepare<C>(*r.inst.cs, r.pf, ctx->gens_cap, r.vp);
-        if (r.rc) return;
+        if (!vfy_points_ok(all_ok.data(), xoff[j], xoff[j + 1])) { r.rc = BP_E_FORMAT; return; }
+        if (vfy_replay_one<C>(ctx, prov, r.k, lps[r.k], all_pts.data() + xoff[j], r)) return;
         if (r.vp.tail_scalars.size() != 6 + prov.m_of(r.k) + 5 + 2 * r.kk || r.vp.N != ((size_t)1 << r.kk) || r.vp.k != r.kk) { r.rc = BP_E_VERIFICATION; return; }
         r.pf = host::ProofData();
     });
@@ -245,16 +227,8 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
         live.push_back(&rep[j]);
     }
     // 4. templates: by structure digest; a miss records the matrices from this instance (upload + sync, once per gadget)
-    if (!live.empty() && ctx->templates.size() >= VFY_TEMPLATE_CACHE) {   // bounded cache: only entries no instance of this call resolves to leave it
-        std::set<std::string> used;
-        for (auto* r : live) used.insert(vfy_template_key(r->vp.digest));
-        BPCHK(vfy_templates_trim(ctx, used));
-    }
-    for (auto* r : live) {
-        const VerifyPrep<C>& vp = r->vp;
-        BPCHK(vfy_template_get<C>(ctx, vp.digest, r->inst.cs, vp.n, vp.n1, vp.nq, vp.ncoef, "verify_batch", r->keep, r->tm));
-        r->own_tab = vfy_own_table<C>(*r->tm, vp);
-    }
+    // (bounded cache: only entries no instance of this call resolves to leave it)
+    BPCHK((vfy_resolve_templates<C>(ctx, live.size(), [&live](size_t j) -> VfyReplayed<C>& { return *live[j]; }, "verify_batch", nullptr)));
     {   // one kind of coefficient table per template: when any instance carries values of its own (public constants, the challenges of
         // randomized constraints), every instance of the template ships its table — the template's creator among them — so that the
         // groups do not depend on which instance happened to build the template
@@ -289,7 +263,7 @@ static int verify_each_core(bp_ctx* ctx, size_t count, const VfyProvider<C>& pro
             for (size_t j = 0; j < P; j++) {
                 const size_t k = live[lo + j]->k;
                 stv[k] = flags[j] ? BP_OK : BP_E_VERIFICATION;
-                if (points && !flags[j]) { memcpy(points + 8 * k, apts[j].x.v, 32); memcpy(points + 8 * k + 4, apts[j].y.v, 32); }
+                if (points && !flags[j]) aff_out<C>(points + 8 * k, apts[j]);
             }
         }
         j0 = j1;
