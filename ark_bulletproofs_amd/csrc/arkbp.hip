@@ -271,9 +271,9 @@ struct bp_ctx {
     hipStream_t stream = nullptr;
     bool profiling = false;
     size_t tune_fold_batch_min = 65536;   // BP_TUNE_FOLD_BATCH_MIN
-    size_t tune_msm_bin_min = 64;         // BP_TUNE_MSM_BIN_MIN
+    size_t tune_msm_bin_min = MsmKnobs().bin_min;         // BP_TUNE_MSM_BIN_MIN
     size_t tune_ipa_freeze_len = 8192;    // BP_TUNE_IPA_FREEZE_LEN (measured at 2^20, one proof at a time: 1024 -> 51.0 ms of inner-product argument, 4096 -> 49.0, 8192 -> 47.5, 16384 -> 46.8 with a slower prove() around it; throughput unchanged)
-    size_t tune_msm_wsum_min = (size_t)1 << 18;   // BP_TUNE_MSM_WSUM_MIN: buckets from which running-sum window aggregation replaces the marginals
+    size_t tune_msm_wsum_min = MsmKnobs().wsum_min;   // BP_TUNE_MSM_WSUM_MIN: buckets from which running-sum window aggregation replaces the marginals
     KTimer timers[BP_K_COUNT];
     std::vector<hipEvent_t> event_pool;
     // MSM workspaces
@@ -343,14 +343,14 @@ struct bp_ctx {
     uint64_t coll_count = 0;
     double coll_seconds = 0;
     size_t tune_cyclic_min = (size_t)1 << 14;   // BP_TUNE_CYCLIC_MIN: padded size from which a sharded prover partitions the IPA
-    size_t tune_msm_fixed_min = (size_t)1 << 20;   // BP_TUNE_MSM_FIXED_MIN: terms from which MSMs over the generator tables use the fixed-base rows
+    size_t tune_msm_fixed_min = MsmKnobs().fixed_min;   // BP_TUNE_MSM_FIXED_MIN: terms from which MSMs over the generator tables use the fixed-base rows
     size_t tune_host_threads = 0;                  // BP_TUNE_HOST_THREADS: size of this ctx's host pool (0 = host_pool_threads())
     hipEvent_t sync_ev_aux = nullptr;              // event of ctx_aux_stream_wait
     unsigned tune_wait_sleep = 0;                  // BP_TUNE_WAIT_SLEEP: host waits poll and sleep this many microseconds in between instead of busy-waiting (see event_wait)
     bool msm_latency_first = false;                // set by the bp_msm* entry points for the duration of the call (see msm_use_quad)
-    size_t tune_msm_chunk_cap = 0;                 // BP_TUNE_MSM_CHUNK_CAP: entries per level-1 chunk of the fixed-shape MSM pipeline (0 = fs_chunk_cap's choice)
+    size_t tune_msm_chunk_cap = MsmKnobs().chunk_cap;                 // BP_TUNE_MSM_CHUNK_CAP: entries per level-1 chunk of the fixed-shape MSM pipeline (0 = fs_chunk_cap's choice)
     size_t tune_fold_quad_max = 0;                 // BP_TUNE_FOLD_QUAD_MAX: fold rounds with at most this many output points run four lanes per point (0 = never)
-    size_t tune_msm_glv_min = 256;                 // BP_TUNE_MSM_GLV_MIN: terms from which an MSM on a GLV curve splits its scalars
+    size_t tune_msm_glv_min = MsmKnobs().glv_min;                 // BP_TUNE_MSM_GLV_MIN: terms from which an MSM on a GLV curve splits its scalars
     DevBuf cyc_a, cyc_b, cyc_Gf, cyc_Hf;
     // fixed-base MSM rows of the generators (bp_gens_msm_tables): row r of a table = 2^(4r) * base, r < FB_ROWS, layout [r][i]
     DevBuf fb_G, fb_H, fb_pc;
@@ -414,7 +414,7 @@ struct bp_ctx {
     IpaState ipa_step;         // bp_ipa_begin .. bp_ipa_finish
     bool ipa_step_active = false;
     u32* h_totals = nullptr;  // pinned
-    u32* h_T = nullptr;       // pinned
+    void* h_T = nullptr;      // pinned: the result points of an MSM chain (msm_host_T_ensure)
     size_t h_T_cap = 0;
 };
 
@@ -541,196 +541,62 @@ static void collect_timers(bp_ctx* c) {
 extern "C" int bp_points_import(bp_ctx* c, const void* d_in, void* d_out, size_t n);
 
 // ---- MSM orchestration ---------------------------------------------------------------------------
-static MsmPlan msm_plan(size_t n, int bits) {
-    double best = 1e300; int bc = 4;
-    for (int c = 3; c <= 16; c++) {
-        double W = bits / c + 1, NBk = std::ldexp(1.0, c - 1), B = W * NBk;
-        double cost = n * W + (n * W / MSM_CH + B) * 1.45 + B * (0.5 * c) * 1.45 + 256.0 * c * W * 0.05;
-        if (cost < best) { best = cost; bc = c; }
-    }
-    static const int c_env = getenv("ARKBP_MSM_C") ? atoi(getenv("ARKBP_MSM_C")) : 0;   // experiments
-    if (c_env >= 3 && c_env <= 16 && n >= 4096) bc = c_env;
-    MsmPlan pl; pl.c = bc; pl.W = bits / bc + 1; pl.NB = 1 << (bc - 1); pl.B = (u32)pl.W * pl.NB; pl.n = (u32)n;
-    pl.w_lo = 0; pl.w_hi = pl.W;
-    return pl;
-}
-
-// quad-cooperative additions in the latency-bound kernels of the fixed-shape pipeline (ecq.cuh); ARKBP_MSM_NOQUAD=1 restores the
-// lane-per-addition kernels (A/B: profiles/r03_msm_quad_ab.txt)
-// Policy (measured, profiles/r03_msm_quad_glv_ab.txt): the GLV split and the quad-cooperative trees shorten ONE mid-size MSM
-// (2^16 terms: 0.607 -> 0.513 ms wall) but do not lower its arithmetic — the split adds an endomorphism product to every second
-// mixed addition, a quad addition issues 20 products where a lane issues 16 — so a caller that keeps the GPU full with many MSMs in
-// flight (the prover pipeline: eight streams) gains nothing and pays ~5 % on the accumulate.  They are therefore used where the
-// caller waits for the one result: the bp_msm* entry points.  ARKBP_MSM_LATENCY=1 / =0 forces them on / off everywhere (A/B).
+// The shapes — windows, bins, slots, chunk sizes, per-job strides — are made by msm_plan.hpp, pure functions of (terms, scalar bits,
+// MsmKnobs) that its self-test checks on the CPU; here the knobs are filled and the kernels launched.
+// Policy of the latency-first knob (measured, profiles/r03_msm_quad_glv_ab.txt): the GLV split and the quad-cooperative additions in
+// the latency-bound kernels of the fixed-shape pipeline (ecq.cuh; against the lane-per-addition kernels: profiles/r03_msm_quad_ab.txt)
+// shorten ONE mid-size MSM (2^16 terms: 0.607 -> 0.513 ms wall) but do not lower its arithmetic — the split adds an endomorphism
+// product to every second mixed addition, a quad addition issues 20 products where a lane issues 16 — so a caller that keeps the GPU
+// full with many MSMs in flight (the prover pipeline: eight streams) gains nothing and pays ~5 % on the accumulate.  They are
+// therefore used where the caller waits for the one result: the bp_msm* entry points.  ARKBP_MSM_LATENCY=1 / =0 forces them on / off
+// everywhere (A/B).
 static int msm_latency_env() { static const int v = getenv("ARKBP_MSM_LATENCY") ? atoi(getenv("ARKBP_MSM_LATENCY")) : -1; return v; }
 static bool msm_use_quad(const bp_ctx* ctx) { const int e = msm_latency_env(); return e >= 0 ? e != 0 : ctx->msm_latency_first; }
 static bool msm_quad_trees(const bp_ctx* ctx) { static const bool force = getenv("ARKBP_MSM_QUAD_TREES") != nullptr; return force || msm_use_quad(ctx); }   // (experiment: the quad trees without the GLV split)
+// what the planners read: the ctx's knobs as they are now (no ctx: the defaults), the environment's experiment switches as they were
+// at the first MSM
+static MsmKnobs msm_knobs(const bp_ctx* ctx) {
+    static const MsmKnobs env = [] {
+        const auto num = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 0; };
+        MsmKnobs e;
+        e.env_c = num("ARKBP_MSM_C"); e.env_fs_cap = num("ARKBP_MSM_FS_CAP"); e.env_tpt = num("ARKBP_MSM_TPT"); e.env_fixed_c = num("ARKBP_MSM_FIXED_C");
+        e.env_nobin = getenv("ARKBP_MSM_NOBIN") != nullptr; e.env_nofs = getenv("ARKBP_MSM_NOFS") != nullptr;
+        e.env_marginals = getenv("ARKBP_MSM_MARGINALS") != nullptr;   // A/B: the bit-marginal bucket aggregation everywhere
+        return e;
+    }();
+    MsmKnobs kn = env;
+    if (!ctx) return kn;
+    kn.wsum_min = ctx->tune_msm_wsum_min; kn.bin_min = ctx->tune_msm_bin_min; kn.glv_min = ctx->tune_msm_glv_min; kn.chunk_cap = ctx->tune_msm_chunk_cap;
+    kn.fixed_min = ctx->tune_msm_fixed_min; kn.quad = msm_use_quad(ctx);
+    return kn;
+}
 // (direct launches in both branches: a kernel template named only inside a conditional expression is not emitted for the device)
 #define MSM_LAUNCH_REDUCE_FS(red_g, grid, ...) do { if (msm_quad_trees(ctx) && (red_g) == 4u) hipLaunchKernelGGL((k_msm_reduce_fs<C, true>), grid, dim3(256), 0, st, __VA_ARGS__); \
                                                     else hipLaunchKernelGGL((k_msm_reduce_fs<C, false>), grid, dim3(256), 0, st, __VA_ARGS__); } while (0)
 #define MSM_LAUNCH_MARGINALS_FS(grid, ...) do { if (msm_quad_trees(ctx)) hipLaunchKernelGGL((k_msm_marginals_fs<C, 256, true>), grid, dim3(256), 0, st, __VA_ARGS__); \
                                                 else hipLaunchKernelGGL((k_msm_marginals_fs<C, 256, false>), grid, dim3(256), 0, st, __VA_ARGS__); } while (0)
-// Entries per level-1 chunk of the fixed-shape pipeline.  Throughput callers keep 16.  For a caller waiting on ONE mid-size MSM the
-// accumulate is a single round of workgroups whose duration is (entries per lane) x (latency of a mixed addition at the fill of
-// the lane's SIMD: 6.7 us alone, ~5.6 us per resident wave from two up — tools/ubench_coop.hip): 2^16 terms at 16 entries per chunk
-// make ~100 K lanes = 1.5 waves per SIMD, i.e. every lane waits for the SIMDs that hold two.  The cap is chosen so that the lanes
-// fill a whole number of waves per SIMD with as few entries per lane as that allows (measured at 2^16 terms, secq256k1, accumulate /
-// wall: cap 11 0.200 / 0.520 ms, 12 0.157 / 0.468, 13 0.169 / 0.479, 14 0.181 / 0.487, 16 0.205 / 0.506: profiles/r03_msm_chunk_cap.txt).
-// binned: entries / buckets of the binned windows (bucket populations ~ Poisson); top: the narrow top window (a few full buckets).
-static u32 fs_chunk_cap(const bp_ctx* ctx, double binned_entries, double binned_buckets, double top_entries, double top_buckets) {
-    static const int cap_env = getenv("ARKBP_MSM_FS_CAP") ? atoi(getenv("ARKBP_MSM_FS_CAP")) : 0;   // experiments
-    if (cap_env >= 8 && cap_env <= 64) return (u32)cap_env;
-    if (ctx->tune_msm_chunk_cap) return (u32)ctx->tune_msm_chunk_cap;
-    if (!msm_use_quad(ctx) || binned_buckets < 1.0) return 1u << MSM_CHL_BINNED;
-    const double lanes_per_fill = 256.0 * 4 * 64;   // one wave on every SIMD of the chip
-    const double mu = binned_entries / binned_buckets, sd = std::sqrt(std::max(mu, 1e-9));
-    u32 best_cap = 1u << MSM_CHL_BINNED; double best_t = 1e300;
-    for (u32 cap = 8; cap <= 32; cap++) {
-        double e_chunks = 0, e_work = 0, wsum = 0;   // E ceil(X / cap) and E X / ceil(X / cap) for X ~ N(mu, mu)
-        for (int q = -30; q <= 30; q++) {
-            const double z = q / 10.0, x = std::max(1.0, mu + sd * z), w = std::exp(-0.5 * z * z), k = std::ceil(x / cap);
-            e_chunks += w * k; e_work += w * x / k; wsum += w;
-        }
-        const double chunks = binned_buckets * e_chunks / wsum + top_entries / cap + 0.5 * top_buckets;
-        const double fill = std::ceil(chunks / lanes_per_fill - 0.004);
-        if (fill > 4.0) continue;   // throughput-bound anyway: the default
-        const double t = (e_work / wsum) * (fill <= 1.0 ? 6.7 : 5.6 * fill) + 0.02 * (chunks / 1000.0);   // (+ the partials the next kernel has to add)
-        if (t < best_t) { best_t = t; best_cap = cap; }
-    }
-    return best_cap;
-}
-// ---- the fixed-shape pipeline over GLV-split scalars (msm.cuh "GLV split"): 2n half-terms of 128 bits ------------------------------
-// Same five launches as the fixed-shape pipeline in msm_run; what changes is the plan — half the windows, hence half the buckets
-// for the reduction / aggregation trees and half the doublings (and marginal sums) of the host's Horner tail.  *done = false when it
-// does not apply or a region overflowed (skewed scalars): the caller then runs the ordinary schedule, which recomputes everything.
-template <class C> static int msm_run_fs_glv(bp_ctx* ctx, const BaseSegs& segs_in, const ScalSegs& d_scalars, size_t n, int scalars_mont, J4& result, bool& done) {
+// The pinned block the MSM chains copy their result points into
+static int msm_host_T_ensure(bp_ctx* ctx, size_t bytes, size_t slack = 4096) { return pinned_ensure(ctx->h_T, ctx->h_T_cap, bytes, slack); }
+// Host tail of an MSM: the Horner sum, from the top position down, over the points a chain left in the pinned block (T: 12 words per
+// point, Z = 0 for the identity).  Every position costs `dbls` doublings of ONE point — a serial chain that a scalar core runs ~40x
+// faster than a GPU lane.  Positions below nlow hold one point each (T[j]); the nhigh positions above hold `parts` points each, behind
+// those.  The three forms:
+//   bit marginals, sum_{w,k} 2^(c*w+k) T[w][k]:                         nlow = W * c, nhigh = 0, dbls = 1
+//   ... with the slot window's bits as top_parts partial points each:   nlow = wb * c, nhigh = top_bits, parts = top_parts, dbls = 1
+//   window sums, sum_w 2^(c*w) (sum_j T[w][j]):                         nlow = 0, nhigh = W, parts = workgroups per window, dbls = c
+template <class C> static J4 msm_horner_tail(const u64* T, int nlow, int nhigh, u32 parts, int dbls) {
     typedef host::Grp<C> G;
-    done = false;
-    if constexpr (!C::HAS_GLV) { (void)ctx; (void)segs_in; (void)d_scalars; (void)n; (void)scalars_mont; (void)result; return BP_OK; }
-    else {
-    hipStream_t st = ctx->stream;
-    constexpr int BITS = 128;                       // magnitudes of the halves (glv_split guarantees < 2^128 or flags the MSM)
-    const size_t ne = 2 * n;                        // half-terms
-    MsmPlan pl = msm_plan(ne, BITS);
-    pl.n = (u32)n;                                  // scalars the partition kernel reads
-    if (pl.W > MSM_MAXW || pl.B >= ctx->tune_msm_wsum_min) return BP_OK;
-    const int bits_last = BITS - pl.c * (pl.W - 1);
-    const int wbn = bits_last < pl.c - 1 ? pl.W - 1 : pl.W;
-    if (wbn <= 0) return BP_OK;
-    BinPlan bp; memset(&bp, 0, sizeof bp);
-    {
-        u32 nbin = 1, lg = 0;
-        while ((size_t)nbin * 8192 < ne && nbin < (u32)pl.NB) { nbin <<= 1; lg++; }
-        int LB = pl.c - 1 - (int)lg;
-        while (LB > 11) { nbin <<= 1; LB--; }
-        const double mu = (double)ne / nbin;
-        const size_t cap = std::min<size_t>(ne, (size_t)(mu + 8.0 * std::sqrt(mu) + 64.0));
-        const size_t lds_sort = (((size_t)1 << LB) + 8 + cap) * 4;
-        if (!(ne < ((size_t)1 << (30 - LB)) && lds_sort <= 64 * 1024 && (size_t)wbn * nbin * cap < ((size_t)1 << 31))) return BP_OK;
-        bp.LB = (u32)LB; bp.NBIN = nbin; bp.cap = (u32)cap; bp.wb = (u32)wbn; bp.glv = 1;
-        bp.tpt = (u32)std::min<size_t>(16, std::max<size_t>(1, n / (256 * 512)));
-        if (wbn < pl.W) {
-            const size_t nb_top = std::min<size_t>((size_t)pl.NB, ((size_t)1 << std::max(bits_last, 0)) + 1);
-            if (nb_top > 2049) return BP_OK;   // (k_msm_marginals_fs holds top_nb + 1 prefix counts in 2052 words)
-            bp.top_nb = (u32)nb_top;
-        }
-    }
-    if (!(bp.wb == (u32)pl.W || bp.top_nb > 0) || (size_t)bp.wb * bp.NBIN + 1 > MSM_FS_MAXBINS) return BP_OK;
-    // slots of the narrow top window: the halves are not uniform below 2^128 (|k2| reaches 1.27 * 2^127, |k1| 1.08 * 2^127), so its
-    // low buckets are fuller than a uniform spread: four times the mean
-    SlotPlan sp; memset(&sp, 0, sizeof sp);
-    size_t nslots = (size_t)bp.wb * bp.NBIN * bp.cap;
-    for (int w = (int)bp.wb; w < pl.W; w++) {
-        const size_t cap = std::min<size_t>(ne, 4 * ((ne + bp.top_nb - 1) / bp.top_nb) + 64);
-        sp.base[w] = (u32)nslots; sp.cap[w] = (u32)cap;
-        nslots += (size_t)bp.top_nb * cap;
-    }
-    const u32 chl_fs = fs_chunk_cap(ctx, (double)ne * bp.wb * (1.0 - std::ldexp(1.0, -pl.c)), (double)bp.wb * pl.NB, bp.wb < (u32)pl.W ? (double)ne : 0.0, (double)bp.top_nb);   // (entries per chunk; any value from 8)
-    FsPlan fp; memset(&fp, 0, sizeof fp);
-    fp.has_top = bp.wb < (u32)pl.W ? 1u : 0u;
-    fp.nbins = bp.wb * bp.NBIN + fp.has_top;
-    if (fp.has_top) { u32 t = bp.top_nb; while (t) { fp.top_bits++; t >>= 1; } }
-    const size_t nwin = (size_t)pl.W;
-    const u32 red_g = (size_t)bp.wb * pl.NB > 49152 ? 1u : 4u;
-    const size_t maxch = (ne * nwin) / chl_fs + std::min<size_t>(ne * nwin, nwin * (size_t)pl.NB) + 64;
-    fp.max_chunks = (u32)maxch;
-    fp.top_parts = (u32)std::min<size_t>(MSM_TOP_PARTS_MAX, std::max<size_t>(4, ne >> 15));
-    const size_t tc = (size_t)bp.wb * pl.c + (size_t)fp.top_bits * fp.top_parts;
-    const size_t tb = tc * 96 + 64;
-    if (nslots >= ((size_t)1 << 32) || maxch >= ((size_t)1 << 31)) return BP_OK;
-    constexpr int NL = MSM_NLMAX;
-    BPCHK(ctx->canon.ensure(n * MSM_GLV_WORDS * 4));
-    BPCHK(ctx->hist.ensure_zeroed((size_t)pl.B * 4, st));
-    BPCHK(ctx->totals.ensure_zeroed((NL + 2) * 4 + 4096, st));
-    BPCHK(ctx->slots.ensure(nslots * 4));
-    BPCHK(ctx->bin_cur.ensure_zeroed((size_t)pl.W * bp.NBIN * 4, st));
-    BPCHK(ctx->boff.ensure((size_t)pl.B * 4));
-    BPCHK(ctx->fs_bcnt.ensure((size_t)pl.B * 4));
-    BPCHK(ctx->fs_loff.ensure((size_t)pl.B * 4));
-    BPCHK(ctx->fs_binch.ensure((MSM_FS_MAXBINS + 1) * 4));
-    BPCHK(ctx->fs_sums.ensure((size_t)bp.wb * pl.NB * 96));
-    BPCHK(ctx->lvA.ensure(maxch * 96));
-    BPCHK(ctx->Tbuf.ensure(tb));
-    if (ctx->h_T_cap < tb) {
-        if (ctx->h_T) HIPCHK(hipHostFree(ctx->h_T));
-        HIPCHK(hipHostMalloc((void**)&ctx->h_T, tb + 4096));
-        ctx->h_T_cap = tb + 4096;
-    }
-    BaseSegs segs = segs_in;
-    segs.glv = 1;
-    ScopedK total(ctx, BP_K_MSM_TOTAL);
-    u32* d_over = ctx->totals.as<u32>() + (NL + 1);
-    u32* d_info = ctx->Tbuf.as<u32>() + tc * 24;
-    const int wg = std::max(1, (int)(12288 / bp.NBIN));
-    const u32 gp = (u32)((n + (size_t)256 * bp.tpt - 1) / ((size_t)256 * bp.tpt));
-    for (int wa = 0; wa < (int)bp.wb; wa += wg) {
-        const int we = std::min<int>((int)bp.wb, wa + wg);
-        hipLaunchKernelGGL(k_msm_bin_partition<C>, dim3(gp), dim3(256), ((size_t)(we - wa) * bp.NBIN + (wa == 0 ? bp.top_nb : 0)) * 4, st, PerJob<ScalSegs>{{d_scalars}}, ctx->canon.as<u32>(),
-                           ctx->hist.as<u32>(), pl, scalars_mont, bp, sp, ctx->bin_cur.as<u32>(), ctx->slots.as<u32>(), d_over, wa, we, wa == 0 ? 1 : 0, FsJobs{});
-    }
-    hipLaunchKernelGGL(k_msm_bin_sort_fs, dim3(bp.NBIN, bp.wb + fp.has_top), dim3(256), (((size_t)1 << bp.LB) + 8 + bp.cap) * 4, st, ctx->slots.as<u32>(),
-                       ctx->bin_cur.as<u32>(), ctx->hist.as<u32>(), ctx->boff.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(), ctx->fs_binch.as<u32>(),
-                       d_over, pl, bp, sp, chl_fs, FsJobs{});
-    {
-        ScopedK acc(ctx, BP_K_MSM_ACCUM_FS);
-        hipLaunchKernelGGL(k_msm_accum_fs<C>, dim3((u32)((maxch + 255) / 256)), dim3(256), 0, st, PerJob<BaseSegs>{{segs}}, ctx->slots.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
-                           ctx->boff.as<u32>(), ctx->fs_binch.as<u32>(), ctx->lvA.as<u32>(), pl, bp, fp, chl_fs, d_info, FsJobs{});
-    }
-    {
-        ScopedK agg(ctx, BP_K_MSM_AGG);
-        MSM_LAUNCH_REDUCE_FS(red_g, dim3((u32)(((size_t)bp.wb * pl.NB * red_g + 255) / 256)), ctx->lvA.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
-                           ctx->fs_binch.as<u32>(), ctx->fs_sums.as<u32>(), pl, bp, fp, chl_fs, red_g, FsJobs{});
-        MSM_LAUNCH_MARGINALS_FS(dim3((u32)tc), ctx->fs_sums.as<u32>(), ctx->lvA.as<u32>(), ctx->fs_bcnt.as<u32>(), ctx->fs_loff.as<u32>(),
-                           ctx->Tbuf.as<u32>(), pl, bp, fp, chl_fs, d_info, d_over, FsJobs{});
-    }
-    HIPCHK(hipMemcpyAsync(ctx->h_T, ctx->Tbuf.p, tb, hipMemcpyDeviceToHost, st));
-    total.stop();
-    HIPCHK(ctx_stream_wait(ctx));
-    HIPCHK(hipGetLastError());
-    const u32* info = (const u32*)((const uint8_t*)ctx->h_T + tc * 96);
-    static const bool mtrace = getenv("ARKBP_MSM_TRACE") != nullptr;
-    if (info[2] != 0) {
-        if (mtrace) fprintf(stderr, "[msm-glv] n=%zu: overflow, the ordinary schedule takes over\n", n);
-        return BP_OK;
-    }
     J4 acc = G::inf();
-    const u64* T = (const u64*)ctx->h_T;
     auto add_T = [&](size_t idx) {
-        const u64* t = T + idx * 12;
-        J4 p; memcpy(p.X.v, t, 32); memcpy(p.Y.v, t + 4, 32); memcpy(p.Z.v, t + 8, 32);
+        const J4 p = jac_from_words(T + idx * 12);
         if (!p.Z.is_zero()) acc = G::add(acc, p);
     };
-    const int ngen = (int)bp.wb * pl.c;
-    for (int j = ngen + (int)fp.top_bits - 1; j >= 0; j--) {
-        acc = G::dbl(acc);
-        if (j >= ngen) { for (u32 q = 0; q < fp.top_parts; q++) add_T((size_t)ngen + (size_t)(j - ngen) * fp.top_parts + q); }
+    for (int j = nlow + nhigh - 1; j >= 0; j--) {
+        for (int d = 0; d < dbls; d++) acc = G::dbl(acc);
+        if (j >= nlow) { for (u32 q = 0; q < parts; q++) add_T((size_t)nlow + (size_t)(j - nlow) * parts + q); }
         else add_T((size_t)j);
     }
-    result = acc;
-    done = true;
-    if (mtrace) fprintf(stderr, "[msm-glv] n=%zu c=%d W=%d bins=%u chunks=%u/%u  marginals=%zu\n", n, pl.c, pl.W, fp.nbins, info[0], fp.max_chunks, tc);
-    return BP_OK;
-    }
+    return acc;
 }
 
 // A rank's partial point -> the sum over the ranks of a sharded ctx (one small exchange): RCCL all-gather of the Jacobian partials
@@ -763,89 +629,24 @@ template <class C> static int shard_point_reduce(bp_ctx* ctx, J4& part) {
     return BP_OK;
 }
 
-// ---- plans shared by msm_run and msm_run_pair -----------------------------------------------------------------------------------
-static bool msm_use_marginals(const bp_ctx* ctx, const MsmPlan& pl) {
-    static const bool force_marginals = getenv("ARKBP_MSM_MARGINALS") != nullptr;   // A/B: the bit-marginal bucket aggregation everywhere
-    return force_marginals || pl.B < ctx->tune_msm_wsum_min;
-}
-// two-level (binned) sort for large MSMs: the full windows go to bin regions, the short top window keeps its slots behind them
-template <class C> static bool msm_bin_plan(const bp_ctx* ctx, size_t n, const MsmPlan& pl, BinPlan& bp) {
-    memset(&bp, 0, sizeof bp);
-    const int bits_last = C::Fr::BITS - pl.c * (pl.W - 1);
-    const int wbn = bits_last < pl.c - 1 ? pl.W - 1 : pl.W;
-    static const bool no_bins = getenv("ARKBP_MSM_NOBIN") != nullptr;
-    if (!(n >= ctx->tune_msm_bin_min && wbn > 0 && !no_bins)) return false;
-    u32 nbin = 1, lg = 0;
-    while ((size_t)nbin * 8192 < n && nbin < (u32)pl.NB) { nbin <<= 1; lg++; }
-    // bins of up to 12 K entries (43 KB of LDS in the bin sort) where that keeps the MSM inside the fixed-shape pipeline's bin
-    // limit: 2^20 < n <= 1.5 * 2^20, e.g. the 1.25 M-term MSM of a 4096-proof batch verification
-    if ((size_t)wbn * nbin + 1 > MSM_FS_MAXBINS && nbin >= 2 && (size_t)(nbin / 2) * 12288 >= n && (size_t)wbn * (nbin / 2) + 1 <= MSM_FS_MAXBINS) { nbin >>= 1; lg--; }
-    int LB = pl.c - 1 - (int)lg;
-    while (LB > 11) { nbin <<= 1; LB--; }
-    const double mu = (double)n / nbin;
-    const size_t cap = std::min<size_t>(n, (size_t)(mu + 8.0 * std::sqrt(mu) + 64.0));
-    const size_t lds_sort = (((size_t)1 << LB) + 4 + cap) * 4;
-    if (!(n < ((size_t)1 << (31 - LB)) && lds_sort <= 64 * 1024 && (size_t)wbn * nbin * cap < ((size_t)1 << 31))) return false;
-    bp.LB = (u32)LB; bp.NBIN = nbin; bp.cap = (u32)cap; bp.wb = (u32)wbn;
-    static const int tpt_env = getenv("ARKBP_MSM_TPT") ? atoi(getenv("ARKBP_MSM_TPT")) : 0;
-    bp.tpt = tpt_env > 0 ? (u32)tpt_env : (u32)std::min<size_t>(16, std::max<size_t>(1, n / (256 * 512)));
-    if (wbn < pl.W) {   // same-address device atomics serialise (~170 ns each): count a narrow top window per workgroup
-        const size_t nb_top = std::min<size_t>((size_t)pl.NB, ((size_t)1 << std::max(bits_last, 0)) + 1);
-        if (nb_top <= 2048) bp.top_nb = (u32)nb_top;
-    }
-    return true;
-}
-// slot plan of the one-pass sort for the windows from w_first on, behind first_slot entries; returns the entries in all
-template <class C> static size_t msm_make_slots(const MsmPlan& pl, size_t n, SlotPlan& sp, int w_first, size_t first_slot) {
-    memset(&sp, 0, sizeof sp);
-    size_t nslots = first_slot;
-    for (int w = w_first; w < pl.W; w++) {
-        const int bits_left = C::Fr::BITS - pl.c * w;  // scalar bits at or above this window's base
-        size_t nb_eff = (size_t)pl.NB;
-        if (bits_left < pl.c - 1) nb_eff = std::min<size_t>(nb_eff, ((size_t)1 << std::max(bits_left, 0)) + 1);
-        size_t cap = std::min<size_t>(n, 2 * ((n + nb_eff - 1) / nb_eff) + 32);
-        sp.base[w] = (u32)nslots; sp.cap[w] = (u32)cap;
-        nslots += nb_eff * cap;
-    }
-    return nslots;
-}
-// the MSM goes through the fixed-shape pipeline (msm.cuh 7)
-static bool msm_fs_fits(const bp_ctx* ctx, const MsmPlan& pl, const BinPlan& bp, bool binned, const BaseSegs& segs) {
-    static const bool no_fs = getenv("ARKBP_MSM_NOFS") != nullptr;
-    return binned && msm_use_marginals(ctx, pl) && !no_fs && (bp.wb == (u32)pl.W || bp.top_nb > 0) && (size_t)bp.wb * bp.NBIN + 1 <= MSM_FS_MAXBINS && !segs.fixed_c4;
-}
-// The fixed-shape pipeline for J <= MSM_JOBS MSMs of n terms each — same plan, own scalars and bases — as ONE chain of launches with
-// the job in grid.z: no host wait before the last kernel, one D2H copy of the J result blocks, one wait, the J host Horner tails.
-// Every job works in its own stride of the ctx's buffers (FsJobs), so each result is the sum it is alone.  ran = false: the shape
-// does not fit, nothing was launched.  over[j]: job j raised its overflow word (skewed scalars) and results[j] is not written; the
-// caller redoes that job on the general path.
-template <class C> static int msm_fs_jobs(bp_ctx* ctx, int J, const BaseSegs* segs, const ScalSegs* scalars, size_t n, int scalars_mont, const MsmPlan& pl,
-                                          const BinPlan& bp, J4* results, bool* over, bool& ran) {
-    typedef host::Grp<C> G;
+// ---- the fixed-shape pipeline (msm.cuh 7) ------------------------------------------------------------------------------------------
+// One shape (msm_plan.hpp msm_fs_shape, sh.fits) for J <= MSM_JOBS MSMs of sh.pl.n terms each — own scalars and bases — as ONE chain
+// of five launches with the job in grid.z: no host wait before the last kernel, one D2H copy of the J result blocks, one wait, the J
+// host Horner tails.  Every job works in its own stride of the ctx's buffers (FsJobs), so each result is the sum it is alone.
+// A GLV shape (sh.bp.glv; msm.cuh "GLV split": 2n half-terms of 128 bits) runs the same chain: what differs is the plan — half the
+// windows, hence half the buckets for the reduction / aggregation trees and half the doublings (and marginal sums) of the Horner tail
+// —, that the kernels read the bases as half-terms (BaseSegs::glv) and the canon stride (MSM_GLV_WORDS words per scalar, in sh.jb).
+// over[j]: job j raised its overflow word (skewed scalars) and results[j] is not written; the caller redoes that job on the general
+// path, which recomputes everything.
+template <class C> static int msm_fs_jobs(bp_ctx* ctx, int J, const BaseSegs* segs, const ScalSegs* scalars, int scalars_mont, const FsShape& sh, J4* results, bool* over) {
     static const bool mtrace = getenv("ARKBP_MSM_TRACE") != nullptr;
     hipStream_t st = ctx->stream;
-    ran = false;
+    const MsmPlan& pl = sh.pl; const BinPlan& bp = sh.bp; const SlotPlan& sp = sh.sp; const FsPlan& fp = sh.fp; const FsJobs& jb = sh.jb;
+    const size_t n = pl.n, nj = (size_t)J, maxch = sh.maxch, tc = sh.tc, tb = sh.tb;
+    const u32 chl_fs = sh.chl_fs, red_g = sh.red_g;
+    if (!sh.fits || J < 1 || J > MSM_JOBS) { g_err = "msm_fs_jobs: a shape that does not fit"; return BP_E_ARG; }
     const auto tfs = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_f0 = mtrace ? tfs() : 0;
-    const u32 chl_fs = fs_chunk_cap(ctx, (double)n * bp.wb * (1.0 - std::ldexp(1.0, -pl.c)), (double)bp.wb * pl.NB, bp.wb < (u32)pl.W ? (double)n : 0.0, (double)bp.top_nb);   // (entries per chunk; any value from 8)
-    FsPlan fp; memset(&fp, 0, sizeof fp);
-    fp.has_top = bp.wb < (u32)pl.W ? 1u : 0u;
-    fp.nbins = bp.wb * bp.NBIN + fp.has_top;
-    if (fp.has_top) { u32 t = bp.top_nb; while (t) { fp.top_bits++; t >>= 1; } }
-    const size_t nwin = (size_t)(pl.w_hi - pl.w_lo);
-    const u32 red_g = (size_t)bp.wb * pl.NB > 49152 ? 1u : 4u;   // lanes per bucket of k_msm_reduce_fs: groups while the lanes fit the chip at once, one lane per bucket beyond
-    const size_t maxch = (n * nwin) / chl_fs + std::min<size_t>(n * nwin, nwin * (size_t)pl.NB) + 64;
-    fp.max_chunks = (u32)maxch;
-    SlotPlan sp;
-    const size_t nslots = msm_make_slots<C>(pl, n, sp, (int)bp.wb, (size_t)bp.wb * bp.NBIN * bp.cap);
-    fp.top_parts = (u32)std::min<size_t>(MSM_TOP_PARTS_MAX, std::max<size_t>(4, n >> 15));
-    const size_t tc = (size_t)bp.wb * pl.c + (size_t)fp.top_bits * fp.top_parts;
-    const size_t tb = tc * 96 + 64;
-    if (J < 1 || J > MSM_JOBS || !(nslots < ((size_t)1 << 32) && maxch < ((size_t)1 << 31))) return BP_OK;
-    const size_t nj = (size_t)J;
-    FsJobs jb; memset(&jb, 0, sizeof jb);
-    jb.canon = n * 8; jb.hist = pl.B; jb.bin_cur = (size_t)pl.W * bp.NBIN; jb.slots = nslots; jb.buckets = pl.B; jb.binch = MSM_FS_MAXBINS + 1;
-    jb.part = maxch * 24; jb.sums = (size_t)bp.wb * pl.NB * 24; jb.T = tb / 4; jb.over = 1;
     BPCHK(ctx->canon.ensure(nj * jb.canon * 4));
     // hist, the bin cursors and the overflow words are all-zero between MSMs in every job's region: their last readers restore that
     BPCHK(ctx->hist.ensure_zeroed(nj * jb.hist * 4, st));
@@ -859,20 +660,14 @@ template <class C> static int msm_fs_jobs(bp_ctx* ctx, int J, const BaseSegs* se
     BPCHK(ctx->fs_sums.ensure(nj * jb.sums * 4));
     BPCHK(ctx->lvA.ensure(nj * jb.part * 4));
     BPCHK(ctx->Tbuf.ensure(nj * tb));
-    if (ctx->h_T_cap < nj * tb) {
-        if (ctx->h_T) HIPCHK(hipHostFree(ctx->h_T));
-        ctx->h_T = nullptr; ctx->h_T_cap = 0;
-        HIPCHK(hipHostMalloc((void**)&ctx->h_T, nj * tb + 4096));
-        ctx->h_T_cap = nj * tb + 4096;
-    }
+    BPCHK(msm_host_T_ensure(ctx, nj * tb));
     PerJob<ScalSegs> sj; memset(&sj, 0, sizeof sj);
     PerJob<BaseSegs> bj; memset(&bj, 0, sizeof bj);
-    for (int j = 0; j < J; j++) { sj.j[j] = scalars[j]; bj.j[j] = segs[j]; }
-    ran = true;
+    for (int j = 0; j < J; j++) { sj.j[j] = scalars[j]; bj.j[j] = segs[j]; if (bp.glv) bj.j[j].glv = 1; }
     ScopedK total(ctx, BP_K_MSM_TOTAL);
     u32* d_over = ctx->fs_over.as<u32>();
     u32* d_info = ctx->Tbuf.as<u32>() + tc * 24;
-    const int wg = std::max(1, (int)(12288 / bp.NBIN));
+    const int wg = std::max(1, (int)(12288 / bp.NBIN));   // windows per launch: 48 KiB of LDS counters
     const u32 gp = (u32)((n + (size_t)256 * bp.tpt - 1) / ((size_t)256 * bp.tpt));
     const u32 gz = (u32)J;
     for (int wa = 0; wa < (int)bp.wb; wa += wg) {
@@ -906,26 +701,24 @@ template <class C> static int msm_fs_jobs(bp_ctx* ctx, int J, const BaseSegs* se
         const u32* info = (const u32*)(blk + tc * 96);
         over[jn] = info[2] != 0;
         if (over[jn]) {
-            if (mtrace) fprintf(stderr, "[msm-fs] n=%zu job %d: overflow, the general path takes over\n", n, jn);
+            if (mtrace) fprintf(stderr, "[msm-fs] n=%zu glv=%u job %d: overflow, the general path takes over\n", n, bp.glv, jn);
             continue;
         }
-        J4 acc = G::inf();
-        const u64* T = (const u64*)blk;
-        auto add_T = [&](size_t idx) {
-            const u64* t = T + idx * 12;
-            J4 p; memcpy(p.X.v, t, 32); memcpy(p.Y.v, t + 4, 32); memcpy(p.Z.v, t + 8, 32);
-            if (!p.Z.is_zero()) acc = G::add(acc, p);
-        };
-        const int ngen = (int)bp.wb * pl.c;
-        for (int j = ngen + (int)fp.top_bits - 1; j >= 0; j--) {
-            acc = G::dbl(acc);
-            if (j >= ngen) { for (u32 q = 0; q < fp.top_parts; q++) add_T((size_t)ngen + (size_t)(j - ngen) * fp.top_parts + q); }
-            else add_T((size_t)j);
-        }
-        results[jn] = acc;
-        if (mtrace) fprintf(stderr, "[msm-fs] n=%zu job %d/%d c=%d W=%d bins=%u chunks=%u/%u  enqueue %.1f us  wait %.1f us  host tails so far %.1f us\n", n, jn, J, pl.c, pl.W, fp.nbins,
-                            info[0], fp.max_chunks, (t_f1 - t_f0) * 1e6, (t_f2 - t_f1) * 1e6, (tfs() - t_f2) * 1e6);
+        results[jn] = msm_horner_tail<C>((const u64*)blk, (int)bp.wb * pl.c, (int)fp.top_bits, fp.top_parts, 1);
+        if (mtrace) fprintf(stderr, "[msm-fs] n=%zu glv=%u job %d/%d c=%d W=%d bins=%u chunks=%u/%u  enqueue %.1f us  wait %.1f us  host tails so far %.1f us\n", n, bp.glv, jn, J, pl.c,
+                            pl.W, fp.nbins, info[0], fp.max_chunks, (t_f1 - t_f0) * 1e6, (t_f2 - t_f1) * 1e6, (tfs() - t_f2) * 1e6);
     }
+    return BP_OK;
+}
+// Mid-size MSMs on a curve with the endomorphism, for callers that wait for the one result: the chain over GLV-split scalars.
+// *done = false when the GLV shape does not fit or a region overflowed (skewed scalars): the caller then runs the ordinary schedule.
+template <class C> static int msm_run_fs_glv(bp_ctx* ctx, const BaseSegs& segs, const ScalSegs& d_scalars, size_t n, int scalars_mont, J4& result, bool& done) {
+    done = false;
+    const FsShape sh = msm_fs_shape(n, C::Fr::BITS, 1, true, msm_knobs(ctx));
+    if (!sh.fits) return BP_OK;
+    bool over = false;
+    BPCHK(msm_fs_jobs<C>(ctx, 1, &segs, &d_scalars, scalars_mont, sh, &result, &over));
+    done = !over;
     return BP_OK;
 }
 // the mid-size MSM takes the GLV-split pipeline (msm_run_fs_glv) when it applies: callers that wait for one result
@@ -933,8 +726,58 @@ template <class C> static bool msm_glv_route(const bp_ctx* ctx, const BaseSegs& 
     if constexpr (!C::HAS_GLV) { (void)ctx; (void)segs; (void)n; (void)sharded; (void)w_hi; return false; }
     else {
         static const bool no_glv = getenv("ARKBP_MSM_NOGLV") != nullptr, no_fs0 = getenv("ARKBP_MSM_NOFS") != nullptr;
-        return !no_glv && !no_fs0 && msm_use_quad(ctx) && !sharded && w_hi < 0 && ctx->shard_world == 1 && !segs.fixed_c4 && n >= std::max<size_t>(ctx->tune_msm_bin_min, ctx->tune_msm_glv_min) && n < ((size_t)1 << 27);
+        return !no_glv && !no_fs0 && !sharded && w_hi < 0 && ctx->shard_world == 1 && !segs.fixed_c4 && msm_glv_sizes(msm_knobs(ctx), n);
     }
+}
+
+// The back end that msm_run's general path and the fixed-base schedule share.  The front end has sorted the entries by bucket and
+// left the totals on the host (tot[k]: chunks of level k, tot[MSM_NLMAX]: the fullest bucket) and the level offsets in ctx->lvl_off.
+// Level 1 is k_msm_accum (one lane per chunk of 2^chl entries: mixed additions of gathered bases; `mode`: how it finds a bucket's
+// entries), levels 2 .. K the k_msm_reduce tree, until a bucket holds one point.  special: the buckets from b_gen on (top_nb buckets
+// of a narrow top window, a few holding ~n/2 entries each) go through the first spl levels like every other and are finished by
+// k_msm_reduce_special in one launch.  finish(points, offsets) enqueues what sums the buckets — inside the BP_K_MSM_AGG region.
+// deep: the fullest bucket needs nl levels or more; nothing was launched.  wave (A/B): one wavefront per bucket, no tree above.
+template <class C, class Finish>
+static int msm_tree_back(bp_ctx* ctx, const BaseSegs& segs, const u32* entries, int mode, const SlotPlan& sp, const MsmPlan& pl, const u32* tot, int nl, int chl,
+                         bool special, int spl, u32 b_gen, u32 top_nb, bool wave, int& K, bool& deep, Finish&& finish) {
+    hipStream_t st = ctx->stream;
+    const int TB = 256;
+    const size_t Bp1 = (size_t)pl.B + 1;
+    u32* lvl = ctx->lvl_off.as<u32>();
+    // levels: 1 = chunks of entries; k >= 2 = chunks of level k-1 partials; stop when a bucket holds <= 1
+    K = 1;
+    { u64 cap = (u64)1 << chl; while (cap < tot[MSM_NLMAX]) { cap <<= chl; K++; } }
+    if (special && K < spl + 1) K = spl + 1;   // the special buckets' partials meet in level spl + 1
+    deep = K >= nl;
+    if (deep) return BP_OK;
+    BPCHK(ctx->lvA.ensure((size_t)tot[1] * 96));
+    if (K >= 2) BPCHK(ctx->lvB.ensure((size_t)tot[2] * 96));
+    if (wave && !special) {
+        // the bucket sums go straight to the last level's slots (<= 1 per bucket)
+        ScopedK acc(ctx, BP_K_MSM_ACCUM);
+        hipLaunchKernelGGL(k_msm_accum_wave<C>, dim3((pl.B + 3) / 4), dim3(256), 0, st, segs, entries, lvl, lvl + Bp1 * K, ctx->lvA.as<u32>(), pl.B, mode, sp, (u32)pl.NB,
+                           ctx->boff.as<u32>());
+        acc.stop();
+        finish(ctx->lvA.as<u32>(), lvl + Bp1 * K);
+        return BP_OK;
+    }
+    {
+        ScopedK acc(ctx, BP_K_MSM_ACCUM);
+        hipLaunchKernelGGL(k_msm_accum<C>, dim3((tot[1] + TB - 1) / TB), dim3(TB), 0, st, segs, entries, lvl, lvl + Bp1, ctx->lvA.as<u32>(), pl.B, tot[1], mode, sp, (u32)pl.NB,
+                           ctx->boff.as<u32>(), chl);
+    }
+    u32* cur = ctx->lvA.as<u32>();
+    u32* nxt = ctx->lvB.as<u32>();
+    ScopedK agg(ctx, BP_K_MSM_AGG);
+    for (int k = 2; k <= K; k++) {
+        hipLaunchKernelGGL(k_msm_reduce<C>, dim3((tot[k] + TB - 1) / TB), dim3(TB), 0, st, cur, lvl + Bp1 * (k - 1), lvl + Bp1 * k, nxt, pl.B, tot[k], chl,
+                           (k == spl + 1 && special) ? b_gen : pl.B);
+        if (k == spl + 1 && special)
+            hipLaunchKernelGGL(k_msm_reduce_special<C>, dim3(top_nb), dim3(256), 0, st, cur, lvl + Bp1 * spl, lvl + Bp1 * (spl + 1), nxt, b_gen, pl.B);
+        u32* t = cur; cur = nxt; nxt = t;
+    }
+    finish(cur, lvl + Bp1 * K);
+    return BP_OK;
 }
 
 template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u32* d_scalars_one, size_t n, int scalars_mont, J4& result,
@@ -946,12 +789,12 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
     ScalSegs d_scalars; memset(&d_scalars, 0, sizeof d_scalars);
     if (sseg) d_scalars = *sseg; else { d_scalars.nseg = 1; d_scalars.ptr[0] = d_scalars_one; d_scalars.start[0] = 0; d_scalars.start[1] = (u32)n; }
     typedef host::Grp<C> G;
-    typedef host::Fld<typename C::Fq> F;
     result = G::inf();
     if (n == 0) return BP_OK;
     if (n >= (1u << 31)) { g_err = "msm: n too large"; return BP_E_ARG; }
     hipStream_t st = ctx->stream;
-    MsmPlan pl = msm_plan(n, C::Fr::BITS);
+    const MsmKnobs kn = msm_knobs(ctx);
+    MsmPlan pl = msm_plan(n, C::Fr::BITS, kn);
     const bool sharded = w_hi < 0 && ctx->shard_world > 1 && shard_mode != 0;
     if (sharded && shard_mode != 2) {   // contiguous block partition of the windows (the same rule as parallel.shard_range)
         const int base = pl.W / ctx->shard_world, rem = pl.W % ctx->shard_world, r = ctx->shard_rank;
@@ -984,21 +827,19 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
     BPCHK(ctx->lvl_off.ensure(Bp1 * NL * 4));
     BPCHK(ctx->totals.ensure_zeroed((NL + 2) * 4 + (size_t)ntiles * (NL + 1) * 4, st));
     BPCHK(ctx->cursor.ensure(pl.B * 4));
-    const bool use_marginals = msm_use_marginals(ctx, pl);
+    const bool use_marginals = msm_use_marginals(kn, pl);
     const u32 nblk_ws = (u32)((pl.NB + 256 * MSM_SEG - 1) / (256 * MSM_SEG));   // workgroups per window of k_msm_window_sums
     const size_t tcount = use_marginals ? (size_t)pl.W * pl.c : (size_t)pl.W * nblk_ws;
     BPCHK(ctx->Tbuf.ensure(tcount * 96));
     if (!ctx->h_totals) HIPCHK(hipHostMalloc((void**)&ctx->h_totals, 64));
     const size_t tbytes = tcount * 96;
-    if (ctx->h_T_cap < tbytes) {
-        if (ctx->h_T) HIPCHK(hipHostFree(ctx->h_T));
-        HIPCHK(hipHostMalloc((void**)&ctx->h_T, tbytes + 4096));
-        ctx->h_T_cap = tbytes + 4096;
-    }
+    BPCHK(msm_host_T_ensure(ctx, tbytes));
     if (pl.W > MSM_MAXW) { g_err = "msm: too many windows"; return BP_E_ARG; }
-    BinPlan bp;
-    bool binned = msm_bin_plan<C>(ctx, n, pl, bp);
-    auto make_slots = [&](SlotPlan& sp, int w_first, size_t first_slot) -> size_t { return msm_make_slots<C>(pl, n, sp, w_first, first_slot); };
+    // the fixed-shape pipeline's shape; its window and bin plans also serve the general path
+    const FsShape sh = msm_fs_shape(n, C::Fr::BITS, 1, false, kn, pl.w_lo, pl.w_hi, segs.fixed_c4 != 0);
+    const BinPlan& bp = sh.bp;
+    bool binned = sh.binned;
+    auto make_slots = [&](SlotPlan& sp, int w_first, size_t first_slot) -> size_t { return msm_make_slots(pl, C::Fr::BITS, n, false, sp, w_first, first_slot); };
     SlotPlan sp;
     u32* lvl = ctx->lvl_off.as<u32>();
     u32* d_tot = ctx->totals.as<u32>();
@@ -1045,10 +886,10 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
     };
     static const bool mtrace = getenv("ARKBP_MSM_TRACE") != nullptr;   // host-side phase times of every MSM on stderr
     // ---- the fixed-shape pipeline (msm.cuh 7): no host wait before the last kernel; falls through to the general path on overflow ----
-    if (!no_fixed_shape && msm_fs_fits(ctx, pl, bp, binned, segs)) {
-        bool ran = false, over = false;
-        BPCHK(msm_fs_jobs<C>(ctx, 1, &segs, &d_scalars, n, scalars_mont, pl, bp, &result, &over, ran));
-        if (ran && !over) return finish_sharded(result);
+    if (!no_fixed_shape && sh.fits) {
+        bool over = false;
+        BPCHK(msm_fs_jobs<C>(ctx, 1, &segs, &d_scalars, scalars_mont, sh, &result, &over));
+        if (!over) return finish_sharded(result);
     }
     ScopedK total(ctx, BP_K_MSM_TOTAL);
     const auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1068,78 +909,28 @@ template <class C> static int msm_run(bp_ctx* ctx, const BaseSegs& segs, const u
         entries_ptr = ctx->entries.as<u32>();
     }
     const u32* tot = ctx->h_totals;
-    const u32 maxcnt = tot[NL];
     if (tot[0] == 0) { total.stop(); return finish_sharded(result); }  // every digit zero: the identity
-    // levels: 1 = chunks of entries; k >= 2 = chunks of level k-1 partials; stop when a bucket holds <= 1
-    int K = 1;
-    { u64 cap = (u64)1 << chl; while (cap < maxcnt) { cap <<= chl; K++; } }
-    const bool special = b_gen < pl.B;
-    if (special && K < spl + 1) K = spl + 1;   // the special buckets' partials meet in level spl + 1
-    if (K >= nl) { g_err = "msm: bucket population exceeds the reduction depth"; return BP_E_ARG; }
-    BPCHK(ctx->lvA.ensure((size_t)tot[1] * 96));
-    if (K >= 2) BPCHK(ctx->lvB.ensure((size_t)tot[2] * 96));
     static const bool accum_wave = getenv("ARKBP_MSM_ACCUM") && !strcmp(getenv("ARKBP_MSM_ACCUM"), "wave");   // A/B: one wavefront per bucket
-    if (accum_wave && !special) {
-        // the bucket sums go straight to the last level's slots (<= 1 per bucket): no tree above
-        ScopedK acc(ctx, BP_K_MSM_ACCUM);
-        hipLaunchKernelGGL(k_msm_accum_wave<C>, dim3((pl.B + 3) / 4), dim3(256), 0, st, segs, entries_ptr, lvl, lvl + Bp1 * K, ctx->lvA.as<u32>(), pl.B,
-                           slotted ? (binned ? 2 : 1) : 0, sp, (u32)pl.NB, ctx->boff.as<u32>());
-        acc.stop();
-        const u32* last_off = lvl + Bp1 * K;
-        if (use_marginals) hipLaunchKernelGGL(k_msm_marginals<C>, dim3(pl.W, pl.c), dim3(256), 0, st, ctx->lvA.as<u32>(), last_off, ctx->Tbuf.as<u32>(), pl);
-        else hipLaunchKernelGGL(k_msm_window_sums<C>, dim3(nblk_ws, pl.W), dim3(256), 0, st, ctx->lvA.as<u32>(), last_off, ctx->Tbuf.as<u32>(), pl, nblk_ws);
-    } else {
-    {
-        ScopedK acc(ctx, BP_K_MSM_ACCUM);
-        hipLaunchKernelGGL(k_msm_accum<C>, dim3((tot[1] + TB - 1) / TB), dim3(TB), 0, st, segs, entries_ptr, lvl, lvl + Bp1, ctx->lvA.as<u32>(), pl.B,
-                           tot[1], slotted ? (binned ? 2 : 1) : 0, sp, (u32)pl.NB, ctx->boff.as<u32>(), chl);
-    }
-    u32* cur = ctx->lvA.as<u32>();
-    u32* nxt = ctx->lvB.as<u32>();
-    ScopedK agg(ctx, BP_K_MSM_AGG);
-    for (int k = 2; k <= K; k++) {
-        hipLaunchKernelGGL(k_msm_reduce<C>, dim3((tot[k] + TB - 1) / TB), dim3(TB), 0, st, cur, lvl + Bp1 * (k - 1), lvl + Bp1 * k, nxt, pl.B, tot[k], chl,
-                           (k == spl + 1 && special) ? b_gen : pl.B);
-        if (k == spl + 1 && special)
-            hipLaunchKernelGGL(k_msm_reduce_special<C>, dim3(bp.top_nb), dim3(256), 0, st, cur, lvl + Bp1 * spl, lvl + Bp1 * (spl + 1), nxt, b_gen, pl.B);
-        u32* t = cur; cur = nxt; nxt = t;
-    }
-    if (use_marginals) hipLaunchKernelGGL(k_msm_marginals<C>, dim3(pl.W, pl.c), dim3(256), 0, st, cur, lvl + Bp1 * K, ctx->Tbuf.as<u32>(), pl);
-    else hipLaunchKernelGGL(k_msm_window_sums<C>, dim3(nblk_ws, pl.W), dim3(256), 0, st, cur, lvl + Bp1 * K, ctx->Tbuf.as<u32>(), pl, nblk_ws);
-    agg.stop();
-    }
+    int K = 1; bool deep = false;
+    BPCHK(msm_tree_back<C>(ctx, segs, entries_ptr, slotted ? (binned ? 2 : 1) : 0, sp, pl, tot, nl, chl, b_gen < pl.B, spl, b_gen, bp.top_nb, accum_wave, K, deep,
+                           [&](const u32* pts, const u32* off) {
+        if (use_marginals) hipLaunchKernelGGL(k_msm_marginals<C>, dim3(pl.W, pl.c), dim3(256), 0, st, pts, off, ctx->Tbuf.as<u32>(), pl);
+        else hipLaunchKernelGGL(k_msm_window_sums<C>, dim3(nblk_ws, pl.W), dim3(256), 0, st, pts, off, ctx->Tbuf.as<u32>(), pl, nblk_ws);
+    }));
+    if (deep) { g_err = "msm: bucket population exceeds the reduction depth"; return BP_E_ARG; }
     HIPCHK(hipMemcpyAsync(ctx->h_T, ctx->Tbuf.p, tbytes, hipMemcpyDeviceToHost, st));
     total.stop();
     const double t_m2 = mtrace ? tnow() : 0;
     HIPCHK(ctx_stream_wait(ctx));
     HIPCHK(hipGetLastError());
     const double t_m3 = mtrace ? tnow() : 0;
-    J4 acc = G::inf();
-    const u64* T = (const u64*)ctx->h_T;
-    auto add_T = [&](size_t idx) {
-        const u64* t = T + idx * 12;
-        J4 p; memcpy(p.X.v, t, 32); memcpy(p.Y.v, t + 4, 32); memcpy(p.Z.v, t + 8, 32);
-        if (!p.Z.is_zero()) acc = G::add(acc, p);
-    };
-    if (use_marginals) {
-        // host tail: sum_{w,k} 2^(c*w+k) T[w][k], Horner from the top bit down
-        for (int j = pl.W * pl.c - 1; j >= 0; j--) { acc = G::dbl(acc); add_T((size_t)j); }
-    } else {
-        // host tail: sum_w 2^(c*w) * (sum_j T[w][j]), Horner over the windows (c doublings of ONE point between them)
-        for (int w = pl.W - 1; w >= 0; w--) {
-            for (int d = 0; d < pl.c; d++) acc = G::dbl(acc);
-            for (u32 j = 0; j < nblk_ws; j++) add_T((size_t)w * nblk_ws + j);
-        }
-    }
-    (void)sizeof(F);
-    result = acc;
+    result = use_marginals ? msm_horner_tail<C>((const u64*)ctx->h_T, pl.W * pl.c, 0, 0, 1) : msm_horner_tail<C>((const u64*)ctx->h_T, 0, pl.W, nblk_ws, pl.c);
     if (mtrace) fprintf(stderr, "[msm] n=%zu c=%d W=%d K=%d  front(enqueue+sync) %.1f us  back enqueue %.1f us  back wait %.1f us  host tail %.1f us\n", n, pl.c, pl.W, K,
                         (t_m1 - t_m0) * 1e6, (t_m2 - t_m1) * 1e6, (t_m3 - t_m2) * 1e6, (tnow() - t_m3) * 1e6);
     return finish_sharded(result);
 }
 
 // ---- fixed-base MSM over the generator tables (msm.cuh 1c) -----------------------------------------------------------------
-static constexpr u32 FB_ROWS = 65;   // rows at bit positions 0, 4, 8, .., 256: any window width c that is a multiple of 4 finds its rows (the last one serves the carry window)
 // A run of generator-table bases of a fixed-base MSM: which table (0 = G, 1 = H, 2 = PedersenGens {B, B_blinding}), first index, count
 struct FbRun { int table; size_t first, count; size_t stride = 1; };   // stride: base j of the run is table[first + j * stride] (an index-cyclic slice)
 // the rows of `count` bases, slab by slab through the caller's scratch (tmp: 96 B, pref: 32 B, outb: 64 B per row and slab base)
@@ -1185,9 +976,9 @@ static int msm_fixed_run_one(bp_ctx* ctx, const FbRun* runs, int nruns, const Sc
     const bool reduce_after = ctx->shard_world > 1 && shard_mode == 2;
     if (ctx->shard_world > 1 && !reduce_after) FBX(1);
     static const bool off = getenv("ARKBP_MSM_NOFIXED") != nullptr;   // A/B switch
-    // pays from ~2^20 terms (2^21: all kernels 5.6 -> 4.5 ms; at 2^19 and below the single latency-bound aggregation pass costs more
-    // than the saved additions: tools/exp_msm_gens.py)
-    if (off || !ctx->fb_cap || n < std::max<size_t>(ctx->tune_msm_fixed_min, 4096) || n >= ((size_t)1 << 24) || nruns > MSM_MAXSEG) FBX(2);
+    if (off || !ctx->fb_cap || nruns > MSM_MAXSEG) FBX(2);
+    const FbPlan fb = fb_plan(n, C::Fr::BITS, msm_knobs(ctx));   // window width, entry word, bins (msm_plan.hpp)
+    if (fb.decline == 2) FBX(2);
     BaseSegs segs; memset(&segs, 0, sizeof segs);
     u32 at = 0;
     for (int k = 0; k < nruns; k++) {
@@ -1202,42 +993,13 @@ static int msm_fixed_run_one(bp_ctx* ctx, const FbRun* runs, int nruns, const Sc
     segs.start[nruns] = at; segs.nseg = nruns;
     if (at != n) { g_err = "msm_fixed: runs and term count differ"; return BP_E_ARG; }
     hipStream_t st = ctx->stream;
-    // window width: a multiple of 4 (the table rows); cost = mixed adds (n * W) + bucket aggregation (~6 add-equivalents per bucket)
-    const int bits = C::Fr::BITS;
-    int bc = 8; double best = 1e300;
-    for (int c = 8; c <= 24; c += 4) {
-        const double W = bits / c + 1, NBk = std::ldexp(1.0, c - 1);
-        const double cost = n * W * 1.1 + NBk * 6.0;
-        if (cost < best) { best = cost; bc = c; }
-    }
-    static const int c_env = getenv("ARKBP_MSM_FIXED_C") ? atoi(getenv("ARKBP_MSM_FIXED_C")) : 0;
-    if (c_env >= 8 && c_env <= 24 && c_env % 4 == 0) bc = c_env;
-    MsmPlan pl; pl.c = bc; pl.W = bits / bc + 1; pl.NB = 1 << (bc - 1); pl.B = (u32)pl.NB; pl.n = (u32)n; pl.w_lo = 0; pl.w_hi = pl.W;
-    if ((u32)(pl.W - 1) * (u32)(bc / 4) >= FB_ROWS) FBX(4);
-    u32 tbits = 1; while (((size_t)1 << tbits) < n) tbits++;   // (term indices are < n: n itself need not fit)
-    u32 wbits = 1; while ((1 << wbits) < pl.W) wbits++;
-    const u32 vbits = tbits + wbits;
-    // bins: ~6 K entries each; the entry word must hold vterm | fine bucket | sign
-    const double entries = (double)n * (pl.W - 1) + (double)n * 0.5;
-    u32 nbin = 1, lg = 0;
-    while ((double)nbin * 6000.0 < entries && nbin < (u32)pl.NB) { nbin <<= 1; lg++; }
-    int LB = bc - 1 - (int)lg;
-    while (LB > 0 && (LB > 11 || vbits + (u32)LB + 1 > 32)) { nbin <<= 1; LB--; }
-    if (vbits + (u32)LB + 1 > 32 || (size_t)nbin * 4 > 64 * 1024) FBX(5);
-    // expected load of the fullest bin: every full window spreads n(1 - 2^-c) digits uniformly; the top window (tb bits) only reaches
-    // the lowest 2^(tb-1) buckets
-    const int tb = bits - bc * (pl.W - 1);
-    double mu = (double)n * (pl.W - 1) / nbin;
-    if (tb > 0) { const double reach = std::max(1.0, std::ldexp(1.0, tb - 1) / (double)((u32)1 << LB)); mu += (double)n / std::min<double>(reach, nbin); }
-    const size_t cap = (size_t)(mu + 8.0 * std::sqrt(mu) + 64.0);
-    if ((((size_t)1 << LB) + 4 + cap) * 4 > 64 * 1024 || (size_t)nbin * cap >= ((size_t)1 << 31)) FBX(6);
-    BinPlan bp; memset(&bp, 0, sizeof bp);
-    bp.LB = (u32)LB; bp.NBIN = nbin; bp.cap = (u32)cap; bp.wb = 1; bp.tpt = (u32)std::min<size_t>(16, std::max<size_t>(1, n / (256 * 512)));
+    if (fb.decline) FBX(fb.decline);
+    const MsmPlan& pl = fb.pl; const BinPlan& bp = fb.bp;
+    const u32 nbin = bp.NBIN, tbits = fb.tbits;
+    const size_t cap = bp.cap;
+    const int LB = (int)bp.LB, nl = fb.nl;
     SlotPlan sp; memset(&sp, 0, sizeof sp);
     constexpr int NL = MSM_NLMAX;
-    int nl = 2;
-    { u64 capl = MSM_CH; while (capl < entries + 1 && nl < NL) { capl *= MSM_CH; nl++; } }
-    if (nl < 4) nl = 4;
     const size_t Bp1 = (size_t)pl.B + 1;
     const u32 ntiles = (pl.B + MSM_SCAN_TILE - 1) / MSM_SCAN_TILE;
     const u32 nblk_ws = (u32)((pl.NB + 256 * MSM_SEG - 1) / (256 * MSM_SEG));
@@ -1245,7 +1007,7 @@ static int msm_fixed_run_one(bp_ctx* ctx, const FbRun* runs, int nruns, const Sc
     BPCHK(ctx->totals.ensure_zeroed((NL + 2) * 4 + (size_t)ntiles * (NL + 1) * 4, st)); BPCHK(ctx->bin_cur.ensure_zeroed((size_t)nbin * 4, st)); BPCHK(ctx->boff.ensure((size_t)pl.B * 4));
     BPCHK(ctx->slots.ensure((size_t)nbin * cap * 4)); BPCHK(ctx->Tbuf.ensure(((size_t)nblk_ws + 1) * 96));
     if (!ctx->h_totals) HIPCHK(hipHostMalloc((void**)&ctx->h_totals, 64));
-    if (ctx->h_T_cap < 96) { if (ctx->h_T) HIPCHK(hipHostFree(ctx->h_T)); HIPCHK(hipHostMalloc((void**)&ctx->h_T, 4096)); ctx->h_T_cap = 4096; }
+    BPCHK(msm_host_T_ensure(ctx, 96, 4000));
     ScopedK total(ctx, BP_K_MSM_TOTAL);
     u32* lvl = ctx->lvl_off.as<u32>();
     u32* d_tot = ctx->totals.as<u32>();
@@ -1273,35 +1035,18 @@ static int msm_fixed_run_one(bp_ctx* ctx, const FbRun* runs, int nruns, const Sc
     result = G::inf();
     done = true;
     if (tot[0] == 0) { total.stop(); return BP_OK; }
-    const u32 maxcnt = tot[NL];
-    int K = 1;
-    { u64 capl = (u64)1 << chl; while (capl < maxcnt) { capl <<= chl; K++; } }
-    if (K >= nl) { done = false; total.stop(); return BP_OK; }
-    BPCHK(ctx->lvA.ensure((size_t)tot[1] * 96));
-    if (K >= 2) BPCHK(ctx->lvB.ensure((size_t)tot[2] * 96));
-    segs.fixed_c4 = (u32)(bc / 4); segs.tbits = tbits;
-    {
-        ScopedK acc(ctx, BP_K_MSM_ACCUM);
-        hipLaunchKernelGGL(k_msm_accum<C>, dim3((tot[1] + 255) / 256), dim3(256), 0, st, segs, ctx->slots.as<u32>(), lvl, lvl + Bp1, ctx->lvA.as<u32>(), pl.B, tot[1], 2, sp,
-                           (u32)pl.NB, ctx->boff.as<u32>(), chl);
-    }
-    u32* cur = ctx->lvA.as<u32>();
-    u32* nxt = ctx->lvB.as<u32>();
-    {
-    ScopedK agg(ctx, BP_K_MSM_AGG);
-    for (int k = 2; k <= K; k++) {
-        hipLaunchKernelGGL(k_msm_reduce<C>, dim3((tot[k] + 255) / 256), dim3(256), 0, st, cur, lvl + Bp1 * (k - 1), lvl + Bp1 * k, nxt, pl.B, tot[k], chl, pl.B);
-        u32* t2 = cur; cur = nxt; nxt = t2;
-    }
-    hipLaunchKernelGGL(k_msm_window_sums<C>, dim3(nblk_ws, 1), dim3(256), 0, st, cur, lvl + Bp1 * K, ctx->Tbuf.as<u32>(), pl1, nblk_ws);
-    hipLaunchKernelGGL(k_msm_sum_partials<C>, dim3(1), dim3(256), 0, st, ctx->Tbuf.as<u32>(), nblk_ws, ctx->Tbuf.as<u32>() + (size_t)nblk_ws * 24);
-    }
+    segs.fixed_c4 = (u32)(pl.c / 4); segs.tbits = tbits;
+    int K = 1; bool deep = false;
+    BPCHK(msm_tree_back<C>(ctx, segs, ctx->slots.as<u32>(), 2, sp, pl, tot, nl, chl, false, 1, pl.B, 0, false, K, deep, [&](const u32* pts, const u32* offs) {
+        hipLaunchKernelGGL(k_msm_window_sums<C>, dim3(nblk_ws, 1), dim3(256), 0, st, pts, offs, ctx->Tbuf.as<u32>(), pl1, nblk_ws);
+        hipLaunchKernelGGL(k_msm_sum_partials<C>, dim3(1), dim3(256), 0, st, ctx->Tbuf.as<u32>(), nblk_ws, ctx->Tbuf.as<u32>() + (size_t)nblk_ws * 24);
+    }));
+    if (deep) { done = false; total.stop(); return BP_OK; }
     HIPCHK(hipMemcpyAsync(ctx->h_T, ctx->Tbuf.as<u32>() + (size_t)nblk_ws * 24, 96, hipMemcpyDeviceToHost, st));
     total.stop();
     HIPCHK(ctx_stream_wait(ctx));
     HIPCHK(hipGetLastError());
-    const u64* T = (const u64*)ctx->h_T;
-    J4 pnt; memcpy(pnt.X.v, T, 32); memcpy(pnt.Y.v, T + 4, 32); memcpy(pnt.Z.v, T + 8, 32);
+    const J4 pnt = jac_from_words((const u64*)ctx->h_T);
     if (!pnt.Z.is_zero()) result = pnt;   // no Horner tail: the rows already carry the powers of two
     return BP_OK;
 }
@@ -1959,17 +1704,14 @@ template <class C> static int msm_run_pair(bp_ctx* ctx, const BaseSegs segs[2], 
         return BP_OK;
     };
     if (!ctx->tune_msm_pair || n == 0 || n >= (1u << 31) || ctx->shard_world > 1 || shard_mode != -1) return two_calls();
-    MsmPlan pl = msm_plan(n, C::Fr::BITS);
-    if (pl.W > MSM_MAXW) return two_calls();
-    BinPlan bp;
-    const bool binned = msm_bin_plan<C>(ctx, n, pl, bp);   // (false below tune_msm_bin_min)
     for (int j = 0; j < 2; j++)
-        if (msm_glv_route<C>(ctx, segs[j], n, false, -1) || !msm_fs_fits(ctx, pl, bp, binned, segs[j])) return two_calls();
+        if (msm_glv_route<C>(ctx, segs[j], n, false, -1)) return two_calls();
+    const FsShape sh = msm_fs_shape(n, C::Fr::BITS, 2, false, msm_knobs(ctx), 0, -1, segs[0].fixed_c4 || segs[1].fixed_c4);   // (does not fit below tune_msm_bin_min)
+    if (!sh.fits) return two_calls();
     ScalSegs ss[2]; memset(ss, 0, sizeof ss);
     for (int j = 0; j < 2; j++) { ss[j].nseg = 1; ss[j].ptr[0] = d_scalars[j]; ss[j].start[0] = 0; ss[j].start[1] = (u32)n; results[j] = G::inf(); }
-    bool over[2] = {false, false}, ran = false;
-    BPCHK(msm_fs_jobs<C>(ctx, 2, segs, ss, n, scalars_mont, pl, bp, results, over, ran));
-    if (!ran) return two_calls();
+    bool over[2] = {false, false};
+    BPCHK(msm_fs_jobs<C>(ctx, 2, segs, ss, scalars_mont, sh, results, over));
     ctx->pair_passes++;
     for (int j = 0; j < 2; j++) {
         if (!over[j]) continue;
@@ -3933,7 +3675,7 @@ int bp_msm_gens(bp_ctx* c, int use_G, int use_H, size_t off, size_t n, const uin
 }
 int bp_msm_window_count(int curve, size_t n, int* windows, int* window_bits) {
     if ((curve != 0 && curve != 1) || !windows) return BP_E_ARG;
-    MsmPlan pl = msm_plan(n ? n : 1, curve == 0 ? Secq::Fr::BITS : Zorro::Fr::BITS);
+    MsmPlan pl = msm_plan(n ? n : 1, curve == 0 ? Secq::Fr::BITS : Zorro::Fr::BITS, msm_knobs(nullptr));
     *windows = pl.W;
     if (window_bits) *window_bits = pl.c;
     return BP_OK;

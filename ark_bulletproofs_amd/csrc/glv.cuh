@@ -2,6 +2,7 @@
 // the CPU against Python integers; msm.cuh uses it in the MSM partition kernel).
 #pragma once
 #include "fp29.cuh"
+#include "msm_plan.hpp"   // MSM_GLV_WORDS
 
 namespace arkbp {
 
@@ -14,7 +15,6 @@ namespace arkbp {
 // < 1.09 * 2^127, |k2| <= (-b1 + b2) / 2 + eps < 1.28 * 2^127 (tools/gen_params.py asserts the basis; tests check 2 * 10^5 scalars
 // against big integers); a magnitude that does not fit 128 bits returns false and the caller takes the ordinary schedule.
 // out: mag1[4] | mag2[4] | signs (bit 0: k1 < 0, bit 1: k2 < 0) | 3 unused words.
-static constexpr int MSM_GLV_WORDS = 12;
 template <class C> ARKBP_HD void glv_mulhi(const u32 k[8], const u32 (&G)[9], u32 c[5]) {
     u32 acc[17];
 #pragma unroll

@@ -23,17 +23,10 @@
 #include "fe_io.cuh"
 #include "ecq.cuh"
 #include "glv.cuh"
+#include "msm_plan.hpp"   // the plan structs these kernels take as arguments, their constants, and the host planners
 
 namespace arkbp {
 
-#ifndef ARKBP_MSM_CH
-#define ARKBP_MSM_CH 16
-#endif
-static constexpr int MSM_CH = ARKBP_MSM_CH;  // entries per level-1 lane / fan-in of the reduction tree on the skew-tolerant path
-static constexpr int MSM_CHL = MSM_CH == 8 ? 3 : MSM_CH == 16 ? 4 : MSM_CH == 32 ? 5 : 6;
-static_assert((1 << MSM_CHL) == MSM_CH, "ARKBP_MSM_CH must be 8, 16, 32 or 64");
-static constexpr int MSM_CHL_BINNED = MSM_CHL;   // measured: whole-bucket lanes (64) lose more to divergence and a thin grid than the tree levels cost
-static constexpr int MSM_MAXLVL = 8;   // 16^8 = 2^32 >= any bucket population
 static constexpr int MSM_MAXSEG = 6;   // (the deferred second IPA round reads G and H in two pieces each, plus B)
 
 // A logical base vector made of up to MSM_MAXSEG device-resident segments (e.g. G_R || H_L || Q) — the
@@ -85,31 +78,8 @@ __device__ __forceinline__ const u32* seg_scalar_ptr(const ScalSegs& s, u32 idx)
     return s.ptr[k] + (size_t)(idx - s.start[k]) * 8;
 }
 
-// Jobs of the fixed-shape pipeline (section 7): blockIdx.z of its five kernels is the job.  The jobs of one launch have the same
-// term count, hence the same plans; each has its own scalars and bases and its own copy of every buffer the kernels read or write,
-// FsJobs words further per job.  Nothing is shared between jobs, so a job computes exactly what it computes alone; a launch with
-// gridDim.z == 1 needs no strides (FsJobs{}).
-static constexpr int MSM_JOBS = 2;   // (L and R of an inner-product round)
+// One argument per job of the fixed-shape pipeline (section 7; FsJobs in msm_plan.hpp holds the jobs' strides in the buffers)
 template <class T> struct PerJob { T j[MSM_JOBS]; };
-struct FsJobs {   // per-job strides in 32-bit words
-    u64 canon, hist, bin_cur, slots, buckets /* boff, bcnt, loff */, binch, part, sums, T /* the marginals with the info words behind */, over;
-};
-
-struct MsmPlan {
-    int c, W, NB;        // window bits, windows, buckets per window (2^(c-1))
-    u32 B;               // W * NB
-    u32 n;
-    int w_lo, w_hi;      // windows this call accumulates (multi-GPU window sharding); [0, W) = all
-};
-
-// One-pass sort: bucket (w, v) owns the fixed slot range [base[w] + v*cap[w], +cap[w]) so the histogram pass can place
-// entries directly; cap[w] is ~2x the expected population (windows with few possible digit values get wider slots).  A bucket
-// that outgrows its slots raises `overflow` and the exact two-pass path (k_msm_scatter) is used for that MSM instead.
-static constexpr int MSM_MAXW = 88;
-struct SlotPlan {
-    u32 base[MSM_MAXW];
-    u32 cap[MSM_MAXW];
-};
 
 __device__ __forceinline__ Aff load_aff_dev(const u32* p) {
     u32 w[16];
@@ -257,15 +227,6 @@ k_msm_digits(ScalSegs scalars, u32* __restrict__ canon, u32* __restrict__ hist, 
 // and places its entries; k_msm_bin_sort then sorts every bin region by the remaining LB bucket bits inside LDS and emits
 // the per-bucket population (hist) and start (boff) with plain stores.  Bin regions have fixed capacity (mean + 8 sigma);
 // an overflow flags the MSM for the exact path.  The short top window (few distinct digits) keeps the slot scheme.
-struct BinPlan {
-    u32 LB;      // bucket bits resolved inside a bin
-    u32 NBIN;    // bins per window = NB >> LB
-    u32 cap;     // entries per bin region
-    u32 wb;      // windows [0, wb) are binned; [wb, W) use SlotPlan
-    u32 tpt;     // terms per lane in k_msm_bin_partition
-    u32 top_nb;  // > 0: the slot window has this many possible buckets (<= 2048) and is counted per workgroup in LDS
-    u32 glv;     // the scalars are split (glv_split): every term contributes two half-terms 2 * i, 2 * i + 1 of 128 bits
-};
 // entry in a bin region: (term << (LB+1)) | (fine bucket << 1) | sign; with bp.glv the term field is 2 * i + half and `canon` holds
 // MSM_GLV_WORDS words per scalar (the split magnitudes and signs) instead of the 8 canonical words
 template <class C> __global__ void __launch_bounds__(256)
@@ -488,7 +449,6 @@ k_msm_fb_rows(const u32* __restrict__ gens, u32* __restrict__ tmp, u32 n, u32 R)
 // 2. scans.  lvl_off[k] (k = 0..nl-1) has B+1 entries: level 0 counts entries, level k >= 1 counts
 // ceil(cnt / CH^k) chunks.  totals[k] = lvl_off[k][B]; totals[NLMAX] = max bucket population.
 // Three launches: per-tile sums, one-workgroup scan of the tile sums, per-tile exclusive scan.
-static constexpr int MSM_NLMAX = MSM_MAXLVL + 1;
 // population of a bucket at level k+1 given level k (level 0 = entries, level k >= 1 = partial sums).  "Special" buckets (the
 // narrow top window: a handful of buckets holding ~n/2 entries each) go through the first spl levels like everyone else (fully
 // parallel over chunks) and are then finished by k_msm_reduce_special in ONE launch (one workgroup per bucket, <= 32 partials
@@ -900,18 +860,8 @@ k_msm_sum_partials(const u32* __restrict__ T_in, u32 count, u32* __restrict__ T_
 //                        stretching a tree for its sake; copies and clears the overflow flag into the result block
 // One D2H copy, one wait, the host Horner tail.  A bucket above 256 entries or a full bin raises the flag: the MSM is then redone by
 // the general path (skew-tolerant).  Results are identical either way (a sum of the same group elements).
-// blockIdx.z of the five kernels is the JOB (FsJobs above): up to MSM_JOBS MSMs of the same term count share one chain of launches, each
+// blockIdx.z of the five kernels is the JOB (FsJobs, msm_plan.hpp): up to MSM_JOBS MSMs of the same term count share one chain of launches, each
 // in its own stride of every buffer and with its own flag; gridDim.z == 1 with FsJobs{} is the single MSM.
-static constexpr u32 MSM_FS_MAXBINS = 4096;
-static constexpr u32 MSM_FS_BUCKET_MAX = 256;   // entries of a binned bucket; with chcap >= 8 at most 32 partials reach k_msm_reduce_fs
-static constexpr u32 MSM_TOP_PARTS_MAX = 32;   // (a bit of the slot window collects ~n/32 partials: 4 .. 32 workgroups share them)
-struct FsPlan {
-    u32 nbins;      // wb * NBIN (+ 1 when the slot window exists: the last "bin" is that window)
-    u32 has_top;    // the slot window (w = wb) exists
-    u32 top_bits;   // bit length of its largest |digit|
-    u32 max_chunks; // grid bound of k_msm_accum_fs
-    u32 top_parts;  // workgroups per bit of the slot window in k_msm_marginals_fs
-};
 // exclusive scan of src[0..n) (n <= MSM_FS_MAXBINS) into sh[0..n], sh[n] = total; 256 lanes; sh has MSM_FS_MAXBINS + 1 words, ws 4
 __device__ __forceinline__ void fs_block_scan(const u32* __restrict__ src, u32 n, u32* __restrict__ sh, u32* __restrict__ ws) {
     const u32 tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;

@@ -447,8 +447,8 @@ def test_msm_glv_split_schedule_matches_ordinary_and_oracle(oracle):
         sc = np.array([O.fe_from_int(FR, special[i % len(special)]) for i in range(n)])
         e.set_tuning(7, 256)
         assert (e.msm(G, sc) == O.msm(cv, G, sc)).all()
-        # lane-per-addition trees (ARKBP_MSM_NOQUAD has no run-time switch): the quad-cooperative trees are what ran above; the same
-        # inputs through the general path (two-level sort minimum above n) must agree
+        # the quad-cooperative trees are what ran above (a latency-first caller always takes them); the same inputs through the general
+        # path (two-level sort minimum above n) must agree
         sc = O.fe_rand(FR, bytes([77]) * 32, n)
         a = e.msm(G, sc)
         e.set_tuning(1, 1 << 30)
@@ -456,6 +456,33 @@ def test_msm_glv_split_schedule_matches_ordinary_and_oracle(oracle):
         b = e.msm(G, sc)
         e.set_tuning(1, 64)
         assert (a == b).all() and (a == O.msm(cv, G, sc)).all()
+    finally:
+        e.close()
+
+
+def test_msm_glv_overflow_word_is_raised_and_cleared_between_msms(oracle):
+    """The GLV route keeps its overflow word where the other jobs of the fixed-shape chain keep theirs.  2^15 equal scalars put all
+    2^16 half-terms of a window into one bin region, which holds fewer (csrc/msm_plan_selftest.cpp asserts cap < 2n and NBIN > 1 for
+    this plan): the word is raised and the ordinary schedule takes over.  A spread MSM on the same engine must then find the word
+    clear and complete on the GLV route, and the skewed one must overflow again after it.  Every result equals the plain schedule's
+    (BP_TUNE_MSM_GLV_MIN turns the split off), which the tests above tie to the oracle."""
+    import ark_bulletproofs_amd as A
+
+    O, cv = oracle, 0
+    FR = O.fid(cv, True)
+    n = 1 << 15
+    G, H = O.bp_gens(cv, n // 2)
+    bases = np.concatenate([G, H])
+    same = np.repeat(O.fe_rand(FR, bytes([41]) * 32, 1), n, axis=0)
+    spread = O.fe_rand(FR, bytes([42]) * 32, n)
+    e = A.Engine(curve=cv)
+    try:
+        e.set_tuning(7, 256)
+        got = [e.msm(bases, sc) for sc in (same, spread, same)]
+        e.set_tuning(7, 1 << 40)
+        want = [e.msm(bases, sc) for sc in (same, spread)]
+        assert (want[0] != want[1]).any()
+        assert (got[0] == want[0]).all() and (got[1] == want[1]).all() and (got[2] == want[0]).all()
     finally:
         e.close()
 
