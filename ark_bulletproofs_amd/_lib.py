@@ -42,6 +42,8 @@ EXPORTS = [
     "bp_prover_new_like", "bp_prover_assign_multipliers", "bp_ctx_prover_like_stats",
     # a like-prover's witness from device memory
     "bp_prover_assign_multipliers_dev", "bp_witness_range_bits_dev", "bp_ctx_witness_dev_stats",
+    # the resident generators pinned: chain re-derivation and a digest
+    "bp_gens_check", "bp_gens_digest", "bp_host_gens_digest",
 ]
 
 

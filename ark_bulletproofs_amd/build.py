@@ -1,7 +1,7 @@
 """Builds the HIP engine in-tree: ark_bulletproofs_amd/libarkbp_hip.so (gfx950 only).
 hipcc cross-compiles without a GPU, so this also runs in the CPU-only container.
 Three translation units (compiled side by side, linked into one library): arkbp.hip — context, MSM / IPA / R1CS kernels, host
-orchestration, the C ABI —, vfe.hip — the verifier front end (codec, transcript sponge, challenge arithmetic) — and dbg_raw.hip — the
+orchestration, the C ABI —, vfe.hip — the verifier front end (codec, transcript sponge, challenge arithmetic) and the generator digest — and dbg_raw.hip — the
 kernels of the raw-representative unit-test hooks, kept out of the product kernels' code object."""
 import os
 import subprocess
@@ -15,7 +15,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["arkbp.hip", "vfe.hip", "dbg_raw.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Xarch_host", "-march=x86-64-v3", "-Wno-unused-result", "-Wno-c++20-extensions"]
 # what each unit includes beyond the shared field / curve headers (a change there rebuilds only that unit)
-ONLY = {"arkbp.hip": {"host_proto.hpp", "host_math.hpp", "keccak_unrolled.inc", "r1cs_host.inc", "verify_steps.inc", "prove_batch.inc", "verify_each.inc", "verify_locate.inc", "vfy_each.cuh", "msm_batch.inc", "msm_batch.cuh", "pedersen.cuh", "glv.cuh", "blind.cuh", "prove_steps.hpp", "witness_check.cuh", "witness_dev.cuh"}, "vfe.hip": set(), "dbg_raw.hip": {"dbg_raw.cuh"}}
+ONLY = {"arkbp.hip": {"host_proto.hpp", "host_math.hpp", "keccak_unrolled.inc", "r1cs_host.inc", "verify_steps.inc", "prove_batch.inc", "verify_each.inc", "verify_locate.inc", "vfy_each.cuh", "msm_batch.inc", "msm_batch.cuh", "pedersen.cuh", "glv.cuh", "blind.cuh", "prove_steps.hpp", "gens_digest.hpp", "witness_check.cuh", "witness_dev.cuh"}, "vfe.hip": set(), "dbg_raw.hip": {"dbg_raw.cuh"}}
 
 
 def _headers():

@@ -25,6 +25,7 @@
 #include <chrono>
 #include "host_proto.hpp"
 #include "prove_steps.hpp"
+#include "gens_digest.hpp"
 #include "r1cs.cuh"
 #include "pedersen.cuh"
 #include "small.cuh"
@@ -3815,6 +3816,26 @@ int bp_gens_direct_tables_check(bp_ctx* c, uint64_t bad[BP_TABLES_KINDS], uint64
     if (c->host_only) return BP_E_NO_DEVICE;
     HIPCHK(hipSetDevice(c->device));
     return c->curve == 0 ? direct_tables_check<Secq>(c, bad, first_bad, checked) : direct_tables_check<Zorro>(c, bad, first_bad, checked);
+}
+int bp_gens_check(bp_ctx* c, bp_gens_report* out) {
+    if (!c || !out) { g_err = "bp_gens_check: null ctx or report"; return BP_E_ARG; }
+    if (c->host_only) return BP_E_NO_DEVICE;
+    if (!c->gens_cap) { g_err = "bp_gens_check: generators not installed"; return BP_E_GENS_LENGTH; }
+    HIPCHK(hipSetDevice(c->device));
+    return c->curve == 0 ? gens_check<Secq>(c, out) : gens_check<Zorro>(c, out);
+}
+int bp_gens_digest(bp_ctx* c, size_t n, uint8_t out[128]) {
+    if (!c || !out) { g_err = "bp_gens_digest: null ctx or output"; return BP_E_ARG; }
+    if (c->host_only) return BP_E_NO_DEVICE;
+    if (!n) { g_err = "bp_gens_digest: n must be at least 1"; return BP_E_ARG; }
+    if (n > c->gens_cap) { g_err = "bp_gens_digest: n exceeds the installed generators"; return BP_E_GENS_LENGTH; }
+    HIPCHK(hipSetDevice(c->device));
+    return gens_digest_dev(c, n, out);
+}
+int bp_host_gens_digest(int curve, const uint64_t* G_xy, const uint64_t* H_xy, size_t n, const uint64_t B_xy[8], const uint64_t B_blinding_xy[8], uint8_t out[128]) {
+    if ((curve != 0 && curve != 1) || !G_xy || !H_xy || !n || !B_xy || !B_blinding_xy || !out) { g_err = "bp_host_gens_digest: bad argument"; return BP_E_ARG; }
+    host::gens_digest(curve, G_xy, H_xy, n, B_xy, B_blinding_xy, out);
+    return BP_OK;
 }
 int bp_debug_tables_ptr(bp_ctx* c, int which, void** dptr, size_t* nbytes) {
     if (!c || !dptr || !nbytes || which < 0 || which > 9) return BP_E_ARG;

@@ -39,6 +39,15 @@ static inline void sha3_512(u8 out[64], const u8* m, size_t n) {
     keccakf(s);
     memcpy(out, b, 64);
 }
+static inline void sha3_256(u8 out[32], const u8* m, size_t n) {   // FIPS 202: rate 136
+    u64 s[25] = {0};
+    u8* b = (u8*)s;
+    size_t pos = 0;
+    for (size_t i = 0; i < n; i++) { b[pos++] ^= m[i]; if (pos == 136) { keccakf(s); pos = 0; } }
+    b[pos] ^= 0x06; b[135] ^= 0x80;
+    keccakf(s);
+    memcpy(out, b, 32);
+}
 
 // Large host vectors (witness, constraints, blinding draws: 32-170 MB each at 2^20 multipliers) come from fresh mmap'd pages in
 // every statement; with 4 KiB pages that is ~75 k page faults per statement, all serialised on the process's mmap lock against

@@ -1263,5 +1263,26 @@ k_points_on_curve(const u32* __restrict__ pts, u32 n, u32 index0, unsigned long 
     }
     check_tally(wrong, (unsigned long long)index0 + i, bad, first);
 }
+// ---- resident points against re-derived ones (bp_gens_check) --------------------------------------------------------------------------
+// One lane per point.  Both sides are in the resident layout and every kernel stores the canonical representatives, so a point is
+// right iff its 16 words are equal.  A lane that differs adds 1 to *bad and lowers *first to its index; a clean table issues no atomic.
+template <class C> __global__ void __launch_bounds__(256)
+k_points_compare(const u32* __restrict__ want, const u32* __restrict__ have, u32 cnt, unsigned long long index0, unsigned long long* __restrict__ bad,
+                 unsigned long long* __restrict__ first) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    u32 a[16], b[16];
+    load_words8(a, want + (size_t)i * 16);
+    load_words8(a + 8, want + (size_t)i * 16 + 8);
+    load_words8(b, have + (size_t)i * 16);
+    load_words8(b + 8, have + (size_t)i * 16 + 8);
+    u32 diff = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) diff |= a[j] ^ b[j];
+    if (diff) {
+        atomicAdd(bad, 1ull);
+        atomicMin(first, index0 + i);
+    }
+}
 
 }  // namespace arkbp

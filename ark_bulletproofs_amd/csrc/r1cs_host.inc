@@ -205,6 +205,85 @@ template <class C> static int gens_derive(bp_ctx* ctx, size_t cap) {
     ctx->dt_cap = 0;   // (the direct window tables are sized by the capacity: built again on first use)
     return BP_OK;
 }
+// bp_gens_check: the resident generators against party 0's chain, derived again as derive_table_gpu derives it — the same stream walk,
+// the same k_points_decompress, the successes gathered in stream order — but in chunks of at most GENS_CHECK_CHUNK attempts, into
+// scratch, and compared there with the resident slice (k_points_compare); the resident pair against the pair the ctx holds on the
+// host.  Reads and compares only.  Scratch (all sized up front, so that no buffer moves under the counters):
+//   io_out = [6 counters | attempts as points | ok flags | the gathered successes],   io_pts = the pair (ark, resident), then the attempts' x.
+static constexpr size_t GENS_CHECK_CHUNK = (size_t)1 << 16;
+template <class C> static int gens_check(bp_ctx* ctx, bp_gens_report* out) {
+    typedef typename C::Fq FqP;
+    hipStream_t st = ctx->stream;
+    const size_t cap = ctx->gens_cap;
+    const size_t wmax = (std::min(GENS_CHECK_CHUNK, cap * 2 + cap / 8 + 64) + 3) & ~(size_t)3;   // (a multiple of 4: the regions below stay 16-byte aligned)
+    BPCHK(ctx->io_pts.ensure(std::max<size_t>(wmax * 32, 256))); BPCHK(ctx->io_scal.ensure(wmax * 4)); BPCHK(ctx->io_out.ensure(64 + wmax * (64 + 4 + 64)));
+    unsigned long long* d_bad = ctx->io_out.as<unsigned long long>();
+    unsigned long long* d_first = d_bad + BP_GENS_KINDS;
+    u32* d_xy = ctx->io_out.as<u32>() + 16;
+    u32* d_ok = d_xy + wmax * 16;
+    u32* d_sel = d_ok + wmax;
+    HIPCHK(hipMemsetAsync(d_bad, 0, BP_GENS_KINDS * 8, st));
+    HIPCHK(hipMemsetAsync(d_first, 0xff, BP_GENS_KINDS * 8, st));
+    {   // the pair: what the ctx holds on the host (default() or the installed one), imported into scratch
+        host::PedersenGens<C> pc;
+        pc_pair<C>(ctx, pc);
+        uint64_t two[16];
+        memcpy(two, pc.B.x.v, 32); memcpy(two + 4, pc.B.y.v, 32); memcpy(two + 8, pc.B_blinding.x.v, 32); memcpy(two + 12, pc.B_blinding.y.v, 32);
+        u32* d_two = ctx->io_pts.as<u32>();
+        HIPCHK(hipMemcpyAsync(d_two, two, 128, hipMemcpyHostToDevice, st));   // (pageable: the copy has left `two` when the call returns)
+        BPCHK(bp_points_import(ctx, d_two, d_two + 32, 2));
+        hipLaunchKernelGGL(k_points_compare<C>, dim3(1), dim3(256), 0, st, (const u32*)(d_two + 32), (const u32*)ctx->d_pc.as<u32>(), 2u, 0ull, d_bad + BP_GENS_PEDERSEN,
+                           d_first + BP_GENS_PEDERSEN);
+    }
+    std::vector<F4> xs(wmax); std::vector<u32> fl(wmax), ok(wmax), idx;   // (outlive every copy that reads or writes them: each is reused only after a wait)
+    for (int v = 0; ctx->gens_derived && v < 2; v++) {
+        const u32* table = v ? ctx->d_H.as<u32>() : ctx->d_G.as<u32>();
+        host::u8 msg[20]; memcpy(msg, "GeneratorsChain", 15); msg[15] = (host::u8)(v ? 'H' : 'G'); const u32 party = 0; memcpy(msg + 16, &party, 4);
+        host::u8 h[64]; host::sha3_512(h, msg, 20);
+        host::ChaChaRng prng(h);
+        size_t have = 0;
+        while (have < cap) {
+            const size_t want = std::min(wmax, (cap - have) * 2 + (cap - have) / 8 + 64);
+            for (size_t i = 0; i < want; i++) { xs[i] = host::rand_fe<FqP>(prng); fl[i] = ((int32_t)prng.next_u32()) < 0 ? 0x80u : 0u; }
+            HIPCHK(hipMemcpyAsync(ctx->io_pts.p, xs.data(), want * 32, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ctx->io_scal.p, fl.data(), want * 4, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_points_decompress<C>, dim3((u32)((want + 255) / 256)), dim3(256), 0, st, ctx->io_pts.as<u32>(), ctx->io_scal.as<u32>(), d_xy, d_ok, (u32)want);
+            HIPCHK(hipMemcpyAsync(ok.data(), d_ok, want * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx_stream_wait(ctx));
+            HIPCHK(hipGetLastError());
+            idx.clear();
+            for (size_t i = 0; i < want && have + idx.size() < cap; i++) if (ok[i]) idx.push_back((u32)i);
+            if (idx.empty()) continue;
+            const u32 cnt = (u32)idx.size(), gb = (cnt + 255) / 256;
+            HIPCHK(hipMemcpyAsync(ctx->io_scal.p, idx.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_points_gather_import<C>, dim3(gb), dim3(256), 0, st, (const u32*)d_xy, (const u32*)ctx->io_scal.as<u32>(), d_sel, cnt);
+            hipLaunchKernelGGL(k_points_compare<C>, dim3(gb), dim3(256), 0, st, (const u32*)d_sel, table + have * 16, cnt, (unsigned long long)have, d_bad + v, d_first + v);
+            have += cnt;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    unsigned long long hres[2 * BP_GENS_KINDS];
+    HIPCHK(hipMemcpyAsync(hres, d_bad, sizeof hres, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx_stream_wait(ctx));
+    for (int k = 0; k < BP_GENS_KINDS; k++) {
+        out->checked[k] = k == BP_GENS_PEDERSEN ? 2 : ctx->gens_derived ? cap : 0;
+        out->bad[k] = hres[k];
+        out->first_bad[k] = hres[BP_GENS_KINDS + k];
+    }
+    return BP_OK;
+}
+// bp_gens_digest: the kernels are vfe.hip's (next to the sponge's Keccak-f); one copy back, one wait
+static int gens_digest_dev(bp_ctx* ctx, size_t n, uint8_t out[128]) {
+    hipStream_t st = ctx->stream;
+    BPCHK(ctx->io_out.ensure(128 + vfe::gens_digest_ws_bytes(n)));
+    uint8_t* d_out = ctx->io_out.as<uint8_t>();
+    if (vfe::launch_gens_digest(ctx->curve, st, ctx->d_pc.as<u32>(), ctx->d_G.as<u32>(), ctx->d_H.as<u32>(), (u32)n, d_out + 128, d_out)) {
+        g_err = "bp_gens_digest: launch failed"; return BP_E_HIP;
+    }
+    HIPCHK(hipMemcpyAsync(out, d_out, 128, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx_stream_wait(ctx));
+    return BP_OK;
+}
 
 // one commitment MSM: blind * B_blinding + <xs, G[off..]> (+ <ys, H[off..]>)   (prover.rs:516-559, 604-649)
 template <class C> static int commit_msm(bp_ctx* ctx, const F4& blind, const u32* xs, const u32* ys, size_t off, size_t cnt, A4& out) {

@@ -19,6 +19,8 @@
 // Bounds: the sponge is a serial chain per proof (~6 K VALU instructions per permutation, ~150 permutations for m = 256): latency-
 // bound at one wave per 64 proofs, it overlaps with the VALU-bound k_vfy_batch of other batches; k_vfe_points is VALU-bound in the
 // square roots (~370 products per proof point); the rest is small.
+// Also here, because they share keccak_f1600 and nothing else: k_gens_leaves / k_gens_nodes / k_gens_root, the SHA3-256 tree of
+// bp_gens_digest over the resident generators (one lane per leaf or node, every message one block).
 #include <hip/hip_runtime.h>
 #include "fe_io.cuh"
 #include "vfe.hpp"
@@ -434,7 +436,105 @@ k_vfe_sum2(const u32* __restrict__ in, u32 P, u32* __restrict__ sums) {
     }
 }
 
+// ---- digest of the resident generators (bp_gens_digest; the definition is at the declaration in include/arkbp.h) ------------------
+// Every hash is SHA3-256 of ONE block: an 18-byte label, one byte, LE64(index), then NP 64-bit payload words — 27 + 8 NP bytes, 91 for a
+// leaf (one point) and for a node (two children), 123 for the root (three vector roots); the rate is 136.  The 25 state words stay in
+// registers: every index below is a compile-time constant.  out: the first four state words.
+constexpr u64 label_word(const char (&s)[19], int w) {
+    u64 v = 0;
+    for (int i = 0; i < 8; i++) if (8 * w + i < 18) v |= (u64)(u8)s[8 * w + i] << (8 * i);
+    return v;
+}
+template <int NP> __device__ __forceinline__ void gens_hash(u64 out[4], const char (&label)[19], u32 byte18, u64 index, const u64 (&p)[NP]) {
+    static_assert(NP >= 1 && 3 + NP < 17, "one block");
+    const u64 l0 = label_word(label, 0), l1 = label_word(label, 1), l2 = label_word(label, 2);
+    u64 a[25];
+#pragma unroll
+    for (int i = 0; i < 25; i++) a[i] = 0;
+    a[0] = l0; a[1] = l1;
+    a[2] = l2 | ((u64)(byte18 & 0xffu) << 16) | (index << 24);   // bytes 16, 17 of the label | byte 18 | the index's low 5 bytes
+    a[3] = (index >> 40) | (p[0] << 24);                          // the payload starts at byte 27: every word straddles two state words
+#pragma unroll
+    for (int k = 1; k < NP; k++) a[3 + k] = (p[k - 1] >> 40) | (p[k] << 24);
+    a[3 + NP] = (p[NP - 1] >> 40) | (0x06ull << 24);              // SHA-3's domain bits follow the last message byte
+    a[16] ^= 0x80ull << 56;                                       // and the pad ends the 136-byte block
+    keccak_f1600(a);
+#pragma unroll
+    for (int j = 0; j < 4; j++) out[j] = a[j];
+}
+__device__ __forceinline__ void load_hash(u64 h[4], const u8* __restrict__ p) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    const uint4 a = q[0], b = q[1];
+    h[0] = (u64)a.x | ((u64)a.y << 32); h[1] = (u64)a.z | ((u64)a.w << 32); h[2] = (u64)b.x | ((u64)b.y << 32); h[3] = (u64)b.z | ((u64)b.w << 32);
+}
+__device__ __forceinline__ void store_hash(u8* __restrict__ p, const u64 h[4]) {
+    uint4* q = reinterpret_cast<uint4*>(p);
+    q[0] = make_uint4((u32)h[0], (u32)(h[0] >> 32), (u32)h[1], (u32)(h[1] >> 32));
+    q[1] = make_uint4((u32)h[2], (u32)(h[2] >> 32), (u32)h[3], (u32)(h[3] >> 32));
+}
+// one lane per point: the resident words -> the point's ark words (x then y, Montgomery w.r.t. 2^256: what bp_gens_download returns) -> its leaf
+template <class C> __global__ void __launch_bounds__(256)
+k_gens_leaves(const u32* __restrict__ pts, u32 n, u32 tag, u8* __restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 w[16], o[16];
+    load_words8(w, pts + (size_t)i * 16);
+    load_words8(w + 8, pts + (size_t)i * 16 + 8);
+    aff_store_ark<C>(o, aff_load_dev(w));
+    u64 p[8], h[4];
+#pragma unroll
+    for (int k = 0; k < 8; k++) p[k] = (u64)o[2 * k] | ((u64)o[2 * k + 1] << 32);
+    gens_hash<8>(h, "arkbp-gens-leaf-v1", tag, i, p);
+    store_hash(out + (size_t)i * 32, h);
+}
+// one lane per parent: node j of `level` from nodes 2j and 2j + 1 of the level below (m of them); an odd last node goes up unchanged
+__global__ void __launch_bounds__(256)
+k_gens_nodes(const u8* __restrict__ in, u32 m, u32 level, u8* __restrict__ out) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (m + 1) / 2) return;
+    u64 p[8], h[4];
+    load_hash(p, in + (size_t)j * 64);
+    if (2 * j + 1 < m) {
+        load_hash(p + 4, in + (size_t)j * 64 + 32);
+        gens_hash<8>(h, "arkbp-gens-node-v1", level, j, p);
+        store_hash(out + (size_t)j * 32, h);
+    } else {
+        store_hash(out + (size_t)j * 32, p);
+    }
+}
+// one lane: io = [ . | pair root | G root | H root ] -> io[0..32) = the root over the three
+__global__ void __launch_bounds__(64)
+k_gens_root(u8* __restrict__ io, u32 curve, u64 n) {
+    if (threadIdx.x || blockIdx.x) return;
+    u64 p[12], h[4];
+    load_hash(p, io + 32); load_hash(p + 4, io + 64); load_hash(p + 8, io + 96);
+    gens_hash<12>(h, "arkbp-gens-root-v1", curve, n, p);
+    store_hash(io, h);
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
+// root of `m` resident points under `tag` into slot (32 bytes); ws: gens_digest_ws_bytes(m)
+template <class C> static void t_gens_vector(hipStream_t st, const u32* d_pts, u32 m, u32 tag, u8* d_ws, u8* d_slot) {
+    u8* lv[2] = {d_ws, d_ws + (((size_t)m * 32 + 63) & ~(size_t)63)};
+    hipLaunchKernelGGL(k_gens_leaves<C>, dim3((m + 255) / 256), dim3(256), 0, st, d_pts, m, tag, m == 1 ? d_slot : lv[0]);
+    for (u32 level = 1; m > 1; level++) {
+        const u32 parents = (m + 1) / 2;
+        hipLaunchKernelGGL(k_gens_nodes, dim3((parents + 255) / 256), dim3(256), 0, st, lv[(level - 1) & 1], m, level, parents == 1 ? d_slot : lv[level & 1]);
+        m = parents;
+    }
+}
+template <class C> static int t_gens_digest(hipStream_t st, const u32* d_pc, const u32* d_G, const u32* d_H, u32 n, u8* d_ws, u8* d_out) {
+    t_gens_vector<C>(st, d_pc, 2, 0, d_ws, d_out + 32);
+    t_gens_vector<C>(st, d_G, n, 1, d_ws, d_out + 64);
+    t_gens_vector<C>(st, d_H, n, 2, d_ws, d_out + 96);
+    hipLaunchKernelGGL(k_gens_root, dim3(1), dim3(64), 0, st, d_out, (u32)C::ID, (u64)n);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+size_t gens_digest_ws_bytes(size_t n) { return ((n * 32 + 63) & ~(size_t)63) + ((n + 1) / 2) * 32; }
+int launch_gens_digest(int curve, hipStream_t st, const uint32_t* d_pc, const uint32_t* d_G, const uint32_t* d_H, uint32_t n, uint8_t* d_ws, uint8_t* d_out) {
+    return curve == 0 ? t_gens_digest<Secq>(st, d_pc, d_G, d_H, n, d_ws, d_out) : t_gens_digest<Zorro>(st, d_pc, d_G, d_H, n, d_ws, d_out);
+}
+
 template <class C> static int t_points(hipStream_t st, const Shape& sh, const u8* d_proofs, const u32* d_V, u64* d_msg, u32* d_tail_pts, u32* d_status, u32* d_flags) {
     const u64 total = (u64)(11 + 2 * sh.k + sh.m + 5) * sh.P;
     hipLaunchKernelGGL(k_vfe_points<C>, dim3((u32)((total + 255) / 256)), dim3(256), 0, st, sh, d_proofs, d_V, d_msg, d_tail_pts, d_status, d_flags);

@@ -60,5 +60,11 @@ int launch_consts(int curve, hipStream_t st, const Shape& sh, const uint8_t* d_p
 int launch_wv_tab(int curve, hipStream_t st, const Shape& sh, uint32_t p0, uint32_t np, const uint32_t* d_pb, const uint32_t* d_voff, const uint32_t* d_vq,
                   const uint32_t* d_vcid, const uint32_t* d_coefs, uint32_t coef_stride, uint32_t* d_tail_sc);
 
+// bp_gens_digest (include/arkbp.h has the definition): k_gens_leaves over the resident pair d_pc (2 points), d_G[0..n) and d_H[0..n),
+// k_gens_nodes level by level, k_gens_root.  d_ws: gens_digest_ws_bytes(n) bytes of scratch, 64-byte aligned.  d_out: 128 bytes, 32-byte
+// aligned = root | pair root | G root | H root.  n >= 1.
+size_t gens_digest_ws_bytes(size_t n);
+int launch_gens_digest(int curve, hipStream_t st, const uint32_t* d_pc, const uint32_t* d_G, const uint32_t* d_H, uint32_t n, uint8_t* d_ws, uint8_t* d_out);
+
 }  // namespace vfe
 }  // namespace arkbp

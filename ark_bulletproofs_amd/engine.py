@@ -1,4 +1,5 @@
 """Engine: one bp_ctx (one GPU, one HIP stream) and typed wrappers over the C ABI."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -1181,6 +1182,71 @@ def _gens_direct_tables_check(self):
     return tuple([int(v) for v in a] for a in arrs)
 
 
+GENS_G, GENS_H, GENS_PEDERSEN, GENS_KINDS = 0, 1, 2, 3   # include/arkbp.h BP_GENS_*
+
+
+class _GensReportC(C.Structure):
+    _fields_ = [(n, C.c_uint64 * GENS_KINDS) for n in ("checked", "bad", "first_bad")]
+
+
+class GensReport:
+    """bp_gens_report: per kind (GENS_G, GENS_H, GENS_PEDERSEN) the resident entries compared (0: nothing to compare with — the
+    generators were installed by the caller, not derived), those whose words differ, and the smallest index of one (NONE_BAD when none)."""
+
+    def __init__(self, c):
+        self.checked, self.bad, self.first_bad = (tuple(int(v) for v in getattr(c, n)) for n in ("checked", "bad", "first_bad"))
+
+    @property
+    def clean(self):
+        return not any(self.bad)
+
+    def astuple(self):
+        return (self.checked, self.bad, self.first_bad)
+
+    def __eq__(self, other):
+        return isinstance(other, GensReport) and self.astuple() == other.astuple()
+
+    def __repr__(self):
+        return "GensReport(checked=%r, bad=%r, first_bad=%r)" % self.astuple()
+
+
+# bp_gens_digest / bp_host_gens_digest: 32 bytes each — the root over everything, and the roots of the Pedersen pair, of G[0..n) and of
+# H[0..n) it is made of
+GensDigest = collections.namedtuple("GensDigest", "root pair G H")
+
+
+def _gens_digest_of(raw128):
+    raw128 = bytes(raw128)
+    return GensDigest(*(raw128[k * 32:(k + 1) * 32] for k in range(4)))
+
+
+def _gens_check(self):
+    """bp_gens_check: the resident generators against party 0's chain derived again (derived generators only), and the resident
+    Pedersen pair against the pair this engine holds.  Reads and compares; repairs nothing."""
+    r = _GensReportC()
+    check(lib().bp_gens_check(self.ctx, C.byref(r)), "bp_gens_check")
+    return GensReport(r)
+
+
+def _gens_digest(self, n=None):
+    """bp_gens_digest of the resident pair and G[0..n), H[0..n) (n: the installed capacity unless given); host_gens_digest over a copy
+    of the same points gives the same GensDigest"""
+    out = (C.c_uint8 * 128)()
+    check(lib().bp_gens_digest(self.ctx, C.c_size_t(getattr(self, "gens_capacity", 0) if n is None else n), out), "bp_gens_digest")
+    return _gens_digest_of(out)
+
+
+def host_gens_digest(curve, G_xy, H_xy, B, Bb, n=None):
+    """bp_host_gens_digest: the same digest from the caller's own points (ark words), on the host; it hashes bytes and validates nothing"""
+    G, H = u64arr(G_xy, 8), u64arr(H_xy, 8)
+    n = min(len(G), len(H)) if n is None else n
+    assert n <= len(G) and n <= len(H)
+    b, bb = (np.ascontiguousarray(p, dtype=np.uint64).reshape(8) for p in (B, Bb))
+    out = (C.c_uint8 * 128)()
+    check(lib().bp_host_gens_digest(int(curve), ptr(G), ptr(H), C.c_size_t(n), ptr(b), ptr(bb), out), "bp_host_gens_digest")
+    return _gens_digest_of(out)
+
+
 def _debug_tables_ptr(self, which):
     p, n = C.c_void_p(), C.c_size_t(0)
     check(lib().bp_debug_tables_ptr(self.ctx, int(which), C.byref(p), C.byref(n)), "bp_debug_tables_ptr")
@@ -1243,6 +1309,8 @@ def _debug_msm_direct(self, jobs, with_workgroups=False):
 
 Engine.gens_tables_check = _gens_tables_check
 Engine.gens_direct_tables_check = _gens_direct_tables_check
+Engine.gens_check = _gens_check
+Engine.gens_digest = _gens_digest
 Engine.debug_tables_ptr = _debug_tables_ptr
 Engine.debug_table_points = _debug_table_points
 Engine.debug_msm_direct = _debug_msm_direct

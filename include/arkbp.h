@@ -260,6 +260,8 @@ int bp_gens_tables_check(bp_ctx* ctx, uint64_t* bad_fold_entries, uint64_t* bad_
  * WHAT IT CANNOT SEE: BP_TABLES_RESIDENT knows a point only as a point of the curve — two on-curve generators swapped in the
  * resident table, or any other valid point in a generator's place, pass it; the anchors of table 4 then fail (for generators within
  * the tables' reach), and generators beyond the reach are not pinned by anything here.  B and B_blinding are pinned by three anchors.
+ * The resident points themselves are pinned by bp_gens_check (derived generators, against the chain) and bp_gens_digest (any
+ * generators, against the caller's own copy) below.
  * BP_E_ARG for a null ctx, BP_E_NO_DEVICE for a host-only ctx. */
 #define BP_TABLES_DIRECT 0      /* bp_debug_tables_ptr which = 4 */
 #define BP_TABLES_PC_DIRECT 1   /* which = 5 */
@@ -267,6 +269,52 @@ int bp_gens_tables_check(bp_ctx* ctx, uint64_t* bad_fold_entries, uint64_t* bad_
 #define BP_TABLES_RESIDENT 3    /* the resident points themselves: B, B_blinding, G[0..gens_cap), H[0..gens_cap) */
 #define BP_TABLES_KINDS 4
 int bp_gens_direct_tables_check(bp_ctx* ctx, uint64_t bad[BP_TABLES_KINDS], uint64_t first_bad[BP_TABLES_KINDS], uint64_t checked[BP_TABLES_KINDS]);
+/* The anchors of both table checks — the resident generators G[0..gens_capacity), H[0..gens_capacity) and the resident pair B,
+ * B_blinding — against what they should be, word for word (every kernel stores the canonical representatives, so equal points have
+ * equal words).  Three kinds:
+ *   BP_GENS_G, BP_GENS_H  on a ctx whose generators were DERIVED (bp_gens_derive, or bp_gens_share from such a ctx): party 0's
+ *                         GeneratorsChain is walked again as bp_gens_derive walks it — the host draws the ChaCha20 word stream, the GPU
+ *                         tests the attempts, the first successes are gathered in stream order — in chunks of at most 2^16 attempts, into
+ *                         scratch (a few MB at any capacity), and each chunk is compared with the resident slice.  checked = gens_capacity.
+ *                         Caller-installed generators (bp_gens_upload, or a view of such an owner) have no chain to be compared with:
+ *                         checked = 0, bad = 0, first_bad = UINT64_MAX and BP_OK — "0 = nothing to compare with", as "0 = not built"
+ *                         in the table checks; bp_gens_digest below pins those.
+ *   BP_GENS_PEDERSEN      always: the resident pair (index 0 = B, 1 = B_blinding) against the pair the ctx holds on the host
+ *                         (bp_ctx_pedersen_gens: PedersenGens::default() or the installed one).  checked = 2.
+ * bad[k]: the entries whose resident words differ; first_bad[k]: the smallest such index, UINT64_MAX when there is none.  Two swapped
+ * generators count 2; any other point, on the curve or not, in a generator's place counts 1.  The call reads and compares: it builds,
+ * rebuilds and repairs nothing, and the resident table is never written.  A ctx that shares generators checks the owner's points
+ * through its view.  The walk waits for the GPU once per chunk (the same copies of the attempts' verdicts deriving waits for); the
+ * counters come back with one copy after the last launch.  It costs about what bp_gens_derive costs.
+ * BP_E_ARG for a null ctx or report, BP_E_NO_DEVICE for a host-only ctx, BP_E_GENS_LENGTH when no generators are installed. */
+#define BP_GENS_G 0
+#define BP_GENS_H 1
+#define BP_GENS_PEDERSEN 2
+#define BP_GENS_KINDS 3
+typedef struct bp_gens_report {
+    uint64_t checked[BP_GENS_KINDS];   /* entries compared; 0 = nothing to compare with */
+    uint64_t bad[BP_GENS_KINDS];       /* entries whose resident words differ */
+    uint64_t first_bad[BP_GENS_KINDS]; /* smallest such index, UINT64_MAX when none */
+} bp_gens_report;
+int bp_gens_check(bp_ctx* ctx, bp_gens_report* out);
+/* A digest of the resident pair and of G[0..n), H[0..n) that the caller can reproduce from its own copy of the points
+ * (bp_host_gens_digest, or a dozen lines over any SHA3-256): it pins caller-installed generators, and lets the ranks of a multi-GPU
+ * run, or an owner ctx and its views, assert that they hold the same points by comparing 32 bytes.
+ *   H = SHA3-256 (FIPS 202).  P64 = a point's 64 bytes in the ark layout, x then y, each four little-endian u64 Montgomery words: the
+ *   bytes bp_gens_download and bp_ctx_pedersen_gens return.  LE64 = 8 bytes, little-endian.
+ *   leaf(tag, i, P)      = H("arkbp-gens-leaf-v1" || u8 tag || LE64(i) || P64)       tag 0 = the pair (B, B_blinding), 1 = G, 2 = H
+ *   node(level, j, a, b) = H("arkbp-gens-node-v1" || u8 level || LE64(j) || a || b)
+ *   a vector's root: level 0 is its leaves; level k+1 has ceil(m / 2) nodes, node j = node(k + 1, j, N[2j], N[2j+1]) when 2j + 1 < m,
+ *   else N[2j] carried up unchanged; until one node remains (a vector of one point: its leaf).
+ *   root = H("arkbp-gens-root-v1" || u8 curve || LE64(n) || pair root || G root || H root)
+ * out = root | pair root | G root | H root, 32 bytes each.  On the device one lane hashes one leaf or one node (every message is one
+ * Keccak-f block); one copy back of 128 bytes, one wait.  A ctx that shares generators digests the owner's points and pair.
+ * bp_gens_digest: 1 <= n <= gens_capacity; n == 0 or a null pointer is BP_E_ARG, n > gens_capacity BP_E_GENS_LENGTH, a host-only ctx
+ * BP_E_NO_DEVICE.
+ * bp_host_gens_digest (host only): the same over the caller's points.  It validates nothing about them — it hashes bytes; BP_E_ARG
+ * for a null pointer, n == 0 or an unknown curve. */
+int bp_gens_digest(bp_ctx* ctx, size_t n, uint8_t out[128]);
+int bp_host_gens_digest(int curve, const uint64_t* G_xy, const uint64_t* H_xy, size_t n, const uint64_t B_xy[8], const uint64_t B_blinding_xy[8], uint8_t out[128]);
 /* test hook: device address and size in bytes of a table; NULL / 0 when it is not built.  which:
  *   0 / 1  fold tables of G / H, layout [window][digit-1][i] x 64 B;
  *   2 / 3  MSM rows of G / H, layout [row][i] x 64 B;
