@@ -26,6 +26,7 @@
 #include "host_proto.hpp"
 #include "prove_steps.hpp"
 #include "gens_digest.hpp"
+#include "ipa_plan.hpp"
 #include "r1cs.cuh"
 #include "pedersen.cuh"
 #include "small.cuh"
@@ -1776,202 +1777,117 @@ template <class C> static int ipa_begin_dev(bp_ctx* ctx, IpaState& s, const u32*
     BPCHK(ctx->ipa_part.ensure(((std::max(n / 2, fz) + 255) / 256 + 1) * 64));
     return BP_OK;
 }
+// ---- one side of a round's plan (ipa_plan.hpp) as what each MSM runner takes
+// the fixed-base rows: the side's runs; Q = qw * B is row 0 of the Pedersen table, its scalar the inner product scaled by qw
+static inline int ipa_fb_runs(const IpaSide& sd, const u32* sc, FbRun runs[IPA_MAXSEG], ScalSegs& ss) {
+    for (int k = 0; k < sd.nseg; k++) runs[k] = FbRun{sd.seg[k].table, sd.seg[k].first, sd.seg[k].count, sd.seg[k].stride};
+    memset(&ss, 0, sizeof ss);
+    ss.nseg = 2; ss.ptr[0] = sc; ss.start[0] = 0; ss.start[1] = (u32)sd.ip_slot; ss.ptr[1] = sc + (sd.ip_slot + 1) * 8; ss.start[2] = (u32)sd.terms;
+    return sd.nseg;
+}
+// an ordinary MSM over compact vectors (a plan of IpaShape::compact()): G, H name element 0 of the working vectors or of the round's inputs
+static inline BaseSegs ipa_base_segs(const IpaSide& sd, const u32* G, const u32* H, const u32* Q) {
+    const u32* const tab[3] = {G, H, Q};
+    BaseSegs sg; memset(&sg, 0, sizeof sg);
+    sg.nseg = sd.nseg;
+    size_t at = 0;
+    for (int k = 0; k < sd.nseg; k++) { sg.ptr[k] = tab[sd.seg[k].table] + sd.seg[k].first * 16; sg.start[k] = (u32)at; at += sd.seg[k].count; }
+    sg.start[sd.nseg] = (u32)at;
+    return sg;
+}
+// the direct window tables, L and R of a frozen round of half length n: [G | H | B] with c * Q = (c * qw) * B.  Every base belongs to
+// exactly one of L, R (k_ipa_frozen_scalars): L takes G where the element sits in the upper half of its period of the current length
+// and H in the lower half, R the other way round — only those are visited
+static inline void ipa_direct_jobs(const bp_ctx* ctx, const IpaPlan& p, size_t n, const u32* sL, const u32* sR, DtJob jobs[2]) {
+    for (int o = 0; o < 2; o++) {
+        const IpaSide& sd = p.side[o];
+        const u32* sc = o ? sR : sL;
+        DtJob& jb = jobs[o];
+        memset(&jb, 0, sizeof jb);
+        jb.nseg = (u32)sd.nseg;
+        size_t at = 0;
+        for (int k = 0; k < sd.nseg; at += sd.seg[k].count, k++) {
+            const IpaSeg& g = sd.seg[k];
+            if (g.table == IPA_Q) jb.seg[k] = DtSeg{sc + (sd.ip_slot + 1) * 8, dt_base_pc(0), 1, 0, 0, 0};
+            else jb.seg[k] = DtSeg{sc + at * 8, g.table == IPA_G ? dt_base_G(ctx, g.first) : dt_base_H(ctx, g.first), (u32)(g.count / 2), 0, (u32)n, (u32)g.half};
+            jb.terms += jb.seg[k].count;
+        }
+    }
+}
 // L, R of the current round (affine, ark layout): src/inner_product_proof.rs:78-131 (first round) / :166-213
 template <class C> static int ipa_round_lr(bp_ctx* ctx, IpaState& s, uint64_t Lw[8], uint64_t Rw[8]) {
     typedef host::Fld<typename C::Fr> S;
-    typedef host::Grp<C> G;
     if (s.n <= 1 || s.lr_done) { g_err = "ipa: round_LR out of sequence"; return BP_E_ARG; }
     hipStream_t st = ctx->stream;
     const size_t n = s.n / 2;
-    const u32 gb = (u32)((n + 255) / 256);
     u32* sL = ctx->ipa_sL.as<u32>();
     u32* sR = ctx->ipa_sR.as<u32>();
-    if (s.frozen) {
-        const size_t n0 = s.n0;
-        const u32 gf = (u32)((n0 + 255) / 256);
-        if (s.direct) {
-            // one launch: the fold the previous challenge asked for (into the other buffer pair), the scalars, the inner products
-            ScopedK tk(ctx, BP_K_IPA_SCALARS);
-            hipLaunchKernelGGL(k_dt_round<C>, dim3(gf), dim3(256), 0, st, s.d_a, s.d_b, s.d_a_alt, s.d_b_alt, s.d_cG, s.d_cH, (u32)n, (u32)n0, s.fold_pending ? 1 : 0,
-                               words_of<S>(s.pend_u), words_of<S>(s.pend_ui), sL, sR, ctx->ipa_part.as<u32>(), ctx->dt_ticket.as<u32>(), words_of<S>(s.qw));
-            if (s.fold_pending) { std::swap(s.d_a, s.d_a_alt); std::swap(s.d_b, s.d_b_alt); s.fold_pending = false; }
-        } else {
-            ScopedK tk(ctx, BP_K_IPA_SCALARS);
-            hipLaunchKernelGGL(k_ipa_frozen_scalars<C>, dim3(gf), dim3(256), 0, st, s.d_a, s.d_b, s.d_cG, s.d_cH, (u32)n, (u32)n0, sL, sR, ctx->ipa_part.as<u32>());
-            hipLaunchKernelGGL(k_ipa_ip_finish<C>, dim3(1), dim3(256), 0, st, ctx->ipa_part.as<u32>(), gf, sL + 2 * n0 * 8, sR + 2 * n0 * 8, words_of<S>(s.qw), 0);
-        }
-        if (s.direct) {
-            // L and R as sums over the direct window tables, one launch for both: [G[0..n0) | H[0..n0) | B] with c * Q = (c * qw) * B
-            DtJobs jobs; memset(&jobs, 0, sizeof jobs);
-            for (int o = 0; o < 2; o++) {
-                const u32* sc = o ? sR : sL;
-                DtJob& jb = jobs.job[o];
-                // every base belongs to exactly one of L, R (k_ipa_frozen_scalars): L takes G where the element sits in the upper half
-                // of its period of the current length and H in the lower half, R the other way round — only those are visited
-                jb.nseg = 3; jb.terms = (u32)(n0 + 1);
-                jb.seg[0] = DtSeg{sc, dt_base_G(ctx, 0), (u32)(n0 / 2), 0, (u32)n, o == 0 ? 1u : 0u};
-                jb.seg[1] = DtSeg{sc + n0 * 8, dt_base_H(ctx, 0), (u32)(n0 / 2), 0, (u32)n, o == 0 ? 0u : 1u};
-                jb.seg[2] = DtSeg{sc + (2 * n0 + 1) * 8, dt_base_pc(0), 1, 0, 0, 0};
-            }
-            J4 LR[2];
-            BPCHK(msm_direct<C>(ctx, jobs, 2, LR));
-            A4 LRa[2];
-            to_aff_many<C>(LR, 2, LRa);
-            const A4 &La = LRa[0], &Ra = LRa[1];
-            memcpy(Lw, La.x.v, 32); memcpy(Lw + 4, La.y.v, 32);
-            memcpy(Rw, Ra.x.v, 32); memcpy(Rw + 4, Ra.y.v, 32);
-            s.lr_done = true;
-            return BP_OK;
-        }
-        BaseSegs sg; memset(&sg, 0, sizeof sg);
-        sg.nseg = 3; sg.start[0] = 0; sg.start[1] = (u32)n0; sg.start[2] = (u32)(2 * n0); sg.start[3] = (u32)(2 * n0 + 1);
-        sg.ptr[0] = s.d_G; sg.ptr[1] = s.d_H; sg.ptr[2] = s.d_Q;
-        const BaseSegs sgs[2] = {sg, sg};
-        const u32* const scs[2] = {sL, sR};
-        BPCHK(msm_run_pair_aff<C>(ctx, sgs, scs, 2 * n0 + 1, 0, Lw, Rw, s.msm_mode));
-        s.lr_done = true;
-        return BP_OK;
-    }
-    if (s.deferred) {
-        // the round after a deferred first fold: L and R over the generator tables themselves with split scalars (4n + 1 terms each)
-        const size_t n1 = s.n;   // half length of round 1 = current length of a, b
-        {
-            ScopedK tk(ctx, BP_K_IPA_SCALARS);
-            hipLaunchKernelGGL(k_ipa_scalars_deferred<C>, dim3(gb), dim3(256), 0, st, s.d_a, s.d_b, (u32)n, sL, sR, ctx->ipa_part.as<u32>(), s.pending ? (s.h_geo ? 2 : 1) : 0,
-                               words_of<S>(s.gamma_G), words_of<S>(s.gamma_H), s.d_rho_pow, words_of<S>(s.def_tG), words_of<S>(s.def_tH));
-            hipLaunchKernelGGL(k_ipa_ip_finish<C>, dim3(1), dim3(256), 0, st, ctx->ipa_part.as<u32>(), gb, sL + 4 * n * 8, sR + 4 * n * 8, words_of<S>(s.qw), s.have_qw ? 1 : 0);
-        }
-        J4 Lj, Rj; bool dl = false, dr = false;
-        if (s.msm_mode == 2) {
-            // this rank's index-cyclic slice (the working vectors are its compact copy, local element j = table base first + j * stride):
-            // the same four runs read the fixed-base rows with a stride; every MSM ends in exactly one point-reduce, whichever way it ran
-            BaseSegs sg; memset(&sg, 0, sizeof sg);
-            sg.nseg = 5;
-            for (int k = 0; k <= 4; k++) sg.start[k] = (u32)(k * n);
-            sg.start[5] = (u32)(4 * n + 1);
-            const size_t f0 = s.gens_first, sd = s.gens_stride;
-            const bool rows = s.have_qw && ctx->fb_cap;
-            ScalSegs ss; memset(&ss, 0, sizeof ss);
-            ss.nseg = 2; ss.ptr[0] = sL; ss.start[0] = 0; ss.start[1] = (u32)(4 * n); ss.ptr[1] = sL + (4 * n + 1) * 8; ss.start[2] = (u32)(4 * n + 1);
-            if (rows) {
-                FbRun rl[5] = {{0, f0 + (n1 + n) * sd, n, sd}, {0, f0 + n * sd, n, sd}, {1, f0 + n1 * sd, n, sd}, {1, f0, n, sd}, {2, 0, 1}};
-                BPCHK(msm_fixed_run<C>(ctx, rl, 5, ss, 4 * n + 1, 0, Lj, dl, 2));
-            }
-            if (!dl) {
-                sg.ptr[0] = s.d_G_in + (n1 + n) * 16; sg.ptr[1] = s.d_G_in + n * 16; sg.ptr[2] = s.d_H_in + n1 * 16; sg.ptr[3] = s.d_H_in; sg.ptr[4] = s.d_Q;
-                BPCHK(msm_run<C>(ctx, sg, sL, 4 * n + 1, 0, Lj, 0, -1, 2));
-            }
-            if (rows) {
-                ss.ptr[0] = sR; ss.ptr[1] = sR + (4 * n + 1) * 8;
-                FbRun rr[5] = {{0, f0 + n1 * sd, n, sd}, {0, f0, n, sd}, {1, f0 + (n1 + n) * sd, n, sd}, {1, f0 + n * sd, n, sd}, {2, 0, 1}};
-                BPCHK(msm_fixed_run<C>(ctx, rr, 5, ss, 4 * n + 1, 0, Rj, dr, 2));
-            }
-            if (!dr) {
-                sg.ptr[0] = s.d_G_in + n1 * 16; sg.ptr[1] = s.d_G_in; sg.ptr[2] = s.d_H_in + (n1 + n) * 16; sg.ptr[3] = s.d_H_in + n * 16; sg.ptr[4] = s.d_Q;
-                BPCHK(msm_run<C>(ctx, sg, sR, 4 * n + 1, 0, Rj, 0, -1, 2));
-            }
-            A4 La = G::to_aff(Lj), Ra = G::to_aff(Rj);
-            memcpy(Lw, La.x.v, 32); memcpy(Lw + 4, La.y.v, 32);
-            memcpy(Rw, Ra.x.v, 32); memcpy(Rw + 4, Ra.y.v, 32);
-            s.lr_done = true;
-            return BP_OK;
-        }
-        const size_t gofs = (size_t)(s.d_G_in - ctx->d_G.as<u32>()) / 16, hofs = (size_t)(s.d_H_in - ctx->d_H.as<u32>()) / 16;
-        if (s.have_qw && s.msm_mode == -1) {
-            ScalSegs ss; memset(&ss, 0, sizeof ss);
-            ss.nseg = 2; ss.ptr[0] = sL; ss.start[0] = 0; ss.start[1] = (u32)(4 * n); ss.ptr[1] = sL + (4 * n + 1) * 8; ss.start[2] = (u32)(4 * n + 1);
-            FbRun rl[5] = {{0, gofs + n1 + n, n}, {0, gofs + n, n}, {1, hofs + n1, n}, {1, hofs, n}, {2, 0, 1}};
-            BPCHK(msm_fixed_run<C>(ctx, rl, 5, ss, 4 * n + 1, 0, Lj, dl));
-            if (dl) {
-                ss.ptr[0] = sR; ss.ptr[1] = sR + (4 * n + 1) * 8;
-                FbRun rr[5] = {{0, gofs + n1, n}, {0, gofs, n}, {1, hofs + n1 + n, n}, {1, hofs + n, n}, {2, 0, 1}};
-                BPCHK(msm_fixed_run<C>(ctx, rr, 5, ss, 4 * n + 1, 0, Rj, dr));
-            }
-        }
-        if (!(dl && dr)) {
-            BaseSegs sg; memset(&sg, 0, sizeof sg);
-            sg.nseg = 5;
-            for (int k = 0; k <= 4; k++) sg.start[k] = (u32)(k * n);
-            sg.start[5] = (u32)(4 * n + 1);
-            sg.ptr[0] = s.d_G_in + (n1 + n) * 16; sg.ptr[1] = s.d_G_in + n * 16; sg.ptr[2] = s.d_H_in + n1 * 16; sg.ptr[3] = s.d_H_in; sg.ptr[4] = s.d_Q;
-            BPCHK(msm_run<C>(ctx, sg, sL, 4 * n + 1, 0, Lj, 0, -1, s.msm_mode));
-            sg.ptr[0] = s.d_G_in + n1 * 16; sg.ptr[1] = s.d_G_in; sg.ptr[2] = s.d_H_in + (n1 + n) * 16; sg.ptr[3] = s.d_H_in + n * 16;
-            BPCHK(msm_run<C>(ctx, sg, sR, 4 * n + 1, 0, Rj, 0, -1, s.msm_mode));
-        }
-        A4 La = G::to_aff(Lj), Ra = G::to_aff(Rj);
-        memcpy(Lw, La.x.v, 32); memcpy(Lw + 4, La.y.v, 32);
-        memcpy(Rw, Ra.x.v, 32); memcpy(Rw + 4, Ra.y.v, 32);
-        s.lr_done = true;
-        return BP_OK;
-    }
+    const u32* const sc[2] = {sL, sR};
+    // the layout of L and R over compact vectors: the working vectors, or the inputs a first or deferred round still reads (an
+    // index-cyclic rank's vectors are its compact copy of the slice first + j * stride of the generator tables)
+    const IpaShape sh = {s.frozen ? IPA_FROZEN : s.deferred ? IPA_DEFERRED : IPA_PLAIN, n, s.n, s.n0, 0, 0, 1};
+    const IpaPlan plan = ipa_plan(sh);
+    const size_t terms = plan.side[0].terms, ip = plan.side[0].ip_slot;
+    // 1. the scalars of both sides in the order of that layout, the inner products behind them (scaled by qw in the slot after)
     {
         ScopedK tk(ctx, BP_K_IPA_SCALARS);
-        hipLaunchKernelGGL(k_ipa_scalars<C>, dim3(gb), dim3(256), 0, st, s.d_a, s.d_b, s.d_Gf, s.d_Hf, s.first ? 1 : 0, (u32)n, sL, sR, ctx->ipa_part.as<u32>(),
-                           s.pending ? (s.h_geo ? 2 : 1) : 0, words_of<S>(s.gamma_G), words_of<S>(s.gamma_H), s.d_rho_pow);
-        hipLaunchKernelGGL(k_ipa_ip_finish<C>, dim3(1), dim3(256), 0, st, ctx->ipa_part.as<u32>(), gb, sL + 2 * n * 8, sR + 2 * n * 8, words_of<S>(s.qw), s.have_qw ? 1 : 0);
-    }
-    if (s.d_G_in && s.have_qw && s.msm_mode == -1) {
-        // round 1 over the resident generator tables with Q = qw * B: fixed-base MSMs (c_L * Q = (c_L * qw) * B, the scaled
-        // inner products are in slot 2n + 1).  L = <xl, G[n..2n)> + <yl, H[0..n)> + c_L Q,  R = <xr, G[0..n)> + <yr, H[n..2n)> + c_R Q.
-        const size_t gofs = (size_t)(s.d_G_in - ctx->d_G.as<u32>()) / 16, hofs = (size_t)(s.d_H_in - ctx->d_H.as<u32>()) / 16;
-        J4 Lj, Rj; bool dl = false, dr = false;
-        ScalSegs ss; memset(&ss, 0, sizeof ss);
-        ss.nseg = 2; ss.ptr[0] = sL; ss.start[0] = 0; ss.start[1] = (u32)(2 * n); ss.ptr[1] = sL + (2 * n + 1) * 8; ss.start[2] = (u32)(2 * n + 1);
-        FbRun rl[3] = {{0, gofs + n, n}, {1, hofs, n}, {2, 0, 1}};
-        BPCHK(msm_fixed_run<C>(ctx, rl, 3, ss, 2 * n + 1, 0, Lj, dl));
-        if (dl) {
-            ss.ptr[0] = sR; ss.ptr[1] = sR + (2 * n + 1) * 8;
-            FbRun rr[3] = {{0, gofs, n}, {1, hofs + n, n}, {2, 0, 1}};
-            BPCHK(msm_fixed_run<C>(ctx, rr, 3, ss, 2 * n + 1, 0, Rj, dr));
+        const size_t len = s.frozen ? s.n0 : n;
+        const u32 gb = (u32)((len + 255) / 256);
+        const int pend = s.pending ? (s.h_geo ? 2 : 1) : 0;
+        if (s.direct) {
+            // one launch: the fold the previous challenge asked for (into the other buffer pair), the scalars, the inner products
+            hipLaunchKernelGGL(k_dt_round<C>, dim3(gb), dim3(256), 0, st, s.d_a, s.d_b, s.d_a_alt, s.d_b_alt, s.d_cG, s.d_cH, (u32)n, (u32)s.n0, s.fold_pending ? 1 : 0,
+                               words_of<S>(s.pend_u), words_of<S>(s.pend_ui), sL, sR, ctx->ipa_part.as<u32>(), ctx->dt_ticket.as<u32>(), words_of<S>(s.qw));
+            if (s.fold_pending) { std::swap(s.d_a, s.d_a_alt); std::swap(s.d_b, s.d_b_alt); s.fold_pending = false; }
+        } else if (s.frozen) {
+            hipLaunchKernelGGL(k_ipa_frozen_scalars<C>, dim3(gb), dim3(256), 0, st, s.d_a, s.d_b, s.d_cG, s.d_cH, (u32)n, (u32)s.n0, sL, sR, ctx->ipa_part.as<u32>());
+        } else if (s.deferred) {
+            // the round after a deferred first fold: L and R over the generator tables themselves with split scalars
+            hipLaunchKernelGGL(k_ipa_scalars_deferred<C>, dim3(gb), dim3(256), 0, st, s.d_a, s.d_b, (u32)n, sL, sR, ctx->ipa_part.as<u32>(), pend, words_of<S>(s.gamma_G),
+                               words_of<S>(s.gamma_H), s.d_rho_pow, words_of<S>(s.def_tG), words_of<S>(s.def_tH));
+        } else {
+            hipLaunchKernelGGL(k_ipa_scalars<C>, dim3(gb), dim3(256), 0, st, s.d_a, s.d_b, s.d_Gf, s.d_Hf, s.first ? 1 : 0, (u32)n, sL, sR, ctx->ipa_part.as<u32>(), pend,
+                               words_of<S>(s.gamma_G), words_of<S>(s.gamma_H), s.d_rho_pow);
         }
-        if (dl && dr) {
-            A4 La = G::to_aff(Lj), Ra = G::to_aff(Rj);
-            memcpy(Lw, La.x.v, 32); memcpy(Lw + 4, La.y.v, 32);
-            memcpy(Rw, Ra.x.v, 32); memcpy(Rw + 4, Ra.y.v, 32);
-            s.lr_done = true;
-            return BP_OK;
+        if (!s.direct)
+            hipLaunchKernelGGL(k_ipa_ip_finish<C>, dim3(1), dim3(256), 0, st, ctx->ipa_part.as<u32>(), gb, sL + ip * 8, sR + ip * 8, words_of<S>(s.qw), !s.frozen && s.have_qw ? 1 : 0);
+    }
+    // 2. who computes the sums, and over what
+    const bool tables = s.d_G_in != nullptr;   // (never once frozen)
+    const IpaPolicy pol = ipa_policy({s.frozen, s.direct, s.deferred, s.first, tables, s.have_qw, ctx->fb_cap != 0, s.msm_mode, s.gens_stride});
+    BaseSegs segs[2];
+    for (int o = 0; o < 2; o++) segs[o] = ipa_base_segs(plan.side[o], tables ? s.d_G_in : s.d_G, tables ? s.d_H_in : s.d_H, s.d_Q);
+    IpaPlan rows = plan;   // the same layout in the resident tables' own indices
+    if (pol.rows != IPA_ROWS_NONE) {
+        IpaShape rs = sh;
+        if (s.msm_mode == 2) { rs.g_first = rs.h_first = s.gens_first; rs.stride = s.gens_stride; }
+        else { rs.g_first = (size_t)(s.d_G_in - ctx->d_G.as<u32>()) / 16; rs.h_first = (size_t)(s.d_H_in - ctx->d_H.as<u32>()) / 16; }
+        rows = ipa_plan(rs);
+    }
+    // 3. the fixed-base rows of the resident tables first where the policy says so (Q = qw * B rides along as a row of the Pedersen
+    // table; a slice reads the rows with its stride), then what they declined.  Every MSM of a slice ends in exactly one point-reduce.
+    J4 P[2]; bool done[2] = {false, false};
+    for (int o = 0; o < 2; o++) {
+        if (pol.rows == IPA_ROWS_EACH || (pol.rows == IPA_ROWS_L_THEN_R && (o == 0 || done[0]))) {
+            FbRun runs[IPA_MAXSEG]; ScalSegs ss;
+            const int nruns = ipa_fb_runs(rows.side[o], sc[o], runs, ss);
+            BPCHK(msm_fixed_run<C>(ctx, runs, nruns, ss, terms, 0, P[o], done[o], pol.rows == IPA_ROWS_EACH ? 2 : -1));
         }
+        if (pol.fallback == IPA_FB_SIDE && !done[o]) BPCHK(msm_run<C>(ctx, segs[o], sc[o], terms, 0, P[o], 0, -1, s.msm_mode));
     }
-    BaseSegs sg; memset(&sg, 0, sizeof sg);
-    sg.nseg = 3; sg.start[0] = 0; sg.start[1] = (u32)n; sg.start[2] = (u32)(2 * n); sg.start[3] = (u32)(2 * n + 1);
-    const u32* Gb = s.d_G_in ? s.d_G_in : s.d_G;
-    const u32* Hb = s.d_H_in ? s.d_H_in : s.d_H;
-    sg.ptr[0] = Gb + n * 16; sg.ptr[1] = Hb; sg.ptr[2] = s.d_Q;
-    J4 Lj, Rj;
-    // Index-cyclic sharded prover, round 1: this rank's terms are ITS slice of the generator tables (bases first + j * world) — with
-    // fixed-base rows installed they keep the single-GPU schedule, reading the rows with a stride (Q = qw * B rides along as a row of
-    // the Pedersen table with this rank's partial inner product).  A rank whose scalars do not go through it runs the ordinary MSM
-    // over its compact copy: either way one point-reduce per L and per R.
-    const bool cyc_fixed = s.first && s.msm_mode == 2 && s.gens_stride > 1 && s.have_qw && ctx->fb_cap;
-    bool dl = false, dr = false;
-    if (cyc_fixed) {
-        ScalSegs ss; memset(&ss, 0, sizeof ss);
-        ss.nseg = 2; ss.ptr[0] = sL; ss.start[0] = 0; ss.start[1] = (u32)(2 * n); ss.ptr[1] = sL + (2 * n + 1) * 8; ss.start[2] = (u32)(2 * n + 1);
-        const size_t f0 = s.gens_first, sd = s.gens_stride;
-        FbRun rl[3] = {{0, f0 + n * sd, n, sd}, {1, f0, n, sd}, {2, 0, 1}};
-        BPCHK(msm_fixed_run<C>(ctx, rl, 3, ss, 2 * n + 1, 0, Lj, dl, 2));
+    if (pol.fallback == IPA_FB_DIRECT) {
+        DtJobs jobs; memset(&jobs, 0, sizeof jobs);
+        ipa_direct_jobs(ctx, plan, n, sL, sR, jobs.job);
+        BPCHK(msm_direct<C>(ctx, jobs, 2, P));
+    } else if (pol.fallback == IPA_FB_PAIR && !(done[0] && done[1])) {
+        BPCHK(msm_run_pair<C>(ctx, segs, sc, terms, 0, P, s.msm_mode));
+    } else if (pol.fallback == IPA_FB_TWO && !(done[0] && done[1])) {
+        for (int o = 0; o < 2; o++) BPCHK(msm_run<C>(ctx, segs[o], sc[o], terms, 0, P[o], 0, -1, s.msm_mode));
     }
-    if (!cyc_fixed) {   // neither side goes through the fixed-base rows: L over [G_hi | H_lo | Q] and R over [G_lo | H_hi | Q] as one pair
-        BaseSegs sgs[2] = {sg, sg};
-        sgs[1].ptr[0] = Gb; sgs[1].ptr[1] = Hb + n * 16;
-        const u32* const scs[2] = {sL, sR};
-        BPCHK(msm_run_pair_aff<C>(ctx, sgs, scs, 2 * n + 1, 0, Lw, Rw, s.msm_mode));
-        s.lr_done = true;
-        return BP_OK;
-    }
-    if (!dl) BPCHK(msm_run<C>(ctx, sg, sL, 2 * n + 1, 0, Lj, 0, -1, s.msm_mode));
-    sg.ptr[0] = Gb; sg.ptr[1] = Hb + n * 16;
-    if (cyc_fixed) {
-        ScalSegs ss; memset(&ss, 0, sizeof ss);
-        ss.nseg = 2; ss.ptr[0] = sR; ss.start[0] = 0; ss.start[1] = (u32)(2 * n); ss.ptr[1] = sR + (2 * n + 1) * 8; ss.start[2] = (u32)(2 * n + 1);
-        const size_t f0 = s.gens_first, sd = s.gens_stride;
-        FbRun rr[3] = {{0, f0, n, sd}, {1, f0 + n * sd, n, sd}, {2, 0, 1}};
-        BPCHK(msm_fixed_run<C>(ctx, rr, 3, ss, 2 * n + 1, 0, Rj, dr, 2));
-    }
-    if (!dr) BPCHK(msm_run<C>(ctx, sg, sR, 2 * n + 1, 0, Rj, 0, -1, s.msm_mode));
-    A4 La = G::to_aff(Lj), Ra = G::to_aff(Rj);
-    memcpy(Lw, La.x.v, 32); memcpy(Lw + 4, La.y.v, 32);
-    memcpy(Rw, Ra.x.v, 32); memcpy(Rw + 4, Ra.y.v, 32);
+    // 4. the one exit
+    A4 LR[2];
+    to_aff_many<C>(P, 2, LR);
+    aff_out<C>(Lw, LR[0]); aff_out<C>(Rw, LR[1]);
     s.lr_done = true;
     return BP_OK;
 }
@@ -1986,6 +1902,7 @@ template <class C> static int ipa_round_fold(bp_ctx* ctx, IpaState& s, const uin
     const bool first = s.first;
     F4 u; memcpy(u.v, uw, 32);
     F4 ui = S::inv(u);
+    auto advance = [&]() { s.round++; s.n = n; s.lr_done = false; };   // every exit: the round is over
     // the ladder kernels fold in place: they need the round-1 inputs in the working vectors (the table fold reads them from the
     // resident generator tables and needs no copy)
     auto working_copy = [&]() -> int {
@@ -2006,7 +1923,7 @@ template <class C> static int ipa_round_fold(bp_ctx* ctx, IpaState& s, const uin
         } else {
             s.fold_pending = true; s.pend_u = u; s.pend_ui = ui;
         }
-        s.round++; s.n = n; s.lr_done = false;
+        advance();
         return BP_OK;
     }
     if (s.frozen) {
@@ -2015,7 +1932,7 @@ template <class C> static int ipa_round_fold(bp_ctx* ctx, IpaState& s, const uin
         hipLaunchKernelGGL(k_ipa_frozen_fold<C>, dim3((u32)((s.n0 + 255) / 256)), dim3(256), 0, st, s.d_cG, s.d_cH, (u32)n, (u32)s.n0, words_of<S>(u), words_of<S>(ui));
         tk.stop();
         HIPCHK(hipGetLastError());
-        s.round++; s.n = n; s.lr_done = false;
+        advance();
         return BP_OK;
     }
     {
@@ -2085,7 +2002,7 @@ template <class C> static int ipa_round_fold(bp_ctx* ctx, IpaState& s, const uin
                 }
                 s.deferred = false;
             } else
-            BPCHK(launch_uniform_fold<C>(ctx, d_G, d_H, n, S::sqr(ui), s.h_geo ? S::mul(S::sqr(u), s.rho_pw[k]) : S::sqr(u), 3));
+            BPCHK(launch_uniform_fold<C>(ctx, d_G, d_H, n, t2G, t2H, 3));
             s.gamma_G = S::mul(s.gamma_G, u);
             s.gamma_H = s.h_geo ? S::mul(S::mul(s.gamma_H, ui), s.rho_pw[32 + k]) : S::mul(s.gamma_H, ui);
             s.pending = true;
@@ -2094,9 +2011,7 @@ template <class C> static int ipa_round_fold(bp_ctx* ctx, IpaState& s, const uin
     HIPCHK(hipGetLastError());
     s.first = false;
     if (!s.deferred) s.d_G_in = s.d_H_in = nullptr;   // (a deferred fold keeps reading the generator tables for one more round)
-    s.round++;
-    s.n = n;
-    s.lr_done = false;
+    advance();
     if (s.allow_freeze && n >= 2 && n <= ctx->tune_ipa_freeze_len) {   // the vectors just reached the freeze length: coefficients from here on
         BPCHK(ctx->ipa_cG.ensure(n * 32)); BPCHK(ctx->ipa_cH.ensure(n * 32));
         s.d_cG = ctx->ipa_cG.as<u32>(); s.d_cH = ctx->ipa_cH.as<u32>();
@@ -2122,6 +2037,18 @@ template <class C> static int ipa_finish_dev(bp_ctx* ctx, IpaState& s, uint64_t 
     if (ctx->profiling) collect_timers(ctx);
     return BP_OK;
 }
+// the rounds down to length stop_len: L and R of a round into its row of L_out / R_out, the challenge from the callback, the folds
+template <class C> static int ipa_rounds(bp_ctx* ctx, IpaState& s, size_t stop_len, const ChallengeFn& challenge, uint64_t* L_out, uint64_t* R_out) {
+    while (s.n > stop_len) {
+        uint64_t *Lw = L_out + 8 * s.round, *Rw = R_out + 8 * s.round, uw[4];
+        BPCHK(ipa_round_lr<C>(ctx, s, Lw, Rw));
+        int rc = challenge(Lw, Rw, uw);
+        if (rc) { g_err = "ipa_create: challenge callback failed"; return rc < 0 ? rc : BP_E_ARG; }
+        BPCHK(ipa_round_fold<C>(ctx, s, uw));
+    }
+    return BP_OK;
+}
+static inline size_t ipa_gather_len(const bp_ctx* ctx) { return ipa_gather_len(ctx->tune_ipa_freeze_len, (size_t)ctx->shard_world); }
 
 // ---- InnerProductProof::create orchestration (src/inner_product_proof.rs:37-239): all vectors device-resident in the engine's
 // layouts and consumed (folded in place), like the reference's by-value Vec arguments.
@@ -2157,14 +2084,7 @@ static int ipa_create_dev(bp_ctx* ctx, const u32* d_Q, const u32* d_Gf, const u3
         s.d_G_in = s.d_H_in = nullptr;
         s.frozen = true; s.direct = true; s.n0 = n;
     }
-    while (s.n != 1) {
-        uint64_t Lw[8], Rw[8], uw[4];
-        BPCHK(ipa_round_lr<C>(ctx, s, Lw, Rw));
-        memcpy(L_out + 8 * s.round, Lw, 64); memcpy(R_out + 8 * s.round, Rw, 64);
-        int rc = challenge(Lw, Rw, uw);
-        if (rc) { g_err = "ipa_create: challenge callback failed"; return rc < 0 ? rc : BP_E_ARG; }
-        BPCHK(ipa_round_fold<C>(ctx, s, uw));
-    }
+    BPCHK(ipa_rounds<C>(ctx, s, 1, challenge, L_out, R_out));
     return ipa_finish_dev<C>(ctx, s, a_out, b_out);
 }
 
@@ -2184,9 +2104,7 @@ static int ipa_create_cyclic(bp_ctx* ctx, const u32* d_Q, const u32* d_Gf, const
     const size_t W = (size_t)ctx->shard_world, r = (size_t)ctx->shard_rank;
     const int w = ipa_lg2(W);
     const size_t n_loc = N / W;
-    size_t S_glob = std::max<size_t>(std::max<size_t>(ctx->tune_ipa_freeze_len, W), 2);   // global length at which the ranks gather
-    { size_t p = 1; while (p < S_glob) p <<= 1; S_glob = p; }
-    const size_t S_loc = S_glob / W;
+    const size_t S_glob = ipa_gather_len(ctx), S_loc = S_glob / W;   // global, local length at which the ranks gather
     // this rank's slices (the generator tables are read in place: no full working copy)
     BPCHK(ctx->cyc_a.ensure(std::max(n_loc, S_glob) * 32)); BPCHK(ctx->cyc_b.ensure(std::max(n_loc, S_glob) * 32));
     BPCHK(ctx->cyc_Gf.ensure(n_loc * 32)); BPCHK(ctx->cyc_Hf.ensure(n_loc * 32));
@@ -2214,14 +2132,7 @@ static int ipa_create_cyclic(bp_ctx* ctx, const u32* d_Q, const u32* d_Gf, const
     F4 rho_r = S::one(), rho_mr = S::one();   // rho^rank, rho^-rank
     if (geo) for (int k = 0; k < w; k++) if ((r >> k) & 1) { rho_r = S::mul(rho_r, rho_pw[32 + k]); rho_mr = S::mul(rho_mr, rho_pw[k]); }
     s.geo_k0 = rho_r; s.have_k0 = geo;
-    while (s.n > S_loc) {
-        uint64_t Lw[8], Rw[8], uw[4];
-        BPCHK(ipa_round_lr<C>(ctx, s, Lw, Rw));
-        memcpy(L_out + 8 * s.round, Lw, 64); memcpy(R_out + 8 * s.round, Rw, 64);
-        int rc = challenge(Lw, Rw, uw);
-        if (rc) { g_err = "ipa_create: challenge callback failed"; return rc < 0 ? rc : BP_E_ARG; }
-        BPCHK(ipa_round_fold<C>(ctx, s, uw));
-    }
+    BPCHK(ipa_rounds<C>(ctx, s, S_loc, challenge, L_out, R_out));
     // gather: [a | b | G | H] of the S_loc local elements, ark layouts, from every rank; global index = rank + j * W
     const size_t m = s.n;   // == S_loc
     const size_t per = m * (32 + 32 + 64 + 64);
@@ -2271,23 +2182,14 @@ static int ipa_create_cyclic(bp_ctx* ctx, const u32* d_Q, const u32* d_Gf, const
     HIPCHK(hipGetLastError());
     HIPCHK(ctx_stream_wait(ctx));   // ga .. gH are locals
     t.frozen = true; t.n0 = S_glob;
-    while (t.n != 1) {
-        uint64_t Lw[8], Rw[8], uw[4];
-        BPCHK(ipa_round_lr<C>(ctx, t, Lw, Rw));
-        memcpy(L_out + 8 * t.round, Lw, 64); memcpy(R_out + 8 * t.round, Rw, 64);
-        int rc = challenge(Lw, Rw, uw);
-        if (rc) { g_err = "ipa_create: challenge callback failed"; return rc < 0 ? rc : BP_E_ARG; }
-        BPCHK(ipa_round_fold<C>(ctx, t, uw));
-    }
+    BPCHK(ipa_rounds<C>(ctx, t, 1, challenge, L_out, R_out));
     return ipa_finish_dev<C>(ctx, t, a_out, b_out);
 }
 // whether a sharded prover can partition an IPA of padded size N this way
 static inline bool ipa_cyclic_applies(const bp_ctx* ctx, size_t N) {
     const size_t W = (size_t)ctx->shard_world;
     if (W <= 1 || !shard_has_allgather(ctx) || (W & (W - 1)) || N < ctx->tune_cyclic_min) return false;
-    size_t S_glob = std::max<size_t>(std::max<size_t>(ctx->tune_ipa_freeze_len, W), 2);
-    { size_t p = 1; while (p < S_glob) p <<= 1; S_glob = p; }
-    return N >= 2 * S_glob && N / W >= 2;   // at least one partitioned round
+    return N >= 2 * ipa_gather_len(ctx) && N / W >= 2;   // at least one partitioned round
 }
 
 // uploads the host vectors of an IPA instance into the ctx's working buffers (engine layouts)

@@ -130,17 +130,10 @@ template <class C> static int pb_run_group(bp_ctx* ctx, PbGroup<C>& g) {
     for (size_t r = 0; r < lg; r++) {
         const size_t n = N >> (r + 1);
         const bool fold = r > 0;
+        const IpaPlan plan = ipa_plan({IPA_FROZEN, n, 0, N, 0, 0, 1});   // (ipa_round_lr's direct route, every member's vectors frozen at N)
         for (size_t j = 0; j < B; j++) {
             fill_desc(j, fold);
-            for (int o = 0; o < 2; o++) {   // L and R: the same runs as ipa_round_lr's direct path
-                DtJob& jb = hj[2 * j + o];
-                memset(&jb, 0, sizeof jb);
-                const u32* sc = vec(j, o ? L.o_sR : L.o_sL);
-                jb.nseg = 3; jb.terms = (u32)(N + 1);
-                jb.seg[0] = DtSeg{sc, dt_base_G(ctx, 0), (u32)(N / 2), 0, (u32)n, o == 0 ? 1u : 0u};
-                jb.seg[1] = DtSeg{sc + N * 8, dt_base_H(ctx, 0), (u32)(N / 2), 0, (u32)n, o == 0 ? 0u : 1u};
-                jb.seg[2] = DtSeg{sc + (2 * N + 1) * 8, dt_base_pc(0), 1, 0, 0, 0};
-            }
+            ipa_direct_jobs(ctx, plan, n, vec(j, L.o_sL), vec(j, L.o_sR), hj + 2 * j);
         }
         HIPCHK(hipMemcpyAsync(ar + L.desc_off, hs, B * sizeof(DtRoundDesc) + 2 * B * sizeof(DtJob), hipMemcpyHostToDevice, st));
         {
