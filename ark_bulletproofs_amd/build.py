@@ -15,7 +15,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["arkbp.hip", "vfe.hip", "dbg_raw.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Xarch_host", "-march=x86-64-v3", "-Wno-unused-result", "-Wno-c++20-extensions"]
 # what each unit includes beyond the shared field / curve headers (a change there rebuilds only that unit)
-ONLY = {"arkbp.hip": {"host_proto.hpp", "host_math.hpp", "keccak_unrolled.inc", "r1cs_host.inc", "verify_steps.inc", "prove_batch.inc", "verify_each.inc", "verify_locate.inc", "vfy_each.cuh", "msm_batch.inc", "msm_batch.cuh", "pedersen.cuh", "glv.cuh", "blind.cuh", "prove_steps.hpp", "ipa_plan.hpp", "gens_digest.hpp", "witness_check.cuh", "witness_dev.cuh"}, "vfe.hip": set(), "dbg_raw.hip": {"dbg_raw.cuh"}}
+ONLY = {"arkbp.hip": {"host_proto.hpp", "host_math.hpp", "keccak_unrolled.inc", "r1cs_host.inc", "verify_steps.inc", "verify_dev.inc", "vfy_dev_plan.hpp", "prove_batch.inc", "verify_each.inc", "verify_locate.inc", "vfy_each.cuh", "msm_batch.inc", "msm_batch.cuh", "pedersen.cuh", "glv.cuh", "blind.cuh", "prove_steps.hpp", "ipa_plan.hpp", "gens_digest.hpp", "witness_check.cuh", "witness_dev.cuh"}, "vfe.hip": set(), "dbg_raw.hip": {"dbg_raw.cuh"}}
 
 
 def _headers():

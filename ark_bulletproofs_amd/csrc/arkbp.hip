@@ -27,6 +27,7 @@
 #include "prove_steps.hpp"
 #include "gens_digest.hpp"
 #include "ipa_plan.hpp"
+#include "vfy_dev_plan.hpp"
 #include "r1cs.cuh"
 #include "pedersen.cuh"
 #include "small.cuh"

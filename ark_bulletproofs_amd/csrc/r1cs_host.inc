@@ -1963,578 +1963,8 @@ template <class C> static void provider_subset_with_prologue(const VfyProvider<C
     };
 }
 
-// ---- batch_verify with the per-proof front end on the GPU -------------------------------------------------------------------
-// For a batch of like-instances of one single-phase statement the host does NOT replay transcripts: it stages the proofs' bytes,
-// the commitments and the transcript states in pinned memory and enqueues
-//   k_vfe_points -> k_vfe_sponge -> k_vfe_consts / k_vfe_wv / k_vfe_sum2 (vfe.hip) -> per block of 512: k_vfy_tables, k_vfy_batch ->
-//   the mega-check MSM
-// on the ctx's stream; one wait at the end.  The challenges are derived on the device (Keccak-f / STROBE schedule / ChaCha20 /
-// Fr::rand), the decompressed points never leave it.  `handled` stays false when the batch does not qualify or when the kernels
-// flagged anything the reference rejects (malformed bytes, an identity point under validate_and_append_point, ...): the caller then
-// runs the host replay — of the flagged instances alone where the kernels named them (vfy_replay_flagged) —, which reports the
-// reference's error in instance order.
-static constexpr size_t VFY_BLOCK = 512;           // proofs per k_vfy_tables / k_vfy_batch launch
-template <class C> struct VfeClassDev {
-    std::weak_ptr<const host::FrozenRecording> base;
-    const host::FrozenRecording* base_ptr = nullptr;
-    DevBuf sched, voff, vq, vc, coefs, iota;
-    bool coefs_up = false;       // coefs holds this class's coefficient table (uploaded by the first batch that needs it)
-    std::string tkey;            // structure digest of the template this class evaluates with
-    size_t N = 0;
-    ~VfeClassDev() { sched.release(); voff.release(); vq.release(); vc.release(); coefs.release(); iota.release(); }
-};
-// Two-phase batches (BP_TUNE_VFY_DEVICE = 2): what the reference instance's live randomized phase recorded.  Every other instance's
-// callbacks must reproduce it with their own challenges: same labels, multipliers, constraint offsets and term variables, a +-1 where
-// it has +-1, one value per coefficient id.  The coefficient ids are the canonical numbering of the whole recording (CanonState):
-// [0, nbase) the shared phase-1 values, then the phase-2 ones.
-static constexpr size_t VFY2_TABLE_BUDGET = (size_t)256 << 20;   // bytes of per-proof gadget challenges + coefficient tables per batch
-template <class C> struct Vfe2Ref {
-    std::vector<std::string> labels;     // gadget challenges in drawing order
-    std::vector<F4> chal0;               // instance 0's, from its live transcript
-    size_t n = 0, n1 = 0, nbase = 0, ncoef = 0;
-    std::vector<size_t> off;             // the phase-2 part: constraint offsets (cs_off)
-    std::vector<host::Var> vars;         // its terms' variables
-    std::vector<u32> cid;                // its terms' coefficient ids
-    std::vector<F4> base_coefs;          // ids [0, nbase)
-};
-// An event on the ctx's stream, polled with sleeps (HIP's own synchronisation busy-waits on this stack; see event_wait)
-static hipError_t vfe_poll(bp_ctx* ctx, hipEvent_t ev) {
-    wait_thread_setup();
-    const long ns = 1000L * (ctx->tune_wait_sleep ? (long)ctx->tune_wait_sleep : 100L);
-    for (;;) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady) return e;
-        struct timespec ts = {0, ns};
-        nanosleep(&ts, nullptr);
-    }
-}
-// One class of like-instances on its way through the device front end: batch_verify_device runs ONE job that is the whole batch,
-// batch_verify_classes several, which share the g / h accumulators, the tail array, the wait and the mega-check MSM.  The steps:
-// vfy_dev_admit (entry conditions, template, class constants; may decline, may wait for a cold upload) -> vfy_dev_place (where
-// each job lives in the ctx's buffers) -> vfy_dev_reserve (every allocation of the call, the zeroing) -> vfy_dev_launch per job
-// (staging, the launch chain) -> vfy_dev_finish (ONE wait, the head scalars, ONE MSM).
-static constexpr size_t VFY_SLOTS = 96;                              // block result slots (r_small / h_small) of one call, all jobs together
-static constexpr size_t VFY_HS_SUMS = VFY_SLOTS * 32;                // h_small: [deltas (VFY_SLOTS) | B / B_blinding sums (2 per job) | status]
-static constexpr size_t VFY_HS_STATUS = VFY_HS_SUMS + BP_VFY_MAX_CLASSES * 64;
-static_assert(VFY_HS_STATUS + 4 <= 4096 && 64 * 4 + BP_VFY_MAX_CLASSES * 64 <= 4096, "the small result areas are 4096 bytes");
-struct VfyDevPlace { size_t in = 0, msg = 0, chal = 0, ws = 0, inst = 0, tail = 0, blk = 0, cls = 0; };   // a job's offsets: bytes (in), 64-bit words (msg), scalars, instances, tail terms, slots
-struct VfyDevTotals { size_t b_in = 0, msg = 0, chal = 0, ws = 0, inst = 0, tail = 0, blocks = 0, classes = 0, Nmax = 0; };
-struct VfyDrain { bp_ctx* c; bool armed; ~VfyDrain() { if (armed) (void)hipStreamSynchronize(c->stream); } };   // the stream reads pinned memory of this call: a decline waits for it first
-template <class C> struct VfyDevJob {
-    typedef host::ConstraintSystem<C> CS;
-    // the class: member j is instance idx[j] of the call's proofs / poff / alphas (idx null: j itself); db's accessors take j
-    size_t count = 0;
-    VfyDevBatch<C> db;
-    const uint32_t* idx = nullptr;
-    size_t at(size_t j) const { return idx ? idx[j] : j; }
-    // shape and constants (vfy_dev_admit)
-    bool two = false, wire = false, own_coefs = false;
-    size_t plen = 0, k = 0, m = 0, tail = 0, nV = 0, vbytes = 0, nitems = 0, nblocks = 0, n = 0, N = 0, G = 0, ncoef = 0;
-    const host::Strobe* s0 = nullptr;
-    double t_entry = 0;
-    CS like;
-    host::CanonState scratch;
-    host::Digest dg;
-    Vfe2Ref<C> ref;
-    std::vector<u32> v2off, v2q, v2cid;   // two-phase: the terms on commitments by commitment (CSR), coefficient ids
-    std::vector<uint32_t> enc2;
-    std::shared_ptr<void> tkeep, ckeep;   // the template and the class constants stay alive until the call's wait
-    const u32 *d_sched = nullptr, *d_voff = nullptr, *d_vq = nullptr, *d_vc = nullptr, *d_iota = nullptr;
-    // placement (vfy_dev_place)
-    size_t b_proofs = 0, b_V = 0, b_st = 0, b_in = 0;
-    VfyDevPlace pl;
-};
-static bool vfy_device_on(const bp_ctx* ctx) {
-    static const bool off = getenv("ARKBP_VFY_HOST") != nullptr;   // A/B switch: the host replay for every batch
-    return !off && !ctx->host_only && ctx->tune_vfy_device && ctx->shard_world <= 1;
-}
-template <class C>
-static int vfy_dev_admit(bp_ctx* ctx, VfyDevJob<C>& J, const uint8_t* proofs, const size_t* poff, bool& ok) {
-    typedef typename C::Fr FrP;
-    typedef host::Fld<FrP> S;
-    typedef host::ConstraintSystem<C> CS;
-    ok = false;
-    const VfyDevBatch<C>& db = J.db;
-    const size_t count = J.count;
-    if (!vfy_device_on(ctx) || !db.src || !count) return BP_OK;
-    const CS& src = *db.src;
-    const bool two = J.two = !src.deferred.empty();   // randomized constraints: the device derives every challenge, the host runs the callbacks
-    if (two && ctx->tune_vfy_device < 2) return BP_OK;
-    if (!src.base || src.cs_off.size() != 1 || src.phase2 || src.num_vars != src.base->num_vars) return BP_OK;
-    const size_t plen = J.plen = poff[J.at(0) + 1] - poff[J.at(0)];
-    if (plen < 539 || (plen - 539) % 66) return BP_OK;
-    const size_t k = J.k = (plen - 539) / 66, m = J.m = db.m;
-    if (k >= 32) return BP_OK;
-    for (size_t i = 0; i < count; i++) if (poff[J.at(i) + 1] - poff[J.at(i)] != plen) return BP_OK;
-    for (const auto& vt : src.base->vterms) if (vt.j >= m) return BP_OK;                // (a weaker statement than the recorded one: BP_E_ARG there)
-    const size_t tail = J.tail = 6 + m + 5 + 2 * k;
-    J.nV = db.absorb_commitments ? m : 0;
-    const bool wire = J.wire = (bool)db.commit_wire;
-    if (wire && (!db.absorb_commitments || db.commit_xy)) return BP_OK;
-    J.vbytes = wire ? 33 : 64;   // per commitment in the staging area
-    const size_t nitems = J.nitems = J.nV + 11 + 2 * k + 3;
-    if (count > 65535 || m > 65535 || count * tail >= ((size_t)1 << 31) || nitems * vfe::ITEM_WORDS * count >= ((size_t)1 << 32)) return BP_OK;
-    const size_t nblocks = J.nblocks = (count + VFY_BLOCK - 1) / VFY_BLOCK;
-    if (nblocks > VFY_SLOTS) return BP_OK;                                                      // (one result slot per block)
-    const host::Strobe* s0 = J.s0 = db.state_of(0);
-    if (!s0) return BP_OK;
-    if (!db.shared_state) for (size_t i = 1; i < count; i++) { const host::Strobe* si = db.state_of(i); if (!si || si->pos != s0->pos || si->pos_begin != s0->pos_begin) return BP_OK; }
-    J.t_entry = now_s();
-    hipStream_t st = ctx->stream;
-    const F4 one = S::one(), mone = S::neg(S::one());
-    // the circuit template (constraint matrices on the GPU, keyed by structure) and this class's device-side constants
-    CS& like = J.like;
-    like.init_like(src);
-    host::CanonState& scratch = J.scratch;
-    size_t n = src.num_vars, N = host::next_pow2(n);
-    host::Digest& dg = J.dg;
-    Vfe2Ref<C>& ref = J.ref;
-    std::vector<u32>&v2off = J.v2off, &v2q = J.v2q, &v2cid = J.v2cid;
-    std::shared_ptr<void>& tkeep = J.tkeep;
-    auto template_for = [&](const CS& rec, const host::CanonState& cst) -> int {   // look up / build (upload + sync) the template of `rec`
-        dg = cst.digest(rec.n1, n, rec.num_constraints());
-        // a miss with a full cache: the one template this batch needs is the one that is missing, so everything leaves
-        if (ctx->templates.size() >= VFY_TEMPLATE_CACHE && !ctx->templates.count(vfy_template_key(dg))) BPCHK(vfy_templates_trim(ctx, {}));
-        const VTemplate<C>* T;
-        return vfy_template_get<C>(ctx, dg, &rec, n, rec.n1, rec.num_constraints(), cst.coefs.size(), "batch_verify", tkeep, T);
-    };
-    if (!two) {
-        like.n1 = like.num_vars;   // single phase: every multiplier is a phase-1 multiplier (run_randomized with nothing deferred)
-        if (N != ((size_t)1 << k) || ctx->gens_cap < N) return BP_OK;          // (VerificationError / InvalidGeneratorsLength: the host path's to report)
-        BPCHK(template_for(like, like.canonical(scratch, nullptr)));
-    } else {
-        // the reference instance: instance 0's randomized phase for real, on a copy of its transcript through S1 (verifier.rs:403-415)
-        host::Transcript t0;
-        t0.s = *s0;
-        if (db.absorb_commitments) for (size_t j = 0; j < m; j++) {
-            A4 v;
-            if (!wire) memcpy(&v, db.commit_xy(0) + 8 * j, 64);
-            else {   // instance 0's own m roots on the host: the rehearsal needs them in affine form (m per batch, not m x count)
-                ctx->cw_host++;
-                if (!host::Grp<C>::deser_compressed(v, db.commit_wire(0) + 33 * j)) { ctx->vfe_fallbacks++; return BP_OK; }   // the prologue names the instance
-            }
-            host::TP<C>::append_point(t0, "V", v);
-        }
-        t0.append_u64("m", m);
-        A4 p3[3];
-        static const char* const lab3[3] = {"A_I1", "A_O1", "S1"};
-        for (int j = 0; j < 3; j++) {
-            if (!host::Grp<C>::deser_compressed(p3[j], proofs + poff[J.at(0)] + 33 * j) || !host::TP<C>::validate_and_append_point(t0, lab3[j], p3[j])) {
-                ctx->vfe_fallbacks++;   // something the reference rejects: the host replay reports it
-                return BP_OK;
-            }
-        }
-        CS* r0 = db.cs_of ? db.cs_of(0) : &like;
-        typename CS::RandSnap snap0;
-        r0->snapshot(snap0);
-        host::Transcript* tr_save = r0->tr;
-        std::vector<std::pair<std::string, F4>> log;
-        r0->tr = &t0; r0->chal_log = &log;
-        const int rrc = r0->run_randomized();
-        r0->chal_log = nullptr; r0->tr = tr_save;
-        bool ok = !rrc && r0->cs_off.size() >= 1 && r0->n1 == src.base->num_vars && log.size() <= 4096;
-        if (ok) {
-            n = r0->num_vars; N = host::next_pow2(n);
-            ok = N == ((size_t)1 << k) && ctx->gens_cap >= N;
-        }
-        int trc = BP_OK;
-        if (ok) {
-            for (auto& e : log) { ref.labels.push_back(e.first); ref.chal0.push_back(e.second); }
-            ref.n = n; ref.n1 = r0->n1;
-            ref.off = r0->cs_off;
-            // coefficient ids: the canonical walk over both parts (the numbering canonical() and build_template produce)
-            host::CanonState cw;
-            std::vector<host::VTerm> vts;   // (j, q, c.v[0] = id)
-            auto vsink = [&](size_t q, const host::Term& t, u32 cid) { if (t.v.k == host::VK_COMMITTED) { host::VTerm v{t.v.i, (u32)q, F4{}}; v.c.v[0] = cid; vts.push_back(v); } };
-            cw.walk(src.base->terms.data(), src.base->off.data(), src.base->nq(), 0, one, mone, vsink);
-            ref.nbase = cw.coefs.size(); ref.base_coefs = cw.coefs;
-            cw.walk(r0->cs_terms.data(), r0->cs_off.data(), r0->cs_off.size() - 1, r0->base_nq(), one, mone, [&](size_t q, const host::Term& t, u32 cid) {
-                ref.vars.push_back(t.v); ref.cid.push_back(cid); vsink(q, t, cid);
-            });
-            ref.ncoef = cw.coefs.size();
-            for (u32 c : ref.cid) if (!(c & (host::CID_ONE | host::CID_MONE)) && c >= (1u << 30)) ok = false;
-            for (const auto& v : vts) if (v.j >= m) ok = false;
-            if (ok) {
-                v2off.assign(m + 1, 0); v2q.resize(vts.size()); v2cid.resize(vts.size());
-                for (const auto& v : vts) v2off[v.j + 1]++;
-                for (size_t j = 0; j < m; j++) v2off[j + 1] += v2off[j];
-                std::vector<u32> cur(v2off.begin(), v2off.end() - 1);
-                for (const auto& v : vts) { const u32 at = cur[v.j]++; v2q[at] = v.q; v2cid[at] = (u32)v.c.v[0]; }
-                trc = template_for(*r0, r0->canonical(scratch, nullptr));
-            }
-        }
-        r0->restore(snap0);
-        if (trc) return trc;
-        if (!ok) return BP_OK;
-        if (count * (ref.labels.size() + ref.ncoef) * 32 > VFY2_TABLE_BUDGET) return BP_OK;   // (stated in include/arkbp.h)
-    }
-    const VTemplate<C>& T = *(const VTemplate<C>*)tkeep.get();
-    const std::string tkey((const char*)&dg, sizeof dg);
-    J.n = n; J.N = N; J.G = ref.labels.size(); J.ncoef = two ? ref.ncoef : 0;
-    std::shared_ptr<void>& ckeep = J.ckeep;
-    bool& own_coefs = J.own_coefs;
-    const u32 *&d_sched = J.d_sched, *&d_voff = J.d_voff, *&d_vq = J.d_vq, *&d_vc = J.d_vc, *&d_iota = J.d_iota;
-    std::vector<uint32_t>& enc2 = J.enc2;
-    if (!two) {
-        char ckeyb[96];
-        snprintf(ckeyb, sizeof ckeyb, "%p/%zu/%zu/%u/%u/%d", (const void*)src.base.get(), m, k, (unsigned)s0->pos, (unsigned)s0->pos_begin, (int)db.absorb_commitments);
-        const std::string ckey(ckeyb);
-        {
-            auto cit = ctx->vfe_classes.find(ckey);
-            if (cit != ctx->vfe_classes.end()) {
-                VfeClassDev<C>* c = (VfeClassDev<C>*)cit->second.get();
-                if (c->base.lock().get() == src.base.get() && c->tkey == tkey) ckeep = cit->second;   // (same recording still alive, same template)
-                else ctx->vfe_classes.erase(cit);
-            }
-        }
-        if (!ckeep) {
-            if (ctx->vfe_classes.size() >= 16) { HIPCHK(ctx_stream_wait(ctx)); ctx->vfe_classes.clear(); }
-            VfeClassDev<C>* c = new VfeClassDev<C>();
-            ckeep.reset(c, [](void* q) { delete (VfeClassDev<C>*)q; });
-            c->base = src.base; c->base_ptr = src.base.get(); c->tkey = tkey; c->N = N;
-            vfe::Schedule sched;
-            if (!vfe::build_verifier_schedule(sched, s0->pos, s0->pos_begin, db.absorb_commitments, m, (uint32_t)k, N)) return BP_OK;
-            const std::vector<uint32_t> enc = sched.encode();
-            // terms on committed variables by commitment (CSR over j; constraint order inside a commitment)
-            std::vector<u32> voff(m + 1, 0), vq(src.base->vterms.size());
-            std::vector<F4> vc(src.base->vterms.size());
-            for (const auto& vt : src.base->vterms) voff[vt.j + 1]++;
-            for (size_t j = 0; j < m; j++) voff[j + 1] += voff[j];
-            { std::vector<u32> cur(voff.begin(), voff.end() - 1); for (const auto& vt : src.base->vterms) { const u32 at = cur[vt.j]++; vq[at] = vt.q; vc[at] = vt.c; } }
-            std::vector<u32> iota(VFY_BLOCK);
-            for (size_t i = 0; i < VFY_BLOCK; i++) iota[i] = (u32)i;
-            BPCHK(c->sched.ensure(enc.size() * 4)); BPCHK(c->voff.ensure(voff.size() * 4)); BPCHK(c->vq.ensure(std::max<size_t>(vq.size(), 1) * 4));
-            BPCHK(c->vc.ensure(std::max<size_t>(vc.size(), 1) * 32)); BPCHK(c->iota.ensure(iota.size() * 4));
-            HIPCHK(hipMemcpyAsync(c->sched.p, enc.data(), enc.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(c->voff.p, voff.data(), voff.size() * 4, hipMemcpyHostToDevice, st));
-            if (!vq.empty()) HIPCHK(hipMemcpyAsync(c->vq.p, vq.data(), vq.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(c->iota.p, iota.data(), iota.size() * 4, hipMemcpyHostToDevice, st));
-            if (!vc.empty()) BPCHK(upload_scalars<C>(ctx, (u32*)c->vc.p, vc.data(), vc.size()));
-            HIPCHK(ctx_stream_wait(ctx));   // (the host arrays above are locals)
-            ctx->vfe_classes[ckey] = ckeep;
-        }
-        VfeClassDev<C>& cls = *(VfeClassDev<C>*)ckeep.get();
-        // the coefficient table is decided per batch: the template may have been evicted and rebuilt since, from an instance of the
-        // same structure with other public constants
-        const host::CanonState& cst = like.canonical(scratch, nullptr);
-        own_coefs = T.ncoef && memcmp(T.coefs_host.data(), cst.coefs.data(), T.ncoef * 32) != 0;
-        if (own_coefs && !cls.coefs_up) {
-            BPCHK(cls.coefs.ensure(T.ncoef * 32)); BPCHK(upload_scalars<C>(ctx, (u32*)cls.coefs.p, cst.coefs.data(), T.ncoef));
-            HIPCHK(ctx_stream_wait(ctx));
-            cls.coefs_up = true;
-        }
-        d_sched = (u32*)cls.sched.p; d_voff = (u32*)cls.voff.p; d_vq = (u32*)cls.vq.p; d_vc = (u32*)cls.vc.p; d_iota = (u32*)cls.iota.p;
-    } else {
-        vfe::Schedule sched;
-        if (!vfe::build_verifier_schedule_2phase(sched, s0->pos, s0->pos_begin, db.absorb_commitments, m, (uint32_t)k, N, ref.labels)) return BP_OK;
-        enc2 = sched.encode();
-        std::vector<u32> iota(VFY_BLOCK);
-        for (size_t i = 0; i < VFY_BLOCK; i++) iota[i] = (u32)i;
-        BPCHK(ctx->vfe2_sched.ensure(enc2.size() * 4 + VFY_BLOCK * 4)); BPCHK(ctx->vfe2_voff.ensure(v2off.size() * 4));
-        BPCHK(ctx->vfe2_vq.ensure(std::max<size_t>(v2q.size(), 1) * 4)); BPCHK(ctx->vfe2_vcid.ensure(std::max<size_t>(v2cid.size(), 1) * 4));
-        HIPCHK(hipMemcpyAsync(ctx->vfe2_sched.p, enc2.data(), enc2.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->vfe2_sched.as<u32>() + enc2.size(), iota.data(), VFY_BLOCK * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ctx->vfe2_voff.p, v2off.data(), v2off.size() * 4, hipMemcpyHostToDevice, st));
-        if (!v2q.empty()) {
-            HIPCHK(hipMemcpyAsync(ctx->vfe2_vq.p, v2q.data(), v2q.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(ctx->vfe2_vcid.p, v2cid.data(), v2cid.size() * 4, hipMemcpyHostToDevice, st));
-        }
-        HIPCHK(ctx_stream_wait(ctx));   // (the host arrays above are locals)
-        d_sched = ctx->vfe2_sched.as<u32>(); d_iota = d_sched + enc2.size(); d_voff = ctx->vfe2_voff.as<u32>(); d_vq = ctx->vfe2_vq.as<u32>(); d_vc = ctx->vfe2_vcid.as<u32>();
-    }
-    ok = true;
-    return BP_OK;
-}
-// where the jobs of one call live in the ctx's buffers: one after the other, job order = launch order
-template <class C> static void vfy_dev_place(VfyDevJob<C>* const* jobs, size_t nj, VfyDevTotals& tot) {
-    auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    tot = VfyDevTotals();
-    for (size_t c = 0; c < nj; c++) {
-        VfyDevJob<C>& J = *jobs[c];
-        // staging: [proof bytes | commitments | transcript states | weights], 256-byte aligned parts
-        J.b_proofs = up256(J.count * J.plen); J.b_V = up256(J.count * J.m * J.vbytes); J.b_st = up256((J.db.shared_state ? 1 : J.count) * 200);
-        J.b_in = J.b_proofs + J.b_V + J.b_st + up256(J.count * 32);
-        J.pl.in = tot.b_in; J.pl.msg = tot.msg; J.pl.chal = tot.chal; J.pl.ws = tot.ws; J.pl.inst = tot.inst; J.pl.tail = tot.tail; J.pl.blk = tot.blocks; J.pl.cls = tot.classes;
-        tot.b_in += J.b_in; tot.msg += J.nitems * vfe::ITEM_WORDS * J.count; tot.chal += J.count * (6 + J.k + J.G); tot.ws += J.count * 34; tot.inst += J.count;
-        tot.tail += J.count * J.tail; tot.blocks += J.nblocks; tot.classes++;
-        tot.Nmax = std::max(tot.Nmax, J.N);
-    }
-}
-// every buffer of the call at its final size BEFORE the first launch (a later ensure() could move one under a running kernel), the
-// accumulators, the status word and the per-proof flags zeroed.  Pinned staging: [the jobs' inputs | flags, one word per instance |
-// .. | small results (the last 4096 bytes)].
-static size_t vfy_dev_flags_at(const VfyDevTotals& tot) { return tot.b_in; }
-template <class C> static int vfy_dev_reserve(bp_ctx* ctx, const VfyDevTotals& tot) {
-    hipStream_t st = ctx->stream;
-    const size_t need = tot.b_in + ((tot.inst * 4 + 255) & ~(size_t)255);
-    if (ctx->h_vfe_cap < need + 4096) {
-        if (ctx->h_vfe) { HIPCHK(ctx_stream_wait(ctx)); HIPCHK(hipHostFree(ctx->h_vfe)); }
-        ctx->h_vfe = nullptr; ctx->h_vfe_cap = 0;
-        HIPCHK(hipHostMalloc(&ctx->h_vfe, need + need / 8 + 4096));
-        ctx->h_vfe_cap = need + need / 8 + 4096;
-    }
-    BPCHK(ctx->vfe_in.ensure(tot.b_in));
-    BPCHK(ctx->vfe_msg.ensure(tot.msg * 8));
-    BPCHK(ctx->vfe_chal.ensure(tot.chal * 32));
-    BPCHK(ctx->vfe_ws.ensure(tot.ws * 32));
-    BPCHK(ctx->vfe_small.ensure(4096));
-    BPCHK(ctx->vfe_flags.ensure(std::max<size_t>(tot.inst, 1) * 4));
-    BPCHK(ctx->r_g.ensure((2 + 2 * tot.Nmax + tot.tail) * 32));
-    BPCHK(ctx->r_tail.ensure(std::max<size_t>(tot.tail, 1) * 64));
-    BPCHK(ctx->r_small.ensure((tot.blocks + 8) * 32));
-    BPCHK(ctx->v_alpha.ensure(tot.inst * 32));
-    BPCHK(ctx->v_params.ensure(tot.inst * VFY_PB_WORDS * 4));
-    if (!ctx->sync_ev) HIPCHK(hipEventCreateWithFlags(&ctx->sync_ev, hipEventDisableTiming));
-    HIPCHK(hipMemsetAsync(ctx->r_g.p, 0, (2 + 2 * tot.Nmax) * 32, st));
-    HIPCHK(hipMemsetAsync(ctx->vfe_small.p, 0, 256, st));                  // [status | pad .. | sums at word 64, 16 words per job]
-    HIPCHK(hipMemsetAsync(ctx->vfe_flags.p, 0, std::max<size_t>(tot.inst, 1) * 4, st));
-    return BP_OK;
-}
-// staging and the launch chain of one job: k_vfe_points -> k_vfe_sponge -> prepare -> k_vfy_tables / k_vfy_batch per block.  ok stays
-// false when a two-phase batch declines on the way (its kernels flagged something, a callback recorded another structure).
-template <class C>
-static int vfy_dev_launch(bp_ctx* ctx, VfyDevJob<C>& J, const VfyDevTotals& tot, const uint8_t* proofs, const size_t* poff, const F4* alphas, double* timing, bool& ok) {
-    typedef typename C::Fr FrP;
-    typedef host::Fld<FrP> S;
-    typedef host::ConstraintSystem<C> CS;
-    ok = false;
-    const VfyDevBatch<C>& db = J.db;
-    const CS& src = *db.src;
-    const size_t count = J.count, plen = J.plen, k = J.k, m = J.m, tail = J.tail, nV = J.nV, vbytes = J.vbytes, nitems = J.nitems, nblocks = J.nblocks, N = J.N, G = J.G, ncoef = J.ncoef;
-    const bool two = J.two, wire = J.wire, own_coefs = J.own_coefs;
-    const size_t b_proofs = J.b_proofs, b_V = J.b_V, b_st = J.b_st, b_in = J.b_in;
-    const VfyDevPlace& pl = J.pl;
-    const Vfe2Ref<C>& ref = J.ref;
-    const host::Strobe* s0 = J.s0;
-    const VTemplate<C>& T = *(const VTemplate<C>*)J.tkeep.get();
-    const std::shared_ptr<void>& ckeep = J.ckeep;
-    const u32 *d_voff = J.d_voff, *d_vq = J.d_vq, *d_vc = J.d_vc, *d_iota = J.d_iota, *d_sched = J.d_sched;
-    hipStream_t st = ctx->stream;
-    const F4 one = S::one(), mone = S::neg(S::one());
-    // two-phase: [gadget challenges count x G | coefficient tables count x ncoef] (ark words, host form)
-    const size_t b_gch = count * G * 32, b_tab = count * ncoef * 32;
-    if (two && ctx->h_vfe2_cap < b_gch + b_tab + 64) {
-        if (ctx->h_vfe2) { HIPCHK(ctx_stream_wait(ctx)); HIPCHK(hipHostFree(ctx->h_vfe2)); }
-        ctx->h_vfe2 = nullptr; ctx->h_vfe2_cap = 0;
-        HIPCHK(hipHostMalloc(&ctx->h_vfe2, b_gch + b_tab + (b_gch + b_tab) / 8 + 64));
-        ctx->h_vfe2_cap = b_gch + b_tab + (b_gch + b_tab) / 8 + 64;
-    }
-    F4* h_gch = two ? (F4*)ctx->h_vfe2 : nullptr;
-    F4* h_tab = two ? (F4*)((char*)ctx->h_vfe2 + b_gch) : nullptr;
-    uint8_t* hs = (uint8_t*)ctx->h_vfe + pl.in;
-    uint8_t* h_small = (uint8_t*)ctx->h_vfe + ctx->h_vfe_cap - 4096;
-    {
-        const size_t chunk = 64;
-        pool_range(ctx, 0, (count + chunk - 1) / chunk, [&](size_t c) {
-            const size_t lo = c * chunk, hi = std::min(count, lo + chunk);
-            if (!J.idx) memcpy(hs + lo * plen, proofs + poff[lo], (hi - lo) * plen);
-            for (size_t i = lo; i < hi; i++) {
-                if (J.idx) { memcpy(hs + i * plen, proofs + poff[J.idx[i]], plen); memcpy(hs + b_proofs + b_V + b_st + i * 32, alphas + J.idx[i], 32); }
-                if (m) memcpy(hs + b_proofs + i * m * vbytes, wire ? (const void*)db.commit_wire(i) : (const void*)db.commit_xy(i), m * vbytes);
-                if (!db.shared_state) memcpy(hs + b_proofs + b_V + i * 200, db.state_of(i)->st.b, 200);
-            }
-        });
-        if (db.shared_state) memcpy(hs + b_proofs + b_V, s0->st.b, 200);
-        if (!J.idx) memcpy(hs + b_proofs + b_V + b_st, alphas, count * 32);
-    }
-    if (timing) timing[4] = now_s() - J.t_entry;
-    if (two) { BPCHK(ctx->vfe2_gch.ensure(std::max<size_t>(b_gch, 32))); BPCHK(ctx->vfe2_coef.ensure(std::max<size_t>(b_tab, 32))); }
-    u32* sc = ctx->r_g.as<u32>();
-    u32* acc_g = sc + 2 * 8;                                   // every job accumulates into the front of the call's g / h accumulators
-    u32* acc_h = sc + (2 + tot.Nmax) * 8;
-    u32* d_tail_sc = sc + (2 + 2 * tot.Nmax + pl.tail) * 8;    // its tails: scalars behind the accumulators, points in r_tail
-    u32* d_tail_pts = ctx->r_tail.as<u32>() + pl.tail * 16;
-    u32* d_alpha = ctx->v_alpha.as<u32>() + pl.inst * 8;
-    u32* d_pb = ctx->v_params.as<u32>() + pl.inst * VFY_PB_WORDS;
-    u32* d_status = ctx->vfe_small.as<u32>();
-    u32* d_sums = d_status + 64 + 16 * pl.cls;
-    u32* d_flags = ctx->vfe_flags.as<u32>() + pl.inst;
-    u32* d_slots = ctx->r_small.as<u32>() + pl.blk * 8;
-    uint64_t* d_msg = (uint64_t*)ctx->vfe_msg.p + pl.msg;
-    u32* d_chal = ctx->vfe_chal.as<u32>() + pl.chal * 8;
-    u32* d_ws = ctx->vfe_ws.as<u32>() + pl.ws * 8;
-    uint8_t* d_in = (uint8_t*)ctx->vfe_in.p + pl.in;
-    HIPCHK(hipMemcpyAsync(d_in, hs, b_in, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((count + 255) / 256)), dim3(256), 0, st, (const u32*)(d_in + b_proofs + b_V + b_st), d_alpha, (u32)count);
-    vfe::Shape sh;
-    sh.P = (uint32_t)count; sh.m = (uint32_t)m; sh.nV = (uint32_t)nV; sh.k = (uint32_t)k; sh.plen = (uint32_t)plen; sh.tail = (uint32_t)tail; sh.nitems = (uint32_t)nitems;
-    sh.G = (uint32_t)G; sh.vwire = wire ? 1u : 0u;
-    {
-        ScopedK tk(ctx, BP_K_VFE_POINTS);
-        if (vfe::launch_points(C::ID, st, sh, d_in, (const u32*)(d_in + b_proofs), d_msg, d_tail_pts, d_status, d_flags)) { g_err = "k_vfe_points: launch failed"; return BP_E_HIP; }
-    }
-    {
-        ScopedK tk(ctx, BP_K_VFE_SPONGE);
-        if (vfe::launch_sponge(C::ID, st, sh, d_sched, (const uint64_t*)(d_in + b_proofs + b_V), db.shared_state ? 0u : 25u, d_msg, d_chal, nullptr,
-                               two ? ctx->vfe2_gch.as<u32>() : nullptr)) { g_err = "k_vfe_sponge: launch failed"; return BP_E_HIP; }
-    }
-    if (!two) {
-        ScopedK tk(ctx, BP_K_VFE_PREPARE);
-        if (vfe::launch_prepare(C::ID, st, sh, d_in, d_chal, d_alpha, d_voff, d_vq, d_vc, d_pb, d_tail_sc,
-                                d_ws, d_sums)) { g_err = "k_vfe_consts: launch failed"; return BP_E_HIP; }
-        for (size_t blk = 0; blk < nblocks; blk++) {
-            const size_t lo = blk * VFY_BLOCK, nb = std::min(count, lo + VFY_BLOCK) - lo;
-            VfeClassDev<C>& cls = *(VfeClassDev<C>*)ckeep.get();
-            BPCHK(verify_launch_template_group<C>(ctx, T, d_pb + lo * VFY_PB_WORDS, d_iota, own_coefs ? (u32*)cls.coefs.p : nullptr, nb, N, k,
-                                                  acc_g, acc_h, d_slots + blk * 8, true));
-        }
-    } else {
-        // the gadget challenges (and the kernels' reject bits) come back while k_vfe_consts runs; the host then runs every instance's
-        // callbacks with its challenges, block by block, each block's launches behind its tables
-        if (b_gch) HIPCHK(hipMemcpyAsync(h_gch, ctx->vfe2_gch.p, b_gch, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(h_small + VFY_HS_STATUS, d_status, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(ctx->sync_ev, st));
-        {
-            ScopedK tk(ctx, BP_K_VFE_PREPARE);
-            if (vfe::launch_consts(C::ID, st, sh, d_in, d_chal, d_alpha, d_pb, d_tail_sc, d_ws, d_sums)) {
-                g_err = "k_vfe_consts: launch failed"; return BP_E_HIP;
-            }
-        }
-        HIPCHK(vfe_poll(ctx, ctx->sync_ev));
-        u32 status0; memcpy(&status0, h_small + VFY_HS_STATUS, 4);
-        if (status0) { ctx->vfe_fallbacks++; return BP_OK; }
-        for (size_t g = 0; g < G; g++) if (h_gch[g] != ref.chal0[g]) return BP_OK;   // (the device's transcript is not instance 0's: never expected)
-        u32* d_coef = ctx->vfe2_coef.as<u32>();
-        for (size_t blk = 0; blk < nblocks; blk++) {
-            const size_t lo = blk * VFY_BLOCK, nb = std::min(count, lo + VFY_BLOCK) - lo;
-            std::atomic<bool> bad{false};
-            pool_range(ctx, lo, lo + nb, [&](size_t i) {
-                if (bad.load(std::memory_order_relaxed)) return;
-                std::unique_ptr<CS> tmp;
-                CS* ci;
-                typename CS::RandSnap snap;
-                if (db.cs_of) { ci = db.cs_of(i); ci->snapshot(snap); }
-                else { tmp.reset(new CS()); tmp->init_like(src); ci = tmp.get(); }
-                host::Transcript sink;   // ("r1cs-2phase" is appended here: the device's sponge has absorbed it already)
-                memset(&sink.s, 0, sizeof sink.s);
-                host::Transcript* tr_save = ci->tr;
-                ci->tr = &sink;
-                ci->preset = h_gch + i * G; ci->preset_labels = &ref.labels; ci->preset_at = 0; ci->preset_bad = false;
-                const int rc = ci->run_randomized();
-                bool ok = !rc && !ci->preset_bad && ci->preset_at == G && ci->num_vars == ref.n && ci->n1 == ref.n1 && ci->cs_off == ref.off &&
-                          ci->cs_terms.size() == ref.vars.size();
-                F4* tab = h_tab + i * ncoef;
-                if (ok) {
-                    std::vector<char> set(ncoef - ref.nbase, 0);
-                    for (size_t j = 0; j < ref.nbase; j++) tab[j] = ref.base_coefs[j];
-                    for (size_t t = 0; ok && t < ref.vars.size(); t++) {
-                        const host::Term& tm = ci->cs_terms[t];
-                        const u32 cid = ref.cid[t];
-                        if (tm.v.k != ref.vars[t].k || tm.v.i != ref.vars[t].i) ok = false;
-                        else if (cid & host::CID_ONE) ok = tm.c == one;
-                        else if (cid & host::CID_MONE) ok = tm.c == mone;
-                        else if (cid < ref.nbase) ok = tm.c == tab[cid];
-                        else if (!set[cid - ref.nbase]) { tab[cid] = tm.c; set[cid - ref.nbase] = 1; }
-                        else ok = tm.c == tab[cid];
-                    }
-                    for (size_t j = 0; ok && j < set.size(); j++) ok = set[j] != 0;
-                }
-                ci->tr = tr_save;
-                if (db.cs_of) ci->restore(snap);
-                if (!ok) bad.store(true, std::memory_order_relaxed);
-            });
-            if (bad.load()) return BP_OK;   // a callback that records another structure (or draws other challenges): the host replay decides
-            u32* d_tab = d_coef + lo * ncoef * 8;
-            if (ncoef) {
-                HIPCHK(hipMemcpyAsync(d_tab, h_tab + lo * ncoef, nb * ncoef * 32, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_scalars_import<FrP>, dim3((u32)((nb * ncoef + 255) / 256)), dim3(256), 0, st, d_tab, d_tab, (u32)(nb * ncoef));
-            }
-            {
-                ScopedK tk(ctx, BP_K_VFE_PREPARE);
-                if (vfe::launch_wv_tab(C::ID, st, sh, (uint32_t)lo, (uint32_t)nb, d_pb, d_voff, d_vq, d_vc, d_tab, (uint32_t)(ncoef * 8), d_tail_sc)) {
-                    g_err = "k_vfe_wv_tab: launch failed"; return BP_E_HIP;
-                }
-            }
-            BPCHK(verify_launch_template_group<C>(ctx, T, d_pb + lo * VFY_PB_WORDS, d_iota, ncoef ? d_tab : nullptr, nb, N, k,
-                                                  acc_g, acc_h, d_slots + blk * 8, false));
-        }
-    }
-    ok = true;
-    return BP_OK;
-}
-// The mega-check of the host replay and of the device front end alike: the two head scalars up, then ONE MSM over
-// [B, B_blinding | G[0..Nmax) | H[0..Nmax) | tails] with the scalars resident in r_g (accumulators and tails in canonical form by now)
-template <class C> static int vfy_mega_check(bp_ctx* ctx, size_t Nmax, size_t Ttot, const F4& sB, const F4& sBb, J4& r) {
-    u32* sc = ctx->r_g.as<u32>();
-    uint64_t head[8];
-    canon_words<typename C::Fr>(head, sB); canon_words<typename C::Fr>(head + 4, sBb);
-    HIPCHK(hipMemcpyAsync(sc, head, 64, hipMemcpyHostToDevice, ctx->stream));
-    BaseSegs sg; memset(&sg, 0, sizeof sg);
-    sg.nseg = 4;
-    sg.ptr[0] = ctx->d_pc.as<u32>(); sg.ptr[1] = ctx->d_G.as<u32>(); sg.ptr[2] = ctx->d_H.as<u32>(); sg.ptr[3] = ctx->r_tail.as<u32>();
-    sg.start[0] = 0; sg.start[1] = 2; sg.start[2] = (u32)(2 + Nmax); sg.start[3] = (u32)(2 + 2 * Nmax); sg.start[4] = (u32)(2 + 2 * Nmax + Ttot);
-    return msm_run<C>(ctx, sg, sc, 2 + 2 * Nmax + Ttot, 0, r);
-}
-// After the last job: the accumulators to canonical integers, ONE copy back, ONE polled wait, the head scalars summed on the host,
-// the mega-check over every job's tails.  flagged: a kernel raised a reject bit (no MSM then; the
-// per-instance flag words are in pinned memory, vfy_dev_flagged reads them).
-template <class C>
-static int vfy_dev_finish(bp_ctx* ctx, VfyDevJob<C>* const* jobs, size_t nj, const VfyDevTotals& tot, VfyDrain& drain, double* timing, J4& r, bool& flagged) {
-    typedef typename C::Fr FrP;
-    typedef host::Fld<FrP> S;
-    hipStream_t st = ctx->stream;
-    flagged = false;
-    u32* sc = ctx->r_g.as<u32>();
-    const u32* d_status = ctx->vfe_small.as<u32>();
-    uint8_t* h_small = (uint8_t*)ctx->h_vfe + ctx->h_vfe_cap - 4096;
-    const size_t Nmax = tot.Nmax;
-    hipLaunchKernelGGL(k_scalars_to_canon<FrP>, dim3((u32)((2 * Nmax + 255) / 256)), dim3(256), 0, st, sc + 2 * 8, (u32)(2 * Nmax));
-    HIPCHK(hipMemcpyAsync(h_small, ctx->r_small.p, tot.blocks * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h_small + VFY_HS_SUMS, d_status + 64, nj * 64, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h_small + VFY_HS_STATUS, d_status, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync((uint8_t*)ctx->h_vfe + vfy_dev_flags_at(tot), ctx->vfe_flags.p, tot.inst * 4, hipMemcpyDeviceToHost, st));
-    const double t_drain = now_s();
-    // ONE wait per call, ~10 ms long: poll and sleep (HIP's own synchronisation calls busy-wait on this stack: a core per batch in
-    // flight for nothing; see event_wait)
-    HIPCHK(hipEventRecord(ctx->sync_ev, st));
-    HIPCHK(vfe_poll(ctx, ctx->sync_ev));
-    drain.armed = false;
-    HIPCHK(hipGetLastError());
-    u32 status; memcpy(&status, h_small + VFY_HS_STATUS, 4);
-    if (status) { flagged = true; return BP_OK; }   // something the reference rejects: the host replay decides which error, in instance order
-    F4 sB = S::zero(), sBb = S::zero();
-    for (size_t c = 0; c < nj; c++) { F4 a, b; memcpy(a.v, h_small + VFY_HS_SUMS + c * 64, 32); memcpy(b.v, h_small + VFY_HS_SUMS + c * 64 + 32, 32); sB = S::add(sB, a); sBb = S::add(sBb, b); }
-    for (size_t j = 0; j < tot.blocks; j++) { F4 d; memcpy(d.v, h_small + j * 32, 32); sB = S::add(sB, d); }
-    const double t_msm = now_s();
-    BPCHK(vfy_mega_check<C>(ctx, Nmax, tot.tail, sB, sBb, r));
-    const double t_end = now_s(), t_entry = jobs[0]->t_entry;
-    if (timing) { timing[0] = t_end - t_entry; timing[1] = 0; timing[2] = t_msm - t_drain; timing[3] = t_end - t_msm; }
-    if (ctx->profiling) collect_timers(ctx);
-    return BP_OK;
-}
-// the instances the kernels flagged (after a flagged vfy_dev_finish), as instance numbers of the call, ascending
-template <class C> static void vfy_dev_flagged(bp_ctx* ctx, VfyDevJob<C>* const* jobs, size_t nj, const VfyDevTotals& tot, std::vector<uint32_t>& out) {
-    const u32* fl = (const u32*)((const uint8_t*)ctx->h_vfe + vfy_dev_flags_at(tot));
-    for (size_t c = 0; c < nj; c++) for (size_t j = 0; j < jobs[c]->count; j++) if (fl[jobs[c]->pl.inst + j]) out.push_back((uint32_t)jobs[c]->at(j));
-    std::sort(out.begin(), out.end());
-}
-// The whole batch as one job.  flagged (optional): the instances the kernels flagged when the batch is declined for that reason.
-template <class C>
-static int batch_verify_device(bp_ctx* ctx, size_t count, const VfyDevBatch<C>& db, const uint8_t* proofs, const size_t* poff, const F4* alphas, double* timing,
-                               uint64_t* point_out, bool& handled, std::vector<uint32_t>* flagged = nullptr) {
-    handled = false;
-    VfyDevJob<C> J;
-    J.count = count; J.db = db;
-    bool ok = false;
-    BPCHK(vfy_dev_admit<C>(ctx, J, proofs, poff, ok));
-    if (!ok) return BP_OK;
-    VfyDevJob<C>* jobs[1] = {&J};
-    VfyDevTotals tot;
-    vfy_dev_place<C>(jobs, 1, tot);
-    VfyDrain drain{ctx, true};
-    BPCHK(vfy_dev_reserve<C>(ctx, tot));
-    BPCHK(vfy_dev_launch<C>(ctx, J, tot, proofs, poff, alphas, timing, ok));
-    if (!ok) return BP_OK;
-    J4 r;
-    bool bad = false;
-    BPCHK(vfy_dev_finish<C>(ctx, jobs, 1, tot, drain, timing, r, bad));
-    if (bad) { ctx->vfe_fallbacks++; if (flagged) vfy_dev_flagged<C>(ctx, jobs, 1, tot, *flagged); return BP_OK; }
-    if (point_out) aff_out<C>(point_out, host::Grp<C>::to_aff(r));
-    ctx->vfe_batches++;
-    if (J.wire) ctx->cw_front_end += count * J.m;
-    handled = true;
-    return host::Grp<C>::is_inf(r) ? BP_OK : BP_E_VERIFICATION;
-}
+// ---- batch_verify with the per-proof front end on the GPU: the steps over VfyDevJob, vfy_dev_run, batch_verify_device
+#include "verify_dev.inc"
 
 // batch_verify on the host-replay route: batch_verify_host, a short sequence of steps over one VfyHostJob
 #include "verify_steps.inc"
@@ -2650,44 +2080,29 @@ static int batch_verify_classes(bp_ctx* ctx, size_t count, const VfyProvider<C>&
     std::vector<std::unique_ptr<VfyDevJob<C>>> owned;
     std::vector<VfyDevJob<C>*> jobs;
     std::vector<char> on_device(count, 0);
-    {
-        size_t blocks = 0, tails = 0;
-        for (uint32_t c = 0; c < ncls; c++) {
-            std::unique_ptr<VfyDevJob<C>> J(new VfyDevJob<C>());
-            J->count = members[c].size(); J->idx = members[c].data();
-            if (!prov.dev_class(J->idx, J->count, J->db)) continue;
-            bool ok = false;
-            BPCHK(vfy_dev_admit<C>(ctx, *J, proofs, poff, ok));
-            if (!ok || J->two) continue;
-            if (blocks + J->nblocks > VFY_SLOTS || tails + J->count * J->tail + 2 + 2 * std::max<size_t>(J->N, 1) >= ((size_t)1 << 30)) continue;
-            blocks += J->nblocks; tails += J->count * J->tail;
-            for (uint32_t k : members[c]) on_device[k] = 1;
-            jobs.push_back(J.get());
-            owned.push_back(std::move(J));
-        }
+    VfyDevTotals fit;
+    for (uint32_t c = 0; c < ncls; c++) {
+        std::unique_ptr<VfyDevJob<C>> J(new VfyDevJob<C>());
+        J->count = members[c].size(); J->idx = members[c].data();
+        if (!prov.dev_class(J->idx, J->count, J->db)) continue;
+        bool ok = false;
+        BPCHK(vfy_dev_admit<C>(ctx, *J, proofs, poff, ok));
+        if (!ok || J->two || !vfy_dev_fits(fit, J->sh)) continue;
+        (void)vfy_dev_append(fit, J->sh);
+        for (uint32_t k : members[c]) on_device[k] = 1;
+        jobs.push_back(J.get());
+        owned.push_back(std::move(J));
     }
     if (jobs.empty()) return BP_OK;
-    std::vector<uint32_t> rest;
+    std::vector<uint32_t> rest, sub;
     for (size_t k = 0; k < count; k++) if (!on_device[k]) rest.push_back((uint32_t)k);
-    VfyDevTotals tot;
-    vfy_dev_place<C>(jobs.data(), jobs.size(), tot);
     J4 r;
-    bool bad = false;
-    {
-        VfyDrain drain{ctx, true};
-        BPCHK(vfy_dev_reserve<C>(ctx, tot));
-        for (VfyDevJob<C>* J : jobs) {
-            bool ok = false;
-            BPCHK(vfy_dev_launch<C>(ctx, *J, tot, proofs, poff, alphas, jobs.size() == 1 ? timing : nullptr, ok));
-            if (!ok) return BP_OK;   // (single-phase jobs do not decline on the way)
-        }
-        BPCHK(vfy_dev_finish<C>(ctx, jobs.data(), jobs.size(), tot, drain, timing, r, bad));
-    }
+    VfyDevRun ran;
+    BPCHK(vfy_dev_run<C>(ctx, jobs.data(), jobs.size(), proofs, poff, alphas, timing, r, &sub, ran));
+    if (ran == VFY_RUN_DECLINED) return BP_OK;
     ctx->vcl_calls++;
     ctx->vcl_remainder += rest.size();
-    if (bad) {
-        std::vector<uint32_t> sub;
-        vfy_dev_flagged<C>(ctx, jobs.data(), jobs.size(), tot, sub);
+    if (ran == VFY_RUN_FLAGGED) {
         ctx->vfe_fallbacks++;
         sub.insert(sub.end(), rest.begin(), rest.end());
         std::sort(sub.begin(), sub.end());
@@ -2695,7 +2110,7 @@ static int batch_verify_classes(bp_ctx* ctx, size_t count, const VfyProvider<C>&
         return vfy_replay_flagged<C>(ctx, count, prov, sub, proofs, poff, alphas, inst_status, done);
     }
     ctx->vcl_classes += jobs.size();
-    for (VfyDevJob<C>* J : jobs) { ctx->vcl_instances += J->count; if (J->wire) ctx->cw_front_end += J->count * J->m; }
+    for (VfyDevJob<C>* J : jobs) { ctx->vcl_instances += J->count; if (J->sh.wire) ctx->cw_front_end += J->count * J->sh.m; }
     done = true;
     if (!rest.empty()) {
         uint64_t pt[8];

@@ -174,13 +174,13 @@ template <class C> static int vfy_reserve(VfyHostJob<C>& J) {
     bp_ctx* ctx = J.ctx;
     hipStream_t st = ctx->stream;
     const size_t count = J.count, maxN = J.maxN;
-    BPCHK(ctx->r_g.ensure((2 + 2 * maxN + J.Ttot) * 32));
+    BPCHK(ctx->r_g.ensure(vfy_rg_len(maxN, J.Ttot) * 32));   // (the r_g layout: vfy_dev_plan.hpp)
     BPCHK(ctx->r_tail.ensure(std::max<size_t>(J.Ttot, 1) * 64));
     BPCHK(ctx->r_small.ensure((count + 8) * 32));               // one (wc + delta) slot per launched group: at most one per instance
     BPCHK(ctx->v_alpha.ensure(count * 32 + (count + 1) * 4));
-    J.sc = ctx->r_g.as<u32>(); J.acc_g = J.sc + 2 * 8; J.acc_h = J.sc + (2 + maxN) * 8; J.d_tail_sc = J.sc + (2 + 2 * maxN) * 8;
+    J.sc = ctx->r_g.as<u32>(); J.acc_g = J.sc + VFY_RG_G * 8; J.acc_h = J.sc + vfy_rg_h(maxN) * 8; J.d_tail_sc = J.sc + vfy_rg_tails(maxN) * 8;
     J.d_alpha = ctx->v_alpha.as<u32>(); J.d_toff = J.d_alpha + count * 8;
-    HIPCHK(hipMemsetAsync(J.sc, 0, (2 + 2 * maxN) * 32, st));
+    HIPCHK(hipMemsetAsync(J.sc, 0, vfy_rg_tails(maxN) * 32, st));
     BPCHK(upload_scalars<C>(ctx, J.d_alpha, J.alphas, count));
     std::vector<u32> toff32(J.toff.begin(), J.toff.end());
     HIPCHK(hipMemcpyAsync(J.d_toff, toff32.data(), (count + 1) * 4, hipMemcpyHostToDevice, st));
